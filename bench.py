@@ -10,6 +10,12 @@ synthetic linear-padding data already resident in HBM.  Default workload "M" = t
 the metric is quoted on: linear_gaussian dd=3 pad=9 (D=12), latent 20, linear encoder/decoder,
 -tdv, epsilon=-1, lr=1e-3 (seed_linpadding_expts.sh:1) at batch 65 536 PER GPU (weak scaling;
 --scaling strong divides a global 65 536 over the ranks instead).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up (W steps, then 3-10 untimed passes of the timed region), times exactly --steps steps once
+and prints the line.  --full adds everything else the line can carry: 20 timed regions (`value` = the median), the
+kernel-timestamp roofline leg, the per-sample A/B leg, the fresh-inputs leg and the CPU baseline.  --dump-outputs DIR writes
+what the timed path computed in its last step (parameters, gradient buffer with the loss slots, Adam moments and counter) as
+DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -109,6 +115,27 @@ def make_batches(w, B, device, nbuf, seed):
         z = torch.randn(B, L + D, device=device, generator=g)
         out.append((x.contiguous(), z[:, :L].contiguous(), z[:, L:].contiguous()))
     return out
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> tensor.  Writes out_dir/<name>.npy, float32 kept, everything else as float64.  If all of them together
+    pass 64 MB, an array larger than its even share of that is replaced by a fixed sample of its elements (seeded, sorted
+    flat indices), so that two builds still compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    share = DUMP_LIMIT // max(1, len(host))
+    over = sum(a.nbytes for a in host.values()) > DUMP_LIMIT
+    for name, a in host.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def usable_cores():
@@ -235,7 +262,7 @@ def bench_conv(args):
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
     S, widths, L = 64, (32, 64, 128, 256), 32
     B = args.batch or 4096                                   # config 5 names 32 768 over 8 GPUs
-    steps, warm = min(args.steps, 20), min(max(args.warmup, 2), 5)
+    steps, warm = args.steps, min(max(args.warmup, 2), 5)
     net = ConvVAE(B, S, widths, L, -3.0, True, device=local_rank, world=world)
     g = torch.Generator(device="cpu").manual_seed(0)
     params, grads, m, v = net.new_flat(), net.new_flat(), net.new_flat(), net.new_flat()
@@ -286,6 +313,8 @@ def bench_conv(args):
     assert math.isfinite(loss)
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"params": params, "grads": grads, "adam_m": m, "adam_v": v, "adam_step": step, "out4": out4})
     chans = [1, *widths]
     macs = sum((S >> (i + 1)) ** 2 * chans[i + 1] * 16 * chans[i] for i in range(4))       # one conv stack, forward, per sample
     flops = 3 * 2 * (2 * macs + 2 * net.bott * L)                                           # both stacks + the two Dense; fwd + 2 x bwd
@@ -313,6 +342,9 @@ def main():
         ap.add_argument("--warmup", type=int, default=3); ap.add_argument("--batch", type=int, default=0)
         ap.add_argument("--no-cpu-baseline", action="store_true"); ap.add_argument("--rehearse-one-gpu", action="store_true")
         ap.add_argument("--no-graph", action="store_true", help="eager launches on one GPU too (counter profiling)")
+        ap.add_argument("--full", action="store_true", help="accepted for a uniform command line: this workload has no extra legs")
+        ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="write the last timed step's parameters, gradients, Adam state and loss slots as DIR/<name>.npy")
         return bench_conv(ap.parse_args())
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -344,14 +376,22 @@ def main():
     ap.add_argument("--graph", type=int, default=-1,
                     help="steps captured per hipGraph (0 = eager launches; -1 = auto: the largest even size <= 200 dividing --steps)")
     ap.add_argument("--only-main", action="store_true", help="skip the A/B legs (per-sample path, fresh inputs): profiler passes")
-    ap.add_argument("--repeat", type=int, default=20,
+    ap.add_argument("--repeat", type=int, default=None,
                     help="how many times the timed region of exactly --steps steps is run (each time behind its own Infinity Cache sweep, "
-                         "barrier and synchronize); `value` is the MEDIAN region, min / max ride along")
+                         "barrier and synchronize); `value` is the MEDIAN region, min / max ride along.  Default: 1, with --full 20")
     ap.add_argument("--launch", default="auto", choices=["auto", "graph", "direct"],
                     help="vaek_train_steps only: replay a hipGraph of the K steps, or call the library directly with pre-marshalled "
                          "arguments (one persistent launch per 64 steps either way; auto = direct: a graph replay costs the host more "
                          "than the one or two launches it replaces)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: 20 timed regions, the roofline leg (unless --no-roofline), the per-sample "
+                         "A/B and fresh-inputs legs (unless --only-main) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's parameters, gradient buffer (loss slots included), Adam moments "
+                         "and counter as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.repeat is None:
+        args.repeat = 20 if args.full else 1
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -519,6 +559,15 @@ def main():
         sweep_sink.copy_(mall_sweep.sum())
         run_group(len(batches) - 4, 4)
 
+    if not args.full:
+        # A lone timed region right after setup reads slow (measured, 12 regions in a row: 3.73 us/step in the first at 2000
+        # steps, 3.58 from the third on; 6.3 against 5.1 at 20 steps, which settles only by the tenth), so a plain run first runs
+        # the region's exact sequence untimed, three times (ten for a short region; at most 4096 steps each): its one timed
+        # region is then a steady-state one, as --full's median is.
+        for _ in range(max(3, min(10, -(-4096 // max(1, args.steps))))):
+            sweep()
+            run_steps(min(args.steps, 4096))
+            fence()
     regions = []
     for _ in range(max(1, args.repeat)):
         sweep()
@@ -539,11 +588,14 @@ def main():
                                                f"{eng.train_steps_status_word:#x}, {elapsed:.3f} s for {args.steps} steps): results invalid")
     if exch is not None and exch.in_library:
         assert not exch.timed_out(), "p2p gradient exchange gave up waiting for a peer"
+    if args.dump_outputs and rank == 0:
+        # the state the timed path handed back after its last step, before any other leg touches these buffers
+        dump_outputs(args.dump_outputs, {"params": params, "grads": grads, "adam_m": m, "adam_v": v, "adam_step": step_dev})
 
     # ---- A/B (never `value`): the same workload through the drop-in per-sample step, vaek_train_step (two launches per step:
     # the fused forward/backward chain + finalize/Adam), captured and timed the same way -- what `value` was in round 1
     per_sample = None
-    if use_pipe and world == 1 and not args.only_main:
+    if args.full and use_pipe and world == 1 and not args.only_main:
         gs2 = max(2, min(gsteps if gsteps > 0 else 20, 192))
         p2, g2, m2, v2 = params.clone(), eng.new_flat(eng.grad_len), m.clone(), v.clone()
         s2 = step_dev.clone()
@@ -580,7 +632,7 @@ def main():
 
     # ---- roofline leg: the same steps again with every library launch bracketed by its own begin/end timestamps ----
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         rsteps = min(args.steps, 192)                       # kernel-timestamp leg (one event pair per launch)
         sweep()
         eng.profile_begin(max_records=rsteps * 64)
@@ -670,7 +722,7 @@ def main():
     # batch n+1 rides in the finalize launch of step n (vaek_train_step_gen), all inside the hipGraph
     fresh = None
     kind = {"linear_gaussian": 0, "sigmoid": 1, "sphere": 2}[w["dataset"]]
-    if args.only_main:
+    if args.only_main or not args.full:
         pass
     elif world == 1 and use_pipe and eng.supports_train_steps_gen(kind):
         # the loop body of model.py:221-222 as run.py --fast_loop runs it (trainer.GraphLoop): vaek_train_steps_gen, every step's
@@ -729,7 +781,7 @@ def main():
                          "the step before) instead of pre-resident batches"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, B_local, args.cpu_seconds)
         if args.workload == "M":
             cpu["c1"] = cpu_baseline_c1()
@@ -744,7 +796,7 @@ def main():
             "timed_regions": {"count": len(regions), "steps_each": args.steps, "median_ms_per_step": elapsed / args.steps * 1e3,
                               "min_ms_per_step": min(regions) / args.steps * 1e3, "max_ms_per_step": max(regions) / args.steps * 1e3,
                               "note": "value = the median region; each region = exactly --steps train steps between barrier + synchronize"},
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": f"{args.workload}: {w['desc']}", "batch_per_gpu": B_local, "global_batch": B_global,
                        "data_dim": D, "latent_dim": L, "params": eng.P, "path": "fused" if eng.fused else "layer-by-layer",
                        "step_entry_point": ("vaek_train_steps (up to 64 steps per persistent launch: streamers | reducers | updater)" if use_pipe else
