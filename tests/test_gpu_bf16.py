@@ -102,4 +102,4 @@ def test_bf16s_variants_are_bitwise_identical():
                     assert lib.vaek_debug_hs_variant(-1, tn, None, None) == 0
                     assert torch.equal(grads(), ref), f"TN variant {tn} differs"
         finally:
-            lib.vaek_debug_hs_variant(-2, 0, None, None)
+            lib.vaek_debug_hs_variant(-2, -2, None, None)

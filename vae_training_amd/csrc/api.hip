@@ -14,10 +14,6 @@ namespace vaek {
 
 static thread_local char g_err[512] = "";
 thread_local Profiler* g_prof = nullptr;
-struct ProfBind {   // entry points bind the context's profiler for the duration of the call
-    explicit ProfBind(vaek_ctx* c) { g_prof = c ? &c->prof : nullptr; }
-    ~ProfBind() { g_prof = nullptr; }
-};
 void set_error(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);

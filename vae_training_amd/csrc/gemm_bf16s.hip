@@ -1105,12 +1105,13 @@ int launch_cvt_weights(const float* params, __bf16* out, const int* K, const int
 }  // namespace vaek
 
 // Diagnostic hook (not part of include/vaek.h; tools/hs_tune.py): pick the tile / ring variant of the bf16-storage GEMMs
-// for this process (-1 keeps the current one) and report how many exist.
+// for this process (-1 keeps the current one, -2 restores the by-shape default) and report how many exist.
 extern "C" int vaek_debug_hs_variant(int nt, int tn, int* n_nt, int* n_tn) {
     if (nt >= vaek::kNtCount || tn >= vaek::kTnCount) return VAEK_ERR_INVALID;
     if (nt >= 0) vaek::g_hs_variant_nt = nt;
     if (nt == -2) vaek::g_hs_variant_nt = -1;            // back to the by-shape default
     if (tn >= 0) vaek::g_hs_variant_tn = tn;
+    if (tn == -2) vaek::g_hs_variant_tn = -1;
     if (n_nt) *n_nt = vaek::kNtCount;
     if (n_tn) *n_tn = vaek::kTnCount;
     return VAEK_OK;

@@ -528,7 +528,17 @@ __global__ __launch_bounds__(256) void sk_prep_kernel(const float* __restrict__ 
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
+constexpr int kSkGroup = 64;       // partial images summed into one slab
+
 bool sk_supported(int d, int H) { return d >= 1 && d <= 16 && H % 64 == 0 && H >= 64 && H <= 2048; }
+// sk_last_bwd / sk_first_bwd run sk_last_bwd_mfma_kernel: H = 512, d <= 8, whole 16-row blocks per workgroup (S * 64 of them),
+// and rows * d a multiple of 4 -- a block's small operand (dy / x) arrives as 16-byte pieces of the tensor, the one that would
+// cross its end clamped back to its last 16 bytes: with rows * d % 4 != 0 that piece is SHIFTED, and the last rows of the last
+// workgroup saw their neighbours' values (tests/test_gpu_dense16.py, the mfma_tail cases)
+bool sk_bwd_mfma_form(int rows, int H, int d, int S) {
+    const int nwg = S * kSkGroup, rows_per_wg = (rows + nwg - 1) / nwg;
+    return d <= 8 && H == 512 && rows_per_wg % 16 == 0 && (long long)rows * d % 4 == 0 && (long long)rows * d * 4 >= 16;
+}
 
 int launch_sk_first_fwd(const float* x, const float* w, const float* b, __bf16* y, int rows, int d, int H, bool relu, hipStream_t st) {
     SkFwdArgs a{x, w, b, y, rows, d, H, relu ? 1 : 0};
@@ -577,8 +587,6 @@ int launch_sk_first_dx(const __bf16* dy, const __bf16* wp, float* dx, int rows, 
     return sk_rows(a, SK_PLAIN, "sk16_first_dx", st);
 }
 
-constexpr int kSkGroup = 64;       // partial images summed into one slab
-
 // S slabs <- S * 64 workgroups; rows_per_wg = ceil(rows / (S * 64))
 static int sk_reduce(const float* partial, long long n, int S, float* slab0, int64_t slab_stride, hipStream_t st) {
     ProfScope ps("sk16_partials_reduce", st);
@@ -595,7 +603,7 @@ int launch_sk_last_bwd(const __bf16* h, const float* dy, const float* w, __bf16*
     SkBwdArgs a{h, dy, w, dh, partial, rows, d, H, (rows + nwg - 1) / nwg};
     const int cprw = H / 8, rpp = 256 / cprw;
     const size_t lds = (size_t)std::max(rpp - 1, 0) * cprw * (9 * d) * sizeof(float);
-    if (d <= 8 && H == 512 && a.rows_per_wg % 16 == 0 && (long long)rows * d * 4 >= 16) {
+    if (sk_bwd_mfma_form(rows, H, d, S)) {
         // the matrix-core form: rows in blocks of 16 through a ring of four LDS images of h (+ dy)
         ProfScope ps("sk16_last_bwd", st);
         const size_t lds_m = (size_t)4 * (16 * (2 * H + 32) + 1024);
@@ -625,7 +633,7 @@ int launch_sk_first_bwd(const float* x, const __bf16* dy, float* partial, float*
     SkBwdArgs a{dy, x, nullptr, nullptr, partial, rows, d, H, (rows + nwg - 1) / nwg};
     const int cprw = H / 8, rpp = 256 / cprw;
     const size_t lds = (size_t)std::max(rpp - 1, 0) * cprw * ((d + 1) * 8) * sizeof(float);
-    if (d <= 8 && H == 512 && a.rows_per_wg % 16 == 0 && (long long)rows * d * 4 >= 16) {
+    if (sk_bwd_mfma_form(rows, H, d, S)) {
         // the matrix-core form (sk_last_bwd_mfma_kernel's G product with a ones column)
         ProfScope ps("sk16_first_bwd", st);
         const size_t lds_m = (size_t)4 * (16 * (2 * H + 32) + 1024);

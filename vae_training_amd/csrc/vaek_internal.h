@@ -118,6 +118,11 @@ struct vaek_ctx {
 
 namespace vaek {
 
+struct ProfBind {   // entry points bind the context's profiler for the duration of the call
+    explicit ProfBind(vaek_ctx* c) { g_prof = c ? &c->prof : nullptr; }
+    ~ProfBind() { g_prof = nullptr; }
+};
+
 // ---- gemm_f32.hip -------------------------------------------------------------------------
 int launch_dense_fwd(const float* x, const float* w, const float* b, float* y, int rows, int n_in,
                      int n_out, bool relu, hipStream_t st);
@@ -170,6 +175,7 @@ int launch_cvt_weights(const float* params, __bf16* out, const int* K, const int
 
 // gemm_skinny16.hip: first (d -> H) / last (H -> d) layer of a bf16-storage stack, d <= 16: one HBM pass per big tensor
 bool sk_supported(int d, int H);
+bool sk_bwd_mfma_form(int rows, int H, int d, int S);      // which form launch_sk_last_bwd / launch_sk_first_bwd run
 size_t sk_partial_bytes(int d, int H, int S);
 int launch_sk_first_fwd(const float* x, const float* w, const float* b, __bf16* y, int rows, int d, int H, bool relu, hipStream_t st);
 int launch_sk_last_fwd(const __bf16* h, const __bf16* wp, const float* b, float* y, int rows, int H, int d, hipStream_t st);
