@@ -117,13 +117,17 @@ def test_metric_size_and_agreement_with_the_step_by_step_kernels():
 
 def test_pipelined_steps_refuse_what_they_cannot_do():
     from vae_training_amd._lib import VaekError
-    cfg = O.Config(7, 6, (), (), -3.0, True, "sigmoid")           # two decoders with a sigmoid head: not linear in the inputs
-    eng = engine_for(cfg, 64)
-    assert not eng.supports_train_steps()
     z = lambda *s: torch.zeros(*s, device="cuda")
-    with pytest.raises(VaekError):
-        eng.train_steps(eng.new_flat(), eng.new_flat(eng.grad_len), eng.new_flat(), eng.new_flat(),
-                        torch.zeros(1, dtype=torch.int32, device="cuda"), [(z(64, 7), z(64, 6), z(64, 7))], 1e-3)
+    lin = lambda D, L: O.Config(D, L, (), (), -1.0, True, "linear_gaussian")
+    for cfg, B, kw in [(O.Config(7, 6, (), (), -3.0, True, "sigmoid"), 64, {}),    # two decoders with a sigmoid head: not linear in the inputs
+                       (lin(22, 20), 64, {}),                                        # L + 2 D + 1 = 65 features
+                       (lin(12, 20), 64, {"dtype": "bf16"}),
+                       (lin(3, 2), 3, {})]:                                          # B min(D, L) = 6 < 8
+        eng = engine_for(cfg, B, **kw)
+        assert not eng.supports_train_steps() and not eng.supports_train_steps_gen(0) and eng.moment_len() == 0, (cfg.D, cfg.L, B, kw)
+        with pytest.raises(VaekError):
+            eng.train_steps(eng.new_flat(), eng.new_flat(eng.grad_len), eng.new_flat(), eng.new_flat(),
+                            torch.zeros(1, dtype=torch.int32, device="cuda"), [(z(B, cfg.D), z(B, cfg.L), z(B, cfg.D))], 1e-3)
     mlp = engine_for(O.Config(12, 20, (32,), (32,), -1.0, True, "linear_gaussian"), 64)
     assert not mlp.supports_train_steps()
 
@@ -201,6 +205,49 @@ def test_graph_replay_of_pipelined_steps_equals_the_eager_call():
     assert int(sg.item()) == int(se.item()) == 2 * n
     assert torch.equal(pg, pe) and torch.equal(mg, me) and torch.equal(vg, ve) and torch.equal(gg, ge)
     assert torch.equal(ring_g, ring_e) and float(ring_e[2 * n - 1]) < float(ring_e[0])
+
+
+def test_a_captured_first_call_does_not_stand_in_for_the_init():
+    """A context's FIRST vaek_train_steps call captured into a hipGraph that is not replayed: the zeroing of the arrival counters
+    was only recorded, so the next eager call on the same workspace (full of 0xFF) must still zero them -- bitwise the results of
+    another context's eager call -- and the graph, replayed afterwards, runs without a bounded wait expiring."""
+    cfg, dk, _, lr = build("c1_linear_L20")
+    B, n = 3000, 70                                    # two persistent launches per call
+    p, batches = _problem(cfg, dk, B, n)
+    seq = [tuple(dev(a) for a in b) for b in batches]
+
+    def fresh(eng):
+        return [dev(O.flatten(cfg, p)), eng.new_flat(eng.grad_len), eng.new_flat(), eng.new_flat(),
+                torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(n + 8, dtype=torch.float32, device="cuda")]
+
+    def eager(eng):
+        out = fresh(eng)
+        eng.set_loss_history(out[5])
+        eng.train_steps(*out[:5], seq, lr)
+        torch.cuda.synchronize()
+        eng.set_loss_history(None)
+        assert not eng.train_steps_gave_up(), hex(eng.train_steps_status_word)
+        return out
+
+    eng = engine_for(cfg, B)
+    eng.workspace.fill_(0xFF)
+    cap = fresh(eng)
+    eng.set_loss_history(cap[5])
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            eng.train_steps(*cap[:5], seq, lr)
+    torch.cuda.current_stream().wait_stream(side)
+    got = eager(eng)
+    want = eager(engine_for(cfg, B))
+    assert int(got[4].item()) == n
+    assert all(torch.equal(a, b) for a, b in zip(got, want)), "params, grads, m, v, step, loss ring"
+    graph.replay()
+    torch.cuda.synchronize()
+    assert not eng.train_steps_gave_up(), hex(eng.train_steps_status_word)
+    assert all(torch.equal(a, b) for a, b in zip(cap, want))
 
 
 @pytest.mark.parametrize("seed", range(14))

@@ -486,7 +486,8 @@ int vaek_ctx_create(const vaek_config* cfg, vaek_ctx** out) {
     c->ws_wb16 = off; off = align_up(off + (size_t)wb_elems * sizeof(__bf16), 256);
     c->ws_sk16 = off; off = align_up(off + (size_t)sk_elems * sizeof(__bf16), 256);
     c->ws_skpart = off; off = align_up(off + sk_part, 256);
-    c->ws_lin = off; off = align_up(off + lin_steps_workspace_bytes(c), 256);
+    c->lin = lin_plan(c);
+    c->ws_lin = off; off = align_up(off + c->lin.ws_bytes, 256);
     c->ws_lwd = off; off = align_up(off + (c->lwd ? lwd_gpart_bytes(c->B, c->D, c->L) : 0), 256);
     c->ws_total = off;
     *out = c;
@@ -800,14 +801,14 @@ int vaek_train_steps_gen(vaek_ctx* ctx, float* params, float* grads, float* m, f
 
 int vaek_train_steps_moment_len(const vaek_ctx* ctx, int64_t* len) {
     if (!ctx || !len) { set_error("null argument"); return VAEK_ERR_INVALID; }
-    *len = (int64_t)lin_moment_len(ctx);
+    *len = ctx->lin.NO;
     return VAEK_OK;
 }
 
 int vaek_train_steps_moments(vaek_ctx* ctx, const float* x, const float* z1, const float* z2, double* M, void* workspace, void* stream) {
     ProfBind pb(ctx);
     if (!ctx || !x || !z1 || !z2 || !M) { set_error("vaek_train_steps_moments: null argument"); return VAEK_ERR_INVALID; }
-    if (!lin_moments_supported(ctx)) { set_error("vaek_train_steps_moments: not a float32 linear VAE with L + 2 D + 1 <= 64"); return VAEK_ERR_INVALID; }
+    if (!ctx->lin.ok) { set_error("vaek_train_steps_moments: not a float32 linear VAE with L + 2 D + 1 <= 64"); return VAEK_ERR_INVALID; }
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z1) | reinterpret_cast<uintptr_t>(z2)) & 15) {
         set_error("vaek_train_steps_moments: batch pointers must be 16-byte aligned");
         return VAEK_ERR_INVALID;
@@ -821,7 +822,7 @@ int vaek_train_steps_update(vaek_ctx* ctx, float* params, float* grads, float* m
                             void* workspace, void* stream) {
     ProfBind pb(ctx);
     if (!ctx || !params || !grads || !m || !v || !step_dev || !M) { set_error("vaek_train_steps_update: null argument"); return VAEK_ERR_INVALID; }
-    if (!lin_moments_supported(ctx)) { set_error("vaek_train_steps_update: not a float32 linear VAE with L + 2 D + 1 <= 64"); return VAEK_ERR_INVALID; }
+    if (!ctx->lin.ok) { set_error("vaek_train_steps_update: not a float32 linear VAE with L + 2 D + 1 <= 64"); return VAEK_ERR_INVALID; }
     int rc = check_ws(ctx, workspace);
     if (rc) return rc;
     return lin_update(ctx, params, grads, m, v, step_dev, M, lr, (hipStream_t)stream);

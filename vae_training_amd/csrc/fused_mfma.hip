@@ -690,12 +690,12 @@ int fused_mfma_launch(const vaek_ctx* c, const float* params, const void* args_v
     const MfmaVariant* var = pick_mfma(c);
     if (!var) { set_error("mfma fused path not available"); return VAEK_ERR_INVALID; }
     const FusedArgs& a = *static_cast<const FusedArgs*>(args_void);
-    static thread_local const void* lds_set[2][sizeof(kMfmaVariants) / sizeof(kMfmaVariants[0])] = {};
-    const size_t vi = var - kMfmaVariants;
+    static thread_local PerDeviceOnce attr_set[2][sizeof(kMfmaVariants) / sizeof(kMfmaVariants[0])];
+    PerDeviceOnce& once = attr_set[a.single ? 1 : 0][var - kMfmaVariants];
     const MfmaKernel fn = a.single ? var->fn_single : var->fn;
-    if (var->lds_bytes > 64 * 1024 && lds_set[a.single ? 1 : 0][vi] == nullptr) {
+    if (var->lds_bytes > 64 * 1024 && once.need()) {
         VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)var->lds_bytes));
-        lds_set[a.single ? 1 : 0][vi] = (const void*)fn;
+        once.mark();
     }
     {
         ProfScope ps(a.single ? "fused_linear_mfma_single" : "fused_linear_mfma", st);

@@ -1259,7 +1259,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
     const int per_set = a.n_reduce / a.sets;                  // reducer workgroups per set
     if (b < a.has_update) {
         // ---- the updater: one workgroup, parameters and Adam state in registers / LDS across all N steps (the host sends only
-        // shapes the matrix-core updater covers into this form: lin_persist_supported) -------------------------------------------
+        // shapes the matrix-core updater covers into this form: LinPlan::persist) ------------------------------------------------
         LinUpdM<NB, DT, LT> u;
         u.carve(a, lin_smem);
         int tstep = a.step_dev[0];
@@ -1594,90 +1594,95 @@ __global__ void lin_init_kernel(unsigned* cnt, int n_words, unsigned* status) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
-// 16-feature blocks of the kernel instantiation that serves this model: 3 (up to 48 features: the metric's 45) or 4
-static int lin_nb(const vaek_ctx* c) { return (c->L + 2 * c->D + 1 + 15) / 16 <= 3 ? 3 : 4; }
-static int lin_no(const vaek_ctx* c) { const int NB = lin_nb(c); return NB * (NB + 1) / 2 * 256; }
-
-// the model / batch shapes the moment formulation covers (whatever the number of ranks)
-static bool lin_steps_shape_ok(const vaek_ctx* c) {
-    return c->cfg.n_enc_hidden == 0 && c->cfg.n_dec_hidden == 0 && !c->cfg.sigmoid_decoder && c->cfg.dtype == VAEK_F32 &&
-           c->L + 2 * c->D + 1 <= 64 && (long long)c->B * std::min(c->D, c->L) >= 8;
-}
-static bool lin_persist_supported(const vaek_ctx* c);
-// data parallel: the persistent form only, and only once the P2P communicator (vaek_comm_create / _init) carries the moment region
-bool lin_steps_supported(const vaek_ctx* c) {
-    if (!lin_steps_shape_ok(c)) return false;
-    if (c->cfg.world == 1) return true;
-    return lin_persist_supported(c) && c->comm.ready && c->comm.lin_bytes > 0;
-}
-// LDS of a persistent streamer: three tile slots (each doubling as the combine's cross-wave scratch), the two validity columns,
-// the zero word, the batch pointer tables
-static size_t lin_ring_bytes(const vaek_ctx* c, int T) {
-    const LinTile tl(c->D, c->L, T);
-    return 3 * std::max((size_t)tl.bytes, (size_t)lin_scratch_bytes(lin_nb(c))) + 8 * (size_t)T + 16 + 3 * kLinMaxPersist * sizeof(void*) + 64;
-}
 constexpr size_t kLinMaxLds = 160 * 1024;
-// Samples per tile.  256, unless a slightly taller tile lets every streamer of the persistent launch take exactly ONE tile per
-// batch (the metric: 65 536 samples = 228 tiles of 288 on the 231 CUs the updater and the reducers leave).
-static int lin_tile_rows(const vaek_ctx* c) {
-    const int smax = c->n_cu - 1 - kLinReduceSets * kLinReduceWgs;
-    if (smax < 16 || c->B <= 256 * smax) return 256;
-    const int T = 32 * (int)(((long long)c->B + 32ll * smax - 1) / (32ll * smax));
-    const LinTile tl(c->D, c->L, T);
-    return T <= 512 && (tl.np + LNW - kLinCW - 1) / (LNW - kLinCW) <= 18 && lin_ring_bytes(c, T) <= kLinMaxLds ? T : 256;
-}
-static int lin_ntiles(const vaek_ctx* c) { const int T = lin_tile_rows(c); return (c->B + T - 1) / T; }
-static size_t lin_slot_stride(const vaek_ctx* c) {      // one tile slot, large enough to double as the combine's cross-wave scratch
-    const LinTile tl(c->D, c->L, lin_tile_rows(c));
-    return std::max((size_t)tl.bytes, (size_t)lin_scratch_bytes(lin_nb(c)));
-}
-static size_t lin_lds_need(const vaek_ctx* c) {         // launch-per-step form: one slot + validity column + zero word | updater | reducer sums
-    const int NB = lin_nb(c), D = c->D, L = c->L;
-    const size_t upd = std::max(NB == 3 ? LinUpd<3, 0, 0>::lds_bytes(D, L) : LinUpd<4, 0, 0>::lds_bytes(D, L), LinUpdM<3, 0, 0>::lds_bytes(D, L, (int)c->P));
-    return std::max(lin_slot_stride(c) + 4 * (size_t)lin_tile_rows(c) + 16, std::max(upd, (size_t)2 * 16 * 32 * sizeof(double))) + 64;
-}
-// The persistent form gives every workgroup a CU of its own (the updater's float64 chains and the streamers' MFMA loops both
-// lose a factor ~2 when they share one): each workgroup asks for more than half a CU's LDS -- the streamers need it anyway for
-// their ring of tile slots -- and the grid stays within the CU count.
-static size_t lin_persist_lds(const vaek_ctx* c) {
-    return std::max(std::max(lin_lds_need(c), lin_ring_bytes(c, lin_tile_rows(c))), (size_t)82 * 1024);
-}
-static bool lin_persist_supported(const vaek_ctx* c) {
-    const LinTile tl(c->D, c->L, lin_tile_rows(c));
-    return lin_steps_shape_ok(c) && lin_nb(c) == 3 && LinUpdM<3, 0, 0>::shape_ok(c->D, c->L) && lin_persist_lds(c) <= kLinMaxLds &&
-           (tl.np + LNW - kLinCW - 1) / (LNW - kLinCW) <= 18 && c->n_cu >= 1 + kLinReduceSets * kLinReduceWgs + 16;
-}
-// streamer workgroups of the persistent launch: the CUs the updater and the reducers leave, tiles dealt evenly
-static int lin_persist_streamers(const vaek_ctx* c) {
-    const int ntiles = lin_ntiles(c), smax = c->n_cu - 1 - kLinReduceSets * kLinReduceWgs;
-    const int per = (ntiles + smax - 1) / smax;
-    return (ntiles + per - 1) / per;
-}
-
 // workspace: [cnt_stream: 64 batches x 8 shards x 128 B][cnt_reduce: 64 words][status word, init mark][M slots][partial image slots]
 constexpr size_t kLinCntStreamBytes = (size_t)kLinMaxPersist * kLinShards * kLinShardStride * 4, kLinCntBytes = kLinCntStreamBytes + 1024, kLinHeadBytes = kLinCntBytes + 256;
-struct LinWs { float* partial; double* M; unsigned* cnt; unsigned* cnt_reduce; unsigned* status; size_t total; };
-static LinWs lin_carve(const vaek_ctx* c, char* base) {
-    const size_t no = lin_no(c), ntiles = lin_ntiles(c);
-    const int slots = lin_persist_supported(c) ? kLinMaxPersist : 2;
-    LinWs w{};
-    size_t off = 0;
-    w.cnt = reinterpret_cast<unsigned*>(base + off); w.cnt_reduce = reinterpret_cast<unsigned*>(base + kLinCntStreamBytes);
-    w.status = reinterpret_cast<unsigned*>(base + kLinCntBytes); off += kLinHeadBytes;
-    w.M = reinterpret_cast<double*>(base + off); off += (size_t)slots * no * sizeof(double) + 256;
-    w.partial = reinterpret_cast<float*>(base + off); off += (size_t)slots * ntiles * no * sizeof(float) + 256;
-    w.total = (off + 255) / 256 * 256;
-    return w;
-}
-size_t lin_steps_workspace_bytes(const vaek_ctx* c) { return lin_steps_shape_ok(c) ? lin_carve(c, nullptr).total : 0; }
-// bytes of the moment-exchange region of the P2P communicator's buffer (0: this context never exchanges moments)
-size_t lin_comm_bytes(const vaek_ctx* c) {
-    if (c->cfg.world < 2 || !lin_persist_supported(c)) return 0;
-    return (size_t)kLinCommBanks * c->cfg.world * 2 * lin_no(c) * sizeof(unsigned long long);
+
+LinPlan lin_plan(const vaek_ctx* c) {
+    LinPlan p{};
+    const int D = c->D, L = c->L;
+    p.ok = c->cfg.n_enc_hidden == 0 && c->cfg.n_dec_hidden == 0 && !c->cfg.sigmoid_decoder && c->cfg.dtype == VAEK_F32 &&
+           L + 2 * D + 1 <= 64 && (long long)c->B * std::min(D, L) >= 8;
+    if (!p.ok) return p;
+    // 16-feature blocks of the kernel instantiation that serves this model: 3 (up to 48 features: the metric's 45) or 4
+    p.NB = (L + 2 * D + 1 + 15) / 16 <= 3 ? 3 : 4;
+    p.NO = p.NB * (p.NB + 1) / 2 * 256;
+    // a tile slot doubles as the combine's cross-wave scratch; a persistent streamer's LDS: three slots, the two validity columns,
+    // the zero word, the batch pointer tables
+    const auto slot_bytes = [&](int T) { return std::max((size_t)LinTile(D, L, T).bytes, (size_t)lin_scratch_bytes(p.NB)); };
+    const auto ring_bytes = [&](int T) { return 3 * slot_bytes(T) + 8 * (size_t)T + 16 + 3 * kLinMaxPersist * sizeof(void*) + 64; };
+    const auto ksteps_ok = [&](int T) { return (LinTile(D, L, T).np + LNW - kLinCW - 1) / (LNW - kLinCW) <= 18; };
+    // Samples per tile.  256, unless a slightly taller tile lets every streamer of the persistent launch take exactly ONE tile per
+    // batch (the metric: 65 536 samples = 228 tiles of 288 on the 231 CUs the updater and the reducers leave).
+    const int smax = c->n_cu - 1 - kLinReduceSets * kLinReduceWgs;
+    p.T = 256;
+    if (smax >= 16 && c->B > 256 * smax) {
+        const int T = 32 * (int)(((long long)c->B + 32ll * smax - 1) / (32ll * smax));
+        if (T <= 512 && ksteps_ok(T) && ring_bytes(T) <= kLinMaxLds) p.T = T;
+    }
+    p.ntiles = (c->B + p.T - 1) / p.T;
+    // launch-per-step form: one slot + validity column + zero word | updater | reducer sums
+    const size_t upd = std::max(p.NB == 3 ? LinUpd<3, 0, 0>::lds_bytes(D, L) : LinUpd<4, 0, 0>::lds_bytes(D, L), LinUpdM<3, 0, 0>::lds_bytes(D, L, (int)c->P));
+    p.lds_step = std::max(slot_bytes(p.T) + 4 * (size_t)p.T + 16, std::max(upd, (size_t)2 * 16 * 32 * sizeof(double))) + 64;
+    // The persistent form gives every workgroup a CU of its own (the updater's float64 chains and the streamers' MFMA loops both
+    // lose a factor ~2 when they share one): each workgroup asks for more than half a CU's LDS -- the streamers need it anyway for
+    // their ring of tile slots -- and the grid stays within the CU count.
+    p.lds_persist = std::max(std::max(p.lds_step, ring_bytes(p.T)), (size_t)82 * 1024);
+    p.persist = p.NB == 3 && LinUpdM<3, 0, 0>::shape_ok(D, L) && p.lds_persist <= kLinMaxLds && ksteps_ok(p.T) && smax >= 16;
+    if (p.persist) {      // streamers: the CUs the updater and the reducers leave, tiles dealt evenly
+        const int per = (p.ntiles + smax - 1) / smax;
+        p.n_stream = (p.ntiles + per - 1) / per;
+        p.n_reduce = kLinReduceSets * std::min(kLinReduceWgs, p.NO / 32);
+    }
+    // the metric's shape with its dimensions (and the k-steps per wave of its 288-row tile) at compile time; every other linear
+    // model on the run-time instantiations
+    p.which_persist = D == 12 && L == 20 && p.T == 288 ? 0 : 1;
+    p.which_step = D == 12 && L == 20 ? 2 : p.NB - 3;
+    const int slots = p.persist ? kLinMaxPersist : 2;
+    p.M_off = kLinHeadBytes;
+    p.partial_off = p.M_off + (size_t)slots * p.NO * sizeof(double) + 256;
+    p.ws_bytes = (p.partial_off + (size_t)slots * p.ntiles * p.NO * sizeof(float) + 256 + 255) / 256 * 256;
+    if (c->cfg.world > 1 && p.persist) p.comm_bytes = (size_t)kLinCommBanks * c->cfg.world * 2 * p.NO * sizeof(unsigned long long);
+    return p;
 }
 
-static int lin_fill_common(const vaek_ctx* c, LinArgs& a, float* params, float* grads, float* m, float* v, int32_t* step_dev, float lr) {
-    a.B = c->B; a.D = c->D; a.L = c->L; a.T = lin_tile_rows(c); a.ntiles = lin_ntiles(c);
+// data parallel: the persistent form only, and only once the P2P communicator (vaek_comm_create / _init) carries the moment region
+bool lin_steps_supported(const vaek_ctx* c) {
+    return c->lin.ok && (c->cfg.world == 1 || (c->lin.persist && c->comm.ready && c->comm.lin_bytes > 0));
+}
+// the in-launch batch generator serves the datasets a linear VAE can be trained on (the sigmoid dataset brings a second decoder)
+bool lin_steps_gen_supported(const vaek_ctx* c, int kind) { return lin_steps_supported(c) && c->lin.persist && (kind == 0 || kind == 2); }
+
+struct LinWs { float* partial; double* M; unsigned* cnt; unsigned* cnt_reduce; unsigned* status; };
+static LinWs lin_ws(const vaek_ctx* c, void* ws) {
+    char* base = static_cast<char*>(ws) + c->ws_lin;
+    LinWs w;
+    w.cnt = reinterpret_cast<unsigned*>(base); w.cnt_reduce = reinterpret_cast<unsigned*>(base + kLinCntStreamBytes);
+    w.status = reinterpret_cast<unsigned*>(base + kLinCntBytes);
+    w.M = reinterpret_cast<double*>(base + c->lin.M_off); w.partial = reinterpret_cast<float*>(base + c->lin.partial_off);
+    return w;
+}
+
+// The kernels by LinPlan::which_persist / which_step, each given the LDS cap (not a request) the first time it is launched on a
+// device.  The device code lists the instantiations in the order these tables name them.
+typedef void (*LinStepKernel)(const LinArgs);
+typedef void (*LinPersistKernel)(const LinArgs, const LinPtrs);
+typedef void (*LinPersistGenKernel)(const LinArgs, const BatchArgs);
+static const LinPersistKernel kLinPersist[] = {lin_persist_kernel<3, 12, 20, 18, false>, lin_persist_kernel<3, 0, 0, 0, false>};
+static const LinPersistGenKernel kLinPersistGen[] = {lin_persist_kernel<3, 12, 20, 18, true>, lin_persist_kernel<3, 0, 0, 0, true>};
+static const LinStepKernel kLinStep[] = {lin_step_kernel<3, 0, 0>, lin_step_kernel<4, 0, 0>, lin_step_kernel<3, 12, 20>};
+template <typename K, size_t N> static int lin_kernel(const K (&table)[N], int which, K* fn) {
+    static thread_local PerDeviceOnce attr_set[N];
+    if (attr_set[which].need()) {
+        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)table[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLinMaxLds));
+        attr_set[which].mark();
+    }
+    *fn = table[which];
+    return VAEK_OK;
+}
+
+static void lin_fill_common(const vaek_ctx* c, LinArgs& a, float* params, float* grads, float* m, float* v, int32_t* step_dev, float lr) {
+    a.B = c->B; a.D = c->D; a.L = c->L; a.T = c->lin.T; a.ntiles = c->lin.ntiles;
     a.params = params; a.grads = grads; a.m = m; a.v = v; a.step_dev = step_dev; a.lr = lr;
     // data parallel: M is summed over the ranks before the updater sees it, so its "rows" are the GLOBAL batch
     const double rows = c->cfg.world > 1 ? (double)c->Bt : (double)c->B;
@@ -1686,58 +1691,41 @@ static int lin_fill_common(const vaek_ctx* c, LinArgs& a, float* params, float* 
     a.comm = LinComm{};
     a.comm.world = 1;
     if (c->cfg.world > 1 && c->comm.ready && c->comm.lin_bytes > 0) {
-        a.comm.world = c->cfg.world; a.comm.rank = c->cfg.rank; a.comm.ng2 = 2 * lin_no(c);
+        a.comm.world = c->cfg.world; a.comm.rank = c->cfg.rank; a.comm.ng2 = 2 * c->lin.NO;
         for (int r = 0; r < c->cfg.world; ++r)
             a.comm.peer[r] = reinterpret_cast<unsigned long long*>(static_cast<char*>(c->comm.peers[r]) + c->comm.lin_off);
     }
     a.loss_hist = c->loss_hist; a.loss_hist_cap = c->loss_hist_cap;
     static const int stagger = getenv("VAEK_LIN_STAGGER") ? atoi(getenv("VAEK_LIN_STAGGER")) : 3;      // diagnostic override
     a.stagger = stagger;
-    return 0;
 }
 
-// once per (context, workspace): the arrival counters start from zero (every persistent launch leaves them zero again)
+// The arrival counters start from zero (every persistent launch leaves them zero again): zeroed once per (context, workspace) by a
+// launch that has run in stream order.  A launch recorded into a graph being captured has not, and may never run.
 static int lin_ensure_init(vaek_ctx* c, const LinWs& w, void* ws, hipStream_t st) {
-    if (c->lin_ws_inited == ws && !c->lin_ws_reinit) return VAEK_OK;
+    if (c->lin_ws_ready == ws) return VAEK_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    VAEK_HIP_CHECK(hipStreamIsCapturing(st, &cap));
     hipLaunchKernelGGL(lin_init_kernel, dim3(1), dim3(1024), 0, st, w.cnt, (int)(kLinCntBytes / 4), w.status);
     VAEK_HIP_CHECK(hipGetLastError());
-    c->lin_ws_inited = ws;
-    c->lin_ws_reinit = false;
+    c->lin_ws_issued = ws;
+    c->lin_ws_ready = cap == hipStreamCaptureStatusNone ? ws : nullptr;
     return VAEK_OK;
 }
-
-// the in-launch batch generator serves the datasets a linear VAE can be trained on (the sigmoid dataset brings a second decoder)
-bool lin_steps_gen_supported(const vaek_ctx* c, int kind) { return lin_steps_supported(c) && lin_persist_supported(c) && (kind == 0 || kind == 2); }
 
 // gen != nullptr: the batches are drawn inside the launch (xs / z1s / z2s unused)
 static int lin_train_steps_impl(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* const* xs,
                                 const float* const* z1s, const float* const* z2s, const BatchArgs* gen, int n_steps, float lr, void* ws, hipStream_t st) {
-    const int NB = lin_nb(c), no = lin_no(c), ntiles = lin_ntiles(c);
-    const LinWs w = lin_carve(c, static_cast<char*>(ws) + c->ws_lin);
+    const LinPlan& p = c->lin;
+    const LinWs w = lin_ws(c, ws);
     static const char* env = getenv("VAEK_LIN_PERSIST");              // diagnostic: 0 forces the launch-per-step form
-    const bool persistent = lin_persist_supported(c) && (gen || c->cfg.world > 1 || !(env && atoi(env) == 0));   // data parallel, in-launch draw: persistent form only
+    static const int roles = getenv("VAEK_LIN_ROLES") ? atoi(getenv("VAEK_LIN_ROLES")) : 7;   // diagnostic: 1 stream, 2 reduce, 4 update
+    const bool persistent = p.persist && (gen || c->cfg.world > 1 || !(env && atoi(env) == 0));   // data parallel, in-launch draw: persistent form only
     if (gen && !persistent) { set_error("vaek_train_steps_gen: this context has no persistent form"); return VAEK_ERR_INVALID; }
-    // the metric's shape with its dimensions (and the k-steps per wave of its 288-row tile) at compile time; every other linear
-    // model on the run-time instantiations
-    const int which = (c->D == 12 && c->L == 20 && (!persistent || lin_tile_rows(c) == 288)) ? 0 : (NB <= 3 ? 1 : 2);
-    const size_t lds = persistent ? lin_persist_lds(c) : lin_lds_need(c);
-    int dev = 0;
-    VAEK_HIP_CHECK(hipGetDevice(&dev));
-    static thread_local unsigned char attr_set[3][3][64] = {};        // hipFuncSetAttribute is per device
-    const auto set_attr = [&](const void* fn) -> int {
-        unsigned char& done = attr_set[persistent ? (gen ? 2 : 1) : 0][which][dev & 63];
-        if (!done) {
-            VAEK_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLinMaxLds));   // a cap, not a request
-            done = 1;
-        }
-        return VAEK_OK;
-    };
     if (persistent) {
-        typedef void (*LinPersist)(const LinArgs, const LinPtrs);
-        typedef void (*LinPersistGen)(const LinArgs, const BatchArgs);
-        const LinPersist fn = which == 0 ? lin_persist_kernel<3, 12, 20, 18, false> : lin_persist_kernel<3, 0, 0, 0, false>;
-        const LinPersistGen fng = which == 0 ? lin_persist_kernel<3, 12, 20, 18, true> : lin_persist_kernel<3, 0, 0, 0, true>;
-        if (int rc = set_attr(gen ? (const void*)fng : (const void*)fn)) return rc;
+        LinPersistKernel fn = nullptr;
+        LinPersistGenKernel fng = nullptr;
+        if (int rc = gen ? lin_kernel(kLinPersistGen, p.which_persist, &fng) : lin_kernel(kLinPersist, p.which_persist, &fn)) return rc;
         if (int rc = lin_ensure_init(c, w, ws, st)) return rc;
         for (int s0 = 0; s0 < n_steps; s0 += kLinMaxPersist) {
             const int n = std::min(kLinMaxPersist, n_steps - s0);
@@ -1745,45 +1733,42 @@ static int lin_train_steps_impl(vaek_ctx* c, float* params, float* grads, float*
             lin_fill_common(c, a, params, grads, m, v, step_dev, lr);
             a.persistent = 1; a.n_steps = n;
             a.sets = kLinReduceSets;
-            a.has_update = 1; a.n_reduce = kLinReduceSets * std::min(kLinReduceWgs, no / 32); a.n_stream = lin_persist_streamers(c);
-            static const int proles = getenv("VAEK_LIN_ROLES") ? atoi(getenv("VAEK_LIN_ROLES")) : 7;    // diagnostic (tools/lin_roles.sh)
-            if (!(proles & 4)) a.has_update = 0;
-            if (!(proles & 2)) { a.has_update = 0; a.n_reduce = 0; }
-            if (!(proles & 1)) a.n_stream = 0;
-            if (proles != 7) c->lin_ws_reinit = true;          // nobody re-zeroes the counters without the updater: start over next call
+            a.has_update = 1; a.n_reduce = p.n_reduce; a.n_stream = p.n_stream;
+            if (!(roles & 4)) a.has_update = 0;
+            if (!(roles & 2)) { a.has_update = 0; a.n_reduce = 0; }
+            if (!(roles & 1)) a.n_stream = 0;
+            if (roles != 7) c->lin_ws_ready = nullptr;        // nobody re-zeroes the counters without the updater: start over next call
             a.partial_base = w.partial; a.M_base = w.M;
             a.cnt_stream = w.cnt; a.cnt_reduce = w.cnt_reduce; a.status = w.status;
             const dim3 grid((unsigned)(a.has_update + a.n_reduce + a.n_stream));
             if (gen) {
                 ProfScope ps("lin_moments_persistent_gen", st);
-                launch_k(ps, fng, grid, dim3(LNT), lds, st, a, *gen);
+                launch_k(ps, fng, grid, dim3(LNT), p.lds_persist, st, a, *gen);
             } else {
                 LinPtrs ptrs{};
                 for (int i = 0; i < n; ++i) { ptrs.x[i] = xs[s0 + i]; ptrs.z1[i] = z1s[s0 + i]; ptrs.z2[i] = z2s[s0 + i]; }
                 ProfScope ps("lin_moments_persistent", st);
-                launch_k(ps, fn, grid, dim3(LNT), lds, st, a, ptrs);
+                launch_k(ps, fn, grid, dim3(LNT), p.lds_persist, st, a, ptrs);
             }
         }
         VAEK_HIP_CHECK(hipGetLastError());
         return VAEK_OK;
     }
-    typedef void (*LinKernel)(const LinArgs);
-    const LinKernel fn = which == 0 ? lin_step_kernel<3, 12, 20> : which == 1 ? lin_step_kernel<3, 0, 0> : lin_step_kernel<4, 0, 0>;
-    if (int rc = set_attr((const void*)fn)) return rc;
-    static const int roles = getenv("VAEK_LIN_ROLES") ? atoi(getenv("VAEK_LIN_ROLES")) : 7;   // diagnostic: 1 stream, 2 reduce, 4 update
-    const size_t pstride = (size_t)ntiles * no;
+    LinStepKernel fn = nullptr;
+    if (int rc = lin_kernel(kLinStep, p.which_step, &fn)) return rc;
+    const size_t pstride = (size_t)p.ntiles * p.NO;
     for (int n = 0; n < n_steps + 2; ++n) {       // launch n: stream batch n, reduce batch n - 1, update batch n - 2
         LinArgs a{};
         lin_fill_common(c, a, params, grads, m, v, step_dev, lr);
         a.has_update = (n >= 2 && (roles & 4)) ? 1 : 0;
-        a.n_reduce = (n >= 1 && n <= n_steps && (roles & 2)) ? no / 32 : 0;
-        a.n_stream = (n < n_steps && (roles & 1)) ? ntiles : 0;
+        a.n_reduce = (n >= 1 && n <= n_steps && (roles & 2)) ? p.NO / 32 : 0;
+        a.n_stream = (n < n_steps && (roles & 1)) ? p.ntiles : 0;
         if (a.has_update + a.n_reduce + a.n_stream == 0) continue;
         if (a.n_stream) { a.x = xs[n]; a.z1 = z1s[n]; a.z2 = z2s[n]; a.partial_out = w.partial + (n & 1) * pstride; }
-        if (a.n_reduce) { a.partial_in = w.partial + ((n - 1) & 1) * pstride; a.M_out = w.M + ((n - 1) & 1) * no; }
-        a.M_in = w.M + (n & 1) * no;               // (n - 2) & 1
+        if (a.n_reduce) { a.partial_in = w.partial + ((n - 1) & 1) * pstride; a.M_out = w.M + ((n - 1) & 1) * p.NO; }
+        a.M_in = w.M + (n & 1) * p.NO;             // (n - 2) & 1
         ProfScope ps(a.n_stream ? "lin_moments_step" : "lin_moments_drain", st);
-        launch_k(ps, fn, dim3((unsigned)(a.has_update + a.n_reduce + a.n_stream)), dim3(LNT), lds, st, a);
+        launch_k(ps, fn, dim3((unsigned)(a.has_update + a.n_reduce + a.n_stream)), dim3(LNT), p.lds_step, st, a);
     }
     VAEK_HIP_CHECK(hipGetLastError());
     return VAEK_OK;
@@ -1803,55 +1788,45 @@ int lin_train_steps_gen(vaek_ctx* c, float* params, float* grads, float* m, floa
 // (the loss is a batch mean, networks.py:97-98), so a rank forms the M of its shard (lin_moments: streamers, then reducers, two
 // launches ordered by the stream), torch.distributed sums the 12 KB float64 image over the ranks (RCCL; gloo in rehearsal -- every
 // rank receives the same bits), and every rank applies the identical update (lin_update: rows = the GLOBAL batch).
-size_t lin_moment_len(const vaek_ctx* c) { return lin_steps_shape_ok(c) ? (size_t)lin_no(c) : 0; }
 int lin_moments(vaek_ctx* c, const float* x, const float* z1, const float* z2, double* M_out, void* ws, hipStream_t st) {
-    const int NB = lin_nb(c), no = lin_no(c), ntiles = lin_ntiles(c);
-    const LinWs w = lin_carve(c, static_cast<char*>(ws) + c->ws_lin);
-    const int which = (c->D == 12 && c->L == 20) ? 0 : (NB <= 3 ? 1 : 2);
-    typedef void (*LinKernel)(const LinArgs);
-    const LinKernel fn = which == 0 ? lin_step_kernel<3, 12, 20> : which == 1 ? lin_step_kernel<3, 0, 0> : lin_step_kernel<4, 0, 0>;
-    VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLinMaxLds));
-    const size_t lds = lin_lds_need(c);
+    const LinPlan& p = c->lin;
+    LinStepKernel fn = nullptr;
+    if (int rc = lin_kernel(kLinStep, p.which_step, &fn)) return rc;
     LinArgs a{};
     lin_fill_common(c, a, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f);
-    a.n_stream = ntiles; a.x = x; a.z1 = z1; a.z2 = z2; a.partial_out = w.partial;
-    { ProfScope ps("lin_moments_stream", st); launch_k(ps, fn, dim3((unsigned)ntiles), dim3(LNT), lds, st, a); }
-    a.n_stream = 0; a.n_reduce = no / 32; a.partial_in = w.partial; a.M_out = M_out;
+    a.n_stream = p.ntiles; a.x = x; a.z1 = z1; a.z2 = z2; a.partial_out = lin_ws(c, ws).partial;
+    { ProfScope ps("lin_moments_stream", st); launch_k(ps, fn, dim3((unsigned)p.ntiles), dim3(LNT), p.lds_step, st, a); }
+    a.n_stream = 0; a.n_reduce = p.NO / 32; a.partial_in = a.partial_out; a.M_out = M_out;
     a.comm = LinComm{}; a.comm.world = 1;                      // the ranks meet on the host, not in the reducers
-    { ProfScope ps("lin_moments_reduce", st); launch_k(ps, fn, dim3((unsigned)a.n_reduce), dim3(LNT), lds, st, a); }
+    { ProfScope ps("lin_moments_reduce", st); launch_k(ps, fn, dim3((unsigned)a.n_reduce), dim3(LNT), p.lds_step, st, a); }
     VAEK_HIP_CHECK(hipGetLastError());
     return VAEK_OK;
 }
 int lin_update(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const double* M_in, float lr, hipStream_t st) {
-    const int NB = lin_nb(c);
-    const int which = (c->D == 12 && c->L == 20) ? 0 : (NB <= 3 ? 1 : 2);
-    typedef void (*LinKernel)(const LinArgs);
-    const LinKernel fn = which == 0 ? lin_step_kernel<3, 12, 20> : which == 1 ? lin_step_kernel<3, 0, 0> : lin_step_kernel<4, 0, 0>;
-    VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLinMaxLds));
+    LinStepKernel fn = nullptr;
+    if (int rc = lin_kernel(kLinStep, c->lin.which_step, &fn)) return rc;
     LinArgs a{};
     lin_fill_common(c, a, params, grads, m, v, step_dev, lr);
     a.has_update = 1; a.M_in = M_in;
     ProfScope ps("lin_moments_update", st);
-    launch_k(ps, fn, dim3(1), dim3(LNT), lin_lds_need(c), st, a);
+    launch_k(ps, fn, dim3(1), dim3(LNT), c->lin.lds_step, st, a);
     VAEK_HIP_CHECK(hipGetLastError());
     return VAEK_OK;
 }
-bool lin_moments_supported(const vaek_ctx* c) { return lin_steps_shape_ok(c); }
 
 // synchronous: did a bounded wait of the persistent form ever give up (a workgroup that never became resident, a lost store)?
 // The word is STICKY -- no launch clears it, and while it is set every wait of every later launch returns at once (the grid
 // drains, its results are garbage) -- until this call reads it: read-and-clear.
 int lin_steps_status(vaek_ctx* c, void* ws, int* gave_up) {
     *gave_up = 0;
-    if (!lin_steps_shape_ok(c)) return VAEK_OK;
-    const LinWs w = lin_carve(c, static_cast<char*>(ws) + c->ws_lin);
-    if (c->lin_ws_inited != ws) return VAEK_OK;            // no persistent launch has used this workspace yet
+    if (c->lin_ws_issued != ws) return VAEK_OK;            // no persistent launch has been issued on this workspace yet
+    const LinWs w = lin_ws(c, ws);
     unsigned s = 0;
     VAEK_HIP_CHECK(hipMemcpy(&s, w.status, sizeof(s), hipMemcpyDeviceToHost));
     *gave_up = (int)s;
     if (s) {
         VAEK_HIP_CHECK(hipMemset(w.status, 0, sizeof(unsigned)));
-        c->lin_ws_reinit = true;                           // the counters of the launch that gave up are in an unknown state
+        c->lin_ws_ready = nullptr;                         // the counters of the launch that gave up are in an unknown state
     }
     return VAEK_OK;
 }

@@ -287,13 +287,11 @@ int launch_lwd(const float* samples, const float* Wd, const float* bd, const flo
     a.gpart = gpart; a.slab0 = slab0; a.slab_stride = slab_stride; a.part = part; a.B = B; a.D = D; a.L = L; a.RB = RB; a.ncb = D / WDC;
     const int nrb = (B + RB - 1) / RB;
     const size_t lds = sizeof(float) * (2 * WSR * WLP + 2 * WW * 32 * WGS + WW * 2 * WSR * WTS + 2 * WW) + 64;
-    int dev = 0;
-    VAEK_HIP_CHECK(hipGetDevice(&dev));
-    static thread_local unsigned char attr_set[64] = {};
-    if (!attr_set[dev & 63]) {
+    static thread_local PerDeviceOnce attr_set;
+    if (attr_set.need()) {
         VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)lwd_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
         VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)lwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_set[dev & 63] = 1;
+        attr_set.mark();
     }
     ProfScope ps("lwd_decoder_fwd_bwd", st);
     if (L <= 20) launch_k(ps, lwd_kernel<5>, dim3((unsigned)(nrb * a.ncb)), dim3(WT), lds, st, a);

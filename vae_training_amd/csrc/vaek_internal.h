@@ -89,6 +89,19 @@ struct Comm {
     size_t lin_off = 0, lin_bytes = 0;   // the moment-exchange region of vaek_train_steps (linear_moments.hip), behind the status line
 };
 
+// How vaek_train_steps runs this context (linear_moments.hip: lin_plan, once in vaek_ctx_create).  All zero unless ok.
+struct LinPlan {
+    bool ok = false;                  // the moment form covers the model: float32 linear VAE, L + 2 D + 1 <= 64, B min(D, L) >= 8
+    int NB = 0, NO = 0;               // 16-feature blocks of the instantiation (3 or 4); doubles in a moment image
+    int T = 0, ntiles = 0;            // samples per tile, tiles per batch
+    bool persist = false;             // the persistent form applies
+    int n_stream = 0, n_reduce = 0;   // its streamer / reducer workgroups
+    size_t lds_persist = 0, lds_step = 0;      // dynamic LDS of the persistent / launch-per-step form
+    int which_persist = 0, which_step = 0;     // instantiation: 0 / 2 the metric's D = 12, L = 20 at compile time, else run-time (step: NB - 3)
+    size_t M_off = 0, partial_off = 0, ws_bytes = 0;   // within the context's workspace region at ws_lin
+    size_t comm_bytes = 0;            // the moment-exchange region of the P2P communicator's buffer (world > 1, persistent form)
+};
+
 }  // namespace vaek
 
 struct vaek_ctx {
@@ -112,8 +125,9 @@ struct vaek_ctx {
     unsigned long long* dbg_stamps = nullptr;   // diagnostic builds (-DVAEK_STAMPS) only
     float* loss_hist = nullptr;                 // optional device ring: loss of Adam step t -> [(t-1) % cap]
     int64_t loss_hist_cap = 0;
-    bool lin_ws_reinit = false;                 // ... and must be zeroed again before the next launch (a wait gave up; a diagnostic launch without updater)
-    void* lin_ws_inited = nullptr;              // workspace whose vaek_train_steps arrival counters have been zeroed (linear_moments.hip)
+    vaek::LinPlan lin;
+    void* lin_ws_issued = nullptr;              // workspace for which an init of vaek_train_steps' arrival counters was launched or captured
+    void* lin_ws_ready = nullptr;               // ... and has run in stream order; cleared when the counters are in doubt (linear_moments.hip)
 };
 
 namespace vaek {
@@ -303,9 +317,8 @@ bool fused_mfma_supported(const vaek_ctx* c);
 int fused_mfma_launch(const vaek_ctx* c, const float* params, const void* fused_args, int grid, hipStream_t st);
 
 // ---- linear_moments.hip: N pipelined steps of a linear VAE through the batch's second-moment matrix --------------------
+LinPlan lin_plan(const vaek_ctx* c);
 bool lin_steps_supported(const vaek_ctx* c);
-size_t lin_comm_bytes(const vaek_ctx* c);
-size_t lin_steps_workspace_bytes(const vaek_ctx* c);
 int lin_train_steps(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* const* xs,
                     const float* const* z1s, const float* const* z2s, int n_steps, float lr, void* ws, hipStream_t st);
 int lin_steps_status(vaek_ctx* c, void* ws, int* gave_up);
@@ -318,8 +331,6 @@ int launch_lwd(const float* samples, const float* Wd, const float* bd, const flo
                float inv_bt, float* gpart, float* slab0, int64_t slab_stride, float* part, int B, int D, int L, int RB, hipStream_t st);
 int launch_lwd_second(const float* gpart, int ncb, float* dsamp, const float* mu, const float* z1, float* partial, int rows, int L, int S,
                       int rows_per_split, float inv_bt, const float* part, int nblk, float* epartial, int32_t* step_dev, hipStream_t st);
-bool lin_moments_supported(const vaek_ctx* c);
-size_t lin_moment_len(const vaek_ctx* c);
 int lin_moments(vaek_ctx* c, const float* x, const float* z1, const float* z2, double* M_out, void* ws, hipStream_t st);
 int lin_update(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const double* M_in, float lr, hipStream_t st);
 struct BatchArgs;

@@ -70,6 +70,8 @@ class Engine:
         self.P = n.value
         _lib.check(self.lib.vaek_grad_len(h, C.byref(n)))
         self.grad_len = n.value
+        _lib.check(self.lib.vaek_train_steps_moment_len(h, C.byref(n)))
+        self._moment_len = n.value
         nl = C.c_int32()
         _lib.check(self.lib.vaek_leaf_count(h, C.byref(nl)))
         self.leaves = OrderedDict()
@@ -169,9 +171,7 @@ class Engine:
 
     def moment_len(self):
         """doubles in the second-moment image of a batch (0: the moment form does not cover this model)."""
-        n = C.c_int64()
-        _lib.check(self.lib.vaek_train_steps_moment_len(self.h, C.byref(n)))
-        return int(n.value)
+        return self._moment_len
 
     def moments(self, x, z1, z2, M):
         """M (float64 device tensor of moment_len()) <- the second-moment image of this rank's batch shard (vaek_train_steps_moments)."""
