@@ -66,94 +66,172 @@ static inline int64_t slab_stride(const vaek_ctx* c) { return (int64_t)align_up(
 template <typename T>
 static T* at(void* ws, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(ws) + off); }
 
-// dtype = VAEK_BF16 routes the WIDE layers (both dims >= 64) through the bf16 matrix-core kernels; skinny
-// input/output layers (D, L of a handful of features) stay on the exact f32 kernels -- they are
-// bandwidth-bound and carry the reparameterisation / ELBO inputs.
-static bool use_bf16(const vaek_ctx* c, int n_in, int n_out) { return c->cfg.dtype == VAEK_BF16 && n_in >= 64 && n_out >= 64; }
-
-// bf16-STORAGE mode of a stack (Net::b16, vaek_internal.h): with at least two hidden layers whose widths are all multiples
-// of 64, the hidden activations / gradients are kept as bf16 and the hidden -> hidden layers run gemm_bf16s.hip.  Other
-// stacks under dtype = VAEK_BF16 keep f32 storage and the round-1 kernels (gemm_bf16.hip) for their wide layers.
-static bool net_is_b16(const vaek_ctx* c, const Net& net) {
-    if (c->cfg.dtype != VAEK_BF16 || net.layers.size() < 3) return false;
+// ---- a Dense layer's kernels: its kind, decided once per layer in vaek_ctx_create ---------------------------------------------
+// dtype = VAEK_BF16 routes the WIDE layers (both dims >= 64) of an f32-storage stack through the bf16 matrix-core kernels; skinny
+// input/output layers (D, L of a handful of features) stay on the exact f32 kernels -- they are bandwidth-bound and carry the
+// reparameterisation / ELBO inputs.  A b16 stack's ends keep an exact f32 product too, with the hidden side stored as bf16.
+Kind dense_kind(int dtype, bool b16, Pos pos, int n_in, int n_out) {
+    if (!b16) return dtype == VAEK_BF16 && n_in >= 64 && n_out >= 64 ? Kind::BF16 : Kind::F32;
+    if (pos == Pos::FIRST) return sk_supported(n_in, n_out) ? Kind::FIRST_SK : Kind::FIRST16;
+    if (pos == Pos::LAST) return sk_supported(n_out, n_in) ? Kind::LAST_SK : Kind::LAST16;
+    return Kind::HIDDEN16;
+}
+// bf16-STORAGE mode of a stack: with at least two hidden layers whose widths are all multiples of 64, the hidden activations /
+// gradients are kept as bf16 and the hidden -> hidden layers run gemm_bf16s.hip.  Other stacks under dtype = VAEK_BF16 keep f32
+// storage and the round-1 kernels (gemm_bf16.hip) for their wide layers.
+static bool net_is_b16(int dtype, const Net& net) {
+    if (dtype != VAEK_BF16 || net.layers.size() < 3) return false;
     for (size_t i = 0; i + 1 < net.layers.size(); ++i)
-        if (net.layers[i].n_out % 64) return false;
+        if (!b16_width(net.layers[i].n_out)) return false;
     return true;
 }
-static inline __bf16* wb16(const vaek_ctx* c, void* ws, const Net& net, size_t i, bool transposed) {
-    const Layer& l = net.layers[i];
-    return reinterpret_cast<__bf16*>(static_cast<char*>(ws) + c->ws_wb16) + net.wb_off[i] + (transposed ? (int64_t)l.n_in * l.n_out : 0);
+// batch split of the layer's dW|db launch: slabs sized so that (tiles x S) fills the chip
+static void plan_split(Layer& l, int B) {
+    if (is_sk(l.kind)) {
+        // gemm_skinny16.hip: S slabs, each the fixed-order sum of 64 workgroups' partial images
+        l.S = std::min(8, std::max(1, B / 4096));
+        l.rows_per_split = (B + l.S - 1) / l.S;
+        return;
+    }
+    int s_target;
+    if (l.kind == Kind::HIDDEN16) {
+        // gemm_bf16s.hip, 128 x 128 tiles, 64-row k-tiles: ~512 workgroups
+        const int tiles = ((l.n_in + 127) / 128) * ((l.n_out + 127) / 128);
+        s_target = std::min(256, std::max(1, 512 / tiles));
+    } else {
+        // wide layers run 128 x 128 tiles (gemm_f32.hip) and want ~3 workgroups per CU; the rest 64-wide tiles
+        const bool wide = l.n_in + 1 >= 128 && l.n_out >= 128;
+        // ... counted in the tile shape gemm_f32.hip's launch() picks: 128 x 128, 128 x 32 (n_out <= 32), 32 x 128 (n_in < 32)
+        const int tiles = wide ? ((l.n_in + 1 + 127) / 128) * ((l.n_out + 127) / 128)
+                        : l.n_out <= 32 ? (l.n_in + 1 + 127) / 128
+                        : l.n_in + 1 <= 32 ? (l.n_out + 127) / 128
+                        : ((l.n_in + 1 + 63) / 64) * ((l.n_out + 63) / 64);
+        // at most 64 slabs: the fixed-order slab sum (bulk_finalize_kernel) is a chain of S / 8 memory round trips per output,
+        // and a 256-slab skinny layer (C3's 6 -> 512) held the whole finalize launch for ~60 us
+        s_target = std::min(64, std::max(4, (wide ? 768 : 1024) / tiles));
+    }
+    l.rows_per_split = std::max(64, (int)align_up((size_t)(B + s_target - 1) / s_target, 64));
+    l.S = (B + l.rows_per_split - 1) / l.rows_per_split;
 }
-// bf16 copies (W and W^T) of every hidden -> hidden kernel, once per entry point that runs a b16 stack
+
+int prep_weights(const float* params, const Layer* const* ls, int count, __bf16* wb16, __bf16* sk16, hipStream_t st) {
+    int K[24], N[24], n = 0, H[16], d[16], tr[16], m = 0;
+    int64_t woff[24], ooff[24], sw[16], so[16];
+    for (int i = 0; i < count; ++i) {
+        const Layer& l = *ls[i];
+        if ((l.kind == Kind::HIDDEN16 && n == 24) || (is_sk(l.kind) && m == 16)) { set_error("too many bf16 layers"); return VAEK_ERR_INVALID; }
+        if (l.kind == Kind::HIDDEN16) { K[n] = l.n_in; N[n] = l.n_out; woff[n] = l.w_off; ooff[n] = l.w16_off; ++n; }
+        if (is_sk(l.kind)) { H[m] = sk_H(l); d[m] = sk_d(l); tr[m] = l.kind == Kind::LAST_SK; sw[m] = l.w_off; so[m] = l.w16_off; ++m; }
+    }
+    int rc = launch_cvt_weights(params, wb16, K, N, woff, ooff, n, st);
+    return rc ? rc : launch_sk_prep(params, sk16, H, d, tr, sw, so, m, st);
+}
+// bf16 copies of every b16 layer's kernel, once per entry point that runs the layer-by-layer step
 static int convert_weights(vaek_ctx* c, const float* params, void* ws, hipStream_t st) {
-    int K[24], N[24], n = 0; int64_t woff[24], ooff[24];
-    for (const Net* net : {&c->enc, &c->dec, &c->sig}) {
-        if (!net->b16) continue;
-        for (size_t i = 1; i + 1 < net->layers.size(); ++i) {
-            if (n == 24) { set_error("too many wide layers"); return VAEK_ERR_INVALID; }
-            K[n] = net->layers[i].n_in; N[n] = net->layers[i].n_out; woff[n] = net->layers[i].w_off; ooff[n] = net->wb_off[i]; ++n;
-        }
-    }
-    int rc = launch_cvt_weights(params, reinterpret_cast<__bf16*>(static_cast<char*>(ws) + c->ws_wb16), K, N, woff, ooff, n, st);
-    if (rc) return rc;
-    // 32-row padded bf16 copies for the skinny first / last layers (gemm_skinny16.hip)
-    int H[16], d[16], tr[16], m = 0; int64_t sw[16], so[16];
-    for (const Net* net : {&c->enc, &c->dec, &c->sig}) {
-        if (!net->b16) continue;
-        const Layer& f = net->layers.front(); const Layer& l = net->layers.back();
-        if (f.sk && m < 16) { H[m] = f.n_out; d[m] = f.n_in; tr[m] = 0; sw[m] = f.w_off; so[m] = f.sk_off; ++m; }
-        if (l.sk && m < 16) { H[m] = l.n_in; d[m] = l.n_out; tr[m] = 1; sw[m] = l.w_off; so[m] = l.sk_off; ++m; }
-    }
-    return launch_sk_prep(params, reinterpret_cast<__bf16*>(static_cast<char*>(ws) + c->ws_sk16), H, d, tr, sw, so, m, st);
+    const Layer* ls[32];
+    int n = 0;
+    for (const Net* net : {&c->enc, &c->dec, &c->sig})
+        for (const Layer& l : net->layers) ls[n++] = &l;
+    return prep_weights(params, ls, n, at<__bf16>(ws, c->ws_wb16), at<__bf16>(ws, c->ws_sk16), st);
 }
-static inline __bf16* sk16(const vaek_ctx* c, void* ws, const Layer& l) {
-    return reinterpret_cast<__bf16*>(static_cast<char*>(ws) + c->ws_sk16) + l.sk_off;
+static DenseW layer_weights(const vaek_ctx* c, const float* params, void* ws, const Layer& l) {
+    const float* w = params + l.w_off;
+    return {w, w + (int64_t)l.n_in * l.n_out, at<__bf16>(ws, l.kind == Kind::HIDDEN16 ? c->ws_wb16 : c->ws_sk16) + l.w16_off};
 }
 
-// ---- forward through one Dense/relu stack; `reparam` fuses networks.py:73-74 into the last layer
-struct ElboFuse {           // decoder's last layer with the ELBO epilogue (gemm_f32.hip EPI_ELBO): inputs, and the tile map out
-    const float* x; const float* z2; const float* eps_param; float eps_cli, inv_bt; float* part; int bm, nbx;
-};
+// ---- the launch functions: the only code that knows each kind's launchers and their argument conventions ------------------
+int dense_fwd(const Layer& l, const DenseW& p, const void* x, void* y, int rows, Epilogue* e, hipStream_t st) {
+    const Epi epi = e ? e->kind : Epi::NONE;
+    const float* xf = static_cast<const float*>(x);
+    const __bf16* x16 = static_cast<const __bf16*>(x);
+    float* yf = static_cast<float*>(y);
+    __bf16* y16 = static_cast<__bf16*>(y);
+    switch (l.kind) {
+    case Kind::F32:
+        if (epi == Epi::ELBO)
+            return launch_dense_fwd_elbo(xf, p.w, p.b, yf, e->x, e->z2, e->eps_param, e->eps_cli, e->inv_bt, e->part, rows, l.n_in,
+                                         l.n_out, &e->bm, &e->nbx, st);
+        if (epi == Epi::REPARAM) return launch_dense_fwd_reparam(xf, p.w, p.b, yf, e->samples, e->z1, e->lv, rows, l.n_in, l.n_out, st);
+        return launch_dense_fwd(xf, p.w, p.b, yf, rows, l.n_in, l.n_out, l.relu, st);
+    case Kind::BF16:
+        if (epi == Epi::ELBO) break;          // gemm_bf16.hip has none: generic_grads runs the ELBO pass on its own
+        if (epi == Epi::REPARAM)
+            return launch_dense_fwd_reparam_bf16(xf, p.w, p.b, yf, e->samples, e->z1, e->lv, rows, l.n_in, l.n_out, st);
+        return launch_dense_fwd_bf16(xf, p.w, p.b, yf, rows, l.n_in, l.n_out, l.relu, st);
+    // a b16 stack's first and hidden layers are never the last: no epilogue
+    case Kind::FIRST_SK: return launch_sk_first_fwd(xf, p.w, p.b, y16, rows, l.n_in, l.n_out, l.relu, st);
+    case Kind::FIRST16: return launch_dense_fwd_out16(xf, p.w, p.b, y16, rows, l.n_in, l.n_out, l.relu, st);
+    case Kind::HIDDEN16: return launch_hs_fwd(x16, p.w16 + (int64_t)l.n_in * l.n_out, p.b, y16, rows, l.n_in, l.n_out, l.relu, st);
+    case Kind::LAST_SK:
+        if (epi == Epi::ELBO)
+            return launch_sk_last_fwd_elbo(x16, p.w16, p.b, yf, e->x, e->z2, e->eps_param, e->eps_cli, e->inv_bt, e->part, rows, l.n_in,
+                                           l.n_out, &e->bm, &e->nbx, st);
+        if (epi == Epi::REPARAM)
+            return launch_sk_last_fwd_reparam(x16, p.w16, p.b, yf, e->samples, e->z1, e->lv, rows, l.n_in, l.n_out, st);
+        return launch_sk_last_fwd(x16, p.w16, p.b, yf, rows, l.n_in, l.n_out, st);
+    case Kind::LAST16:
+        if (epi == Epi::ELBO)
+            return launch_dense_fwd_elbo_in16(x16, p.w, p.b, yf, e->x, e->z2, e->eps_param, e->eps_cli, e->inv_bt, e->part, rows, l.n_in,
+                                              l.n_out, &e->bm, &e->nbx, st);
+        if (epi == Epi::REPARAM)
+            return launch_dense_fwd_reparam_in16(x16, p.w, p.b, yf, e->samples, e->z1, e->lv, rows, l.n_in, l.n_out, st);
+        return launch_dense_fwd_in16(x16, p.w, p.b, yf, rows, l.n_in, l.n_out, st);
+    }
+    set_error("dense_fwd: no ELBO epilogue on gemm_bf16.hip");
+    return VAEK_ERR_INVALID;
+}
 
+int dense_dx(const Layer& l, const DenseW& p, const void* dy, const void* x_post, void* dx, int rows, bool relu, bool accumulate,
+             hipStream_t st) {
+    const float* dyf = static_cast<const float*>(dy);
+    const __bf16* dy16 = static_cast<const __bf16*>(dy);
+    float* dxf = static_cast<float*>(dx);
+    __bf16* dx16 = static_cast<__bf16*>(dx);
+    switch (l.kind) {
+    case Kind::F32:
+        return launch_dense_bwd_dx(dyf, p.w, static_cast<const float*>(x_post), dxf, rows, l.n_in, l.n_out, relu, accumulate, st);
+    case Kind::BF16:
+        return launch_dense_bwd_dx_bf16(dyf, p.w, static_cast<const float*>(x_post), dxf, rows, l.n_in, l.n_out, relu, accumulate, st);
+    case Kind::FIRST_SK: return launch_sk_first_dx(dy16, p.w16, dxf, rows, l.n_out, l.n_in, accumulate, st);
+    case Kind::FIRST16: return launch_dense_bwd_dx_in16(dy16, p.w, dxf, rows, l.n_in, l.n_out, accumulate, st);
+    case Kind::HIDDEN16:
+        return launch_hs_dx(dy16, p.w16, static_cast<const __bf16*>(x_post), dx16, rows, l.n_in, l.n_out, st);
+    case Kind::LAST_SK: return VAEK_OK;          // dense_dw's launch_sk_last_bwd wrote it
+    case Kind::LAST16:
+        return launch_dense_bwd_dx_out16(dyf, p.w, static_cast<const __bf16*>(x_post), dx16, rows, l.n_in, l.n_out, accumulate, st);
+    }
+    return VAEK_ERR_INVALID;
+}
+
+int dense_dw(const Layer& l, const DenseW& p, const void* x, const void* dy, void* dx, float* slab0, int64_t slab_stride, float* skpart,
+             int rows, hipStream_t st) {
+    const float* xf = static_cast<const float*>(x);
+    const __bf16* x16 = static_cast<const __bf16*>(x);
+    const float* dyf = static_cast<const float*>(dy);
+    const __bf16* dy16 = static_cast<const __bf16*>(dy);
+    switch (l.kind) {
+    case Kind::F32: return launch_dense_bwd_dw(xf, dyf, slab0, slab_stride, l.S, l.rows_per_split, rows, l.n_in, l.n_out, st);
+    case Kind::BF16: return launch_dense_bwd_dw_bf16(xf, dyf, slab0, slab_stride, l.S, l.rows_per_split, rows, l.n_in, l.n_out, st);
+    case Kind::FIRST_SK: return launch_sk_first_bwd(xf, dy16, skpart, slab0, slab_stride, l.S, rows, l.n_out, l.n_in, st);
+    case Kind::FIRST16: return launch_dense_bwd_dw_dy16(xf, dy16, slab0, slab_stride, l.S, l.rows_per_split, rows, l.n_in, l.n_out, st);
+    case Kind::HIDDEN16: return launch_hs_dw(x16, dy16, slab0, slab_stride, l.S, l.rows_per_split, rows, l.n_in, l.n_out, st);
+    case Kind::LAST_SK:          // dW|db AND dX from one pass over x
+        return launch_sk_last_bwd(x16, dyf, p.w, static_cast<__bf16*>(dx), skpart, slab0, slab_stride, l.S, rows, l.n_in, l.n_out, st);
+    case Kind::LAST16: return launch_dense_bwd_dw_x16(x16, dyf, slab0, slab_stride, l.S, l.rows_per_split, rows, l.n_in, l.n_out, st);
+    }
+    return VAEK_ERR_INVALID;
+}
+
+// ---- forward through one Dense/relu stack; `reparam` fuses networks.py:73-74 into the last layer, `ef` the ELBO pass
 static int net_forward(vaek_ctx* c, const Net& net, const float* params, const float* in, void* ws, int rows,
-                       bool reparam, const float* z1, hipStream_t st, ElboFuse* ef = nullptr) {
-    const float* h = in;
+                       bool reparam, const float* z1, hipStream_t st, Epilogue* ef = nullptr) {
+    Epilogue rp{Epi::REPARAM, at<float>(ws, c->ws_samples), z1, params + c->off_epsp};
+    const void* h = in;
     for (size_t i = 0; i < net.layers.size(); ++i) {
         const Layer& l = net.layers[i];
-        const float* w = params + l.w_off;
-        const float* b = w + (int64_t)l.n_in * l.n_out;
         float* y = at<float>(ws, net.act_off[i]);
-        int rc;
-        if (net.b16) {
-            const bool last = i + 1 == net.layers.size();
-            const __bf16* h16p = reinterpret_cast<const __bf16*>(h);
-            if (i == 0 && l.sk) rc = launch_sk_first_fwd(h, w, b, reinterpret_cast<__bf16*>(y), rows, l.n_in, l.n_out, l.relu, st);
-            else if (i == 0) rc = launch_dense_fwd_out16(h, w, b, reinterpret_cast<__bf16*>(y), rows, l.n_in, l.n_out, l.relu, st);
-            else if (!last) rc = launch_hs_fwd(h16p, wb16(c, ws, net, i, true), b, reinterpret_cast<__bf16*>(y), rows, l.n_in, l.n_out, l.relu, st);
-            else if (l.sk && ef) rc = launch_sk_last_fwd_elbo(h16p, sk16(c, ws, l), b, y, ef->x, ef->z2, ef->eps_param, ef->eps_cli, ef->inv_bt,
-                                                              ef->part, rows, l.n_in, l.n_out, &ef->bm, &ef->nbx, st);
-            else if (l.sk && reparam) rc = launch_sk_last_fwd_reparam(h16p, sk16(c, ws, l), b, y, at<float>(ws, c->ws_samples), z1,
-                                                                      params + c->off_epsp, rows, l.n_in, l.n_out, st);
-            else if (l.sk) rc = launch_sk_last_fwd(h16p, sk16(c, ws, l), b, y, rows, l.n_in, l.n_out, st);
-            else if (ef) rc = launch_dense_fwd_elbo_in16(h16p, w, b, y, ef->x, ef->z2, ef->eps_param, ef->eps_cli, ef->inv_bt, ef->part, rows,
-                                                         l.n_in, l.n_out, &ef->bm, &ef->nbx, st);
-            else if (reparam) rc = launch_dense_fwd_reparam_in16(h16p, w, b, y, at<float>(ws, c->ws_samples), z1, params + c->off_epsp, rows,
-                                                                 l.n_in, l.n_out, st);
-            else rc = launch_dense_fwd_in16(h16p, w, b, y, rows, l.n_in, l.n_out, st);
-            if (rc) return rc;
-            h = y;
-            continue;
-        }
-        const bool h16 = use_bf16(c, l.n_in, l.n_out);
-        if (ef && i + 1 == net.layers.size())
-            rc = launch_dense_fwd_elbo(h, w, b, y, ef->x, ef->z2, ef->eps_param, ef->eps_cli, ef->inv_bt, ef->part, rows, l.n_in,
-                                       l.n_out, &ef->bm, &ef->nbx, st);
-        else if (reparam && i + 1 == net.layers.size())
-            rc = (h16 ? launch_dense_fwd_reparam_bf16 : launch_dense_fwd_reparam)(h, w, b, y, at<float>(ws, c->ws_samples), z1,
-                                                                                  params + c->off_epsp, rows, l.n_in, l.n_out, st);
-        else
-            rc = (h16 ? launch_dense_fwd_bf16 : launch_dense_fwd)(h, w, b, y, rows, l.n_in, l.n_out, l.relu, st);
-        if (rc) return rc;
+        Epilogue* e = i + 1 < net.layers.size() ? nullptr : ef ? ef : reparam ? &rp : nullptr;
+        if (int rc = dense_fwd(l, layer_weights(c, params, ws, l), h, y, rows, e, st)) return rc;
         h = y;
     }
     return VAEK_OK;
@@ -167,65 +245,25 @@ struct BucketSink {          // bucketed mode: where finished layers go and whic
 
 static int net_backward(vaek_ctx* c, const Net& net, const float* params, const float* in, float* d_out, void* ws,
                         float* dx_first, bool accumulate_first, hipStream_t st, BucketSink* sink = nullptr) {
-    float* d = d_out;
+    const void* d = d_out;
     float* gb[2] = {at<float>(ws, c->ws_gbuf0), at<float>(ws, c->ws_gbuf1)};
     int tog = 0;
     float* slabs = at<float>(ws, c->ws_slabs);
     for (int i = (int)net.layers.size() - 1; i >= 0; --i) {
         const Layer& l = net.layers[i];
-        const float* w = params + l.w_off;
+        const DenseW p = layer_weights(c, params, ws, l);
         const float* h_in = i == 0 ? in : at<float>(ws, net.act_off[i - 1]);
-        const bool h16 = !net.b16 && use_bf16(c, l.n_in, l.n_out);
-        int rc;
-        if (net.b16) {
-            // hidden tensors are bf16: d is f32 only for the last layer (dL/d output), h_in is f32 only for layer 0
-            const bool last = i + 1 == (int)net.layers.size();
-            const __bf16* h_in16 = reinterpret_cast<const __bf16*>(h_in);
-            const __bf16* d16 = reinterpret_cast<const __bf16*>(d);
-            float* skpart = at<float>(ws, c->ws_skpart);
-            if (last && l.sk)        // dW|db AND dX (into the ping-pong buffer the dX branch below would have used) from one pass over h
-                rc = launch_sk_last_bwd(h_in16, d, w, reinterpret_cast<__bf16*>(gb[tog]), skpart, slabs + l.w_off, slab_stride(c), l.S, c->B,
-                                        l.n_in, l.n_out, st);
-            else if (i == 0 && l.sk) rc = launch_sk_first_bwd(h_in, d16, skpart, slabs + l.w_off, slab_stride(c), l.S, c->B, l.n_out, l.n_in, st);
-            else if (last) rc = launch_dense_bwd_dw_x16(h_in16, d, slabs + l.w_off, slab_stride(c), l.S, l.rows_per_split, c->B, l.n_in, l.n_out, st);
-            else if (i == 0) rc = launch_dense_bwd_dw_dy16(h_in, d16, slabs + l.w_off, slab_stride(c), l.S, l.rows_per_split, c->B, l.n_in, l.n_out, st);
-            else rc = launch_hs_dw(h_in16, d16, slabs + l.w_off, slab_stride(c), l.S, l.rows_per_split, c->B, l.n_in, l.n_out, st);
-        } else {
-            rc = (h16 ? launch_dense_bwd_dw_bf16 : launch_dense_bwd_dw)(h_in, d, slabs + l.w_off, slab_stride(c), l.S, l.rows_per_split,
-                                                                        c->B, l.n_in, l.n_out, st);
-        }
+        float* dx = i > 0 ? gb[tog] : dx_first;      // a hidden layer's dX: the ping-pong buffers
+        int rc = dense_dw(l, p, h_in, d, dx, slabs + l.w_off, slab_stride(c), at<float>(ws, c->ws_skpart), c->B, st);
         if (rc) return rc;
         if (sink) {     // this layer's [kernel | bias] slice is final once its slabs are summed: announce it
             const int64_t cnt = (int64_t)(l.n_in + 1) * l.n_out;
             if ((rc = launch_sum_slabs(slabs + l.w_off, slab_stride(c), l.S, sink->grads + l.w_off, cnt, st))) return rc;
             VAEK_HIP_CHECK(hipEventRecord((hipEvent_t)sink->events[sink->next++], st));
         }
-        if (i > 0) {
-            float* dx = gb[tog];
-            tog ^= 1;
-            if (net.b16) {
-                const __bf16* h_in16 = reinterpret_cast<const __bf16*>(h_in);
-                if (i + 1 == (int)net.layers.size())
-                    rc = l.sk ? VAEK_OK      // already written by launch_sk_last_bwd above
-                              : launch_dense_bwd_dx_out16(d, w, h_in16, reinterpret_cast<__bf16*>(dx), c->B, l.n_in, l.n_out, false, st);
-                else
-                    rc = launch_hs_dx(reinterpret_cast<const __bf16*>(d), wb16(c, ws, net, i, false), h_in16, reinterpret_cast<__bf16*>(dx),
-                                      c->B, l.n_in, l.n_out, st);
-            } else {
-                rc = (h16 ? launch_dense_bwd_dx_bf16 : launch_dense_bwd_dx)(d, w, h_in, dx, c->B, l.n_in, l.n_out, true, false, st);
-            }
-            if (rc) return rc;
-            d = dx;
-        } else if (dx_first) {
-            if (net.b16 && l.sk)
-                rc = launch_sk_first_dx(reinterpret_cast<const __bf16*>(d), sk16(c, ws, l), dx_first, c->B, l.n_out, l.n_in, accumulate_first, st);
-            else if (net.b16)
-                rc = launch_dense_bwd_dx_in16(reinterpret_cast<const __bf16*>(d), w, dx_first, c->B, l.n_in, l.n_out, accumulate_first, st);
-            else
-                rc = (h16 ? launch_dense_bwd_dx_bf16 : launch_dense_bwd_dx)(d, w, nullptr, dx_first, c->B, l.n_in, l.n_out, false,
-                                                                            accumulate_first, st);
-            if (rc) return rc;
-        }
+        // dX through relu' of the layer below; the first layer's (to dx_first) unmasked, optionally added
+        if (dx && (rc = dense_dx(l, p, d, i > 0 ? h_in : nullptr, dx, c->B, i > 0, i == 0 && accumulate_first, st))) return rc;
+        if (i > 0) { d = dx; tog ^= 1; }
     }
     return VAEK_OK;
 }
@@ -263,10 +301,10 @@ static int generic_grads(vaek_ctx* c, const float* params, int32_t* step_dev, co
             return rc;
         return net_backward(c, c->enc, params, x, dsamp, ws, nullptr, false, st, sink);
     }
-    if (!sig && (c->dec.b16 || !use_bf16(c, last.n_in, last.n_out))) {
+    if (!sig && last.kind != Kind::BF16) {
         // one decoder, exact f32 output layer: the ELBO's elementwise pass runs in that layer's epilogue -- its output never
         // goes to HBM, dL/dx_hat lands where the backward pass expects it
-        ElboFuse ef{x, z2, eps_param, c->cfg.eps_cli, inv_bt, at<float>(ws, c->ws_eblk), 0, 0};
+        Epilogue ef{Epi::ELBO, nullptr, nullptr, nullptr, x, z2, eps_param, c->cfg.eps_cli, inv_bt, at<float>(ws, c->ws_eblk), 0, 0};
         if ((rc = net_forward(c, c->dec, params, samples, ws, c->B, false, nullptr, st, &ef))) return rc;
         if ((rc = launch_elbo_reduce(ef.part, ef.bm, ef.nbx, mu, at<float>(ws, c->ws_epart), c->B, c->L, c->Se, c->rows_per_esplit,
                                      step_dev, st)))
@@ -397,67 +435,31 @@ int vaek_ctx_create(const vaek_config* cfg, vaek_ctx** out) {
         c->leaves.push_back({"epsilon", c->P, 1, 1});
         c->P += 1;
     }
-    // batch splits: dW|db GEMM slabs sized so that (tiles x S) fills the chip; elementwise
-    // partials one per <= 1024 row-blocks
-    c->S = 1; c->rows_per_split = c->B;
-    auto splits = [&](Net& n) {
-        for (auto& l : n.layers) {
-            // wide layers run 128 x 128 tiles (gemm_f32.hip) and want ~3 workgroups per CU; the rest 64-wide tiles
-            const bool wide = l.n_in + 1 >= 128 && l.n_out >= 128;
-            // ... counted in the tile shape gemm_f32.hip's launch() picks: 128 x 128, 128 x 32 (n_out <= 32), 32 x 128 (n_in < 32)
-            const int tiles = wide ? ((l.n_in + 1 + 127) / 128) * ((l.n_out + 127) / 128)
-                            : l.n_out <= 32 ? (l.n_in + 1 + 127) / 128
-                            : l.n_in + 1 <= 32 ? (l.n_out + 127) / 128
-                            : ((l.n_in + 1 + 63) / 64) * ((l.n_out + 63) / 64);
-            // at most 64 slabs: the fixed-order slab sum (bulk_finalize_kernel) is a chain of S / 8 memory round trips per output,
-            // and a 256-slab skinny layer (C3's 6 -> 512) held the whole finalize launch for ~60 us
-            const int s_target = std::min(64, std::max(4, (wide ? 768 : 1024) / tiles));
-            l.rows_per_split = std::max(64, (int)align_up((size_t)(c->B + s_target - 1) / s_target, 64));
-            l.S = (c->B + l.rows_per_split - 1) / l.rows_per_split;
-            if (l.S > c->S) { c->S = l.S; c->rows_per_split = l.rows_per_split; }
-        }
-    };
-    c->enc.b16 = net_is_b16(c, c->enc); c->dec.b16 = net_is_b16(c, c->dec); c->sig.b16 = net_is_b16(c, c->sig);
-    splits(c->enc); splits(c->dec); splits(c->sig);
-    // hidden -> hidden layers of a bf16-storage stack (gemm_bf16s.hip, 128 x 128 tiles, 64-row k-tiles): ~512 workgroups
-    int64_t wb_elems = 0;
+    // per layer: its kind, the batch split of its dW|db launch and the place of its bf16 kernel copies
+    int64_t wb_elems = 0, sk_elems = 0; size_t sk_part = 0;
     for (Net* net : {&c->enc, &c->dec, &c->sig}) {
-        net->wb_off.assign(net->layers.size(), 0);
-        if (!net->b16) continue;
-        for (size_t i = 1; i + 1 < net->layers.size(); ++i) {
+        const bool b16 = net_is_b16(cfg->dtype, *net);
+        for (size_t i = 0; i < net->layers.size(); ++i) {
             Layer& l = net->layers[i];
-            const int tiles = ((l.n_in + 127) / 128) * ((l.n_out + 127) / 128);
-            const int s_target = std::min(256, std::max(1, 512 / tiles));
-            l.rows_per_split = std::max(64, (int)align_up((size_t)(c->B + s_target - 1) / s_target, 64));
-            l.S = (c->B + l.rows_per_split - 1) / l.rows_per_split;
-            net->wb_off[i] = wb_elems;
-            wb_elems += 2 * (int64_t)l.n_in * l.n_out;
-        }
-    }
-    // ... and its skinny ends (gemm_skinny16.hip): S slabs, each the fixed-order sum of 64 workgroups' partial images
-    int64_t sk_elems = 0; size_t sk_part = 0;
-    for (Net* net : {&c->enc, &c->dec, &c->sig}) {
-        if (!net->b16) continue;
-        for (Layer* l : {&net->layers.front(), &net->layers.back()}) {
-            const bool first = l == &net->layers.front();
-            const int d = first ? l->n_in : l->n_out, H = first ? l->n_out : l->n_in;
-            if (!sk_supported(d, H)) continue;
-            l->sk = true;
-            l->S = std::min(8, std::max(1, c->B / 4096));
-            l->rows_per_split = (c->B + l->S - 1) / l->S;
-            l->sk_off = sk_elems; sk_elems += 32ll * H;
-            sk_part = std::max(sk_part, sk_partial_bytes(d, H, l->S));
+            l.kind = dense_kind(cfg->dtype, b16, i == 0 ? Pos::FIRST : i + 1 < net->layers.size() ? Pos::HIDDEN : Pos::LAST, l.n_in, l.n_out);
+            plan_split(l, c->B);
+            if (l.kind == Kind::HIDDEN16) { l.w16_off = wb_elems; wb_elems += 2 * (int64_t)l.n_in * l.n_out; }
+            if (is_sk(l.kind)) {
+                l.w16_off = sk_elems; sk_elems += 32ll * sk_H(l);
+                sk_part = std::max(sk_part, sk_partial_bytes(sk_d(l), sk_H(l), l.S));
+            }
         }
     }
     // wide linear decoder (BASELINE config 4): one fused kernel for its forward, the ELBO pass and both backward products; its
-    // [kernel | bias] gradient comes in one slab per ROW BLOCK of that kernel's grid
-    c->lwd = !cfg->force_generic && !cfg->sigmoid_decoder && cfg->n_dec_hidden == 0 && !c->dec.b16 && lwd_supported(c->B, c->D, c->L) &&
-             !(cfg->dtype == VAEK_BF16 && use_bf16(c, c->L, c->D));
+    // [kernel | bias] gradient comes in one slab per ROW BLOCK of that kernel's grid.  Its one layer would run gemm_f32.hip.
+    c->lwd = !cfg->force_generic && !cfg->sigmoid_decoder && cfg->n_dec_hidden == 0 && c->dec.layers.back().kind == Kind::F32 &&
+             lwd_supported(c->B, c->D, c->L);
     if (c->lwd) {
         Layer& l = c->dec.layers.back();
         c->lwd_rb = lwd_row_block(c->B, c->D, c->n_cu);
         l.rows_per_split = c->lwd_rb; l.S = (c->B + c->lwd_rb - 1) / c->lwd_rb;
     }
+    // the slab area holds the largest split of any layer; elementwise partials one per <= 1024 row-blocks
     c->S = 1; c->rows_per_split = c->B;
     for (const Net* net : {&c->enc, &c->dec, &c->sig})
         for (const auto& l : net->layers) if (l.S > c->S) { c->S = l.S; c->rows_per_split = l.rows_per_split; }

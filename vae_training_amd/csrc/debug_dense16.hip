@@ -1,9 +1,9 @@
 // Diagnostic entry (not part of include/vaek.h; tests/test_gpu_dense16.py): run ONE Dense launcher of dtype = VAEK_BF16 -- the
 // round-1 kernels of gemm_bf16.hip, the bf16-storage kernels of gemm_bf16s.hip and gemm_skinny16.hip, and the bf16-stored forms
-// of gemm_f32.hip -- on caller tensors, exactly as net_forward / net_backward (api.hip) call it: the same launch_* function with
-// the same argument conventions, weights prepared by the step's own prep kernels (launch_cvt_weights, launch_sk_prep) into the
-// caller's scratch, dW|db slabs summed by launch_sum_slabs into the flat-gradient layout [(n_in + 1), n_out].  Every predicate
-// the launcher or the step relies on is checked before the first launch; a shape the step would not send launches nothing.
+// of gemm_f32.hip -- on caller tensors through the step's own code (api.hip): the op names a layer kind and a launch function
+// (dense_fwd / dense_dx / dense_dw), weights are prepared by prep_weights into the caller's scratch, dW|db slabs summed by
+// launch_sum_slabs into the flat-gradient layout [(n_in + 1), n_out].  Every predicate the launcher relies on is checked before
+// the first launch, and so is the step's route: a shape dense_kind gives another kind launches nothing.
 #include <algorithm>
 
 #include "vaek_internal.h"
@@ -39,82 +39,75 @@ struct vaek_dense16_args {
 namespace vaek {
 namespace {
 
+// each op as the step reaches it: the layer kind, and which launch function (api.hip) with which epilogue
+enum Dir { FWD, DX, DW };
+struct Route { Kind kind; Dir dir; Epi epi = Epi::NONE; };
+constexpr Route kRoute[VAEK_D16_COUNT] = {
+    {Kind::BF16, FWD}, {Kind::BF16, FWD, Epi::REPARAM}, {Kind::BF16, DX}, {Kind::BF16, DW},
+    {Kind::HIDDEN16, FWD}, {Kind::HIDDEN16, DX}, {Kind::HIDDEN16, DW},
+    {Kind::FIRST_SK, FWD}, {Kind::LAST_SK, FWD}, {Kind::LAST_SK, FWD, Epi::REPARAM}, {Kind::LAST_SK, FWD, Epi::ELBO},
+    {Kind::FIRST_SK, DX}, {Kind::LAST_SK, DW}, {Kind::FIRST_SK, DW},
+    {Kind::FIRST16, FWD}, {Kind::LAST16, FWD}, {Kind::LAST16, FWD, Epi::REPARAM}, {Kind::LAST16, FWD, Epi::ELBO},
+    {Kind::LAST16, DX}, {Kind::FIRST16, DX}, {Kind::LAST16, DW}, {Kind::FIRST16, DW},
+};
+Pos position(Kind k) {       // the f32-storage kinds' choice does not depend on it
+    return k == Kind::FIRST_SK || k == Kind::FIRST16 ? Pos::FIRST : k == Kind::LAST_SK || k == Kind::LAST16 ? Pos::LAST : Pos::HIDDEN;
+}
+// the ops whose launch reads the layer's bf16 kernel copies (DenseW::w16)
+bool reads_w16(const Route& r) {
+    return (r.kind == Kind::HIDDEN16 && r.dir != DW) || (r.kind == Kind::LAST_SK && r.dir == FWD) || (r.kind == Kind::FIRST_SK && r.dir == DX);
+}
+
 size_t up256(size_t v) { return (v + 255) / 256 * 256; }
 
-struct D16Scratch { size_t wb, sk, slabs, skpart, epart, total; int64_t slab_stride; };
+struct D16Scratch { size_t wb, skw, slabs, skpart, epart, total; int64_t slab_stride; };
 
-bool is_dw(int op) {
-    return op == VAEK_D16_DENSE_DW_BF16 || op == VAEK_D16_HS_DW || op == VAEK_D16_SK_LAST_BWD || op == VAEK_D16_SK_FIRST_BWD ||
-           op == VAEK_D16_DW_X16 || op == VAEK_D16_DW_DY16;
-}
-bool is_sk(int op) { return op >= VAEK_D16_SK_FIRST_FWD && op <= VAEK_D16_SK_FIRST_BWD; }
-bool sk_first(int op) { return op == VAEK_D16_SK_FIRST_FWD || op == VAEK_D16_SK_FIRST_DX || op == VAEK_D16_SK_FIRST_BWD; }
-
-D16Scratch scratch_layout(int op, const vaek_dense16_args& a) {
+D16Scratch scratch_layout(const Route& r, const Layer& l, int rows) {
     D16Scratch s{};
-    const int d = sk_first(op) ? a.n_in : a.n_out, H = sk_first(op) ? a.n_out : a.n_in;
     size_t off = 0;
     s.wb = off;
-    if (op == VAEK_D16_HS_FWD || op == VAEK_D16_HS_DX) off = up256(off + 2 * (size_t)a.n_in * a.n_out * sizeof(__bf16));
-    s.sk = off;
-    if (op == VAEK_D16_SK_LAST_FWD || op == VAEK_D16_SK_LAST_FWD_REPARAM || op == VAEK_D16_SK_LAST_FWD_ELBO || op == VAEK_D16_SK_FIRST_DX)
-        off = up256(off + 32 * (size_t)H * sizeof(__bf16));
-    s.slab_stride = (int64_t)(((size_t)(a.n_in + 1) * a.n_out + 63) / 64 * 64);
+    if (reads_w16(r) && r.kind == Kind::HIDDEN16) off = up256(off + 2 * (size_t)l.n_in * l.n_out * sizeof(__bf16));
+    s.skw = off;
+    if (reads_w16(r) && is_sk(r.kind)) off = up256(off + 32 * (size_t)sk_H(l) * sizeof(__bf16));
+    s.slab_stride = (int64_t)(((size_t)(l.n_in + 1) * l.n_out + 63) / 64 * 64);
     s.slabs = off;
-    if (is_dw(op)) off = up256(off + (size_t)a.S * s.slab_stride * sizeof(float));
+    if (r.dir == DW) off = up256(off + (size_t)l.S * s.slab_stride * sizeof(float));
     s.skpart = off;
-    if (op == VAEK_D16_SK_LAST_BWD || op == VAEK_D16_SK_FIRST_BWD) off = up256(off + sk_partial_bytes(d, H, a.S));
+    if (r.dir == DW && is_sk(r.kind)) off = up256(off + sk_partial_bytes(sk_d(l), sk_H(l), l.S));
     s.epart = off;     // {mse, d eps} per output tile: tiles are at least 32 x 32
-    if (op == VAEK_D16_SK_LAST_FWD_ELBO || op == VAEK_D16_FWD_ELBO_IN16)
-        off = up256(off + (size_t)((a.rows + 31) / 32) * ((a.n_out + 31) / 32) * 2 * sizeof(float));
+    if (r.epi == Epi::ELBO) off = up256(off + (size_t)((rows + 31) / 32) * ((l.n_out + 31) / 32) * 2 * sizeof(float));
     s.total = off;
     return s;
 }
 
-// The step's predicates (api.hip vaek_ctx_create, net_forward, net_backward) and the launchers' own, checked up front.
+// The launchers' predicates and the step's route, checked up front.
 int validate(int op, const vaek_dense16_args& a) {
     auto bad = [](const char* why) { set_error("vaek_debug_dense16: %s", why); return VAEK_ERR_INVALID; };
     if (op < 0 || op >= VAEK_D16_COUNT) return bad("unknown op");
     if (a.rows <= 0 || a.n_in <= 0 || a.n_out <= 0) return bad("rows, n_in and n_out must be positive");
-    const bool fwd = op == VAEK_D16_DENSE_FWD_BF16 || op == VAEK_D16_DENSE_FWD_REPARAM_BF16 || op == VAEK_D16_HS_FWD ||
-                     op == VAEK_D16_SK_FIRST_FWD || op == VAEK_D16_SK_LAST_FWD || op == VAEK_D16_SK_LAST_FWD_REPARAM ||
-                     op == VAEK_D16_SK_LAST_FWD_ELBO || op == VAEK_D16_FWD_OUT16 || op == VAEK_D16_FWD_IN16 ||
-                     op == VAEK_D16_FWD_REPARAM_IN16 || op == VAEK_D16_FWD_ELBO_IN16;
-    const bool dx = op == VAEK_D16_DENSE_DX_BF16 || op == VAEK_D16_HS_DX || op == VAEK_D16_SK_FIRST_DX || op == VAEK_D16_DX_OUT16 ||
-                    op == VAEK_D16_DX_IN16;
-    const bool reparam = op == VAEK_D16_DENSE_FWD_REPARAM_BF16 || op == VAEK_D16_SK_LAST_FWD_REPARAM || op == VAEK_D16_FWD_REPARAM_IN16;
-    const bool elbo = op == VAEK_D16_SK_LAST_FWD_ELBO || op == VAEK_D16_FWD_ELBO_IN16;
-    if (!a.w && (!is_dw(op) || op == VAEK_D16_SK_LAST_BWD)) return bad("w is required");
-    if ((fwd || is_dw(op) || op == VAEK_D16_SK_LAST_BWD) && !a.x) return bad("x is required");
-    if ((dx || is_dw(op)) && !a.dy) return bad("dy is required");
+    const Route r = kRoute[op];
+    const bool fwd = r.dir == FWD, dx = r.dir == DX, dw = r.dir == DW, sk_bwd = dw && r.kind == Kind::LAST_SK;
+    if (!a.w && (!dw || sk_bwd)) return bad("w is required");
+    if ((fwd || dw) && !a.x) return bad("x is required");
+    if ((dx || dw) && !a.dy) return bad("dy is required");
     if (fwd && !a.b) return bad("b is required");
-    if ((fwd || dx || op == VAEK_D16_SK_LAST_BWD) && !a.out) return bad("out is required");
-    if (is_dw(op) && !a.dwb) return bad("dwb is required");
-    if (reparam && (!a.out2 || !a.z1 || !a.lv)) return bad("out2, z1 and lv are required");
-    if (elbo && (!a.xdata || !a.z2)) return bad("xdata and z2 are required");
-    if ((op == VAEK_D16_HS_DX || op == VAEK_D16_DX_OUT16) && !a.x_post) return bad("x_post is required");
-    if (a.accumulate && !(op == VAEK_D16_DENSE_DX_BF16 || op == VAEK_D16_SK_FIRST_DX || op == VAEK_D16_DX_OUT16 || op == VAEK_D16_DX_IN16))
-        return bad("this op does not accumulate");
-    // the width classes the step sends to each family
-    if (op <= VAEK_D16_DENSE_DW_BF16 && (a.n_in < 64 || a.n_out < 64)) return bad("gemm_bf16 layers have both widths >= 64");
-    if (op >= VAEK_D16_HS_FWD && op <= VAEK_D16_HS_DW && (a.n_in % 64 || a.n_out % 64))
-        return bad("bf16-storage hidden layers have widths that are multiples of 64");
-    if (is_sk(op)) {
-        const int d = sk_first(op) ? a.n_in : a.n_out, H = sk_first(op) ? a.n_out : a.n_in;
-        if (!sk_supported(d, H)) return bad("skinny kernels need 1 <= d <= 16 and H a multiple of 64 in [64, 2048]");
-    }
-    if (op >= VAEK_D16_FWD_OUT16) {        // the first (out16, dx_in16, dw_dy16) or last layer of a b16 stack that sk_supported refused
-        const bool first = op == VAEK_D16_FWD_OUT16 || op == VAEK_D16_DX_IN16 || op == VAEK_D16_DW_DY16;
-        const int d = first ? a.n_in : a.n_out, H = first ? a.n_out : a.n_in;
-        if (H % 64) return bad("the bf16-stored side is a hidden width, a multiple of 64");
-        if (sk_supported(d, H)) return bad("this layer runs on the skinny kernels in the step");
-    }
-    const bool has_relu = op == VAEK_D16_DENSE_FWD_BF16 || op == VAEK_D16_DENSE_DX_BF16 || op == VAEK_D16_HS_FWD ||
-                          op == VAEK_D16_SK_FIRST_FWD || op == VAEK_D16_FWD_OUT16;
+    if ((fwd || dx || sk_bwd) && !a.out) return bad("out is required");
+    if (dw && !a.dwb) return bad("dwb is required");
+    if (r.epi == Epi::REPARAM && (!a.out2 || !a.z1 || !a.lv)) return bad("out2, z1 and lv are required");
+    if (r.epi == Epi::ELBO && (!a.xdata || !a.z2)) return bad("xdata and z2 are required");
+    if (dx && (r.kind == Kind::HIDDEN16 || r.kind == Kind::LAST16) && !a.x_post) return bad("x_post is required");
+    if (a.accumulate && !(dx && r.kind != Kind::HIDDEN16)) return bad("this op does not accumulate");
+    // the step's route: dense_kind gives this kind to this shape at this position, in a stack that can hold the layer
+    const Pos pos = position(r.kind);
+    const bool b16 = r.kind != Kind::F32 && r.kind != Kind::BF16;
+    if (dense_kind(VAEK_BF16, b16, pos, a.n_in, a.n_out) != r.kind) return bad("the step runs another kernel on this layer");
+    if (b16 && ((pos != Pos::FIRST && !b16_width(a.n_in)) || (pos != Pos::LAST && !b16_width(a.n_out))))
+        return bad("the hidden widths of a bf16-storage stack are multiples of 64");
+    const bool has_relu = (fwd && r.epi == Epi::NONE && pos != Pos::LAST) || (dx && r.kind == Kind::BF16);
     if (a.relu && !has_relu) return bad("this op has no relu switch");
-    if (is_dw(op)) {
+    if (dw) {
         if (a.S < 1) return bad("S must be >= 1");
-        if (op == VAEK_D16_SK_LAST_BWD || op == VAEK_D16_SK_FIRST_BWD) {
+        if (is_sk(r.kind)) {
             if (a.S > 64) return bad("skinny dW: S <= 64");
         } else {
             if (a.rows_per_split <= 0 || a.rows_per_split % 64) return bad("rows_per_split must be a positive multiple of 64");
@@ -137,7 +130,11 @@ extern "C" int vaek_debug_dense16(vaek_ctx* ctx, int32_t op, vaek_dense16_args* 
     a.form = -1;
     int rc = validate(op, a);
     if (rc) return rc;
-    const D16Scratch s = scratch_layout(op, a);
+    const Route r = kRoute[op];
+    // the one layer: its [W | b] at offset 0 of the caller's w, its bf16 copies at offset 0 of their scratch areas
+    Layer l;
+    l.n_in = a.n_in; l.n_out = a.n_out; l.w_off = 0; l.relu = a.relu != 0; l.kind = r.kind; l.S = a.S; l.rows_per_split = a.rows_per_split;
+    const D16Scratch s = scratch_layout(r, l, a.rows);
     if (!a.scratch) { a.scratch_bytes = (int64_t)s.total; return VAEK_OK; }
     if (a.scratch_bytes < (int64_t)s.total || (reinterpret_cast<uintptr_t>(a.scratch) & 255)) {
         set_error("vaek_debug_dense16: scratch must be 256-byte aligned and hold %zu bytes", s.total);
@@ -146,78 +143,17 @@ extern "C" int vaek_debug_dense16(vaek_ctx* ctx, int32_t op, vaek_dense16_args* 
     if (!ctx) { set_error("vaek_debug_dense16: null context"); return VAEK_ERR_INVALID; }
     ProfBind pb(ctx);
     hipStream_t st = (hipStream_t)stream;
-    const int rows = a.rows, n_in = a.n_in, n_out = a.n_out;
-    const float* xf = static_cast<const float*>(a.x);
-    const __bf16* x16 = static_cast<const __bf16*>(a.x);
-    const float* dyf = static_cast<const float*>(a.dy);
-    const __bf16* dy16 = static_cast<const __bf16*>(a.dy);
-    float* outf = static_cast<float*>(a.out);
-    __bf16* out16 = static_cast<__bf16*>(a.out);
+    const Layer* ls[1] = {&l};
+    // weight prep, as convert_weights (api.hip) runs it for the step
+    if (reads_w16(r) && (rc = prep_weights(a.w, ls, 1, at<__bf16>(a.scratch, s.wb), at<__bf16>(a.scratch, s.skw), st))) return rc;
+    const DenseW p{a.w, a.b, at<__bf16>(a.scratch, r.kind == Kind::HIDDEN16 ? s.wb : s.skw)};
+    if (r.dir == FWD) {
+        Epilogue e{r.epi, a.out2, a.z1, a.lv, a.xdata, a.z2, a.eps_param, a.eps_cli, a.inv_bt, at<float>(a.scratch, s.epart), 0, 0};
+        return dense_fwd(l, p, a.x, a.out, a.rows, &e, st);
+    }
+    if (r.dir == DX) return dense_dx(l, p, a.dy, a.x_post, a.out, a.rows, a.relu != 0, a.accumulate != 0, st);
+    if (is_sk(r.kind)) a.form = sk_bwd_mfma_form(a.rows, sk_H(l), sk_d(l), a.S) ? 1 : 0;
     float* slabs = at<float>(a.scratch, s.slabs);
-    float* epart = at<float>(a.scratch, s.epart);
-    int bm = 0, nbx = 0;
-
-    // weight prep, as convert_weights (api.hip) runs it for the step: the parameters are the one layer's [W | b] at offset 0
-    if (op == VAEK_D16_HS_FWD || op == VAEK_D16_HS_DX) {
-        const int K[1] = {n_in}, N[1] = {n_out};
-        const int64_t woff[1] = {0}, ooff[1] = {0};
-        if ((rc = launch_cvt_weights(a.w, at<__bf16>(a.scratch, s.wb), K, N, woff, ooff, 1, st))) return rc;
-    }
-    __bf16* wp = at<__bf16>(a.scratch, s.sk);
-    if (op == VAEK_D16_SK_LAST_FWD || op == VAEK_D16_SK_LAST_FWD_REPARAM || op == VAEK_D16_SK_LAST_FWD_ELBO || op == VAEK_D16_SK_FIRST_DX) {
-        const bool first = op == VAEK_D16_SK_FIRST_DX;
-        const int H[1] = {first ? n_out : n_in}, d[1] = {first ? n_in : n_out}, tr[1] = {first ? 0 : 1};
-        const int64_t woff[1] = {0}, ooff[1] = {0};
-        if ((rc = launch_sk_prep(a.w, wp, H, d, tr, woff, ooff, 1, st))) return rc;
-    }
-    const __bf16* wb16 = at<__bf16>(a.scratch, s.wb);
-    const __bf16* wT16 = wb16 + (int64_t)n_in * n_out;
-
-    switch (op) {
-    case VAEK_D16_DENSE_FWD_BF16: rc = launch_dense_fwd_bf16(xf, a.w, a.b, outf, rows, n_in, n_out, a.relu != 0, st); break;
-    case VAEK_D16_DENSE_FWD_REPARAM_BF16:
-        rc = launch_dense_fwd_reparam_bf16(xf, a.w, a.b, outf, a.out2, a.z1, a.lv, rows, n_in, n_out, st); break;
-    case VAEK_D16_DENSE_DX_BF16:
-        rc = launch_dense_bwd_dx_bf16(dyf, a.w, static_cast<const float*>(a.x_post), outf, rows, n_in, n_out, a.relu != 0, a.accumulate != 0, st);
-        break;
-    case VAEK_D16_DENSE_DW_BF16:
-        rc = launch_dense_bwd_dw_bf16(xf, dyf, slabs, s.slab_stride, a.S, a.rows_per_split, rows, n_in, n_out, st); break;
-    case VAEK_D16_HS_FWD: rc = launch_hs_fwd(x16, wT16, a.b, out16, rows, n_in, n_out, a.relu != 0, st); break;
-    case VAEK_D16_HS_DX: rc = launch_hs_dx(dy16, wb16, static_cast<const __bf16*>(a.x_post), out16, rows, n_in, n_out, st); break;
-    case VAEK_D16_HS_DW: rc = launch_hs_dw(x16, dy16, slabs, s.slab_stride, a.S, a.rows_per_split, rows, n_in, n_out, st); break;
-    case VAEK_D16_SK_FIRST_FWD: rc = launch_sk_first_fwd(xf, a.w, a.b, out16, rows, n_in, n_out, a.relu != 0, st); break;
-    case VAEK_D16_SK_LAST_FWD: rc = launch_sk_last_fwd(x16, wp, a.b, outf, rows, n_in, n_out, st); break;
-    case VAEK_D16_SK_LAST_FWD_REPARAM:
-        rc = launch_sk_last_fwd_reparam(x16, wp, a.b, outf, a.out2, a.z1, a.lv, rows, n_in, n_out, st); break;
-    case VAEK_D16_SK_LAST_FWD_ELBO:
-        rc = launch_sk_last_fwd_elbo(x16, wp, a.b, outf, a.xdata, a.z2, a.eps_param, a.eps_cli, a.inv_bt, epart, rows, n_in, n_out, &bm, &nbx, st);
-        break;
-    case VAEK_D16_SK_FIRST_DX: rc = launch_sk_first_dx(dy16, wp, outf, rows, n_out, n_in, a.accumulate != 0, st); break;
-    case VAEK_D16_SK_LAST_BWD:
-        a.form = sk_bwd_mfma_form(rows, n_in, n_out, a.S) ? 1 : 0;
-        rc = launch_sk_last_bwd(x16, dyf, a.w, out16, at<float>(a.scratch, s.skpart), slabs, s.slab_stride, a.S, rows, n_in, n_out, st);
-        break;
-    case VAEK_D16_SK_FIRST_BWD:
-        a.form = sk_bwd_mfma_form(rows, n_out, n_in, a.S) ? 1 : 0;
-        rc = launch_sk_first_bwd(xf, dy16, at<float>(a.scratch, s.skpart), slabs, s.slab_stride, a.S, rows, n_out, n_in, st);
-        break;
-    case VAEK_D16_FWD_OUT16: rc = launch_dense_fwd_out16(xf, a.w, a.b, out16, rows, n_in, n_out, a.relu != 0, st); break;
-    case VAEK_D16_FWD_IN16: rc = launch_dense_fwd_in16(x16, a.w, a.b, outf, rows, n_in, n_out, st); break;
-    case VAEK_D16_FWD_REPARAM_IN16:
-        rc = launch_dense_fwd_reparam_in16(x16, a.w, a.b, outf, a.out2, a.z1, a.lv, rows, n_in, n_out, st); break;
-    case VAEK_D16_FWD_ELBO_IN16:
-        rc = launch_dense_fwd_elbo_in16(x16, a.w, a.b, outf, a.xdata, a.z2, a.eps_param, a.eps_cli, a.inv_bt, epart, rows, n_in, n_out, &bm, &nbx,
-                                        st);
-        break;
-    case VAEK_D16_DX_OUT16:
-        rc = launch_dense_bwd_dx_out16(dyf, a.w, static_cast<const __bf16*>(a.x_post), out16, rows, n_in, n_out, a.accumulate != 0, st); break;
-    case VAEK_D16_DX_IN16: rc = launch_dense_bwd_dx_in16(dy16, a.w, outf, rows, n_in, n_out, a.accumulate != 0, st); break;
-    case VAEK_D16_DW_X16:
-        rc = launch_dense_bwd_dw_x16(x16, dyf, slabs, s.slab_stride, a.S, a.rows_per_split, rows, n_in, n_out, st); break;
-    case VAEK_D16_DW_DY16:
-        rc = launch_dense_bwd_dw_dy16(xf, dy16, slabs, s.slab_stride, a.S, a.rows_per_split, rows, n_in, n_out, st); break;
-    }
-    if (rc) return rc;
-    if (is_dw(op)) return launch_sum_slabs(slabs, s.slab_stride, a.S, a.dwb, (int64_t)(n_in + 1) * n_out, st);
-    return VAEK_OK;
+    if ((rc = dense_dw(l, p, a.x, a.dy, a.out, slabs, s.slab_stride, at<float>(a.scratch, s.skpart), a.rows, st))) return rc;
+    return launch_sum_slabs(slabs, s.slab_stride, a.S, a.dwb, (int64_t)(a.n_in + 1) * a.n_out, st);
 }

@@ -1,4 +1,4 @@
-// The skinny ends of a bf16-storage stack (api.hip, Net::b16): the first layer d -> H and the last layer H -> d of an MLP
+// The skinny ends of a bf16-storage stack (Kind::FIRST_SK / LAST_SK): the first layer d -> H and the last layer H -> d of an MLP
 // whose hidden width H is wide and whose data / latent dimension d is a handful of features (every shipped experiment:
 // d = 6, 7, 12, 20; networks.py:26-44 via vae.py:53-54).  Each of these layers touches ONE big tensor, the [B, H] bf16
 // activation or gradient (67 MB at C3), so its roofline is that tensor's HBM stream; on the general f32 matrix-core kernel

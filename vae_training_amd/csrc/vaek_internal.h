@@ -30,24 +30,33 @@ struct Leaf {
     int rows, cols;   // bias / epsilon_p / epsilon: rows == 1
 };
 
+// Which kernels one Dense layer of the layer-by-layer step runs (dense_kind, once per layer in vaek_ctx_create).  A stack in
+// bf16-STORAGE mode (net_is_b16: dtype = VAEK_BF16, >= 2 hidden layers, every hidden width b16_width) keeps its hidden
+// activations and gradients as bf16; its first and last layers have one bf16-stored side.
+enum class Kind : uint8_t {
+    F32,          // gemm_f32.hip
+    BF16,         // gemm_bf16.hip: bf16 arithmetic on f32 storage (dtype = VAEK_BF16, both widths >= 64, not a b16 stack)
+    FIRST_SK,     // first layer of a b16 stack, d -> H with sk_supported(d, H): gemm_skinny16.hip
+    FIRST16,      // ... otherwise: gemm_f32.hip's *_out16 / dw_dy16 / dx_in16 forms
+    HIDDEN16,     // hidden -> hidden layer of a b16 stack: gemm_bf16s.hip
+    LAST_SK,      // last layer of a b16 stack, H -> d with sk_supported(d, H): gemm_skinny16.hip
+    LAST16,       // ... otherwise: gemm_f32.hip's *_in16 / dx_out16 / dw_x16 forms
+};
+enum class Pos : uint8_t { FIRST, HIDDEN, LAST };
+
 struct Layer {
     int n_in, n_out;
     int64_t w_off;    // kernel offset in the flat buffers; bias follows at w_off + n_in*n_out
     bool relu;        // relu after this layer (every layer but the last, networks.py:35-39)
-    int S, rows_per_split;   // batch split of this layer's dW|db GEMM (skinny layers get more, smaller splits)
-    bool sk = false;         // first / last layer of a bf16-storage stack on the skinny kernels (gemm_skinny16.hip)
-    int64_t sk_off = 0;      // element offset of its padded bf16 kernel copy in ws_sk16
+    Kind kind = Kind::F32;
+    int S, rows_per_split;   // batch split of this layer's dW|db launch (one rule per kind)
+    int64_t w16_off = 0;     // element offset of its bf16 kernel copies: HIDDEN16 W, then W^T in ws_wb16; *_SK the padded copy in ws_sk16
 };
 
 struct Net {
     std::vector<Layer> layers;
     // workspace byte offsets of each layer's OUTPUT activation [B, n_out] (float32; bf16 for the hidden layers of a b16 net)
     std::vector<size_t> act_off;
-    // bf16-storage mode (dtype = VAEK_BF16, >= 2 hidden layers, every hidden width a multiple of 64): hidden activations
-    // and gradients are bf16; layer 0 and the last layer run the exact f32 kernel with one bf16-stored side, the layers in
-    // between gemm_bf16s.hip.  wb_off[i]: element offset of layer i's bf16 kernel copies (W, then W^T) in ws_wb16.
-    bool b16 = false;
-    std::vector<int64_t> wb_off;
 };
 
 // Event-pair pool for vaek_profile_*: one pair per kernel launch while enabled.
@@ -189,6 +198,9 @@ int launch_cvt_weights(const float* params, __bf16* out, const int* K, const int
 
 // gemm_skinny16.hip: first (d -> H) / last (H -> d) layer of a bf16-storage stack, d <= 16: one HBM pass per big tensor
 bool sk_supported(int d, int H);
+inline bool is_sk(Kind k) { return k == Kind::FIRST_SK || k == Kind::LAST_SK; }
+inline int sk_d(const Layer& l) { return l.kind == Kind::FIRST_SK ? l.n_in : l.n_out; }      // a skinny layer's d
+inline int sk_H(const Layer& l) { return l.kind == Kind::FIRST_SK ? l.n_out : l.n_in; }      // ... and its H
 bool sk_bwd_mfma_form(int rows, int H, int d, int S);      // which form launch_sk_last_bwd / launch_sk_first_bwd run
 size_t sk_partial_bytes(int d, int H, int S);
 int launch_sk_first_fwd(const float* x, const float* w, const float* b, __bf16* y, int rows, int d, int H, bool relu, hipStream_t st);
@@ -205,6 +217,32 @@ int launch_sk_first_bwd(const float* x, const __bf16* dy, float* partial, float*
                         int d, hipStream_t st);
 int launch_sk_prep(const float* params, __bf16* out, const int* H, const int* d, const int* transposed, const int64_t* w_off,
                    const int64_t* out_off, int n, hipStream_t st);
+
+// ---- api.hip: a Dense layer's kernels by kind -- the step's and vaek_debug_dense16's only route to the launchers above ----------
+inline bool b16_width(int n) { return n % 64 == 0; }      // a hidden width a bf16-storage stack can hold
+Kind dense_kind(int dtype, bool b16, Pos pos, int n_in, int n_out);      // pure: no context, no HIP call
+struct DenseW {             // a layer's parameters as its kind reads them
+    const float* w; const float* b;      // f32 kernel [n_in, n_out] and bias
+    const __bf16* w16;                   // HIDDEN16: bf16 W, then W^T (launch_cvt_weights); *_SK: the 32-row padded copy (launch_sk_prep)
+};
+// the last layer's fused epilogue: the reparameterisation samples = y + exp(lv / 2) z1 (networks.py:73-74), or the decoder's ELBO
+// pass (y becomes dL/dx_hat; {mse, d eps} per output tile into part, and the tile map out)
+enum class Epi : uint8_t { NONE, REPARAM, ELBO };
+struct Epilogue {
+    Epi kind;
+    float* samples; const float* z1; const float* lv;
+    const float* x; const float* z2; const float* eps_param; float eps_cli, inv_bt; float* part; int bm, nbx;
+};
+// bf16 copies (DenseW::w16) of the HIDDEN16 and *_SK layers among ls[0..n), from params + w_off to wb16 / sk16 + w16_off
+int prep_weights(const float* params, const Layer* const* ls, int n, __bf16* wb16, __bf16* sk16, hipStream_t st);
+// y = act(x W + b), the epilogue e (nullptr: none) on a last layer
+int dense_fwd(const Layer& l, const DenseW& p, const void* x, void* y, int rows, Epilogue* e, hipStream_t st);
+// dX = dy W^T, masked where x_post (relu: the f32-storage kinds' switch) is zero, written or added (accumulate)
+int dense_dx(const Layer& l, const DenseW& p, const void* dy, const void* x_post, void* dx, int rows, bool relu, bool accumulate,
+             hipStream_t st);
+// dW|db into l.S slabs (skpart: the skinny kinds' partials); LAST_SK writes its dX too, from the same pass
+int dense_dw(const Layer& l, const DenseW& p, const void* x, const void* dy, void* dx, float* slab0, int64_t slab_stride, float* skpart,
+             int rows, hipStream_t st);
 
 // ---- elbo.hip -----------------------------------------------------------------------------
 struct ElboArgs {
