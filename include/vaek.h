@@ -228,7 +228,8 @@ int vaek_train_step_gen(vaek_ctx* ctx, float* params, float* grads, float* m, fl
  * matrix (csrc/linear_moments.hip), which takes the parameters off the streaming pass, so that the pass over batch n + 2,
  * the cross-workgroup sum of batch n + 1 and the Adam update of batch n run side by side -- as resident workgroup roles of one
  * persistent launch per 64 steps (arrival counters, bounded waits: vaek_train_steps_status), or where that form does not apply as
- * n_steps + 2 launches ordered by the stream alone.  Capturable into a hipGraph.  A context recognises a workspace whose arrival
+ * n_steps + 2 launches ordered by the stream alone.  The persistent form covers L <= 32 with L + 2 D + 1 <= 48 and D <= 16, or with
+ * 49 <= L + 2 D + 1 <= 64 (four 16-feature blocks); data parallelism and vaek_train_steps_gen need it.  Capturable into a hipGraph.  A context recognises a workspace whose arrival
  * counters it has initialised by the workspace's address.  Linear encoder / decoder, one decoder, float32, L + 2 D + 1 <= 64,
  * and, with world > 1, an initialised P2P communicator (vaek_comm_create / vaek_comm_init: the moment matrix is additive over the
  * ranks' shards and is exchanged inside the launch; every rank must make the same calls, and the Adam step counter must not restart
@@ -250,7 +251,8 @@ int vaek_train_steps_status(vaek_ctx* ctx, void* workspace, int32_t* gave_up);
  * earlier tile.  This is the loop body of the reference, model.py:221-222 (dataset.get_batch -> vae.py:123-130 sample_latent,
  * VAE.train_step), N times per launch.  kind: 0 linear_gaussian, 2 sphere (a linear VAE on the sigmoid dataset has two decoders:
  * not covered).  Data parallel: every rank passes its own row0 (global row indices).  Capturable into a hipGraph (the RNG step
- * is the device-resident Adam counter).  vaek_supports_train_steps_gen says whether this context / dataset kind qualifies;
+ * is the device-resident Adam counter).  Shapes: those of the persistent form (vaek_train_steps).  vaek_supports_train_steps_gen
+ * says whether this context / dataset kind qualifies;
  * status as vaek_train_steps. */
 int vaek_supports_train_steps_gen(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
 /* The two halves of ONE step of vaek_train_steps' launch-per-step form, for data parallelism over a HOST collective (no P2P

@@ -1,20 +1,24 @@
 # Diagnostic build (-DVAEK_LIN_STAMPS): where the updater workgroup of vaek_train_steps spends its cycles.
+# WORKLOAD=M (default) or M20: bench.py's workload at B = 65 536.  LIN_STAMPS_LIB=path: a stamps build made beforehand (no build here).
 set -e
+LIB=${LIN_STAMPS_LIB:-/tmp/linst/libvaek.so}
+if [ -z "$LIN_STAMPS_LIB" ]; then
 cd $GRAFT_REPO_ROOT/vae_training_amd/csrc
 mkdir -p /tmp/linst && for f in $(ls *.hip | sed "s/\.hip$//"); do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-gpu-rdc -DVAEK_LIN_STAMPS=${STAMPS:-1} -c $f.hip -o /tmp/linst/$f.o &
 done; wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /tmp/linst/libvaek.so /tmp/linst/*.o
+fi
 cd $GRAFT_REPO_ROOT
 # PERSIST=1: the persistent form with all roles (stamps of the LAST step of the launch; 9 = params published, 8 = wait over)
 if [ "${PERSIST:-0}" = "1" ]; then export VAEK_LIN_PERSIST=1; else export VAEK_LIN_PERSIST=0 VAEK_LIN_ROLES=${ROLES:-4}; fi
-VAEK_LIB_PATH=/tmp/linst/libvaek.so python3 - <<'PY'
+VAEK_LIB_PATH=$LIB python3 - <<'PY'
 import ctypes as C, sys, os
 sys.path.insert(0, os.getcwd())
 import torch
 from bench import WORKLOADS, data_dim, init_params_flat, make_batches
 from vae_training_amd.engine import Engine
-w = WORKLOADS["M"]; B = 65536
+w = WORKLOADS[os.environ.get("WORKLOAD", "M")]; B = 65536
 persist = os.environ.get("VAEK_LIN_PERSIST") == "1"
 eng = Engine(B, data_dim(w), w["L"], (), (), w["eps"], w["tdv"], False)
 params = init_params_flat(eng, 0); grads = eng.new_flat(eng.grad_len); m = eng.new_flat(); v = eng.new_flat()
@@ -30,7 +34,7 @@ for nsteps in ((40, NS, NS) if persist else (4, 4, 4)):
     e0.record()
     if os.environ.get("LIN_GEN") == "1":       # the drawing form (vaek_train_steps_gen)
         A = torch.randn(3, 3, generator=torch.Generator().manual_seed(2)).cuda().contiguous()
-        eng.train_steps_gen(params, grads, m, v, step, nsteps, 1e-3, 0, A, 3, 3, 9, 0.0, 7)
+        eng.train_steps_gen(params, grads, m, v, step, nsteps, 1e-3, 0, A, 3, 3, data_dim(w) - 3, 0.0, 7)
     else:
         eng.train_steps(params, grads, m, v, step, [batches[(off + i) % len(batches)] for i in range(nsteps)], 1e-3)      # (the rotation keeps a short call's inputs out of the Infinity Cache)
     off += nsteps

@@ -1,5 +1,5 @@
 """Steps/s of the reference-shaped Python loop vs the graph-captured loop at the reference's own
-batch size (run.py default 100; seed_linpadding_expts.sh:1 model)."""
+batch size (run.py default 100; seed_linpadding_expts.sh:1 model, D = 12 -- PAD=17: line 2's D = 20)."""
 import os, sys, time, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -7,9 +7,11 @@ from vae_training_amd.run import get_dataset, parse_arguments
 from vae_training_amd.trainer import GraphLoop
 from vae_training_amd.vae import VAEModel
 
+PAD = int(os.environ.get("PAD", 9))
+
 def build(B):
-    args = parse_arguments(["t", "--dataset", "linear_gaussian", "--padding_dim", "9", "-dd", "3", "-ds", "2"])
-    ds = get_dataset("linear_gaussian", 2, 9, B, args)
+    args = parse_arguments(["t", "--dataset", "linear_gaussian", "--padding_dim", str(PAD), "-dd", "3", "-ds", "2"])
+    ds = get_dataset("linear_gaussian", 2, PAD, B, args)
     return VAEModel(dirname=tempfile.mkdtemp(), num_batches=10, num_epochs=1, batch_size=B, learning_rate=1e-3, layer_sizes="",
                     encoder_layer_sizes="", state_dict=None, data_fn=None, epsilon=-1.0, tqdm=False, dataset=ds,
                     latent_dimension=20, tunable_decoder_var=True, dataset_name="linear_gaussian")

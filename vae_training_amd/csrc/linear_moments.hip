@@ -99,7 +99,12 @@ struct LinArgs {
 #define VAEK_LIN_ABL 0       //   8 no LDS-DMA at all (the slots keep whatever they hold).  Results are garbage unless 0.
 #endif
 #ifdef VAEK_LIN_STAMPS      // diagnostic build (tools/lin_stamps.sh): s_memtime at the updater's phase boundaries, into a buffer nothing reads
+#ifdef VAEK_LIN_FOUR_BLOCK_TU
+static __device__ unsigned long long* g_lin_stamp_buf = nullptr;     // the four-block translation unit's own: lin_stamps_four sets it
+#else
 __device__ unsigned long long* g_lin_stamp_buf = nullptr;
+#endif
+int lin_stamps_four(unsigned long long* buf);
 #define LIN_STAMP(i)                                                                                         \
     do {                                                                                                     \
         if (VAEK_LIN_STAMPS == 2) break;      /* light build: only the drain-free time stamps (LIN_NOWQ) */    \
@@ -363,6 +368,9 @@ __device__ __forceinline__ void st_sc1_x4(float* p, f32x4 v) {
 // matrix pipe).  JT > 0: the k-step count at compile time -- the loop unrolls, the reads carry immediate offsets and the waits
 // are counted (with a run-time count hipcc waits lgkmcnt(0) before every group of products, prefetched operands included).
 constexpr int lin_scratch_bytes(int NB) { return LNW * (NB * (NB + 1) / 2) * 1024; }       // (at 8 images; the persistent form's 4 need half)
+// what a slot of the persistent streamers' ring reserves for that scratch: four blocks take the half they need (80 KB would put
+// three slots over the LDS), three keep the size their plans were made with
+constexpr int lin_ring_scratch_bytes(int NB) { return NB == 3 ? lin_scratch_bytes(NB) : lin_scratch_bytes(NB) / 2; }
 constexpr int kLinCW = 4;      // persistent form: waves 0 .. 3 multiply (one per SIMD), waves 4 .. 7 load
 template <int NB, int JT, int CW, typename Hook>
 __device__ __forceinline__ void lin_tile_products(const LinArgs& a, const LinTile& tl, const char* smem, int slot_off, int v_off, int c_off,
@@ -830,18 +838,20 @@ struct LinUpd {
     }
 };
 
-// ---- updater on the float64 matrix cores (persistent form; D <= 16, L <= 32, L + 2 D + 1 <= 48) ------------------------------------
+// ---- updater on the float64 matrix cores (persistent form; L <= 32 and three feature blocks with D <= 16, or four) --------------------
 // The same algebra as LinUpd, laid out so that the dependent chain SM -> P1 -> G never leaves the registers: with the FEATURE index
 // on the MFMA column (lane & 15) every product is  Out = Weights x Prev  and an accumulator tile of v_mfma_f64_16x16x4_f64
 // (lane (col, g), register r = row g + 4 r) is exactly the B operand of the next product's k-step r in natural k order (probed
-// with exact integers: tools/mfma_f64_probe.hip; 64 cycles per instruction, dependent or not).  Wave w < 3 owns feature block w:
+// with exact integers: tools/mfma_f64_probe.hip; 64 cycles per instruction, dependent or not).  Wave w < NB owns feature block w:
 //     SM[:, blk]  = diag(s) M[z1 rows, blk] + be (x) M[one, blk]  (accumulator init)  +  We^T . M[x rows, blk]        (2 row tiles x KD k-steps)
 //     P1[:, blk]  = -M[x rows] + sigma M[z2 rows] + bd (x) M[one]  (init)              +  Wd^T . SM                     (4 + RL1 k-steps)
 //     G[:, blk]   =                                                                       Wd . P1                       (2 x KD)
 // and every gradient that is an ELEMENT of those tiles is finished in place: dWe / dbe = c0 G + (SM - s M[z1 row]) / B on the x and
 // "one" columns, d lv on the diagonal of the z1 columns, dbd = c0 P1[:, one].  Only dWd = S P1^T sums over the feature index, i.e.
-// across lanes: the chain waves drop P1 (4.6 KB) into LDS and wave 3 forms dwd^T = P1[:, x cols] We + ... with 2 x KD MFMAs while
-// the chain waves run G.  The four scalar sums are wave reductions of values the lanes hold anyway.  Per step: 3 barriers,
+// across lanes: the chain waves drop P1 (4.6 KB) into LDS and wave NB forms dwd^T = P1[:, x cols] We + ... with 2 x KD MFMAs while
+// the chain waves run G; wave NB + 1 sums the KL term.  The four scalar sums are wave reductions of values the lanes hold anyway.
+// Four blocks (49 .. 64 features, D up to 31): P1 gets a second row tile (d = 16 .. 31: PT = 2, its own 4 + RL1 k-steps), G takes
+// KD <= 8 k-steps, the first four from P1's first tile and the rest from its second, and dWd has two output row tiles.  Per step: 3 barriers,
 // ~17 dependent MFMAs (1.1 k cycles) instead of ~7 k cycles of LDS-bound float64 FMAs.  M arrives straight from the reducers'
 // image into registers (17 write-through loads per lane at offsets fixed for the launch, prefetched a step ahead when the
 // reducers are ahead): no symmetric copy in LDS.
@@ -868,14 +878,18 @@ __device__ __forceinline__ double lin_wave_sum(double x) {
 }
 // e^x in float64 (|x| < 700): k = round(x / ln 2), degree-13 Taylor polynomial on |r| <= ln 2 / 2 (truncation 5e-18), one ldexp.
 // ~20 fused multiply-adds on the updater's critical path instead of the library routine's ~3x that.
+template <bool InLoop = false>
 __device__ __forceinline__ double lin_exp(double x) {
-    const double k = rint(x * 1.4426950408889634);
-    double r = fma(-k, 6.93147180369123816490e-01, x);
-    r = fma(-k, 1.90821492927058770002e-10, r);
-    double p = 1.0 / 6227020800.0;
-    p = fma(p, r, 1.0 / 479001600.0); p = fma(p, r, 1.0 / 39916800.0); p = fma(p, r, 1.0 / 3628800.0); p = fma(p, r, 1.0 / 362880.0);
-    p = fma(p, r, 1.0 / 40320.0); p = fma(p, r, 1.0 / 5040.0); p = fma(p, r, 1.0 / 720.0); p = fma(p, r, 1.0 / 120.0);
-    p = fma(p, r, 1.0 / 24.0); p = fma(p, r, 1.0 / 6.0); p = fma(p, r, 0.5); p = fma(p, r, 1.0); p = fma(p, r, 1.0);
+    // InLoop: every coefficient through an empty asm that pins it to scalar registers (the four-block updater's step loop: left
+    // alone, hoisted out of the loop into vector registers, the 14 float64 constants pushed the run-time instantiation into scratch)
+    auto c = [](double v) __attribute__((always_inline)) { if constexpr (InLoop) asm volatile("" : "+s"(v)); return v; };
+    const double k = rint(x * c(1.4426950408889634));
+    double r = fma(-k, c(6.93147180369123816490e-01), x);
+    r = fma(-k, c(1.90821492927058770002e-10), r);
+    double p = c(1.0 / 6227020800.0);
+    p = fma(p, r, c(1.0 / 479001600.0)); p = fma(p, r, c(1.0 / 39916800.0)); p = fma(p, r, c(1.0 / 3628800.0)); p = fma(p, r, c(1.0 / 362880.0));
+    p = fma(p, r, c(1.0 / 40320.0)); p = fma(p, r, c(1.0 / 5040.0)); p = fma(p, r, c(1.0 / 720.0)); p = fma(p, r, c(1.0 / 120.0));
+    p = fma(p, r, c(1.0 / 24.0)); p = fma(p, r, c(1.0 / 6.0)); p = fma(p, r, 0.5); p = fma(p, r, 1.0); p = fma(p, r, 1.0);
     return ldexp(p, (int)k);
 }
 // element (r, c) of the symmetric moment matrix in the packed image (upper block triangle, accumulator layout)
@@ -884,6 +898,8 @@ __device__ __forceinline__ int lin_m_index(int NB, int r, int c) {
     const int b1 = br <= bc ? br : bc, b2 = br <= bc ? bc : br, i = br <= bc ? (r & 15) : (c & 15), j = br <= bc ? (c & 15) : (r & 15);
     return lin_blk(NB, b1, b2) * 256 + (((i >> 2) * 16 + j) << 2) + (i & 3);
 }
+// (LinUpdMG below is the same updater generalised to four feature blocks; a fix to the algebra, the LDS layout or the Adam phase
+// here belongs there too)
 template <int NB, int DT, int LT>
 struct LinUpdM {
     static constexpr int NFP = 16 * NB;
@@ -1206,6 +1222,400 @@ struct LinUpdM {
     }
 };
 
+// LinUpdM generalised to four feature blocks (49 .. 64 features, D up to 31: see the notes at PT, NPART, PREFETCH, mos, pmv); only
+// four-block kernels instantiate it (LinUpdMFor).  A fix to the algebra, the LDS layout or the Adam phase of LinUpdM belongs here too.
+template <int NB, int DT, int LT>
+struct LinUpdMG {
+    static constexpr int NFP = 16 * NB;
+    static constexpr int KD = DT ? (DT + 3) / 4 : (NB == 3 ? 4 : 8);                   // k-steps over the data dimension (run-time: D <= 16 resp. 31)
+    static constexpr int RL1 = LT ? (LT > 16 ? (LT - 16 + 3) / 4 : 0) : 4;             // registers of the second latent row tile that can hold a row
+    static constexpr int NM = 4 + RL1 + 2 * KD + 1;                                    // M values per chain lane
+    static constexpr int PT = KD > 4 ? 2 : 1;                                          // row tiles of P1 (d = 16 pt + g + 4 r) and of dWd^T
+    // part[]: the chain waves' three sums at 3 w .. 3 w + 2, the dWd wave's at 3 NB, the KL sum at 3 NB + 3, the bias corrections behind it
+    static constexpr int NPART = NB == 3 ? 16 : 20;
+    // the next batch's M loaded under this step when its reducers are done already: three blocks only (four have no registers
+    // left for a second set of up to 25 values -- they would go to scratch)
+    static constexpr bool PREFETCH = NB == 3;
+    int D, L, P, fone, off_be, off_wd, off_bd, off_epsp, off_eps;
+    double *Wed, *Wdd, *bed, *bdd, *sd, *elv, *lvd, *scal, *part, *P1s, *gq;
+    // this thread's parameters and Adam moments (idx = t + 512 k): in LDS, [3][LKOUT][512] -- in registers they went to scratch
+    float* pmv;
+    __device__ __forceinline__ float& pk(int k) const { return pmv[k * LNT + threadIdx.x]; }
+    __device__ __forceinline__ float& mk(int k) const { return pmv[(LKOUT + k) * LNT + threadIdx.x]; }
+    __device__ __forceinline__ float& vk(int k) const { return pmv[(2 * LKOUT + k) * LNT + threadIdx.x]; }
+    // chain lanes: image offsets of their M values, [NM][64 NB] in LDS -- formed once per launch, read back per step (held in
+    // registers across the step loop, up to 25 of them, they pushed the run-time instantiation into scratch)
+    int* mos;
+
+    // (L > 32 would need a third latent row tile)
+    static __host__ __device__ constexpr bool shape_ok(int D, int L) {
+        return NB == 3 ? D <= 16 && L <= 32 && L + 2 * D + 1 <= NFP : NB == 4 && L <= 32 && L + 2 * D + 1 <= NFP && D <= 4 * KD;
+    }
+    static __host__ size_t lds_bytes(int D, int L, int P) {
+        return sizeof(double) * ((size_t)2 * D * L + 4 * L + D + 8 + NPART + 16 * PT * NFP + (size_t)(P + kExtra + 7)) + sizeof(int) * NM * 64 * NB + sizeof(float) * 3 * LKOUT * LNT;
+    }
+    __device__ __forceinline__ void carve(const LinArgs& a, char* smem) {
+        D = DT ? DT : a.D; L = LT ? LT : a.L; P = a.P; fone = L + 2 * D; off_eps = a.off_eps;
+        off_be = D * L; off_wd = off_be + L; off_bd = off_wd + L * D; off_epsp = off_bd + D;
+        Wed = reinterpret_cast<double*>(smem); Wdd = Wed + D * L; bed = Wdd + L * D; bdd = bed + L; sd = bdd + D; elv = sd + L; lvd = elv + L;
+        scal = lvd + L; part = scal + 8; P1s = part + NPART; gq = P1s + 16 * PT * NFP; mos = reinterpret_cast<int*>(gq + P + kExtra + 7);
+        pmv = reinterpret_cast<float*>(smem + sizeof(double) * (size_t)(gq + P + kExtra + 7 - Wed) + sizeof(int) * NM * 64 * NB);
+    }
+    __device__ __forceinline__ void load_state(const LinArgs& a) {
+        const int t = threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < LKOUT; ++k) {
+            const int idx = min(t + LNT * k, P - 1);
+            pk(k) = a.params[idx]; mk(k) = a.m[idx]; vk(k) = a.v[idx];
+        }
+        if (off_eps < 0 && t == 0) { const double e = (double)a.eps_cli; scal[0] = e; scal[1] = lin_exp<true>(0.5 * e); scal[2] = lin_exp<true>(-e); }
+        // image offsets of this lane's M values (chain waves: wave w = feature block w)
+        if (t < 64 * NB) {
+            const int lane = t & 63, j = lane & 15, g = lane >> 4, f = 16 * (t >> 6) + j;
+            int k = 0;
+            auto put = [&](int row) { mos[(k++) * 64 * NB + t] = lin_m_index(NB, row, f); };
+#pragma unroll
+            for (int r = 0; r < 4; ++r) put(g + 4 * r);                                  // z1 rows 0 .. 15
+#pragma unroll
+            for (int r = 0; r < RL1; ++r) put(min(16 + g + 4 * r, NFP - 1));             // z1 rows 16 ..
+#pragma unroll
+            for (int r = 0; r < KD; ++r) put(min(L + g + 4 * r, NFP - 1));               // x rows
+#pragma unroll
+            for (int r = 0; r < KD; ++r) put(min(L + D + g + 4 * r, NFP - 1));           // z2 rows
+            put(fone);
+        }
+    }
+    // (chain lanes only; each reads back the offsets it wrote itself)
+    __device__ __forceinline__ void fetch_M(const double* M_in, double (&r)[NM]) const {
+        const int* mt = mos + threadIdx.x;
+        int o[NM];
+#pragma unroll
+        for (int k = 0; k < NM; ++k) o[k] = mt[k * 64 * NB];
+#pragma unroll
+        for (int k = 0; k < NM; ++k) r[k] = ld_sc1(M_in + o[k]);
+    }
+    // float64 copies of this thread's own parameters into the arrays the products read
+    __device__ __forceinline__ void publish_params(const LinArgs& a) {
+        int t = threadIdx.x;
+        if constexpr (NB == 4) asm volatile("" : "+v"(t));       // (laundered: see step)
+#pragma unroll
+        for (int k = 0; k < LKOUT; ++k) {
+            const int i = t + LNT * k;
+            const double pv = (double)pk(k);
+            if (i < off_be) Wed[i] = pv;
+            else if (i < off_wd) bed[i - off_be] = pv;
+            else if (i < off_bd) Wdd[i - off_wd] = pv;
+            else if (i < off_epsp) bdd[i - off_bd] = pv;
+            else if (i < off_epsp + L || i == off_eps) {
+                // e^{lv / 2} and e^{eps / 2}, e^{-eps}: the same instruction stream for the latent lanes and the epsilon lane
+                const bool is_eps = i == off_eps;
+                const double e = is_eps ? pv * (double)a.eps_cli : pv, h = lin_exp<true>(0.5 * e);
+                if (is_eps) {
+                    const double q = h * h;
+                    double r = __builtin_amdgcn_rcp(q);                // 1 / sigma^2: hardware seed, two Newton steps (full double precision)
+                    r = fma(fma(-q, r, 1.0), r, r); r = fma(fma(-q, r, 1.0), r, r);
+                    scal[0] = e; scal[1] = h; scal[2] = r;
+                }
+                else { sd[i - off_epsp] = h; elv[i - off_epsp] = h * h; lvd[i - off_epsp] = pv; }
+            }
+        }
+    }
+    // one step.  In: parameters published and a barrier behind them; mreg = this lane's values of the batch's M (chain waves).
+    // Out: p / m / v updated, gout[] this thread's gradients.  Ends WITHOUT a barrier: the caller's next publish_params writes arrays
+    // that only the phases before this step's last barrier read.
+    // next_cnt / M_next: the NEXT batch's reducer counter and M (nullptr: none); if its reducers are done already, its M is loaded
+    // into mnext under this step's second half and have_next says so.
+    __device__ __forceinline__ void step(const LinArgs& a, int tstep, const double (&mreg)[NM], float (&gout)[LKOUT], const unsigned* next_cnt,
+                                         unsigned per_set, const double* M_next, double (&mnext)[NM], bool& have_next) {
+        int t = threadIdx.x;
+        // (four blocks: the thread index laundered, so that the LDS addresses of this step are formed in it and not hoisted out of
+        // the launch's step loop, where they would occupy the registers the chain needs)
+        if constexpr (NB == 4) asm volatile("" : "+v"(t));
+        const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63, j = lane & 15, g = lane >> 4;
+        LIN_STAMP(1);
+        if (PREFETCH && t == 64 * (NB + 2)) scal[4] = (next_cnt && __hip_atomic_load(next_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= per_set) ? 1.0 : 0.0;
+        const double eps = scal[0], sigma = scal[1], inv_var = scal[2], inv_bt = (double)a.inv_bt, c0 = inv_var * inv_bt;
+        d4 sm[2], p1;
+        [[maybe_unused]] d4 p1b;                                       // PT == 2: P1's second row tile, d = 16 + g + 4 r
+        auto p1row = [&](int r) -> double { return r < 4 ? p1[r & 3] : p1b[r & 3]; };     // P1 rows 4 r + g, r < 4 PT
+        double musq_p = 0.0, ssq_p = 0.0, z2r_p = 0.0;
+        const int f = 16 * wave + j;                                   // chain waves: this lane's feature column
+        // The chain's WEIGHT operands (functions of the published parameters only) are read from LDS up front: left where they are
+        // used, hipcc issues each ds_read right in front of its MFMA and waits for it -- ds_read, s_waitcnt lgkmcnt(0), v_mfma, 17
+        // times: an LDS round trip (~130 cycles) on top of every 64-cycle product of the dependent chain.
+        // (SM's and P1's weights here; G's and the dWd wave's operands in ONE batch behind the barrier: held across it they spill)
+        double awSMr[KD][2], awP1r[PT][4 + (RL1 ? RL1 : 1)];
+        auto awSM = [&](int kk, int lt) -> double& { return awSMr[kk][lt]; };
+        auto awP1 = [&](int r) -> double& { return awP1r[0][r]; };
+        if (wave < NB) {
+#pragma unroll
+            for (int kk = 0; kk < KD; ++kk)
+#pragma unroll
+                for (int lt = 0; lt < 2; ++lt) {
+                    const int dd = 4 * kk + g, l = 16 * lt + j;
+                    const double w1 = Wed[min(dd, D - 1) * L + min(l, L - 1)];
+                    awSM(kk, lt) = (dd < D && l < L && (lt == 0 || RL1 > 0)) ? w1 : 0.0;
+                }
+#pragma unroll
+            for (int r = 0; r < 4 + RL1; ++r) {
+                const int l = (r < 4 ? 4 * r : 16 + 4 * (r - 4)) + g;
+                const double w = Wdd[min(l, L - 1) * D + min(j, D - 1)];
+                awP1(r) = (j < D && l < L) ? w : 0.0;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (wave < NB) {
+            const double* Mz = mreg; const double* Mx = mreg + 4 + RL1; const double* Mz2 = Mx + KD; const double Mone = mreg[NM - 1];
+            // ---- SM ----
+#pragma unroll
+            for (int lt = 0; lt < 2; ++lt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int l = 16 * lt + g + 4 * r;
+                    const bool ok = l < L && (lt == 0 || r < RL1);
+                    const double sv = sd[min(l, L - 1)], bv = bed[min(l, L - 1)];
+                    const double slv = ok ? sv : 0.0, blv = ok ? bv : 0.0;
+                    sm[lt][r] = (lt == 0 || r < RL1) ? slv * Mz[lt == 0 ? r : min(4 + r, 3 + RL1)] + blv * Mone : 0.0;
+                }
+#pragma unroll
+            for (int kk = 0; kk < KD; ++kk) {
+#pragma unroll
+                for (int lt = 0; lt < 2; ++lt) {
+                    if (lt == 1 && RL1 == 0) continue;
+                    sm[lt] = __builtin_amdgcn_mfma_f64_16x16x4f64(awSM(kk, lt), Mx[kk], sm[lt], 0, 0, 0);
+                }
+            }
+            // ---- P1 ----
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int d = g + 4 * r;
+                p1[r] = (r < KD && d < D) ? -Mx[min(r, KD - 1)] + sigma * Mz2[min(r, KD - 1)] + bdd[min(d, D - 1)] * Mone : 0.0;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(awP1(r), sm[0][r], p1, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < RL1; ++r) p1 = __builtin_amdgcn_mfma_f64_16x16x4f64(awP1(4 + r), sm[1][r], p1, 0, 0, 0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) P1s[(g + 4 * r) * NFP + f] = p1[r];
+            if constexpr (PT == 2) {                                   // rows d = 16 .. 31: the same k-steps with the second tile's weights
+                // (read here, behind the first tile's products: read up front with the others they went to scratch)
+#pragma unroll
+                for (int r = 0; r < 4 + RL1; ++r) {
+                    const int l = (r < 4 ? 4 * r : 16 + 4 * (r - 4)) + g;
+                    const double w = Wdd[min(l, L - 1) * D + min(16 + j, D - 1)];
+                    awP1r[1][r] = (16 + j < D && l < L) ? w : 0.0;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int d = 16 + g + 4 * r;
+                    p1b[r] = (4 + r < KD && d < D) ? -Mx[min(4 + r, KD - 1)] + sigma * Mz2[min(4 + r, KD - 1)] + bdd[min(d, D - 1)] * Mone : 0.0;
+                }
+#pragma unroll
+                for (int r = 0; r < 4; ++r) p1b = __builtin_amdgcn_mfma_f64_16x16x4f64(awP1r[1][r], sm[0][r], p1b, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < RL1; ++r) p1b = __builtin_amdgcn_mfma_f64_16x16x4f64(awP1r[1][4 + r], sm[1][r], p1b, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) P1s[(16 + g + 4 * r) * NFP + f] = p1b[r];
+            }
+        } else if (wave == NB + 1) {
+            // 1 + lv - e^{lv} summed over the latent dimension (the closed-form KL term of the loss)
+            const double kl = lane < L ? 1.0 + lvd[min(lane, L - 1)] - elv[min(lane, L - 1)] : 0.0;
+            const double tot = lin_wave_sum(kl);
+            if (lane == 0) {
+                part[3 * NB + 3] = tot;
+                // Adam's bias corrections 1 - beta^t for everybody (float, as the other paths compute them)
+                part[3 * NB + 4] = (double)(-expm1f((float)tstep * -0.10536051565782628f)); part[3 * NB + 5] = (double)(-expm1f((float)tstep * -0.0010005003335835335f));
+            }
+        }
+        LIN_STAMP(2);
+        __syncthreads();                                               // P1 is in LDS
+        LIN_STAMP(3);
+        have_next = PREFETCH && scal[4] != 0.0;
+        if (wave < NB) {
+            if (have_next) fetch_M(M_next, mnext);
+            // ---- G = Wd P1 ---- (its six weights in one batch of LDS reads first)
+            double awGr[KD][2];
+#pragma unroll
+            for (int kk = 0; kk < KD; ++kk)
+#pragma unroll
+                for (int lt = 0; lt < 2; ++lt) {
+                    const int dd = 4 * kk + g, l = 16 * lt + j;
+                    const double w2 = Wdd[min(l, L - 1) * D + min(dd, D - 1)];
+                    awGr[kk][lt] = (l < L && dd < D && (lt == 0 || RL1 > 0)) ? w2 : 0.0;
+                }
+            double sl[2][4], bl[2][4];
+            auto read_sl_bl = [&]() __attribute__((always_inline)) {
+#pragma unroll
+                for (int lt = 0; lt < 2; ++lt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int l = 16 * lt + g + 4 * r;
+                        const bool ok = l < L && (lt == 0 || r < RL1);
+                        const double sv = sd[min(l, L - 1)], bv = bed[min(l, L - 1)];
+                        sl[lt][r] = ok ? sv : 0.0; bl[lt][r] = ok ? bv : 0.0;
+                    }
+            };
+            if constexpr (PT == 1) read_sl_bl();                       // (read again: held across the barrier they spill)
+            __builtin_amdgcn_sched_barrier(0);
+            d4 G[2];
+            G[0] = d4{0.0, 0.0, 0.0, 0.0}; G[1] = d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int r = 0; r < KD; ++r) {
+#pragma unroll
+                for (int lt = 0; lt < 2; ++lt) {
+                    if (lt == 1 && RL1 == 0) continue;
+                    G[lt] = __builtin_amdgcn_mfma_f64_16x16x4f64(awGr[r][lt], p1row(r), G[lt], 0, 0, 0);
+                }
+            }
+            if constexpr (PT == 2) read_sl_bl();                       // (four blocks: behind the products -- in front, next to G's 2 KD weights, they spill)
+            // ---- the gradients that are elements of these tiles ----
+            const double* Mz = mreg;
+            const bool is_x = f >= L && f < L + D, is_z2 = f >= L + D && f < fone, is_one = f == fone, is_z1 = f < L;
+            if (is_x || is_one) {
+                const int base = is_x ? (f - L) * L : off_be;          // dWe[dd][:] resp. dbe
+#pragma unroll
+                for (int lt = 0; lt < 2; ++lt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (lt == 1 && r >= RL1) continue;
+                        const int l = 16 * lt + g + 4 * r;
+                        if (l < L) {
+                            const double q = sm[lt][r] - sl[lt][r] * Mz[lt == 0 ? r : min(4 + r, 3 + RL1)];           // Q = E M
+                            gq[base + l] = c0 * G[lt][r] + q * inv_bt;
+                            musq_p += (is_x ? Wed[base + l] : bl[lt][r]) * q;
+                        }
+                    }
+            }
+            if (is_one) {
+#pragma unroll
+                for (int r = 0; r < 4 * PT; ++r) {
+                    const int d = g + 4 * r;
+                    if (d < D) { gq[off_bd + d] = c0 * p1row(r); ssq_p += bdd[d] * p1row(r); }
+                }
+            }
+            if (is_z1 && (j & 3) == g) {                               // the lane that holds G[f][f]
+                const int lt = f >> 4, r = j >> 2;
+                double gll = 0.0;
+#pragma unroll
+                for (int q2 = 0; q2 < 2; ++q2)
+#pragma unroll
+                    for (int r2 = 0; r2 < 4; ++r2) gll = (q2 == lt && r2 == r) ? G[q2][r2] : gll;
+                gq[off_epsp + f] = 0.5 * sd[f] * c0 * gll - 0.5 * (1.0 - elv[f]) * (double)a.rows_over_bt;
+            }
+            if (is_x || is_z2) {                                       // the diagonal entries P1[d][x_d], P1[d][z2_d] of the residual sums
+                const int d = is_x ? f - L : f - L - D;
+                if ((d & 3) == g) {
+                    double pd = 0.0;
+#pragma unroll
+                    for (int r2 = 0; r2 < 4 * PT; ++r2) pd = (r2 == (d >> 2)) ? p1row(r2) : pd;
+                    if (is_x) ssq_p -= pd; else { ssq_p += sigma * pd; z2r_p += pd; }
+                }
+            }
+            musq_p = lin_wave_sum(musq_p); ssq_p = lin_wave_sum(ssq_p); z2r_p = lin_wave_sum(z2r_p);
+            if (lane == 0) { part[3 * wave] = ssq_p; part[3 * wave + 1] = musq_p; part[3 * wave + 2] = z2r_p; }
+        } else if (wave == NB) {
+            // ---- dwd^T[d][l] = s_l P1[d][l] + be_l P1[d][one] + sum_dd P1[d][x_dd] We[dd][l]  (rows d = 16 dt + g + 4 r, columns l = 16 ct + j) ----
+            // (every LDS operand first -- We was read in front of the barrier --, then the products back to back: see the chain waves;
+            // two row tiles one after the other)
+            double wsum = 0.0;
+#pragma unroll
+            for (int dt = 0; dt < PT; ++dt) {
+                d4 C[2];
+                double avk[KD], p1l[2][4], p1o[4], dw_sr[2], dw_br[2], dw_wr[KD][2], dw_dr[2][4];
+                auto dw_s = [&](int ct) -> double& { return dw_sr[ct]; };
+                auto dw_b = [&](int ct) -> double& { return dw_br[ct]; };
+                auto dw_w = [&](int kk, int ct) -> double& { return dw_wr[kk][ct]; };
+                auto dw_d = [&](int ct, int r) -> double& { return dw_dr[ct][r]; };
+                const int d0 = 16 * dt;
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    const int l = 16 * ct + j, lc = min(l, L - 1);
+                    const double s_l = sd[lc], b_l = bed[lc];
+                    dw_s(ct) = l < L ? s_l : 0.0; dw_b(ct) = l < L ? b_l : 0.0;
+#pragma unroll
+                    for (int kk = 0; kk < KD; ++kk) {
+                        const int dd = 4 * kk + g;
+                        const double w = Wed[min(dd, D - 1) * L + lc];
+                        dw_w(kk, ct) = (dd < D && l < L) ? w : 0.0;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) dw_d(ct, r) = Wdd[lc * D + min(d0 + g + 4 * r, D - 1)];
+                }
+#pragma unroll
+                for (int kk = 0; kk < KD; ++kk) avk[kk] = P1s[(d0 + j) * NFP + min(L + 4 * kk + g, NFP - 1)];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    p1o[r] = P1s[(d0 + g + 4 * r) * NFP + fone];
+#pragma unroll
+                    for (int ct = 0; ct < 2; ++ct) p1l[ct][r] = P1s[(d0 + g + 4 * r) * NFP + min(16 * ct + j, L - 1)];
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int ct = 0; ct < 2; ++ct) {
+                    if (ct == 1 && RL1 == 0) continue;
+                    const int l = 16 * ct + j;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) C[ct][r] = dw_s(ct) * p1l[ct][r] + dw_b(ct) * p1o[r];
+#pragma unroll
+                    for (int kk = 0; kk < KD; ++kk) C[ct] = __builtin_amdgcn_mfma_f64_16x16x4f64(avk[kk], dw_w(kk, ct), C[ct], 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int d = d0 + g + 4 * r;
+                        if (l < L && d < D) { gq[off_wd + l * D + d] = c0 * C[ct][r]; wsum += dw_d(ct, r) * C[ct][r]; }
+                    }
+                }
+            }
+            wsum = lin_wave_sum(wsum);
+            if (lane == 0) part[3 * NB] = wsum;
+        }
+        LIN_STAMP(4);
+        __syncthreads();                                               // every gradient and partial sum is in LDS
+        LIN_STAMP(5);
+        const double rows = (double)a.rows;
+        const float bc1 = (float)part[3 * NB + 4], bc2 = (float)part[3 * NB + 5];
+#pragma unroll
+        for (int k = 0; k < LKOUT; ++k) {
+            const int idx = t + LNT * k;
+            if (LNT * k >= P + 3) break;                               // (uniform) nothing lives up here
+            double gd = 0.0;
+            if (idx < P && idx != off_eps) gd = gq[idx];
+            else if (idx == off_eps || (idx >= P && idx < P + 3)) {
+                double ssq = part[0], musq = part[1], z2r = part[2];
+#pragma unroll
+                for (int w = 1; w < NB; ++w) { ssq += part[3 * w]; musq += part[3 * w + 1]; z2r += part[3 * w + 2]; }
+                ssq += part[3 * NB];
+                const double klc = part[3 * NB + 3];
+                if (idx == off_eps) gd = (double)a.eps_cli * (-0.5 * ssq * inv_var + 0.5 * rows * D + 0.5 * sigma * z2r * inv_var) * inv_bt;
+                else {
+                    const double dkl = (0.5 * musq - 0.5 * rows * klc) * inv_bt;
+                    const double mse = (0.5 * ssq * inv_var + 0.5 * rows * D * ((double)kLog2Pi + eps)) * inv_bt;
+                    gd = idx == P ? dkl + mse : (idx == P + 1 ? dkl : mse);
+                }
+            }
+            const float gf = (float)gd;
+            gout[k] = gf;
+            if (idx == P && a.loss_hist) a.loss_hist[(long long)(tstep - 1) % a.loss_hist_cap] = gf;
+            if (idx < P) adam_apply_f(pk(k), gf, mk(k), vk(k), a.lr, bc1, bc2);
+        }
+        LIN_STAMP(6);
+    }
+    __device__ __forceinline__ void store_state(const LinArgs& a, const float (&gout)[LKOUT], int tstep) {
+        const int t = threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < LKOUT; ++k) {
+            const int idx = t + LNT * k;
+            if (idx < P + kExtra) a.grads[idx] = gout[k];
+            if (idx < P) { a.params[idx] = pk(k); a.m[idx] = mk(k); a.v[idx] = vk(k); }
+        }
+        if (t == 0) a.step_dev[0] = tstep;
+    }
+};
+
+// Four blocks take the generalised form (LinUpdMG); three keep LinUpdM, whose code the metric's kernels were tuned on (the
+// generalised form computes the same for three blocks, but its code is not the same).
+template <int NB, int DT, int LT>
+using LinUpdMFor = std::conditional_t<NB == 3, LinUpdM<NB, DT, LT>, LinUpdMG<NB, DT, LT>>;
+
 // ---- launch-per-step form ---------------------------------------------------------------------------------------------------------
 template <int NB, int DT, int LT>
 __global__ __launch_bounds__(LNT) void lin_step_kernel(const LinArgs a) {
@@ -1260,14 +1670,14 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
     if (b < a.has_update) {
         // ---- the updater: one workgroup, parameters and Adam state in registers / LDS across all N steps (the host sends only
         // shapes the matrix-core updater covers into this form: LinPlan::persist) ------------------------------------------------
-        LinUpdM<NB, DT, LT> u;
+        LinUpdMFor<NB, DT, LT> u;
         u.carve(a, lin_smem);
         int tstep = a.step_dev[0];
         u.load_state(a);
         float g[LKOUT];
 #pragma unroll
         for (int k = 0; k < LKOUT; ++k) g[k] = 0.f;
-        constexpr int NM = LinUpdM<NB, DT, LT>::NM;
+        constexpr int NM = LinUpdMFor<NB, DT, LT>::NM;
         double mreg[NM], mnext[NM];
         bool have_next = false;
         LIN_STAMP(10);
@@ -1334,7 +1744,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         { [[maybe_unused]] unsigned long long te = 0; LIN_NOWQ(te); if (sid == 0) LIN_PUT(50, te); if (sid == S / 2) LIN_PUT(51, te); if (sid == S - 1) LIN_PUT(52, te); }
         const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
         const LinTile tl(a.D, a.L, a.T);
-        const int stride = max(tl.bytes, lin_scratch_bytes(NB));        // a slot doubles as the combine's cross-wave scratch
+        const int stride = max(tl.bytes, lin_ring_scratch_bytes(NB));   // a slot doubles as the combine's cross-wave scratch
         const int v_off = 3 * stride, vr_off = v_off + 4 * a.T, c_off = vr_off + 4 * a.T;
         const float** tab = reinterpret_cast<const float**>(lin_smem + c_off + 16);            // [3][kLinMaxPersist]
         if constexpr (!GEN) {
@@ -1588,11 +1998,22 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
 // zeroes the arrival counters of a workspace (once per workspace: afterwards every launch leaves them zero) and, unless the
 // workspace carries the mark of an earlier initialisation, the sticky status word
 constexpr unsigned kLinMagic = 0x4c494e33u;
+#ifndef VAEK_LIN_FOUR_BLOCK_TU
 __global__ void lin_init_kernel(unsigned* cnt, int n_words, unsigned* status) {
     for (int k = threadIdx.x; k < n_words; k += blockDim.x) cnt[k] = 0u;
     if (threadIdx.x == 0 && status[1] != kLinMagic) { status[0] = 0u; status[1] = kLinMagic; }
 }
+#endif
 
+typedef void (*LinPersistKernel)(const LinArgs, const LinPtrs);
+typedef void (*LinPersistGenKernel)(const LinArgs, const BatchArgs);
+// The four-block instantiations of the persistent form are compiled in a translation unit of their own (linear_moments4.hip, which
+// includes this file with VAEK_LIN_FOUR_BLOCK_TU defined): in the same device module they change how the three-block kernels
+// are compiled (module-wide attribute inference) and the metric's launch slows down.  0: run-time shapes, 1: D = 20, L = 20.
+LinPersistKernel lin_persist_four(int which);
+LinPersistGenKernel lin_persist_four_gen(int which);
+
+#ifndef VAEK_LIN_FOUR_BLOCK_TU
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 constexpr size_t kLinMaxLds = 160 * 1024;
 // workspace: [cnt_stream: 64 batches x 8 shards x 128 B][cnt_reduce: 64 words][status word, init mark][M slots][partial image slots]
@@ -1610,33 +2031,45 @@ LinPlan lin_plan(const vaek_ctx* c) {
     // a tile slot doubles as the combine's cross-wave scratch; a persistent streamer's LDS: three slots, the two validity columns,
     // the zero word, the batch pointer tables
     const auto slot_bytes = [&](int T) { return std::max((size_t)LinTile(D, L, T).bytes, (size_t)lin_scratch_bytes(p.NB)); };
-    const auto ring_bytes = [&](int T) { return 3 * slot_bytes(T) + 8 * (size_t)T + 16 + 3 * kLinMaxPersist * sizeof(void*) + 64; };
+    const auto ring_slot_bytes = [&](int T) { return std::max((size_t)LinTile(D, L, T).bytes, (size_t)lin_ring_scratch_bytes(p.NB)); };
+    const auto ring_bytes = [&](int T) { return 3 * ring_slot_bytes(T) + 8 * (size_t)T + 16 + 3 * kLinMaxPersist * sizeof(void*) + 64; };
     const auto ksteps_ok = [&](int T) { return (LinTile(D, L, T).np + LNW - kLinCW - 1) / (LNW - kLinCW) <= 18; };
     // Samples per tile.  256, unless a slightly taller tile lets every streamer of the persistent launch take exactly ONE tile per
     // batch (the metric: 65 536 samples = 228 tiles of 288 on the 231 CUs the updater and the reducers leave).
     const int smax = c->n_cu - 1 - kLinReduceSets * kLinReduceWgs;
+    const bool upd_ok = p.NB == 3 ? LinUpdM<3, 0, 0>::shape_ok(D, L) : LinUpdMG<4, 0, 0>::shape_ok(D, L);
     p.T = 256;
-    if (smax >= 16 && c->B > 256 * smax) {
-        const int T = 32 * (int)(((long long)c->B + 32ll * smax - 1) / (32ll * smax));
-        if (T <= 512 && ksteps_ok(T) && ring_bytes(T) <= kLinMaxLds) p.T = T;
+    if (p.NB == 3) {
+        if (smax >= 16 && c->B > 256 * smax) {
+            const int T = 32 * (int)(((long long)c->B + 32ll * smax - 1) / (32ll * smax));
+            if (T <= 512 && ksteps_ok(T) && ring_bytes(T) <= kLinMaxLds) p.T = T;
+        }
+    } else if (upd_ok && smax >= 16) {
+        // Four blocks: rows of up to 252 bytes, and three slots of 256 of them are over the LDS.  The tallest tile whose ring fits
+        // (D = 20, L = 20: 192 rows) -- the fewest partial images, and a batch of up to T rows (run.py's 100) is one tile; the
+        // streamers then take ceil(tiles / streamers) tiles each (the metric's size: 342 tiles of 192, two on each of 171 CUs).
+        int T = 256;
+        while (T > 32 && !(ksteps_ok(T) && ring_bytes(T) <= kLinMaxLds)) T -= 32;
+        p.T = T;
     }
     p.ntiles = (c->B + p.T - 1) / p.T;
     // launch-per-step form: one slot + validity column + zero word | updater | reducer sums
-    const size_t upd = std::max(p.NB == 3 ? LinUpd<3, 0, 0>::lds_bytes(D, L) : LinUpd<4, 0, 0>::lds_bytes(D, L), LinUpdM<3, 0, 0>::lds_bytes(D, L, (int)c->P));
+    const size_t upd = std::max(p.NB == 3 ? LinUpd<3, 0, 0>::lds_bytes(D, L) : LinUpd<4, 0, 0>::lds_bytes(D, L),
+                                p.NB == 3 ? LinUpdM<3, 0, 0>::lds_bytes(D, L, (int)c->P) : LinUpdMG<4, 0, 0>::lds_bytes(D, L, (int)c->P));
     p.lds_step = std::max(slot_bytes(p.T) + 4 * (size_t)p.T + 16, std::max(upd, (size_t)2 * 16 * 32 * sizeof(double))) + 64;
     // The persistent form gives every workgroup a CU of its own (the updater's float64 chains and the streamers' MFMA loops both
     // lose a factor ~2 when they share one): each workgroup asks for more than half a CU's LDS -- the streamers need it anyway for
     // their ring of tile slots -- and the grid stays within the CU count.
     p.lds_persist = std::max(std::max(p.lds_step, ring_bytes(p.T)), (size_t)82 * 1024);
-    p.persist = p.NB == 3 && LinUpdM<3, 0, 0>::shape_ok(D, L) && p.lds_persist <= kLinMaxLds && ksteps_ok(p.T) && smax >= 16;
+    p.persist = upd_ok && p.lds_persist <= kLinMaxLds && ksteps_ok(p.T) && smax >= 16;
     if (p.persist) {      // streamers: the CUs the updater and the reducers leave, tiles dealt evenly
         const int per = (p.ntiles + smax - 1) / smax;
         p.n_stream = (p.ntiles + per - 1) / per;
         p.n_reduce = kLinReduceSets * std::min(kLinReduceWgs, p.NO / 32);
     }
-    // the metric's shape with its dimensions (and the k-steps per wave of its 288-row tile) at compile time; every other linear
-    // model on the run-time instantiations
-    p.which_persist = D == 12 && L == 20 && p.T == 288 ? 0 : 1;
+    // the metric's shape with its dimensions (and the k-steps per wave of its 288-row tile) at compile time, and M20's (D = 20,
+    // L = 20, 192-row tile); every other linear model on the run-time instantiations of its block count
+    p.which_persist = p.NB == 3 ? (D == 12 && L == 20 && p.T == 288 ? 0 : 1) : (D == 20 && L == 20 && p.T == 192 ? 3 : 2);
     p.which_step = D == 12 && L == 20 ? 2 : p.NB - 3;
     const int slots = p.persist ? kLinMaxPersist : 2;
     p.M_off = kLinHeadBytes;
@@ -1666,10 +2099,10 @@ static LinWs lin_ws(const vaek_ctx* c, void* ws) {
 // The kernels by LinPlan::which_persist / which_step, each given the LDS cap (not a request) the first time it is launched on a
 // device.  The device code lists the instantiations in the order these tables name them.
 typedef void (*LinStepKernel)(const LinArgs);
-typedef void (*LinPersistKernel)(const LinArgs, const LinPtrs);
-typedef void (*LinPersistGenKernel)(const LinArgs, const BatchArgs);
-static const LinPersistKernel kLinPersist[] = {lin_persist_kernel<3, 12, 20, 18, false>, lin_persist_kernel<3, 0, 0, 0, false>};
-static const LinPersistGenKernel kLinPersistGen[] = {lin_persist_kernel<3, 12, 20, 18, true>, lin_persist_kernel<3, 0, 0, 0, true>};
+static const LinPersistKernel kLinPersist[] = {lin_persist_kernel<3, 12, 20, 18, false>, lin_persist_kernel<3, 0, 0, 0, false>,
+                                                lin_persist_four(0), lin_persist_four(1)};
+static const LinPersistGenKernel kLinPersistGen[] = {lin_persist_kernel<3, 12, 20, 18, true>, lin_persist_kernel<3, 0, 0, 0, true>,
+                                                     lin_persist_four_gen(0), lin_persist_four_gen(1)};
 static const LinStepKernel kLinStep[] = {lin_step_kernel<3, 0, 0>, lin_step_kernel<4, 0, 0>, lin_step_kernel<3, 12, 20>};
 template <typename K, size_t N> static int lin_kernel(const K (&table)[N], int which, K* fn) {
     static thread_local PerDeviceOnce attr_set[N];
@@ -1831,10 +2264,12 @@ int lin_steps_status(vaek_ctx* c, void* ws, int* gave_up) {
     return VAEK_OK;
 }
 
+#endif  // VAEK_LIN_FOUR_BLOCK_TU
+
 }  // namespace vaek
 
-#ifdef VAEK_LIN_STAMPS
+#if defined(VAEK_LIN_STAMPS) && !defined(VAEK_LIN_FOUR_BLOCK_TU)
 extern "C" int vaek_debug_lin_stamps(unsigned long long* buf) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(vaek::g_lin_stamp_buf), &buf, sizeof(buf)) == hipSuccess ? 0 : -2;
+    return hipMemcpyToSymbol(HIP_SYMBOL(vaek::g_lin_stamp_buf), &buf, sizeof(buf)) == hipSuccess ? vaek::lin_stamps_four(buf) : -2;
 }
 #endif

@@ -106,7 +106,8 @@ struct LinPlan {
     bool persist = false;             // the persistent form applies
     int n_stream = 0, n_reduce = 0;   // its streamer / reducer workgroups
     size_t lds_persist = 0, lds_step = 0;      // dynamic LDS of the persistent / launch-per-step form
-    int which_persist = 0, which_step = 0;     // instantiation: 0 / 2 the metric's D = 12, L = 20 at compile time, else run-time (step: NB - 3)
+    int which_persist = 0, which_step = 0;     // instantiation: 0 / 2 the metric's D = 12, L = 20 at compile time, else run-time (step: NB - 3;
+                                               // persistent: 1 three blocks, 2 four blocks, 3 M20's D = 20, L = 20 at compile time)
     size_t M_off = 0, partial_off = 0, ws_bytes = 0;   // within the context's workspace region at ws_lin
     size_t comm_bytes = 0;            // the moment-exchange region of the P2P communicator's buffer (world > 1, persistent form)
 };
