@@ -98,6 +98,11 @@ int vaek_leaf_info(const vaek_ctx* ctx, int32_t leaf, char* name, int32_t name_c
 int vaek_workspace_bytes(const vaek_ctx* ctx, size_t* bytes);
 /* 1 if the fused small-model path is used for train_step/loss_eval, 0 for layer-by-layer. */
 int vaek_uses_fused_path(const vaek_ctx* ctx, int32_t* fused);
+/* Which form vaek_train_step takes for this context, chosen once at creation, NUL-terminated into name[cap]:
+ * "linear" (fused linear VAE, D, L <= 32), "mlp1" (one hidden layer), "mlp3" (three hidden layers of 64 .. 256 units both
+ * ways, D, L <= 32, float32, one decoder, batch <= 128), "linear_wide" (layer by layer with the fused wide linear decoder)
+ * or "layers" (layer by layer).  The first three are whole-network paths: vaek_uses_fused_path reports 1 for them. */
+int vaek_train_step_path(const vaek_ctx* ctx, char* name, int32_t cap);
 
 /* ---- building blocks (also used by the layer-by-layer path of vaek_train_step) ----------- */
 /* flax.nn.Dense + relu, networks.py:34-39: y[rows,n_out] = act(x[rows,n_in] @ w[n_in,n_out] + b). */
@@ -139,8 +144,9 @@ int vaek_adam_step(vaek_ctx* ctx, float* params, const float* grads, float* m, f
  * updates params/m/v, increments *step_dev (device int32 Adam step counter), leaves the loss
  * in grads[P] (device; the reference keeps it un-synced too, vae.py:130).
  * Launches: linear VAEs with D, L <= 32 (the metric) run two kernels -- forward/backward/partial sums, then
- * reduction + Adam -- or ONE when the batch fits a workgroup (<= 256 rows, single GPU); any other MLP runs layer by
- * layer.  Asynchronous on `stream`, capturable into a hipGraph (no host-side state per step). */
+ * reduction + Adam -- or ONE when the batch fits a workgroup (<= 256 rows, single GPU); one-hidden-layer MLPs and
+ * three-hidden-layer MLPs at small batch (vaek_train_step_path "mlp1" / "mlp3") run two as well; any other MLP runs layer
+ * by layer.  Asynchronous on `stream`, capturable into a hipGraph (no host-side state per step). */
 int vaek_train_step(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
                     const float* x, const float* z1, const float* z2, float lr,
                     void* workspace, void* stream);

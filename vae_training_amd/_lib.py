@@ -42,6 +42,7 @@ SIGNATURES = {
     "vaek_leaf_info": (C.c_int, [_vp, _i32, C.c_char_p, _i32, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)]),
     "vaek_workspace_bytes": (C.c_int, [_vp, C.POINTER(C.c_size_t)]),
     "vaek_uses_fused_path": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "vaek_train_step_path": (C.c_int, [_vp, C.c_char_p, _i32]),
     "vaek_dense_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "vaek_dense_bwd_dx": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "vaek_dense_bwd_dw": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp]),

@@ -336,6 +336,14 @@ static int generic_grads(vaek_ctx* c, const float* params, int32_t* step_dev, co
     return net_backward(c, c->enc, params, x, dsamp, ws, nullptr, false, st, sink);
 }
 
+// the whole-network step of a context with c->fused; `exchange` (the in-kernel P2P sum) exists on fused_train_step's kernels only
+static int whole_step(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x, const float* z1,
+                      const float* z2, float lr, bool apply_adam, bool exchange, void* ws, hipStream_t st, const BatchArgs* gen = nullptr) {
+    if (!c->mlp3) return fused_train_step(c, params, grads, m, v, step_dev, x, z1, z2, lr, apply_adam, exchange, ws, st, gen);
+    if (exchange) { set_error("the three-hidden-layer whole-network step has no in-kernel exchange"); return VAEK_ERR_INVALID; }
+    return mlp3_train_step(c, params, grads, m, v, step_dev, x, z1, z2, lr, apply_adam, ws, st, gen);
+}
+
 constexpr int64_t kBulkFinalizeMin = 65536;      // parameters below which the 64-output finalize alone is faster
 
 static int generic_finalize(vaek_ctx* c, const float* params, float* grads, float* params_rw, float* m, float* v,
@@ -483,8 +491,12 @@ int vaek_ctx_create(const vaek_config* cfg, vaek_ctx** out) {
     c->ws_rpart = off; off = align_up(off + (size_t)c->Se * c->L * sizeof(float), 256);
     // {mse, d eps} per output tile of the decoder's last GEMM: at most (B/64) x (D/32) tiles in any of its tile shapes
     c->ws_eblk = off; off = align_up(off + (size_t)((c->B + 63) / 64) * ((c->D + 31) / 32) * 2 * sizeof(float), 256);
-    c->fused = !cfg->force_generic && fused_supported(c);
+    // the train step's form, chosen here once (vaek_train_step_path names it): a whole-network path -- the linear / one-hidden-layer
+    // kernels behind fused_train_step, or fused_mlp3.hip's -- else the layer-by-layer kernels
+    c->mlp3 = !cfg->force_generic && mlp3_supported(c);
+    c->fused = !cfg->force_generic && (fused_supported(c) || c->mlp3);
     c->ws_fused = off; off = align_up(off + fused_workspace_bytes(c), 256);
+    c->ws_mlp3 = off; off = align_up(off + (c->mlp3 ? mlp3_workspace_bytes(c) : 0), 256);
     c->ws_wb16 = off; off = align_up(off + (size_t)wb_elems * sizeof(__bf16), 256);
     c->ws_sk16 = off; off = align_up(off + (size_t)sk_elems * sizeof(__bf16), 256);
     c->ws_skpart = off; off = align_up(off + sk_part, 256);
@@ -537,6 +549,13 @@ int vaek_workspace_bytes(const vaek_ctx* ctx, size_t* bytes) {
 int vaek_uses_fused_path(const vaek_ctx* ctx, int32_t* fused) {
     if (!ctx || !fused) { set_error("null argument"); return VAEK_ERR_INVALID; }
     *fused = ctx->fused ? 1 : 0;
+    return VAEK_OK;
+}
+int vaek_train_step_path(const vaek_ctx* ctx, char* name, int32_t cap) {
+    if (!ctx || !name || cap <= 0) { set_error("vaek_train_step_path: invalid argument"); return VAEK_ERR_INVALID; }
+    const char* p = ctx->mlp3 ? "mlp3" : ctx->fused ? (mlp1_supported(ctx) ? "mlp1" : "linear") : ctx->lwd ? "linear_wide" : "layers";
+    if ((size_t)cap <= strlen(p)) { set_error("vaek_train_step_path: buffer too small"); return VAEK_ERR_INVALID; }
+    strcpy(name, p);
     return VAEK_OK;
 }
 
@@ -684,8 +703,8 @@ int vaek_train_step_grads_only(vaek_ctx* ctx, const float* params, float* grads,
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (ctx->fused)
-        return fused_train_step(ctx, const_cast<float*>(params), grads, nullptr, nullptr, step_dev, x, z1, z2, 0.f, false,
-                                false, workspace, st);
+        return whole_step(ctx, const_cast<float*>(params), grads, nullptr, nullptr, step_dev, x, z1, z2, 0.f, false,
+                          false, workspace, st);
     if ((rc = generic_grads(ctx, params, step_dev, x, z1, z2, workspace, st))) return rc;
     return generic_finalize(ctx, params, grads, nullptr, nullptr, nullptr, nullptr, 0.f, workspace, st);
 }
@@ -710,13 +729,14 @@ int vaek_train_step(vaek_ctx* ctx, float* params, float* grads, float* m, float*
                       "vaek_train_step_grads_only + all-reduce + vaek_train_step_apply", ctx->cfg.world);
             return VAEK_ERR_COMM;
         }
-        // fused path: the exchange happens inside the finalize kernel (the step stays two launches)
-        if (ctx->fused) return fused_train_step(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, true, true, workspace, st);
+        // fused path: the exchange happens inside the finalize kernel (the step stays two launches); fused_mlp3.hip has no
+        // exchange and takes the three calls below
+        if (ctx->fused && !ctx->mlp3) return whole_step(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, true, true, workspace, st);
         if ((rc = vaek_train_step_grads_only(ctx, params, grads, step_dev, x, z1, z2, workspace, stream))) return rc;
         if ((rc = vaek_comm_allreduce(ctx, grads, ctx->P + kExtra, stream))) return rc;
         return vaek_train_step_apply(ctx, params, grads, m, v, step_dev, lr, stream);
     }
-    if (ctx->fused) return fused_train_step(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, true, false, workspace, st);
+    if (ctx->fused) return whole_step(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, true, false, workspace, st);
     if ((rc = generic_grads(ctx, params, step_dev, x, z1, z2, workspace, st))) return rc;
     return generic_finalize(ctx, params, grads, params, m, v, step_dev, lr, workspace, st);
 }
@@ -742,9 +762,9 @@ int vaek_train_step_gen(vaek_ctx* ctx, float* params, float* grads, float* m, fl
     if (rc) return rc;
     if ((rc = check_ws(ctx, workspace))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const bool comm_ok = ctx->cfg.world == 1 || ctx->comm.ready;
+    const bool comm_ok = ctx->cfg.world == 1 || (ctx->comm.ready && !ctx->mlp3);
     if (ctx->fused && comm_ok)
-        return fused_train_step(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, true, ctx->cfg.world > 1, workspace, st, &gen);
+        return whole_step(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, true, ctx->cfg.world > 1, workspace, st, &gen);
     // layer-by-layer path: the same two operations as separate launches on the one stream
     if ((rc = make_batch_launch(ctx, gen, st))) return rc;
     return vaek_train_step(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, workspace, stream);
@@ -875,8 +895,8 @@ int vaek_train_step_grads_bucketed(vaek_ctx* ctx, const float* params, float* gr
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (ctx->fused) {
-        if ((rc = fused_train_step(ctx, const_cast<float*>(params), grads, nullptr, nullptr, step_dev, x, z1, z2, 0.f, false, false,
-                                   workspace, st)))
+        if ((rc = whole_step(ctx, const_cast<float*>(params), grads, nullptr, nullptr, step_dev, x, z1, z2, 0.f, false, false,
+                             workspace, st)))
             return rc;
         VAEK_HIP_CHECK(hipEventRecord((hipEvent_t)ready_events[0], st));
         return VAEK_OK;

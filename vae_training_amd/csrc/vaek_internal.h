@@ -124,9 +124,10 @@ struct vaek_ctx {
     int64_t off_epsp, off_eps;       // flat offsets; off_eps = -1 without -tdv
     // batch split of the deterministic reductions: S slabs for the dW|db GEMMs, Se for elementwise
     int S, rows_per_split, Se, rows_per_esplit;
-    bool fused;                      // fused small-model path available and selected
+    bool fused;                      // a whole-network path is available and selected (fused_small / fused_mfma / fused_mlp1 / fused_mlp3)
+    bool mlp3 = false;               // ... and it is fused_mlp3.hip's (three hidden layers both ways, small batch)
     // workspace layout (bytes)
-    size_t ws_samples, ws_dsamp, ws_gbuf0, ws_gbuf1, ws_slabs, ws_epart, ws_epart_blk, ws_rpart, ws_eblk, ws_fused, ws_wb16, ws_sk16, ws_skpart, ws_lin, ws_lwd, ws_total;
+    size_t ws_samples, ws_dsamp, ws_gbuf0, ws_gbuf1, ws_slabs, ws_epart, ws_epart_blk, ws_rpart, ws_eblk, ws_fused, ws_mlp3, ws_wb16, ws_sk16, ws_skpart, ws_lin, ws_lwd, ws_total;
     bool lwd = false; int lwd_rb = 0;           // wide linear decoder: fused forward / ELBO / backward (linear_wide.hip), rows per row block
     int max_width;
     int n_cu;
@@ -394,5 +395,12 @@ size_t fused_workspace_bytes(const vaek_ctx* c);
 int fused_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev,
                      const float* x, const float* z1, const float* z2, float lr, bool apply_adam, bool exchange,
                      void* ws, hipStream_t st, const BatchArgs* gen = nullptr);
+
+// ---- fused_mlp3.hip: whole-network step for three-hidden-layer MLP VAEs (64 .. 256 units, D, L <= 32) at small batch ----------
+bool mlp3_supported(const vaek_ctx* c);
+size_t mlp3_workspace_bytes(const vaek_ctx* c);   // the region at ws_mlp3: stored activations / gradients and the partial rows
+// two launches (chain; gradients + tail + Adam); gen != nullptr: the second carries workgroups that draw the NEXT step's batch
+int mlp3_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x, const float* z1,
+                    const float* z2, float lr, bool apply_adam, void* ws, hipStream_t st, const BatchArgs* gen = nullptr);
 
 }  // namespace vaek

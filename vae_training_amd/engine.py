@@ -91,6 +91,8 @@ class Engine:
         f = C.c_int32()
         _lib.check(self.lib.vaek_uses_fused_path(h, C.byref(f)))
         self.fused = bool(f.value)
+        _lib.check(self.lib.vaek_train_step_path(h, buf, 64))
+        self.step_path = buf.value.decode()      # "linear", "mlp1", "mlp3", "linear_wide" or "layers"
         self.batch, self.D, self.L = int(batch), int(data_dim), int(latent_dim)
 
     def __del__(self):

@@ -150,6 +150,10 @@ def main(args):
     if dataset is None:
         raise ValueError("--dataset must be one of sphere, linear_gaussian, sigmoid")
     model = get_model(args, dataset, output_dir, dist)
+    if rank == 0:
+        eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
+        loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")
+        print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), {loop}")
     model.train()
     model.plot()
     model.save(final=True)
