@@ -47,15 +47,21 @@ if persist:
     print(f"   loop entry -> end of last step: {(t[16 + 7] - t[16 + 10]) / 100.0:.1f} us (s_memrealtime, 100 MHz) = {(t[7] - t[10])} s_memtime ticks")
     print(f"   last step: {(t[16 + 7] - t[16 + 0]) / 100.0:.2f} us")
     print(f"   waiting for the reducers: total {t[11] / 100.0:.1f} us, first step {t[13] / 100.0:.1f} us, longest {t[12] / 100.0:.1f} us")
-    t0 = t[16 + 10]
+    t0 = t[16 + 10] if t[16 + 10] else min(t[50], t[51], t[52])      # (STAMPS=2 has no updater stamps: from the first streamer's entry)
     print(f"   reducer workgroup 5 (32 of the launch's batches): waiting {t[40] / 100.0:.1f} us, reducing {t[41] / 100.0:.1f} us")
     print(f"   streamer 7 ({t[46]} work items), us per item: counted wait {t[42] / 100.0 / t[46]:.2f}, barrier {t[43] / 100.0 / t[46]:.2f}, ragged fix {t[44] / 100.0 / t[46]:.2f}, "
           f"products (pieces of a later tile issued between the k-steps) {t[47] / 100.0 / t[46]:.2f}, barrier {t[48] / 100.0 / t[46]:.2f}, cross-wave sum + store {(t[45] - t[47] - t[48]) / 100.0 / t[46]:.2f}")
-    print(f"   streamers 0 / S/2 / S-1 entered the kernel at {(t[50] - t0) / 100.0:.1f} / {(t[51] - t0) / 100.0:.1f} / {(t[52] - t0) / 100.0:.1f} us, signalled batch 0 at {(t[53] - t0) / 100.0:.1f} / {(t[54] - t0) / 100.0:.1f} / {(t[55] - t0) / 100.0:.1f} us")
+    print(f"   streamers 0 / S/2 / S-1 entered the kernel at {(t[50] - t0) / 100.0:.1f} / {(t[51] - t0) / 100.0:.1f} / {(t[52] - t0) / 100.0:.1f} us, streamer 0 signalled its first image at {(t[53] - t0) / 100.0:.1f} us")
     print("   reducer 5, batches 0..2: woke at / done at (us): " + "  ".join(f"{(t[56 + 2 * n] - t0) / 100.0:.1f} / {(t[57 + 2 * n] - t0) / 100.0:.1f}" for n in range(3)))
-    print("   batch: reduced at | updated at  (us after the updater entered its loop; last arrival of each role)")
-    for n in range(0, nsteps, 1 if nsteps <= 24 else 3):
-        print(f"   {n:3d}   {(t[128 + n] - t0) / 100.0:8.1f}   {(t[64 + n] - t0) / 100.0:8.1f}")
+    # the call's LAST launch (each launch overwrites the stamps): with more than 64 steps per call a chained launch, whose reducers
+    # start one batch and whose updater starts two batches behind its streamers (lin_windows); rows count each role's own batches
+    nl = (nsteps + 63) // 64
+    n_str = nsteps - 64 * (nl - 1); n_red = n_str + (nl > 1); n_upd = n_str + 2 * (nl > 1)
+    print(f"   last launch of {nl}: streams {n_str}, reduces {n_red}, updates {n_upd} batches; last streamer done at {(t[49] - t0) / 100.0:.1f} us, "
+          f"last reduce {(t[136 + n_red - 1] - t0) / 100.0:.1f} us, last update {(t[64 + n_upd - 1] - t0) / 100.0:.1f} us")
+    print("   n: the role's n-th batch reduced at | updated at  (us after the updater entered its loop -- STAMPS=2: after the first streamer entered the kernel; last arrival of each role)")
+    for n in list(range(0, n_upd, 1 if n_upd <= 24 else 3)) + [n_upd - 1]:
+        print(f"   {n:3d}   {(t[136 + n] - t0) / 100.0 if n < n_red else float('nan'):8.1f}   {(t[64 + n] - t0) / 100.0:8.1f}")
     print("updater, last step of the launch (s_memtime ticks):")
     print(f"   publish params               {t[9] - t[0]:8d}")
     print(f"   wait for the reducers        {t[8] - t[9]:8d}")

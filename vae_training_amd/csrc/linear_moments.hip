@@ -33,6 +33,13 @@
 // the launch has its OWN partial / M slot, so a streamer never waits for anybody: nothing can dead-lock, whatever the
 // dispatcher does with residency, and every poll is bounded (status word, vaek_train_steps_status).  What it buys on top:
 // no launch boundary and no cold start per step (the updater's instruction stream and parameters stay on one CU).
+// A call of more than 64 steps is several such launches, CHAINED: launch j streams batches [64 j, 64 j + 64), but reduces
+// [64 j - 1, 64 j + 63) and updates [64 j - 2, 64 j + 62) -- the launch-per-step form's shift, across the launch boundary -- and
+// the call's last launch runs every role to the end (lin_windows).  A later launch's reducers and updater so start on batches
+// that are complete (ordered by the stream) while its streamers fill their pipeline, and the three roles end together instead
+// of the streamers idling through the drain.  Batch n of a call lives in slot n % 66 of the workspace (64 + the two carried:
+// partial images, M, arrival counters -- 66 x ntiles x 6 KB of images, 92.5 MB at the metric's 228 tiles); a slot comes round
+// again 66 batches later, when its batch was updated at least a whole launch ago, so still nobody waits for a slot.
 //
 // Numerics: M accumulates exact-f32 products in chains of 72 samples (one multiplying wave's 18 MFMA k-steps at the metric's
 // 288-row tile; 36 in the launch-per-step form), summed further in
@@ -55,7 +62,38 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 
 constexpr int LNT = 512, LNW = LNT / 64;          // threads / waves per workgroup, every role
-constexpr int kLinMaxPersist = 64;                // steps per persistent launch (each owns a partial / M slot)
+constexpr int kLinMaxPersist = 64;                // batches a persistent launch streams
+// Launches of ONE call are chained: a launch that is not the call's last leaves its last batch to the next launch's reducers and
+// its last two to the next launch's updater (the shift the launch-per-step form makes per step), so that launch starts reducing
+// and updating at once, while its streamers fill, and all three roles end together.  Batch n of a call lives in slot n % kLinSlots
+// (partial images, M, arrival counters): a launch's 64 streamed batches and the two carried into it never share a slot.
+constexpr int kLinCarry = 2, kLinSlots = kLinMaxPersist + kLinCarry;
+struct LinWindow { int first, count; };
+struct LinWindows { LinWindow stream, reduce, update; };
+// the batch windows of launch j of a call of K steps
+constexpr LinWindows lin_windows(int K, int j) {
+    const int s0 = kLinMaxPersist * j, s1 = s0 + kLinMaxPersist < K ? s0 + kLinMaxPersist : K;
+    const bool last = s1 == K;
+    const int r0 = s0 >= 1 ? s0 - 1 : 0, u0 = s0 >= 2 ? s0 - 2 : 0;
+    return LinWindows{{s0, s1 - s0}, {r0, (last ? K : s1 - 1) - r0}, {u0, (last ? K : s1 - 2) - u0}};
+}
+constexpr int lin_launches(int K) { return (K + kLinMaxPersist - 1) / kLinMaxPersist; }
+// every role covers [0, K) exactly once, in order; no role takes more batches than it may; a launch's live batches fit the slots
+constexpr bool lin_windows_ok(int K) {
+    int s = 0, r = 0, u = 0;
+    for (int j = 0; j < lin_launches(K); ++j) {
+        const LinWindows w = lin_windows(K, j);
+        if (w.stream.first != s || w.reduce.first != r || w.update.first != u) return false;
+        if (w.stream.count < 1 || w.stream.count > kLinMaxPersist || w.reduce.count < 1 || w.update.count < 1) return false;
+        s += w.stream.count; r += w.reduce.count; u += w.update.count;
+        if (r > s || u > r || s - w.update.first > kLinSlots) return false;      // nobody ahead of its producer; live batches <= slots
+    }
+    return s == K && r == K && u == K;
+}
+static_assert(lin_windows_ok(1) && lin_windows_ok(2) && lin_windows_ok(64) && lin_windows_ok(65) && lin_windows_ok(66) && lin_windows_ok(128) &&
+              lin_windows_ok(129) && lin_windows_ok(130) && lin_windows_ok(960), "launch windows of a vaek_train_steps call");
+static_assert(lin_windows(64, 0).update.count == 64 && lin_windows(130, 1).update.first == 62 && lin_windows(130, 1).reduce.first == 63 &&
+              lin_windows(130, 2).update.count == 4, "launch windows of a vaek_train_steps call");
 constexpr int kLinReduceSets = 1;                 // persistent form: reducer sets taking alternate batches (one set of 24 beat two of 12)
 constexpr int kLinReduceWgs = 24;                 // workgroups per set, each summing NO / 32 / 24 slices of 32 outputs (more resident
                                                   // workgroups measurably slow the streamers: 48 per set cost 2 us per step)
@@ -79,13 +117,18 @@ struct LinArgs {
     const float* x; const float* z1; const float* z2; float* partial_out;        // [ntiles][NBLK * 256]
     const float* partial_in; double* M_out;                                       // [NBLK * 256]
     const double* M_in;
-    // ---- persistent form: n_steps batches, pointer tables in device memory, one slot per batch, arrival counters
+    // ---- persistent form: the updater takes n_steps batches, the reducers n_red, the streamers n_str (lin_windows), each from
+    // its own first slot on, round the kLinSlots slots; pointer tables as kernel arguments, arrival counters per slot
     int persistent, n_steps, sets;                // sets: reducer sets taking alternate batches
-    float* partial_base; double* M_base;                                          // slot n at + n * ntiles * NO resp. + n * NO
+    int n_red, n_str, slot_upd, slot_red, slot_str;
+    int d_red, d_str;                             // the reducers' / streamers' first batch minus the updater's: step_dev[0] counts the updater's
+    float* partial_base; double* M_base;                                          // slot s at + s * ntiles * NO resp. + s * NO
     // arrival counters.  cnt_stream: kLinShards shards per batch, each on a 128-byte line of its own (a streamer adds to shard
     // blockIdx & 7: 228 adders on ONE word serialise at the memory side -- the reducers woke 8 us after the last streamer had
-    // signalled); cnt_reduce: one word per batch.  All zero when a launch starts: the updater re-zeroes what the launch used as
-    // its last act (everybody else is provably done with them by then), lin_init_kernel zeroes them once per workspace.
+    // signalled); cnt_reduce: one word per batch.  A slot's counters are zero when its batch is first streamed: the updater
+    // re-zeroes those of the batches it updated as the launch's last act (everybody else is provably done with them by then --
+    // a batch carried into the next launch keeps its counts, and that launch zeroes them), lin_init_kernel zeroes all once per
+    // workspace.  After a call's last launch every counter is zero again.
     unsigned* cnt_stream; unsigned* cnt_reduce; unsigned* status;                 // status: sticky, outside the zeroed range
     // ---- updater
     float* params; float* grads; float* m; float* v; int32_t* step_dev; float lr;
@@ -1681,13 +1724,15 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         double mreg[NM], mnext[NM];
         bool have_next = false;
         LIN_STAMP(10);
+        int sl = a.slot_upd;                                  // the slot of batch n, and of the batch after it
         for (int n = 0; n < N; ++n) {
+            const int sl_next = sl + 1 == kLinSlots ? 0 : sl + 1;
             LIN_STAMP(0);
             u.publish_params(a);
             LIN_STAMP(9);
             if (!have_next) {
-                lin_wait_count(a.cnt_reduce + n, (unsigned)per_set, a.status, (1u << 28) | ((unsigned)n << 16));     // (also the barrier behind publish_params)
-                if (t < 64 * NB) u.fetch_M(a.M_base + (long long)n * NO, mreg);
+                lin_wait_count(a.cnt_reduce + sl, (unsigned)per_set, a.status, (1u << 28) | ((unsigned)n << 16));     // (also the barrier behind publish_params)
+                if (t < 64 * NB) u.fetch_M(a.M_base + (long long)sl * NO, mreg);
             } else {
                 __syncthreads();
 #pragma unroll
@@ -1695,33 +1740,45 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
             }
             LIN_STAMP(8);
             ++tstep;
-            u.step(a, tstep, mreg, g, n + 1 < N ? a.cnt_reduce + n + 1 : nullptr, (unsigned)per_set, a.M_base + (long long)(n + 1) * NO, mnext, have_next);
+            u.step(a, tstep, mreg, g, n + 1 < N ? a.cnt_reduce + sl_next : nullptr, (unsigned)per_set, a.M_base + (long long)sl_next * NO, mnext, have_next);
             LIN_STAMP(7);
             { [[maybe_unused]] unsigned long long te = 0; LIN_NOWQ(te); LIN_PUT(64 + n, te); }
+            sl = sl_next;
         }
         u.store_state(a, g, tstep);
-        // every reducer has added to the last batch's counter, every streamer long before: nobody reads or writes the arrival
-        // counters any more -- zero them for the next launch (write-through; the kernel boundary orders them)
-        for (int k = t; k < N * kLinShards; k += LNT) __hip_atomic_store(a.cnt_stream + k * kLinShardStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int k = t; k < N; k += LNT) __hip_atomic_store(a.cnt_reduce + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // every reducer has added to the counter of the last batch updated here, every streamer long before: nobody reads or writes
+        // the arrival counters of the batches this launch UPDATED any more -- zero them for the slots' next batches (write-through;
+        // the kernel boundary orders them).  Batches streamed here and left to the next launch keep theirs.
+        for (int k = t; k < N * kLinShards; k += LNT) {
+            int s = a.slot_upd + k / kLinShards;
+            s = s >= kLinSlots ? s - kLinSlots : s;
+            __hip_atomic_store(a.cnt_stream + (s * kLinShards + k % kLinShards) * kLinShardStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        for (int k = t; k < N; k += LNT) {
+            int s = a.slot_upd + k;
+            s = s >= kLinSlots ? s - kLinSlots : s;
+            __hip_atomic_store(a.cnt_reduce + s, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
     } else if (b < a.has_update + a.n_reduce) {
         // ---- reducers: set (rb / per_set) takes batches set, set + 2, ... ------------------------------------------------------
         const int rb = b - a.has_update, set = rb / per_set, ro = rb % per_set;
         const int tstep0 = a.step_dev[0];              // (the updater stores the counter at the very end of the launch)
         [[maybe_unused]] unsigned long long r0 = 0, r1 = 0, r2 = 0, racc_w = 0, racc_r = 0;
-        for (int n = set; n < N; n += a.sets) {
+        int sl = a.slot_red + set;                            // the slot of batch n (set < kLinSlots, sets <= kLinSlots)
+        sl = sl >= kLinSlots ? sl - kLinSlots : sl;
+        for (int n = set; n < a.n_red; n += a.sets, sl = sl + a.sets >= kLinSlots ? sl + a.sets - kLinSlots : sl + a.sets) {
             LIN_NOWQ(r0);
-            lin_wait_shards(a.cnt_stream + n * kLinShards * kLinShardStride, (unsigned)a.ntiles, a.status, (2u << 28) | ((unsigned)n << 16));
+            lin_wait_shards(a.cnt_stream + sl * kLinShards * kLinShardStride, (unsigned)a.ntiles, a.status, (2u << 28) | ((unsigned)n << 16));
             LIN_NOWQ(r1);
             // 32-output slices, two at a time where there are two (a 128-output form reading 16 bytes per lane with sc1 buffer loads
             // measured 8 % SLOWER per step)
             for (int sub = ro; sub < NO / 32; sub += 2 * per_set) {
                 if (sub != ro) __syncthreads();                         // the previous slices' LDS sums have been read
-                const float* pin = a.partial_base + (long long)n * a.ntiles * NO;
-                const unsigned epoch = (unsigned)(tstep0 + n + 1);          // the batch's Adam step: the tag of its exchange granules
+                const float* pin = a.partial_base + (long long)sl * a.ntiles * NO;
+                const unsigned epoch = (unsigned)(tstep0 + a.d_red + n + 1);          // the batch's Adam step: the tag of its exchange granules
                 if (sub + per_set < NO / 32)
-                    lin_reduce_pair(pin, a.M_base + (long long)n * NO, a.ntiles, lin_smem, sub, sub + per_set, NO, a.comm, epoch, a.status);
-                else lin_reduce<true>(pin, a.M_base + (long long)n * NO, a.ntiles, lin_smem, sub, NO, &a.comm, epoch, a.status);
+                    lin_reduce_pair(pin, a.M_base + (long long)sl * NO, a.ntiles, lin_smem, sub, sub + per_set, NO, a.comm, epoch, a.status);
+                else lin_reduce<true>(pin, a.M_base + (long long)sl * NO, a.ntiles, lin_smem, sub, NO, &a.comm, epoch, a.status);
             }
             lin_wait_vmcnt<0>();                               // every storing wave drains its write-through stores ...
             __syncthreads();                                   // ... before the one lane that signals for the workgroup
@@ -1729,8 +1786,8 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
             racc_w += r1 - r0; racc_r += r2 - r1;
             if (rb == 5) { LIN_PUT(40, racc_w); LIN_PUT(41, racc_r); }
             if (rb == 5 && n < 3) { LIN_PUT(56 + 2 * n, r1); LIN_PUT(57 + 2 * n, r2); }
-            if (t == 0) __hip_atomic_fetch_add(a.cnt_reduce + n, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            { [[maybe_unused]] unsigned long long te = 0; LIN_NOW(te); LIN_PUTMAX(128 + n, te); }
+            if (t == 0) __hip_atomic_fetch_add(a.cnt_reduce + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            { [[maybe_unused]] unsigned long long te = 0; LIN_NOW(te); LIN_PUTMAX(136 + n, te); }      // (64 .. 129: the updater's, up to kLinSlots batches)
         }
     } else {
         // ---- streamers: workgroup sid takes tiles sid, sid + S, ... of every batch, in batch order, through a ring of THREE LDS
@@ -1750,7 +1807,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         if constexpr (!GEN) {
             if (t < 3 * kLinMaxPersist) {
                 const int which = t / kLinMaxPersist, n = t % kLinMaxPersist;
-                tab[t] = n < N ? (which == 0 ? src.x : which == 1 ? src.z1 : src.z2)[n] : nullptr;
+                tab[t] = n < a.n_str ? (which == 0 ? src.x : which == 1 ? src.z1 : src.z2)[n] : nullptr;
             }
         }
         [[maybe_unused]] float* const Amat = reinterpret_cast<float*>(lin_smem + c_off + 16);     // GEN: the dataset's mixing matrix (<= 16 x 16), where the other form keeps its pointer tables
@@ -1762,7 +1819,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         lin_write_vcol(reinterpret_cast<float*>(lin_smem + vr_off), a.T, valid_last, t);
         if (t == 0) { *reinterpret_cast<float*>(lin_smem + c_off) = 0.f; *reinterpret_cast<unsigned*>(lin_smem + c_off + 8) = 0u; }      // the zero word; the draw's ticket counter
         __syncthreads();
-        const int per_batch = sid < a.ntiles ? (a.ntiles - sid + S - 1) / S : 0, items = N * per_batch;
+        const int per_batch = sid < a.ntiles ? (a.ntiles - sid + S - 1) / S : 0, items = a.n_str * per_batch;
         // Wave roles inside a streamer: waves 0 .. 3 (one per SIMD) multiply, waves 4 .. 7 load (LDS-DMA pieces of the tile two ahead,
         // or its Philox draw): with all 8 waves doing both, each wave's ~650 scalar / vector / LDS instructions per tile and its 54
         // MFMAs simply added up (streamers alone 4.7 us per tile; without the MFMAs 3.4, without the LDS-DMA 3.2, without both 2.1:
@@ -1774,13 +1831,17 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         const int npw = (GEN || !loader) ? 0 : share(tl.nz1) + share(tl.nx) + share(tl.np - tl.nz1 - tl.nx);  // this wave's pieces of a tile: its share of each tensor's
         const int sw = wave < (NO / 4 + 63) / 64 ? 1 : 0;                                        // does this wave store a share of an image?
         // item i = tile sid + (i % per_batch) S of batch i / per_batch, in slot i % 3: walked by cursors (a run-time integer division
-        // costs ~40 instructions, and the loop wanted a dozen per tile)
+        // costs ~40 instructions, and the loop wanted a dozen per tile).  n counts the launch's streamed batches (pointer tables, the
+        // draw's step); bs is the batch's workspace slot (image, arrival counter), round the kLinSlots from the launch's first.
         struct Pos {
-            int idx, n, r, slot;
-            __device__ __forceinline__ void advance(int per_batch) { ++idx; slot = slot == 2 ? 0 : slot + 1; if (++r == per_batch) { r = 0; ++n; } }
+            int idx, n, r, slot, bs;
+            __device__ __forceinline__ void advance(int per_batch) {
+                ++idx; slot = slot == 2 ? 0 : slot + 1;
+                if (++r == per_batch) { r = 0; ++n; bs = bs == kLinSlots - 1 ? 0 : bs + 1; }
+            }
         };
         auto pos_tile = [&](const Pos& q) { return sid + q.r * S; };
-        Pos p_cur{0, 0, 0, 0}, p_load{0, 0, 0, 0}, p_sig{0, 0, 0, 0};      // the item being multiplied / the next to load or draw / the next to signal
+        Pos p_cur{0, 0, 0, 0, a.slot_str}, p_load{0, 0, 0, 0, a.slot_str}, p_sig{0, 0, 0, 0, a.slot_str};      // the item being multiplied / the next to load or draw / the next to signal
         LinTileSrc nxt;                                       // the item whose pieces are being issued
         nxt.on = false;
         auto prepare = [&]() __attribute__((always_inline)) {             // the next item in order (p_load), which it advances
@@ -1807,7 +1868,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         [[maybe_unused]] const int gD = DT ? DT : a.D, gL = LT ? LT : a.L, nzb = (gL + gD + 3) / 4;
         [[maybe_unused]] const int nlat = a.T * nzb, xr = (a.T + GT - 1) / GT, npair = nlat / (2 * GT), rem = nlat - 2 * GT * npair;
         [[maybe_unused]] const int gen_rounds = xr + npair + (rem + GT - 1) / GT;
-        [[maybe_unused]] const unsigned step0 = (unsigned)a.step_dev[0];          // (the updater stores the counter at the very end of the launch)
+        [[maybe_unused]] const unsigned step0 = (unsigned)(a.step_dev[0] + a.d_str);     // the first streamed batch's (the updater, d_str batches behind, stores the counter at the very end of the launch)
         // (copies: read through `src` the generator's scalars are re-fetched from the kernel-argument segment inside the loops)
         [[maybe_unused]] int g_kind = 0, g_dd = 0, g_did = 0; [[maybe_unused]] float g_noise = 0.f; [[maybe_unused]] unsigned g_tag = 0;
         if constexpr (GEN) { g_kind = src.kind; g_dd = src.dd; g_did = src.did; g_noise = src.noise_std; g_tag = src.tag; }
@@ -1924,7 +1985,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         };
         unsigned* const my_shard = a.cnt_stream + (b & (kLinShards - 1)) * kLinShardStride;
         auto signal = [&]() {                                 // the next image in order is out (ONE lane, behind every wave's drain + a barrier)
-            if (t == 0) __hip_atomic_fetch_add(my_shard + p_sig.n * kLinShards * kLinShardStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (t == 0) __hip_atomic_fetch_add(my_shard + p_sig.bs * kLinShards * kLinShardStride, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             p_sig.advance(per_batch);
         };
         if constexpr (GEN) {
@@ -1970,7 +2031,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
             lin_barrier();                                     // every wave has read its last operand: the slot turns into scratch
             if constexpr (GEN) { if (t == 0) *ticket = 0u; }   // (nobody takes a ticket before the next iteration's first barrier)
             LIN_NOWQ(s6);
-            lin_tile_combine<NB, true, kLinCW>(acc, slot, a.partial_base + ((long long)n * a.ntiles + tile) * NO, t, wave, lane);
+            lin_tile_combine<NB, true, kLinCW>(acc, slot, a.partial_base + ((long long)p_cur.bs * a.ntiles + tile) * NO, t, wave, lane);
             if (i == 0) {                                      // the launch's first image: out at once (pipeline fill), not two tiles later
                 lin_wait_vmcnt<0>();
                 lin_barrier();
@@ -1992,6 +2053,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         lin_barrier();
         if (items - 2 >= 1) signal();
         if (items - 1 >= 1) signal();
+        { [[maybe_unused]] unsigned long long te = 0; LIN_NOWQ(te); LIN_PUTMAX(49, te); }
     }
 }
 
@@ -2016,8 +2078,10 @@ LinPersistGenKernel lin_persist_four_gen(int which);
 #ifndef VAEK_LIN_FOUR_BLOCK_TU
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 constexpr size_t kLinMaxLds = 160 * 1024;
-// workspace: [cnt_stream: 64 batches x 8 shards x 128 B][cnt_reduce: 64 words][status word, init mark][M slots][partial image slots]
-constexpr size_t kLinCntStreamBytes = (size_t)kLinMaxPersist * kLinShards * kLinShardStride * 4, kLinCntBytes = kLinCntStreamBytes + 1024, kLinHeadBytes = kLinCntBytes + 256;
+// workspace: [cnt_stream: kLinSlots (66) batches x 8 shards x 128 B][cnt_reduce: 66 words][status word, init mark][66 M slots][66 partial
+// image slots] -- the metric's shape: 66 x 228 images of 6 KB = 92.5 MB
+constexpr size_t kLinCntStreamBytes = (size_t)kLinSlots * kLinShards * kLinShardStride * 4, kLinCntBytes = kLinCntStreamBytes + 1024, kLinHeadBytes = kLinCntBytes + 256;
+static_assert(kLinSlots * sizeof(unsigned) <= 1024, "cnt_reduce");
 
 LinPlan lin_plan(const vaek_ctx* c) {
     LinPlan p{};
@@ -2071,7 +2135,7 @@ LinPlan lin_plan(const vaek_ctx* c) {
     // L = 20, 192-row tile); every other linear model on the run-time instantiations of its block count
     p.which_persist = p.NB == 3 ? (D == 12 && L == 20 && p.T == 288 ? 0 : 1) : (D == 20 && L == 20 && p.T == 192 ? 3 : 2);
     p.which_step = D == 12 && L == 20 ? 2 : p.NB - 3;
-    const int slots = p.persist ? kLinMaxPersist : 2;
+    const int slots = p.persist ? kLinSlots : 2;
     p.M_off = kLinHeadBytes;
     p.partial_off = p.M_off + (size_t)slots * p.NO * sizeof(double) + 256;
     p.ws_bytes = (p.partial_off + (size_t)slots * p.ntiles * p.NO * sizeof(float) + 256 + 255) / 256 * 256;
@@ -2160,11 +2224,15 @@ static int lin_train_steps_impl(vaek_ctx* c, float* params, float* grads, float*
         LinPersistGenKernel fng = nullptr;
         if (int rc = gen ? lin_kernel(kLinPersistGen, p.which_persist, &fng) : lin_kernel(kLinPersist, p.which_persist, &fn)) return rc;
         if (int rc = lin_ensure_init(c, w, ws, st)) return rc;
-        for (int s0 = 0; s0 < n_steps; s0 += kLinMaxPersist) {
-            const int n = std::min(kLinMaxPersist, n_steps - s0);
+        for (int j = 0; j < lin_launches(n_steps); ++j) {
+            // launch j streams its 64 batches, reduces from the batch the launch before left it, updates from the two it was left
+            const LinWindows win = lin_windows(n_steps, j);
+            const int s0 = win.stream.first, n = win.stream.count;
             LinArgs a{};
             lin_fill_common(c, a, params, grads, m, v, step_dev, lr);
-            a.persistent = 1; a.n_steps = n;
+            a.persistent = 1; a.n_steps = win.update.count; a.n_red = win.reduce.count; a.n_str = n;
+            a.slot_upd = win.update.first % kLinSlots; a.slot_red = win.reduce.first % kLinSlots; a.slot_str = s0 % kLinSlots;
+            a.d_red = win.reduce.first - win.update.first; a.d_str = s0 - win.update.first;
             a.sets = kLinReduceSets;
             a.has_update = 1; a.n_reduce = p.n_reduce; a.n_stream = p.n_stream;
             if (!(roles & 4)) a.has_update = 0;
