@@ -280,6 +280,30 @@ int vaek_train_steps_update(vaek_ctx* ctx, float* params, float* grads, float* m
 int vaek_train_steps_gen(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
                          int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
                          float lr, void* workspace, void* stream);
+/* N consecutive train steps of a SMALL-BATCH linear VAE as a plain loop inside ONE workgroup (csrc/linear_resident.hip) -- the
+ * loop body of the reference, model.py:221-222, at its own batch size (run.py:14: 100 rows), for the linear VAEs the moment form
+ * above does not cover: two decoders (the sigmoid dataset, sigmoid_vae_padding_expts.sh), a one-decoder model with
+ * L + 2 D + 1 > 64, a batch too small for the moment form.  Arguments and meaning are those of vaek_train_steps_gen: step k of the
+ * call takes *step_dev from t to t + 1 and trains on exactly the batch vaek_make_batch(kind, A, dd, did, pad, var_added,
+ * rows = ctx.batch, row0, seed, step = t, tag) would write (the same Philox counters and csrc/rng_dev.h maps, bit for bit).  On
+ * return, in stream order, params / m / v / *step_dev are what n_steps calls of vaek_train_step on those batches leave (float32
+ * tolerance, as between any two of this library's paths), grads is the LAST step's gradient buffer (vaek_grad_len floats, loss slots
+ * included) and the ring of vaek_set_loss_history holds every step's loss at (t - 1) % cap.  Parameters and both Adam moments are
+ * read from HBM once per launch and written once, at its end; a launch runs at most vaek_train_loop_steps_per_launch() = 1024
+ * steps (a cap that bounds one launch to milliseconds, not a tuned value) and a longer call is several launches on the stream, each
+ * starting from memory alone.  One workgroup: no counters, no waits, hence no status to poll.  Asynchronous, allocates nothing,
+ * capturable into a hipGraph (the RNG step is the device-resident Adam counter); nothing is carried from call to call except the
+ * caller's buffers.
+ * vaek_supports_train_loop_gen: float32, no hidden layers, one OR two decoders, D, L <= 32 (a matrix-core variant exists),
+ * world == 1, 1 <= batch <= 256, force_generic == 0 -- decided once in vaek_ctx_create -- and kind 0, 1 or 2.  The call also needs
+ * dd, did <= 16.  Everything else returns VAEK_ERR_INVALID.  WORKSPACE: where the kernel's LDS has no room for the batch next to
+ * its operand image (large D and L with a large batch) the batch is staged in the workspace, so vaek_workspace_bytes of a
+ * qualifying context may be up to 96 KB larger than before this entry point existed. */
+int vaek_supports_train_loop_gen(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_train_loop_gen(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
+                        int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
+                        float lr, void* workspace, void* stream);
+int vaek_train_loop_steps_per_launch(void);
 /* Convolutional VAE of BASELINE config 5 -- NO reference counterpart (the reference has no convolutional model: its only image
  * code is utils.py:129-133); the layer is specified in DESIGN.md 3.4 and checked against oracle/conv_vae_oracle.py:conv_fwd.
  * 4 x 4 / stride 2 / pad 1 convolution, NHWC float32 tensors, HWIO kernel [4][4][c_in][c_out], bf16 matrix-core products with

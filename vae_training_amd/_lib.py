@@ -78,6 +78,10 @@ SIGNATURES = {
     "vaek_train_steps_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp]),
     "vaek_train_steps_gen": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, C.c_int64, C.c_uint64, C.c_uint32, _i32,
                                        _f32, _vp, _vp]),
+    "vaek_supports_train_loop_gen": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_train_loop_gen": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, C.c_int64, C.c_uint64, C.c_uint32, _i32,
+                                      _f32, _vp, _vp]),
+    "vaek_train_loop_steps_per_launch": (C.c_int, []),
     "vaek_conv2d_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vaek_to_bf16": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "vaek_conv2d_forward_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_size_t)]),

@@ -503,6 +503,8 @@ int vaek_ctx_create(const vaek_config* cfg, vaek_ctx** out) {
     c->lin = lin_plan(c);
     c->ws_lin = off; off = align_up(off + c->lin.ws_bytes, 256);
     c->ws_lwd = off; off = align_up(off + (c->lwd ? lwd_gpart_bytes(c->B, c->D, c->L) : 0), 256);
+    c->resident = resident_supported(c);
+    c->ws_resident = off; off = align_up(off + resident_workspace_bytes(c), 256);
     c->ws_total = off;
     *out = c;
     return VAEK_OK;
@@ -820,6 +822,36 @@ int vaek_train_steps_gen(vaek_ctx* ctx, float* params, float* grads, float* m, f
     if (n_steps == 0) return VAEK_OK;
     return lin_train_steps_gen(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream);
 }
+
+int vaek_supports_train_loop_gen(const vaek_ctx* ctx, int32_t kind, int32_t* yes) {
+    if (!ctx || !yes) { set_error("null argument"); return VAEK_ERR_INVALID; }
+    *yes = ctx->resident && kind >= 0 && kind <= 2 ? 1 : 0;
+    return VAEK_OK;
+}
+
+int vaek_train_loop_gen(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
+                        int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
+                        float lr, void* workspace, void* stream) {
+    ProfBind pb(ctx);
+    if (!ctx || !params || !grads || !m || !v || !step_dev || n_steps < 0) { set_error("vaek_train_loop_gen: invalid argument"); return VAEK_ERR_INVALID; }
+    if (!ctx->resident) {
+        set_error("vaek_train_loop_gen: needs a single-GPU float32 linear VAE (no hidden layers, one or two decoders) with D, L <= 32 and "
+                  "1 <= batch <= 256 (use vaek_train_step_gen)");
+        return VAEK_ERR_INVALID;
+    }
+    int rc = check_ws(ctx, workspace);
+    if (rc) return rc;
+    BatchArgs gen;
+    // (the kernel points the generator at its own batch image: a dummy non-null x / z pair passes the argument check,
+    // which also fences kind to 0 .. 2 and dd, did to <= 16)
+    float* dummy = reinterpret_cast<float*>(workspace);
+    if ((rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, dummy, dummy, dummy, ctx->B, row0, seed, step_dev, 0, nullptr, 0, tag, &gen))) return rc;
+    gen.x = gen.z1 = gen.z2 = nullptr;
+    if (n_steps == 0) return VAEK_OK;
+    return resident_train_loop(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream);
+}
+
+int vaek_train_loop_steps_per_launch(void) { return resident_steps_per_launch(); }
 
 int vaek_train_steps_moment_len(const vaek_ctx* ctx, int64_t* len) {
     if (!ctx || !len) { set_error("null argument"); return VAEK_ERR_INVALID; }

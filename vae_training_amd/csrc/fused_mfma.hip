@@ -25,12 +25,11 @@
 // operands.  Bias / epsilon_p gradients are column sums: accumulated per lane, reduced over the 16
 // lanes of a row with DPP-class shuffles once per kernel.
 #include "comm_dev.h"
+#include "mfma_geom.h"
 #include "rng_dev.h"
 #include "vaek_internal.h"
 
 namespace vaek {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 #ifdef VAEK_STAMPS
 #define VAEK_MSTAMP(i)                                                                       \
@@ -44,41 +43,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 #else
 #define VAEK_MSTAMP(i) do {} while (0)
 #endif
-
-// ---- block geometry of a feature axis of padded length N (<= 32) ----------------------------------
-template <int N>
-struct Axis {
-    static constexpr int NB = (N + 15) / 16;
-    static constexpr bool full(int b) { return N - 16 * b >= 16; }
-    static constexpr int rem(int b) { return N - 16 * b >= 16 ? 16 : N - 16 * b; }
-    static constexpr int nreg(int b) { return full(b) ? 4 : (rem(b) + 3) / 4; }     // registers = k-steps used
-    // feature held by lane group g, register r of block b
-    static __device__ __forceinline__ constexpr int feat(int b, int g, int r) { return full(b) ? 16 * b + 4 * g + r : 16 * b + 4 * r + g; }
-};
-
-template <int DP, int LP, bool SIG>
-struct MGeom {
-    using AD = Axis<DP>;
-    using AL = Axis<LP>;
-    static constexpr int TILE = 256, NW = 4, NSUB = 4;
-    static constexpr int TS = TILE + 2;
-    static constexpr int NB1 = DP * (SIG ? 2 : 1);
-    // A ROW OF ONES behind the samples rows / behind the x rows of the operand image, where the last 16-row block of that
-    // operand has a spare row anyway (LP resp. DP not a multiple of 16): [samples | 1]^T dy and [x | 1]^T dmu then deliver
-    // the bias gradients as one more output row of MFMAs that run regardless -- no per-sample column-sum adds in the
-    // chain, no DPP row reductions and LDS traffic for them on the tail.
-    static constexpr int ONE1 = LP % 16 != 0 ? 1 : 0, ONE2 = DP % 16 != 0 ? 1 : 0;
-    static constexpr int FS = 0, FX = FS + LP + ONE1, FDY = FX + DP + ONE2, FDM = FDY + NB1, NF = FDM + LP;
-    static constexpr int IB1 = (LP + 15) / 16, JB1 = (NB1 + 15) / 16, IB2 = (DP + 15) / 16, JB2 = (LP + 15) / 16;
-    static constexpr int NBLK = IB1 * JB1 + IB2 * JB2;
-    static constexpr int NF_PAD = FDM + JB2 * 16;
-    static constexpr int T_FLOATS = NF_PAD * TS;
-    // cross-wave reduction image: MFMA blocks, then column sums [dy | dys | dmu | gz], then 3 scalars
-    static constexpr int NCS = NB1 + 2 * LP;
-    static constexpr int R_PER_WAVE = NBLK * 256 + NCS + 4;
-    static constexpr int R_FLOATS = NW * R_PER_WAVE;
-    static constexpr int LDS_FLOATS = (T_FLOATS > R_FLOATS ? T_FLOATS : R_FLOATS);
-};
 
 // SINGLE: the one-workgroup (batch <= 256 rows) form that finalizes itself -- a separate instantiation, so that the
 // metric's multi-workgroup kernel is compiled exactly as if this form did not exist (folded into one kernel behind a
@@ -661,16 +625,9 @@ struct MfmaVariant { int dp, lp, sig, exact; MfmaKernel fn, fn_single; size_t ld
      fused_linear_mfma_kernel<DP, LP, (SIG) != 0, (EXACT) != 0, true>, sizeof(float) * MGeom<DP, LP, (SIG) != 0>::LDS_FLOATS}
 
 static const MfmaVariant kMfmaVariants[] = {
-    // exact shapes of seed_linpadding_expts.sh (the metric's configuration first)
-    VAEK_MFMA(12, 20, 0, 1),
-#ifndef VAEK_FUSED_ONLY_M
-    VAEK_MFMA(20, 20, 0, 1), VAEK_MFMA(20, 10, 0, 1),
-    // zero-padded coverage of every other D, L <= 32
-    VAEK_MFMA(16, 16, 0, 0), VAEK_MFMA(32, 32, 0, 0), VAEK_MFMA(12, 4, 0, 0),
-    // sigmoid dataset (two decoders): sigmoid_vae_padding_expts.sh shapes
-    VAEK_MFMA(8, 8, 1, 0), VAEK_MFMA(12, 12, 1, 0), VAEK_MFMA(16, 16, 1, 0), VAEK_MFMA(20, 8, 1, 0), VAEK_MFMA(24, 16, 1, 0),
-    VAEK_MFMA(28, 24, 1, 1), VAEK_MFMA(32, 32, 1, 0),
-#endif
+#define VAEK_MFMA_ROW(DP, LP, SIG, EXACT) VAEK_MFMA(DP, LP, SIG, EXACT),
+    VAEK_MFMA_SHAPES(VAEK_MFMA_ROW)
+#undef VAEK_MFMA_ROW
 };
 
 static const MfmaVariant* pick_mfma(const vaek_ctx* c) {

@@ -1,0 +1,58 @@
+// Block geometry of the matrix-core linear-VAE kernels (fused_mfma.hip, linear_resident.hip) and the table of shapes they are
+// instantiated for.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace vaek {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+// ---- block geometry of a feature axis of padded length N (<= 32) ----------------------------------
+template <int N>
+struct Axis {
+    static constexpr int NB = (N + 15) / 16;
+    static constexpr bool full(int b) { return N - 16 * b >= 16; }
+    static constexpr int rem(int b) { return N - 16 * b >= 16 ? 16 : N - 16 * b; }
+    static constexpr int nreg(int b) { return full(b) ? 4 : (rem(b) + 3) / 4; }     // registers = k-steps used
+    // feature held by lane group g, register r of block b
+    static __device__ __forceinline__ constexpr int feat(int b, int g, int r) { return full(b) ? 16 * b + 4 * g + r : 16 * b + 4 * r + g; }
+};
+
+template <int DP, int LP, bool SIG>
+struct MGeom {
+    using AD = Axis<DP>;
+    using AL = Axis<LP>;
+    static constexpr int TILE = 256, NW = 4, NSUB = 4;
+    static constexpr int TS = TILE + 2;
+    static constexpr int NB1 = DP * (SIG ? 2 : 1);
+    // A ROW OF ONES behind the samples rows / behind the x rows of the operand image, where the last 16-row block of that
+    // operand has a spare row anyway (LP resp. DP not a multiple of 16): [samples | 1]^T dy and [x | 1]^T dmu then deliver
+    // the bias gradients as one more output row of MFMAs that run regardless -- no per-sample column-sum adds in the
+    // chain, no DPP row reductions and LDS traffic for them on the tail.
+    static constexpr int ONE1 = LP % 16 != 0 ? 1 : 0, ONE2 = DP % 16 != 0 ? 1 : 0;
+    static constexpr int FS = 0, FX = FS + LP + ONE1, FDY = FX + DP + ONE2, FDM = FDY + NB1, NF = FDM + LP;
+    static constexpr int IB1 = (LP + 15) / 16, JB1 = (NB1 + 15) / 16, IB2 = (DP + 15) / 16, JB2 = (LP + 15) / 16;
+    static constexpr int NBLK = IB1 * JB1 + IB2 * JB2;
+    static constexpr int NF_PAD = FDM + JB2 * 16;
+    static constexpr int T_FLOATS = NF_PAD * TS;
+    // cross-wave reduction image: MFMA blocks, then column sums [dy | dys | dmu | gz], then 3 scalars
+    static constexpr int NCS = NB1 + 2 * LP;
+    static constexpr int R_PER_WAVE = NBLK * 256 + NCS + 4;
+    static constexpr int R_FLOATS = NW * R_PER_WAVE;
+    static constexpr int LDS_FLOATS = (T_FLOATS > R_FLOATS ? T_FLOATS : R_FLOATS);
+};
+
+// (DP, LP, SIG, EXACT) of every instantiation; a context takes the smallest that holds it (EXACT: only its own D, L)
+#ifndef VAEK_FUSED_ONLY_M
+#define VAEK_MFMA_SHAPES(X)                                                                          \
+    /* exact shapes of seed_linpadding_expts.sh (the metric's configuration first) */               \
+    X(12, 20, 0, 1) X(20, 20, 0, 1) X(20, 10, 0, 1)                                                  \
+    /* zero-padded coverage of every other D, L <= 32 */                                             \
+    X(16, 16, 0, 0) X(32, 32, 0, 0) X(12, 4, 0, 0)                                                   \
+    /* sigmoid dataset (two decoders): sigmoid_vae_padding_expts.sh shapes */                        \
+    X(8, 8, 1, 0) X(12, 12, 1, 0) X(16, 16, 1, 0) X(20, 8, 1, 0) X(24, 16, 1, 0) X(28, 24, 1, 1) X(32, 32, 1, 0)
+#else
+#define VAEK_MFMA_SHAPES(X) X(12, 20, 0, 1)
+#endif
+
+}  // namespace vaek

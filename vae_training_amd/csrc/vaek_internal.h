@@ -126,8 +126,9 @@ struct vaek_ctx {
     int S, rows_per_split, Se, rows_per_esplit;
     bool fused;                      // a whole-network path is available and selected (fused_small / fused_mfma / fused_mlp1 / fused_mlp3)
     bool mlp3 = false;               // ... and it is fused_mlp3.hip's (three hidden layers both ways, small batch)
+    bool resident = false;           // vaek_train_loop_gen covers this context (linear_resident.hip: resident_supported)
     // workspace layout (bytes)
-    size_t ws_samples, ws_dsamp, ws_gbuf0, ws_gbuf1, ws_slabs, ws_epart, ws_epart_blk, ws_rpart, ws_eblk, ws_fused, ws_mlp3, ws_wb16, ws_sk16, ws_skpart, ws_lin, ws_lwd, ws_total;
+    size_t ws_samples, ws_dsamp, ws_gbuf0, ws_gbuf1, ws_slabs, ws_epart, ws_epart_blk, ws_rpart, ws_eblk, ws_fused, ws_mlp3, ws_wb16, ws_sk16, ws_skpart, ws_lin, ws_lwd, ws_resident, ws_total;
     bool lwd = false; int lwd_rb = 0;           // wide linear decoder: fused forward / ELBO / backward (linear_wide.hip), rows per row block
     int max_width;
     int n_cu;
@@ -375,6 +376,13 @@ int lin_moments(vaek_ctx* c, const float* x, const float* z1, const float* z2, d
 int lin_update(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const double* M_in, float lr, hipStream_t st);
 struct BatchArgs;
 int lin_train_steps_gen(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen, int n_steps,
+                        float lr, void* ws, hipStream_t st);
+
+// ---- linear_resident.hip: N steps of a small-batch linear VAE (one or two decoders) as a loop inside one workgroup -------------
+bool resident_supported(const vaek_ctx* c);       // float32, no hidden layers, D, L <= 32, world 1, 1 <= batch <= 256, not force_generic
+size_t resident_workspace_bytes(const vaek_ctx* c);   // the region at ws_resident: a batch image where LDS has no room for it
+int resident_steps_per_launch();
+int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen, int n_steps,
                         float lr, void* ws, hipStream_t st);
 
 // ---- rng.hip ------------------------------------------------------------------------------

@@ -155,6 +155,23 @@ class Engine:
                                                  int(dd), int(did), int(pad), float(var_added), int(row0), int(seed) & (2**64 - 1), int(tag),
                                                  int(n_steps), float(lr), _ptr(self.workspace), _stream()))
 
+    def supports_train_loop_gen(self, kind):
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_train_loop_gen(self.h, int(kind), C.byref(f)))
+        return bool(f.value)
+
+    @property
+    def train_loop_steps_per_launch(self):
+        return int(self.lib.vaek_train_loop_steps_per_launch())
+
+    def train_loop_gen(self, params, grads, m, v, step_dev, n_steps, lr, kind, A, dd, did, pad, var_added, seed, tag=0, row0=0):
+        """n_steps consecutive train steps as a loop INSIDE one workgroup (vaek_train_loop_gen): small-batch linear VAEs with one or
+        two decoders, parameters and Adam state on chip between steps, the batch of the step that takes the Adam counter from t
+        to t + 1 bit for bit the one make_batch(..., step = t) would write.  Asynchronous; capturable into a hipGraph."""
+        _lib.check(self.lib.vaek_train_loop_gen(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), int(kind), _ptr(A),
+                                                int(dd), int(did), int(pad), float(var_added), int(row0), int(seed) & (2**64 - 1), int(tag),
+                                                int(n_steps), float(lr), _ptr(self.workspace), _stream()))
+
     def plan_train_steps(self, params, grads, m, v, step_dev, batches, lr):
         """The same call with its arguments marshalled once: returns a function that issues vaek_train_steps on these buffers
         again (the pointer arrays, not the data, are frozen) -- for loops that repeat a group of steps, where building three

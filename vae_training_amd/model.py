@@ -243,6 +243,8 @@ class GenerativeModel(Model):
         from .trainer import GraphLoop
         loop = GraphLoop(self)
         self._graph_loop = loop
+        if getattr(self, "rank", 0) == 0:
+            print(f"Train loop: {loop.describe()}")
         events = sorted(set(list(range(0, self.num_batches, self.n_print)) + list(range(0, self.num_batches, self.n_plot))
                             + [self.num_batches - 1]))
         pos = 0

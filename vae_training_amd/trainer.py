@@ -21,14 +21,28 @@ vaek_train_steps_gen, the headline kernel of bench.py (csrc/linear_moments.hip):
 step's batch drawn INSIDE the launch by the workgroups that multiply it -- the same Philox counters as above, so the same
 batches bit for bit, but no batch buffer, no hipGraph and nothing per step on the host: one library call per run of steps
 between two events of the reference's schedule (stats every 5 000, plot + save every 50 000: model.py:213-220).  The losses land
-in the same device ring.  Losses and parameters agree with the per-sample loop to summation order (tests/test_gpu_loop.py)."""
+in the same device ring.  Losses and parameters agree with the per-sample loop to summation order (tests/test_gpu_loop.py).
+
+`resident` (default: RESIDENT_DEFAULT where the model has no moments path and the engine supports it -- small-batch linear VAEs the
+moment form does not cover: the two-decoder models of the sigmoid dataset above all; `moments=False` on a model that HAS a moments
+path still means the hipGraph loop, resident=True asks for this one there too): the steps go through vaek_train_loop_gen
+(csrc/linear_resident.hip), a plain loop of steps inside ONE workgroup with parameters and Adam state on chip and the batches drawn
+in the kernel -- the same Philox counters again.  Like the moments path it is one library call per run of steps, no batch buffer and
+no hipGraph; there is one workgroup, so there is nothing to wait for and check() has nothing to poll.  `moments` keeps priority:
+every model that takes it today still does."""
 from __future__ import annotations
 
 import torch
 
 
+# What GraphLoop(resident=None) resolves to where the engine supports the resident loop and the model has no moments path.  The gate
+# is tools/time_resident.py: True only once the resident loop's slowest repeat has beaten the hipGraph loop's fastest on all seven
+# shapes.  That table has NOT been measured yet (DESIGN 3.8), so the default is off: resident=True asks for the loop explicitly.
+RESIDENT_DEFAULT = False
+
+
 class GraphLoop:
-    def __init__(self, vae_model, steps_per_graph=200, seed=None, loss_capacity=1 << 20, pipeline=True, moments=None):
+    def __init__(self, vae_model, steps_per_graph=200, seed=None, loss_capacity=1 << 20, pipeline=True, moments=None, resident=None):
         m = vae_model
         self.m = m
         ds = m.dataset
@@ -47,9 +61,16 @@ class GraphLoop:
         if moments and not can:
             raise RuntimeError("GraphLoop(moments=True): vaek_train_steps_gen does not cover this model / dataset")
         self.moments = can if moments is None else bool(moments)
+        can_res = not self.moments and self.eng.supports_train_loop_gen(self.kind)
+        if resident and not can_res:
+            raise RuntimeError("GraphLoop(resident=True): " + ("the moments path has priority" if self.moments else
+                                                               "vaek_train_loop_gen does not cover this model / dataset"))
+        # by default only where there is no moments path to take: a caller who switches an available moments path off
+        # (moments=False) has always been asking for the per-sample hipGraph loop, and still gets it
+        self.resident = (can_res and not can and RESIDENT_DEFAULT) if resident is None else bool(resident)
         self.row0 = self.eng.rank * self.B           # ranks draw disjoint rows of the global batch
         self.seed = (ds.key[0] ^ ds.key[1] ^ m.key[1]) if seed is None else seed
-        self.pipeline = bool(pipeline) and not self.moments
+        self.pipeline = bool(pipeline) and not self.moments and not self.resident
         self.G = int(steps_per_graph)
         if self.pipeline and self.G % 2:
             self.G += 1                              # two batch buffers: a replay must start on the parity it was captured on
@@ -59,7 +80,7 @@ class GraphLoop:
             return (torch.empty(self.B, self.eng.D, dtype=torch.float32, device=dev),
                     torch.empty(self.B, self.eng.L, dtype=torch.float32, device=dev),
                     torch.empty(self.B, self.eng.D, dtype=torch.float32, device=dev))
-        self.bufs = [] if self.moments else [bufs() for _ in range(2 if self.pipeline else 1)]
+        self.bufs = [] if self.moments or self.resident else [bufs() for _ in range(2 if self.pipeline else 1)]
         self.loss_ring = torch.zeros(loss_capacity, dtype=torch.float32, device=dev)
         self.eng.set_loss_history(self.loss_ring)
         self.graph = None
@@ -111,12 +132,13 @@ class GraphLoop:
 
     def run(self, n_steps):
         """Exactly n_steps train steps."""
-        if self.moments:
+        if self.moments or self.resident:
             if n_steps > 0:
                 st = self.m.optimizer.state
-                self.eng.train_steps_gen(self.m.model.flat, st.grads, st.m, st.v, st.step_dev, n_steps,
-                                         self.m.optimizer.optimizer_def.learning_rate, self.kind, self.A, self.dd, self.did, self.pad,
-                                         self.var, self.seed, tag=0, row0=self.row0)
+                call = self.eng.train_steps_gen if self.moments else self.eng.train_loop_gen
+                call(self.m.model.flat, st.grads, st.m, st.v, st.step_dev, n_steps,
+                     self.m.optimizer.optimizer_def.learning_rate, self.kind, self.A, self.dd, self.did, self.pad,
+                     self.var, self.seed, tag=0, row0=self.row0)
                 st.step += n_steps
             return
         done = 0
@@ -133,6 +155,14 @@ class GraphLoop:
                 done += self.G
         for _ in range(n_steps - done):
             self._one()
+
+    def describe(self):
+        """One line for run.py: which of the three loops this is."""
+        if self.moments:
+            return "persistent moment launches (vaek_train_steps_gen)"
+        if self.resident:
+            return f"resident linear kernel, {self.eng.train_loop_steps_per_launch} steps per launch"
+        return f"hipGraph of {self.G} steps" + (", next batch drawn inside the step's launch" if self.pipeline else "")
 
     def check(self):
         """Synchronous.  The persistent launches of the moments path wait for each other's hand-offs with bounded spins: one that
