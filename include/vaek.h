@@ -304,6 +304,48 @@ int vaek_train_loop_gen(vaek_ctx* ctx, float* params, float* grads, float* m, fl
                         int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
                         float lr, void* workspace, void* stream);
 int vaek_train_loop_steps_per_launch(void);
+/* The same loop for N INDEPENDENT models of the context's shape in one launch: workgroup r trains replica r (a sweep over dataset
+ * seeds, learning rates, initialisations -- the reference's experiment scripts are all sweeps -- where one vaek_train_loop_gen
+ * launch keeps 1 of the MI355X's 256 CUs busy).  The loop has no cross-workgroup state, so the replica form adds no counter, no wait
+ * and no atomic: nothing to poll.  Replica r owns
+ *   params + r * state_stride, m + r * state_stride, v + r * state_stride   (vaek_param_count floats each; state_stride >= P),
+ *   grads + r * grads_stride                                                (vaek_grad_len floats; grads_stride >= grad_len),
+ *   step_dev[r], seeds[r], lrs[r] (lrs == NULL: the scalar `lr` for every replica),
+ *   A + r * a_stride (a_stride == 0: one matrix shared by all; A may be NULL for kind 2),
+ *   loss_hist + r * loss_hist_cap: the loss of Adam step t at [(t - 1) % loss_hist_cap] (loss_hist == NULL: no ring).
+ * Every array is a caller-owned DEVICE buffer (seeds, lrs and A are only read); floats between two replicas where a stride exceeds
+ * the length are not touched; strides need no alignment beyond a float's.  kind, dd, did, pad, var_added, row0, tag, n_steps and
+ * the context (shape, batch, epsilon) are shared by the launch.
+ * DEFINING PROPERTY: for every r, what the call leaves in replica r's params, m, v, grads, step_dev[r] and ring is BITWISE what
+ * vaek_train_loop_gen leaves when called alone on those buffers with seed = seeds[r], lr = lrs[r], replica r's A and the same
+ * shared arguments (the ring of vaek_set_loss_history standing in for replica r's): the same code on the same inputs.
+ * The ring of vaek_set_loss_history is NOT written by this call.  Asynchronous on `stream`, allocates nothing, does not
+ * synchronise, capturable into a hipGraph; more than vaek_train_loop_steps_per_launch() steps are several launches, each starting
+ * from HBM alone.  Covers exactly the contexts and kinds vaek_supports_train_loop_gen accepts.
+ * vaek_train_loop_max_replicas() = 1024: four rounds of 256 workgroups on 256 CUs -- a cap that bounds the length of one launch on
+ * a shared machine, not a tuned value.  n above the CU count is legal: workgroups are independent, the extra ones queue.
+ * WORKSPACE: the call's OWN buffer of vaek_train_loop_replicas_workspace_bytes(ctx, n) bytes, 16-byte aligned: n times the staged
+ * batch where the kernel's LDS has no room for it, else 0 bytes and `workspace` may be NULL.  It is NOT the buffer of
+ * vaek_workspace_bytes, which this entry point neither needs nor changes.
+ * VAEK_ERR_INVALID (with a message): n < 1 or n > the cap, state_stride < P, grads_stride < grad_len, NULL seeds, a_stride < 0, a
+ * ring with loss_hist_cap < 1, a missing or misaligned workspace where one is needed, dd or did > 16, kind outside 0 .. 2, an
+ * unsupported context, a wrong struct_size.  n_steps == 0 returns VAEK_OK and touches nothing. */
+typedef struct vaek_replicas {
+    int32_t struct_size;                  /* = sizeof(vaek_replicas), ABI guard                    */
+    int32_t n;                            /* replicas = workgroups of the launch                   */
+    int64_t state_stride;                 /* floats between two replicas' params (and m, and v)    */
+    int64_t grads_stride;                 /* floats between two replicas' grads                    */
+    const uint64_t* seeds;                /* device [n]: RNG seed per replica                      */
+    const float* lrs;                     /* device [n] or NULL: learning rate per replica         */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared            */
+    float* loss_hist;                     /* device [n][loss_hist_cap] or NULL                     */
+    int64_t loss_hist_cap;
+} vaek_replicas;
+int vaek_train_loop_max_replicas(void);
+int vaek_train_loop_replicas_workspace_bytes(const vaek_ctx* ctx, int32_t n, size_t* bytes);
+int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                 const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                                 float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream);
 /* Convolutional VAE of BASELINE config 5 -- NO reference counterpart (the reference has no convolutional model: its only image
  * code is utils.py:129-133); the layer is specified in DESIGN.md 3.4 and checked against oracle/conv_vae_oracle.py:conv_fwd.
  * 4 x 4 / stride 2 / pad 1 convolution, NHWC float32 tensors, HWIO kernel [4][4][c_in][c_out], bf16 matrix-core products with

@@ -853,6 +853,67 @@ int vaek_train_loop_gen(vaek_ctx* ctx, float* params, float* grads, float* m, fl
 
 int vaek_train_loop_steps_per_launch(void) { return resident_steps_per_launch(); }
 
+int vaek_train_loop_max_replicas(void) { return resident_max_replicas(); }
+
+int vaek_train_loop_replicas_workspace_bytes(const vaek_ctx* ctx, int32_t n, size_t* bytes) {
+    if (!ctx || !bytes || n < 1 || n > resident_max_replicas()) {
+        set_error("vaek_train_loop_replicas_workspace_bytes: null argument, or n outside 1 .. %d", resident_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    *bytes = ctx->resident ? resident_replicas_workspace_bytes(ctx, n) : 0;
+    return VAEK_OK;
+}
+
+int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                 const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                                 float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream) {
+    ProfBind pb(ctx);
+    if (!ctx || !params || !grads || !m || !v || !step_dev || !rep || n_steps < 0) {
+        set_error("vaek_train_loop_gen_replicas: invalid argument");
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->struct_size != (int32_t)sizeof(vaek_replicas)) {
+        set_error("vaek_train_loop_gen_replicas: vaek_replicas.struct_size %d != %d (header / library mismatch)", rep->struct_size, (int)sizeof(vaek_replicas));
+        return VAEK_ERR_INVALID;
+    }
+    if (!ctx->resident) {
+        set_error("vaek_train_loop_gen_replicas: needs a context vaek_train_loop_gen covers (see vaek_supports_train_loop_gen)");
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->n < 1 || rep->n > resident_max_replicas()) {
+        set_error("vaek_train_loop_gen_replicas: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", rep->n, resident_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->state_stride < ctx->P || rep->grads_stride < ctx->P + kExtra) {
+        set_error("vaek_train_loop_gen_replicas: state_stride %lld < P = %lld or grads_stride %lld < grad_len = %lld", (long long)rep->state_stride,
+                  (long long)ctx->P, (long long)rep->grads_stride, (long long)(ctx->P + kExtra));
+        return VAEK_ERR_INVALID;
+    }
+    if (!rep->seeds) { set_error("vaek_train_loop_gen_replicas: seeds is NULL"); return VAEK_ERR_INVALID; }
+    if (rep->a_stride < 0) { set_error("vaek_train_loop_gen_replicas: a_stride %lld < 0", (long long)rep->a_stride); return VAEK_ERR_INVALID; }
+    if (rep->loss_hist && rep->loss_hist_cap < 1) {
+        set_error("vaek_train_loop_gen_replicas: loss_hist given with loss_hist_cap %lld < 1", (long long)rep->loss_hist_cap);
+        return VAEK_ERR_INVALID;
+    }
+    const size_t ws_bytes = resident_replicas_workspace_bytes(ctx, rep->n);
+    if (ws_bytes && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15))) {
+        set_error("vaek_train_loop_gen_replicas: this context stages its batches in memory: workspace must be a 16-byte aligned device "
+                  "pointer of vaek_train_loop_replicas_workspace_bytes() = %zu bytes", ws_bytes);
+        return VAEK_ERR_INVALID;
+    }
+    BatchArgs gen;
+    // (as vaek_train_loop_gen: the kernel points the generator at its own batch image, and puts seeds[r] in place of the seed; the
+    // dummy non-null x / z pair passes the argument check, which also fences kind to 0 .. 2 and dd, did to <= 16)
+    float* dummy = params;
+    int rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, dummy, dummy, dummy, ctx->B, row0, 0, step_dev, 0, nullptr, 0, tag, &gen);
+    if (rc) return rc;
+    gen.x = gen.z1 = gen.z2 = nullptr;
+    if (n_steps == 0) return VAEK_OK;
+    return resident_train_loop_replicas(ctx, params, grads, m, v, step_dev, gen, rep->n, rep->state_stride, rep->grads_stride,
+                                        reinterpret_cast<const unsigned long long*>(rep->seeds), rep->lrs, rep->a_stride, rep->loss_hist,
+                                        rep->loss_hist_cap, n_steps, lr, workspace, (hipStream_t)stream);
+}
+
 int vaek_train_steps_moment_len(const vaek_ctx* ctx, int64_t* len) {
     if (!ctx || !len) { set_error("null argument"); return VAEK_ERR_INVALID; }
     *len = ctx->lin.NO;

@@ -23,6 +23,11 @@
 // registers (pk / mk / vk) or LDS (the parameter image); params / m / v / *step_dev are loaded before the loop and stored
 // after it; grads and the ring are stored only.  The one thing read back from global memory is a batch staged in the
 // workspace: per-lane addresses (vector loads) through plain pointers, behind __threadfence_block() + __syncthreads().
+//
+// THE REPLICA FORM (vaek_train_loop_gen_replicas).  Because the loop has no cross-workgroup state, N independent models of one
+// shape are N workgroups of one launch: workgroup r runs this very loop on replica r's slices of the caller's buffers, with its
+// own seed, learning rate, dataset matrix, loss ring and (where the batch is staged in memory) stage region.  The rule above is
+// kept: the per-replica tables are never written by the launch, and step_dev[r] is read before the loop and stored after it.
 #include "mfma_geom.h"
 #include "rng_dev.h"
 #include "vaek_internal.h"
@@ -57,8 +62,37 @@ struct RGeom {
     static constexpr int BASE_FLOATS = T_ALLOC + P_ALLOC;         // ... and behind that the batch image, where it fits
 };
 
-template <int DP, int LP, bool SIG, bool EXACT>
-__global__ __launch_bounds__(256) void linear_resident_kernel(const ResidentArgs a) {
+// What the replica form adds to ResidentArgs (vaek_train_loop_gen_replicas): workgroup r trains replica r.  The tables are never
+// written by the launch, so the uniform-address (scalar) loads of seeds[r] / lrs[r] below keep the rule of this file.
+struct ReplicaArgs {
+    long long state_stride, grads_stride, a_stride, stage_stride;      // floats between two replicas' params / m / v, grads, A, stage
+    const unsigned long long* seeds;                                   // [n]
+    const float* lrs;                                                  // [n], or nullptr: ResidentArgs::lr for every replica
+};
+
+// Replica r's launch arguments: its slices of the caller's buffers, its seed, its learning rate.  Every replica's slice is disjoint
+// from every other's (the host checks the strides against the lengths), and a workgroup reads and writes only its own.
+__device__ __forceinline__ const ResidentArgs& replica_slice(const ResidentArgs& a) { return a; }       // the grid-1 form: as given
+__device__ __forceinline__ ResidentArgs replica_slice(const ResidentArgs& a0, const ReplicaArgs& rp) {
+    const long long r = blockIdx.x;
+    ResidentArgs a = a0;
+    a.params += r * rp.state_stride; a.m += r * rp.state_stride; a.v += r * rp.state_stride;
+    a.grads += r * rp.grads_stride;
+    a.step_dev += r;
+    if (a.stage) a.stage += r * rp.stage_stride;
+    if (a.loss_hist) a.loss_hist += r * a.loss_hist_cap;
+    if (a.gen.A) a.gen.A += r * rp.a_stride;
+    a.gen.seed = rp.seeds[r];
+    if (rp.lrs) a.lr = rp.lrs[r];
+    return a;
+}
+
+// RP is empty (vaek_train_loop_gen: one model, grid 1) or ReplicaArgs (vaek_train_loop_gen_replicas: N independent models of one
+// shape, workgroup r training replica r).  The body has no cross-workgroup state -- no counter, no wait, no atomic -- so the
+// replicas share nothing but the code and the launch-wide arguments.
+template <int DP, int LP, bool SIG, bool EXACT, typename... RP>
+__global__ __launch_bounds__(256) void linear_resident_kernel(const ResidentArgs a0, const RP... rp) {
+    const ResidentArgs& a = replica_slice(a0, rp...);
     using G = MGeom<DP, LP, SIG>;
     using RG = RGeom<DP, LP, SIG>;
     using AD = typename G::AD;
@@ -528,9 +562,11 @@ __global__ __launch_bounds__(256) void linear_resident_kernel(const ResidentArgs
 
 // ---- variant table: the shapes of fused_mfma.hip -----------------------------------------------------
 typedef void (*ResidentKernel)(const ResidentArgs);
-struct ResidentVariant { int dp, lp, sig, exact; ResidentKernel fn; size_t base_bytes; };
+typedef void (*ResidentReplicasKernel)(const ResidentArgs, const ReplicaArgs);
+struct ResidentVariant { int dp, lp, sig, exact; ResidentKernel fn; size_t base_bytes; ResidentReplicasKernel fn_replicas; };
 #define VAEK_RESIDENT_ROW(DP, LP, SIG, EXACT) \
-    {DP, LP, SIG, EXACT, linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0>, sizeof(float) * RGeom<DP, LP, (SIG) != 0>::BASE_FLOATS},
+    {DP, LP, SIG, EXACT, linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0>, sizeof(float) * RGeom<DP, LP, (SIG) != 0>::BASE_FLOATS, \
+     linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0, ReplicaArgs>},
 static const ResidentVariant kResidentVariants[] = {VAEK_MFMA_SHAPES(VAEK_RESIDENT_ROW)};
 #undef VAEK_RESIDENT_ROW
 
@@ -588,6 +624,52 @@ int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, floa
         a.n_steps = left < kResidentMaxSteps ? left : kResidentMaxSteps;
         ProfScope ps("linear_resident", st);
         launch_k(ps, var->fn, dim3(1), dim3(256), lds, st, a);
+        VAEK_HIP_CHECK(hipGetLastError());
+    }
+    return VAEK_OK;
+}
+
+// ---- the replica form: vaek_train_loop_gen_replicas -------------------------------------------------------------------------
+// 1024 replicas = 4 rounds of 256 workgroups on the MI355X's 256 CUs: a cap that bounds the length of one launch on a shared
+// machine, not a tuned value.  More replicas than CUs is legal: the workgroups are independent, the extra ones queue.
+constexpr int kResidentMaxReplicas = 1024;
+int resident_max_replicas() { return kResidentMaxReplicas; }
+
+// bytes of the replica call's OWN workspace (not a region of vaek_workspace_bytes): one batch image per replica where the variant
+// stages the batch in memory, nothing where it fits LDS.  stage_floats is a multiple of 4, so every replica's image keeps the
+// 16-byte alignment of the base.
+size_t resident_replicas_workspace_bytes(const vaek_ctx* c, int n) { return (size_t)n * resident_workspace_bytes(c); }
+
+int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
+                                 int n, long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
+                                 long long a_stride, float* loss_hist, long long loss_hist_cap, int n_steps, float lr, void* ws,
+                                 hipStream_t st) {
+    const ResidentVariant* var = c->resident ? pick_resident(c) : nullptr;
+    if (!var) { set_error("resident train loop not available for this configuration"); return VAEK_ERR_INVALID; }
+    const bool in_lds = stage_in_lds(c, var);
+    const size_t lds = var->base_bytes + (in_lds ? stage_bytes(c) : 0);
+    static thread_local PerDeviceOnce attr_set[sizeof(kResidentVariants) / sizeof(kResidentVariants[0])];
+    PerDeviceOnce& once = attr_set[var - kResidentVariants];
+    if (lds > 64 * 1024 && once.need()) {
+        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)var->fn_replicas, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+        once.mark();
+    }
+    ResidentArgs a{};
+    a.params = params; a.grads = grads; a.m = m; a.v = v; a.step_dev = step_dev;
+    a.stage = in_lds ? nullptr : static_cast<float*>(ws);
+    a.B = c->B; a.D = c->D; a.L = c->L; a.P = (int)c->P; a.off_epsp = (int)c->off_epsp; a.off_eps = (int)c->off_eps;
+    a.inv_bt = (float)(1.0 / (double)c->Bt); a.eps_cli = c->cfg.eps_cli; a.lr = lr;
+    a.rows_over_bt = (float)((double)c->B / (double)c->Bt); a.rows = (float)c->B;
+    a.loss_hist = loss_hist; a.loss_hist_cap = loss_hist ? loss_hist_cap : 0;      // the caller's rings, never the context's
+    a.gen = gen;
+    ReplicaArgs rp{};
+    rp.state_stride = state_stride; rp.grads_stride = grads_stride; rp.a_stride = a_stride;
+    rp.stage_stride = stage_floats(c->B, c->D, c->L);
+    rp.seeds = seeds; rp.lrs = lrs;
+    for (int left = n_steps; left > 0; left -= kResidentMaxSteps) {
+        a.n_steps = left < kResidentMaxSteps ? left : kResidentMaxSteps;
+        ProfScope ps("linear_resident_replicas", st);
+        launch_k(ps, var->fn_replicas, dim3((unsigned)n), dim3(256), lds, st, a, rp);
         VAEK_HIP_CHECK(hipGetLastError());
     }
     return VAEK_OK;

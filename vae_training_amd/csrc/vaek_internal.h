@@ -384,6 +384,14 @@ size_t resident_workspace_bytes(const vaek_ctx* c);   // the region at ws_reside
 int resident_steps_per_launch();
 int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen, int n_steps,
                         float lr, void* ws, hipStream_t st);
+// the same loop for n independent models of the context's shape, one workgroup each (vaek_train_loop_gen_replicas); `ws` is the
+// call's own workspace of resident_replicas_workspace_bytes(c, n) bytes, not the context's
+int resident_max_replicas();
+size_t resident_replicas_workspace_bytes(const vaek_ctx* c, int n);
+int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
+                                 int n, long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
+                                 long long a_stride, float* loss_hist, long long loss_hist_cap, int n_steps, float lr, void* ws,
+                                 hipStream_t st);
 
 // ---- rng.hip ------------------------------------------------------------------------------
 // validates the arguments of vaek_make_batch* and fills `out`

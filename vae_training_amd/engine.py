@@ -172,6 +172,40 @@ class Engine:
                                                 int(dd), int(did), int(pad), float(var_added), int(row0), int(seed) & (2**64 - 1), int(tag),
                                                 int(n_steps), float(lr), _ptr(self.workspace), _stream()))
 
+    @property
+    def train_loop_max_replicas(self):
+        return int(self.lib.vaek_train_loop_max_replicas())
+
+    def train_loop_replicas_workspace(self, n):
+        """Bytes of the workspace Engine.train_loop_gen_replicas needs for n replicas (its own buffer, not self.workspace): n staged
+        batches where the kernel's LDS has no room for one, else 0."""
+        b = C.c_size_t()
+        _lib.check(self.lib.vaek_train_loop_replicas_workspace_bytes(self.h, int(n), C.byref(b)))
+        return int(b.value)
+
+    def train_loop_gen_replicas(self, params, grads, m, v, step_dev, n_steps, lr, kind, A, dd, did, pad, var_added, seeds, lrs=None,
+                                a_stride=0, loss_hist=None, workspace=None, tag=0, row0=0, n=None, state_stride=None, grads_stride=None,
+                                loss_hist_cap=None):
+        """n_steps train steps of EACH of n independent models of this engine's shape in one launch, workgroup r training replica r
+        (vaek_train_loop_gen_replicas).  params / m / v: [n, state_stride], grads: [n, grads_stride], step_dev: int32 [n], seeds:
+        int64 [n] (the bits of the uint64 seeds), lrs: float32 [n] or None (then `lr` for all), A: replica r's at A + r * a_stride
+        floats (0: shared), loss_hist: [n, cap] or None -- all device tensors; n, the strides and cap default to the tensors'
+        shapes.  Replica r ends bitwise where train_loop_gen alone on its slices would.  Asynchronous; capturable."""
+        rep = _lib.VaekReplicas()
+        rep.struct_size = C.sizeof(_lib.VaekReplicas)
+        rep.n = int(params.shape[0] if n is None else n)
+        rep.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        rep.grads_stride = int(grads.shape[1] if grads_stride is None else grads_stride)
+        assert seeds is None or seeds.dtype == torch.int64
+        assert lrs is None or lrs.dtype == torch.float32
+        rep.seeds, rep.lrs = _ptr(seeds), _ptr(lrs)
+        rep.a_stride = int(a_stride)
+        rep.loss_hist = _ptr(loss_hist)
+        rep.loss_hist_cap = int((0 if loss_hist is None else loss_hist.shape[-1]) if loss_hist_cap is None else loss_hist_cap)
+        _lib.check(self.lib.vaek_train_loop_gen_replicas(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep),
+                                                         int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(row0),
+                                                         int(tag), int(n_steps), float(lr), _ptr(workspace), _stream()))
+
     def plan_train_steps(self, params, grads, m, v, step_dev, batches, lr):
         """The same call with its arguments marshalled once: returns a function that issues vaek_train_steps on these buffers
         again (the pointer arrays, not the data, are frozen) -- for loops that repeat a group of steps, where building three

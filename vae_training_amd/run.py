@@ -2,7 +2,7 @@
 --dataset linear_gaussian ...` trains a VAE with the HIP kernels and leaves data/NAME/{args.json,
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
-which is rejected (out of scope).  Additions: --device, --force_generic."""
+which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep)."""
 from __future__ import annotations
 
 import argparse
@@ -53,7 +53,21 @@ def build_parser():
                         "hipGraph with on-device Philox batches.  Default: on for the models vaek_train_steps_gen covers")
     p.add_argument("--no_fast_loop", dest="fast_loop", action="store_false",
                    help="the reference's loop shape: one get_batch + one train_step call per iteration (model.py:221-222)")
+    p.add_argument("--sweep_dataset_seeds", dest="sweep_dataset_seeds", type=_int_list, default=None, metavar="S1,S2,...",
+                   help="train one model per dataset seed in ONE launch per run of steps (trainer.ReplicaLoop: workgroup r of "
+                        "vaek_train_loop_gen_replicas trains the model of seed r); output directories NAME_ds<seed>.  Linear VAEs the "
+                        "resident loop covers only, single GPU only")
     return p
+
+
+def _int_list(text):
+    try:
+        vals = [int(t) for t in text.split(",") if t.strip() != ""]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a comma-separated list of integers")
+    if not vals:
+        raise argparse.ArgumentTypeError("an empty list of seeds")
+    return vals
 
 
 def parse_arguments(argv=None):
@@ -128,9 +142,65 @@ def _get_model_dp(args, dataset, output_dir, dist, world, rank):
     return m
 
 
+def main_sweep(args):
+    """--sweep_dataset_seeds: one dataset and one VAEModel per seed, the reference's schedule (model.py:207-222: stats every n_print
+    steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE ReplicaLoop.run between
+    events for all of them."""
+    import copy
+    import os
+
+    from .trainer import ReplicaLoop
+    from .utils import make_output_dir
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise RuntimeError("--sweep_dataset_seeds trains independent models on one GPU: it does not combine with data parallelism")
+    seeds = list(args.sweep_dataset_seeds)
+    if len(set(seeds)) != len(seeds):
+        raise ValueError("--sweep_dataset_seeds: a seed is listed twice (the output directories would collide)")
+    models = []
+    for seed in seeds:
+        a = copy.copy(args)
+        a.dataset_seed = seed
+        out = make_output_dir(f"{args.name}_ds{seed}", args.overwrite, a)
+        ds = get_dataset(args.dataset, seed, args.padding_dim, args.batch_size, args)
+        if ds is None:
+            raise ValueError("--dataset must be one of sphere, linear_gaussian, sigmoid")
+        models.append(get_model(a, ds, out))
+    loop = ReplicaLoop(models)               # refuses, before any step, what the resident loop does not cover
+    eng = loop.eng
+    print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
+    print(f"Train loop: {loop.describe()}")
+    for r, m in enumerate(models):
+        m._graph_loop = loop.view(r)
+        score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
+        print(f"Score for real data (dataset seed {seeds[r]}): { {k: float(v) for k, v in score.items()} if isinstance(score, dict) else score}")
+    m0 = models[0]
+    n, n_print, n_plot = m0.num_batches, m0.n_print, m0.n_plot
+    events = sorted(set(list(range(0, n, n_print)) + list(range(0, n, n_plot)) + [n - 1]))
+    pos = 0
+    for ev in events:
+        loop.run(ev - pos)
+        pos = ev
+        loop.check()
+        for m in models:
+            m.batchnum = ev
+            if ev % n_print == 0:
+                m.write_stats(m.compute_stats())
+            if ev % n_plot == 0 or ev == n - 1:
+                m.plot_epoch()
+                m.save()
+    loop.run(n - pos)
+    loop.check()
+    for m in models:
+        m.plot()
+        m.save(final=True)
+    return 0
+
+
 def main(args):
     import os
 
+    if getattr(args, "sweep_dataset_seeds", None):
+        return main_sweep(args)
     from .utils import get_output_dir, make_output_dir
     dist = None
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))

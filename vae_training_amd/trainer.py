@@ -29,7 +29,10 @@ path still means the hipGraph loop, resident=True asks for this one there too): 
 (csrc/linear_resident.hip), a plain loop of steps inside ONE workgroup with parameters and Adam state on chip and the batches drawn
 in the kernel -- the same Philox counters again.  Like the moments path it is one library call per run of steps, no batch buffer and
 no hipGraph; there is one workgroup, so there is nothing to wait for and check() has nothing to poll.  `moments` keeps priority:
-every model that takes it today still does."""
+every model that takes it today still does.
+
+ReplicaLoop (below GraphLoop) is the resident loop for a SWEEP: R models of one shape, one workgroup each, in one launch per run of
+steps (vaek_train_loop_gen_replicas); `run.py --sweep_dataset_seeds` drives it."""
 from __future__ import annotations
 
 import torch
@@ -182,3 +185,131 @@ class GraphLoop:
             return ring[:n]
         k = n % cap
         return torch.cat([ring[k:], ring[:k]])
+
+
+class _ReplicaLosses:
+    """What VAEModel.model_save_data asks of `model._graph_loop`: the train losses of one replica of a ReplicaLoop."""
+
+    def __init__(self, loop, r):
+        self.loop, self.r = loop, r
+
+    def losses(self):
+        return self.loop.losses(self.r)
+
+
+class ReplicaLoop:
+    """A sweep as ONE launch per run of steps: R VAEModels of one shape -- the same batch size, data and latent dimension,
+    architecture (a linear VAE the resident loop covers), epsilon, dataset kind, -dd, -did, padding and dataset noise -- each with
+    its own dataset matrix, its own parameters and Adam state and its own learning rate, trained by vaek_train_loop_gen_replicas
+    (csrc/linear_resident.hip): workgroup r of the launch is model r's resident loop.  Model r's RNG seed is the one GraphLoop
+    derives for it (ds.key[0] ^ ds.key[1] ^ m.key[1]), so replica r trains on the batches GraphLoop(model r, resident=True) would
+    draw and ends bitwise where that loop ends.
+
+    The states live in [R, stride] stacks owned by the loop.  COPIES AT THE BOUNDARIES OF run(): every run(n) first copies each
+    model's `model.flat` and `optimizer.state.{grads, m, v, step_dev}` into its row of the stacks, makes one library call, and
+    copies the rows back (and advances `state.step`), so between two run() calls the models are ordinary models: compute_stats,
+    plot_epoch, save, checkpoints and anything else that reads or writes their own tensors works unchanged, and a state loaded in
+    between is picked up by the next run().  The copies are 5 R small device copies on each side of the call, per run of steps
+    between two events of the schedule -- not per step.
+
+    One workgroup per model and no cross-workgroup state: nothing to wait for, check() polls nothing."""
+
+    def __init__(self, vae_models, loss_capacity=None):
+        ms = list(vae_models)
+        if not ms:
+            raise RuntimeError("ReplicaLoop: no models")
+        from .datasets import DEVICE_DRAW_MAX_DIM
+        self.ms = ms
+        m0 = ms[0]
+        self.B = m0.batch_size
+        self.eng = m0.model.module.engine(self.B, m0.optimizer.global_batch)
+        specs = [m.dataset.device_spec() for m in ms]
+        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
+        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
+            raise RuntimeError(f"ReplicaLoop draws its batches with libvaek's Philox generator, which supports -dd / -did <= "
+                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
+        if self.eng.world > 1:
+            raise RuntimeError("ReplicaLoop: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
+        if not self.eng.supports_train_loop_gen(self.kind):
+            raise RuntimeError("ReplicaLoop: vaek_train_loop_gen does not cover this model / dataset (it needs a float32 linear VAE with "
+                               "one or two decoders, D, L <= 32 and a batch of at most 256 rows)")
+        R = len(ms)
+        if R > self.eng.train_loop_max_replicas:
+            raise RuntimeError(f"ReplicaLoop: {R} models, at most {self.eng.train_loop_max_replicas} fit one launch "
+                               "(vaek_train_loop_max_replicas)")
+        want = self._signature(m0, specs[0])
+        for r, (m, sp) in enumerate(zip(ms, specs)):
+            got = self._signature(m, sp)
+            if got != want:
+                raise RuntimeError(f"ReplicaLoop: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
+                                   f"{want}): one launch trains replicas of ONE shape")
+        self.R = R
+        dev = self.eng.device
+        P, GL = m0.model.flat.numel(), m0.optimizer.state.grads.numel()
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.params, self.m, self.v, self.grads = f32(R, P), f32(R, P), f32(R, P), f32(R, GL)
+        self.step_dev = torch.zeros(R, dtype=torch.int32, device=dev)
+        seeds = [(m.dataset.key[0] ^ m.dataset.key[1] ^ m.key[1]) & (2 ** 64 - 1) for m in ms]       # GraphLoop's, model by model
+        self.seeds = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device=dev)
+        self.lrs = torch.tensor([float(m.optimizer.optimizer_def.learning_rate) for m in ms], dtype=torch.float32, device=dev)
+        if specs[0][1] is None:
+            self.A, self.a_stride = None, 0
+        else:
+            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
+            self.a_stride = self.A.shape[1]
+        if loss_capacity is None:             # every step of the longest schedule among the models
+            loss_capacity = max(int(getattr(m, "num_batches", 0) or 0) for m in ms) or (1 << 16)
+        self.rings = f32(R, int(loss_capacity))
+        nb = self.eng.train_loop_replicas_workspace(R)
+        self.workspace = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None
+
+    @staticmethod
+    def _signature(m, spec):
+        eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+        cfg = getattr(eng, "cfg", None)
+        arch = None if cfg is None else (cfg.n_enc_hidden, cfg.n_dec_hidden, cfg.sigmoid_decoder, cfg.tunable_eps, cfg.eps_cli, cfg.dtype,
+                                         cfg.force_generic, cfg.global_batch)
+        kind, A, dd, did, pad, var = spec
+        return (m.batch_size, eng.D, eng.L, m.model.flat.numel(), arch, kind, None if A is None else A.numel(), dd, did, pad, float(var))
+
+    def _rows(self, m, r):
+        st = m.optimizer.state
+        return ((self.params[r], m.model.flat), (self.grads[r], st.grads), (self.m[r], st.m), (self.v[r], st.v),
+                (self.step_dev[r:r + 1], st.step_dev))
+
+    def run(self, n_steps):
+        """Exactly n_steps train steps of every model: one library call between the copies in and out."""
+        if n_steps <= 0:
+            return
+        for r, m in enumerate(self.ms):
+            for row, own in self._rows(m, r):
+                row.copy_(own)
+        self.eng.train_loop_gen_replicas(self.params, self.grads, self.m, self.v, self.step_dev, n_steps, 0.0, self.kind, self.A,
+                                         self.dd, self.did, self.pad, self.var, self.seeds, lrs=self.lrs, a_stride=self.a_stride,
+                                         loss_hist=self.rings, workspace=self.workspace, tag=0, row0=0)
+        for r, m in enumerate(self.ms):
+            for row, own in self._rows(m, r):
+                own.copy_(row)
+            m.optimizer.state.step += n_steps
+
+    def describe(self):
+        """One line for run.py."""
+        return (f"resident linear kernel, {self.R} replicas in one launch (vaek_train_loop_gen_replicas), "
+                f"{self.eng.train_loop_steps_per_launch} steps per launch")
+
+    def check(self):
+        """Nothing to poll: the launch has no waits."""
+
+    def losses(self, r):
+        """Losses of all steps model r has run so far, in order (device -> host once)."""
+        n = self.ms[r].optimizer.state.step
+        cap = self.rings.shape[1]
+        ring = self.rings[r].cpu()
+        if n <= cap:
+            return ring[:n]
+        k = n % cap
+        return torch.cat([ring[k:], ring[:k]])
+
+    def view(self, r):
+        """Model r's `_graph_loop`: losses() without an argument, as VAEModel.model_save_data calls it."""
+        return _ReplicaLosses(self, r)
