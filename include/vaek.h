@@ -346,6 +346,47 @@ int vaek_train_loop_replicas_workspace_bytes(const vaek_ctx* ctx, int32_t n, siz
 int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
                                  const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
                                  float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream);
+/* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
+ * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
+ * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an
+ * atomic, so the idle CUs take other models of a sweep with no new synchronisation.  It is vaek_train_step_gen for N models:
+ * replica r trains on its batch x + r * B * D, z1 + r * B * L, z2 + r * B * D ([n][B][D], [n][B][L], [n][B][D] stacks) and draws
+ * its next one into the same slices of x_next / z1_next / z2_next, its generator step read from counter[2 r + which] and
+ * counter[2 r + (which ^ 1)] = step + 1 stored (int32 [n][2]).  `rep` is the vaek_replicas of vaek_train_loop_gen_replicas:
+ * replica r owns params / m / v + r * state_stride, grads + r * grads_stride, step_dev[r], seeds[r], lrs[r] (lrs == NULL: `lr`),
+ * A + r * a_stride (0: shared; A may be NULL for kind 2) and the ring loss_hist + r * loss_hist_cap.  kind, dd, did, pad,
+ * var_added, row0, tag, which and the context (shape, batch, epsilon) belong to the launch.  Floats between two replicas where
+ * a stride exceeds the length are not touched.
+ * STRIDE RULE: state_stride must be a multiple of 4 floats.  The step reads a layer's weights 16 bytes at a time where the
+ * parameter pointer is 16-byte aligned, and one float at a time where it is not, and the two forms sum in different orders: with
+ * that stride every replica's pointer has the base's alignment, so every replica takes the form a solo call on its slice takes.
+ * NO-DRAW FORM: x_next == z1_next == z2_next == NULL draws nothing -- N x vaek_train_step; seeds, A and counter may be NULL and
+ * kind is ignored.
+ * DEFINING PROPERTY: for every r, what the call leaves in replica r's params, m, v, grads, step_dev[r], ring, next batch and
+ * counter[2 r .. 2 r + 1] is BITWISE what vaek_train_step_gen (no-draw form: vaek_train_step) leaves when called alone on those
+ * slices with seed = seeds[r], lr = lrs[r], replica r's A and counter + 2 r, the ring of vaek_set_loss_history standing in for
+ * replica r's: the same code on the same inputs.  The ring of vaek_set_loss_history is NOT written by this call.
+ * Asynchronous on `stream`, allocates nothing, does not synchronise, capturable into a hipGraph; two launches per call whatever
+ * n is (profile labels fused_mlp3_chain_replicas, fused_mlp3_grads_adam[_gen]_replicas).
+ * vaek_supports_train_step_replicas: the step path is "mlp3" and world == 1.  vaek_train_step_max_replicas() = 256: a cap that
+ * bounds the length of one launch on a shared machine, not a tuned value; 36 replicas at batch 100 fill the first round of the chain
+ * launch (7 workgroups each, one per CU), n above that is legal and only queues workgroups.
+ * WORKSPACE: the call's OWN buffer of vaek_train_step_replicas_workspace_bytes(ctx, n) bytes, 16-byte aligned: n times the step's
+ * region of stored activations (its float count rounded up to a multiple of 4).  It is NOT the buffer of vaek_workspace_bytes,
+ * which this entry point neither needs nor changes.
+ * VAEK_ERR_INVALID (with a message, buffers untouched): n < 1 or n > the cap; state_stride < P or not a multiple of 4;
+ * grads_stride < grad_len; a ring with loss_hist_cap < 1; a_stride < 0; NULL seeds or NULL counter in the drawing form; some but
+ * not all of the _next pointers NULL; dd or did > 16; kind outside 0 .. 2 in the drawing form; a missing or misaligned workspace;
+ * a wrong struct_size; a context whose path is not "mlp3", or world > 1.  Data parallelism, gradients-only and the bucketed
+ * entry have no replica form. */
+int vaek_supports_train_step_replicas(const vaek_ctx* ctx, int32_t* yes);
+int vaek_train_step_max_replicas(void);
+int vaek_train_step_replicas_workspace_bytes(const vaek_ctx* ctx, int32_t n, size_t* bytes);
+int vaek_train_step_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                 const vaek_replicas* rep, const float* x, const float* z1, const float* z2, float lr, void* workspace,
+                                 int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, float* x_next,
+                                 float* z1_next, float* z2_next, int64_t row0, int32_t* counter, int32_t which, uint32_t tag,
+                                 void* stream);
 /* Convolutional VAE of BASELINE config 5 -- NO reference counterpart (the reference has no convolutional model: its only image
  * code is utils.py:129-133); the layer is specified in DESIGN.md 3.4 and checked against oracle/conv_vae_oracle.py:conv_fwd.
  * 4 x 4 / stride 2 / pad 1 convolution, NHWC float32 tensors, HWIO kernel [4][4][c_in][c_out], bf16 matrix-core products with

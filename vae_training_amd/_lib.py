@@ -29,7 +29,8 @@ class VaekConfig(C.Structure):
 
 
 class VaekReplicas(C.Structure):
-    """vaek_replicas of include/vaek.h: the per-replica description of vaek_train_loop_gen_replicas (device pointers)."""
+    """vaek_replicas of include/vaek.h: the per-replica description of vaek_train_loop_gen_replicas and
+    vaek_train_step_gen_replicas (device pointers)."""
     _fields_ = [
         ("struct_size", C.c_int32), ("n", C.c_int32), ("state_stride", C.c_int64), ("grads_stride", C.c_int64),
         ("seeds", C.c_void_p), ("lrs", C.c_void_p), ("a_stride", C.c_int64), ("loss_hist", C.c_void_p), ("loss_hist_cap", C.c_int64),
@@ -94,6 +95,11 @@ SIGNATURES = {
     "vaek_train_loop_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),
     "vaek_train_loop_gen_replicas": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(VaekReplicas), _i32, _vp, _i32, _i32, _i32, _f32,
                                                C.c_int64, C.c_uint32, _i32, _f32, _vp, _vp]),
+    "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "vaek_train_step_max_replicas": (C.c_int, []),
+    "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),
+    "vaek_train_step_gen_replicas": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(VaekReplicas), _vp, _vp, _vp, _f32, _vp, _i32, _vp,
+                                               _i32, _i32, _i32, _f32, _vp, _vp, _vp, _i64, _vp, _i32, C.c_uint32, _vp]),
     "vaek_conv2d_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     "vaek_to_bf16": (C.c_int, [_vp, _vp, C.c_int64, _vp]),
     "vaek_conv2d_forward_workspace": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_size_t)]),

@@ -914,6 +914,89 @@ int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, flo
                                         rep->loss_hist_cap, n_steps, lr, workspace, (hipStream_t)stream);
 }
 
+// ---- the replica form of the mlp3 step (fused_mlp3.hip): n models of one shape per step, blockIdx.y = replica ----------------------
+int vaek_supports_train_step_replicas(const vaek_ctx* ctx, int32_t* yes) {
+    if (!ctx || !yes) { set_error("null argument"); return VAEK_ERR_INVALID; }
+    *yes = ctx->mlp3 && ctx->cfg.world == 1 ? 1 : 0;
+    return VAEK_OK;
+}
+
+int vaek_train_step_max_replicas(void) { return mlp3_max_replicas(); }
+
+int vaek_train_step_replicas_workspace_bytes(const vaek_ctx* ctx, int32_t n, size_t* bytes) {
+    if (!ctx || !bytes || n < 1 || n > mlp3_max_replicas()) {
+        set_error("vaek_train_step_replicas_workspace_bytes: null argument, or n outside 1 .. %d", mlp3_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    *bytes = ctx->mlp3 && ctx->cfg.world == 1 ? mlp3_replicas_workspace_bytes(ctx, n) : 0;
+    return VAEK_OK;
+}
+
+int vaek_train_step_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                 const vaek_replicas* rep, const float* x, const float* z1, const float* z2, float lr, void* workspace,
+                                 int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, float* x_next,
+                                 float* z1_next, float* z2_next, int64_t row0, int32_t* counter, int32_t which, uint32_t tag, void* stream) {
+    ProfBind pb(ctx);
+    const char* const fn = "vaek_train_step_gen_replicas";
+    if (!ctx || !params || !grads || !m || !v || !step_dev || !rep || !x || !z1 || !z2) {
+        set_error("%s: null argument", fn);
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->struct_size != (int32_t)sizeof(vaek_replicas)) {
+        set_error("%s: vaek_replicas.struct_size %d != %d (header / library mismatch)", fn, rep->struct_size, (int)sizeof(vaek_replicas));
+        return VAEK_ERR_INVALID;
+    }
+    if (!ctx->mlp3 || ctx->cfg.world != 1) {
+        set_error("%s: needs a single-GPU context whose train step path is \"mlp3\" (see vaek_supports_train_step_replicas)", fn);
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->n < 1 || rep->n > mlp3_max_replicas()) {
+        set_error("%s: %d replicas, need 1 .. %d (vaek_train_step_max_replicas)", fn, rep->n, mlp3_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->state_stride < ctx->P || rep->state_stride % 4 != 0) {
+        // a multiple of 4 floats: every replica's parameters then have the base pointer's 16-byte alignment, so every replica takes the
+        // dX load form a solo call on its slice would take (the two forms are not bitwise equal)
+        set_error("%s: state_stride %lld must be >= P = %lld and a multiple of 4", fn, (long long)rep->state_stride, (long long)ctx->P);
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->grads_stride < ctx->P + kExtra) {
+        set_error("%s: grads_stride %lld < grad_len = %lld", fn, (long long)rep->grads_stride, (long long)(ctx->P + kExtra));
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->loss_hist && rep->loss_hist_cap < 1) {
+        set_error("%s: loss_hist given with loss_hist_cap %lld < 1", fn, (long long)rep->loss_hist_cap);
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->a_stride < 0) { set_error("%s: a_stride %lld < 0", fn, (long long)rep->a_stride); return VAEK_ERR_INVALID; }
+    if (dd > 16 || did > 16) { set_error("%s: dd %d or did %d > 16", fn, dd, did); return VAEK_ERR_INVALID; }
+    const int n_next = (x_next ? 1 : 0) + (z1_next ? 1 : 0) + (z2_next ? 1 : 0);
+    if (n_next != 0 && n_next != 3) {
+        set_error("%s: x_next, z1_next and z2_next must be all NULL (no draw) or all given", fn);
+        return VAEK_ERR_INVALID;
+    }
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
+        set_error("%s: workspace must be a 16-byte aligned device pointer of vaek_train_step_replicas_workspace_bytes() = %zu bytes", fn,
+                  mlp3_replicas_workspace_bytes(ctx, rep->n));
+        return VAEK_ERR_INVALID;
+    }
+    BatchArgs gen;
+    if (n_next) {
+        if (!rep->seeds || !counter) { set_error("%s: the drawing form needs seeds and counter", fn); return VAEK_ERR_INVALID; }
+        if (x_next == x || z1_next == z1 || z2_next == z2) {
+            set_error("%s: the next batch must not alias the current one", fn);
+            return VAEK_ERR_INVALID;
+        }
+        // (the kernel puts seeds[r] in place of the seed; this also fences kind to 0 .. 2, `which` to 0 / 1 and the dataset dimension)
+        int rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, x_next, z1_next, z2_next, ctx->B, row0, 0, nullptr, 0, counter, which,
+                                 tag, &gen);
+        if (rc) return rc;
+    }
+    return mlp3_train_step_replicas(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, workspace, (hipStream_t)stream, n_next ? &gen : nullptr,
+                                    rep->n, rep->state_stride, rep->grads_stride, reinterpret_cast<const unsigned long long*>(rep->seeds),
+                                    rep->lrs, rep->a_stride, rep->loss_hist, rep->loss_hist_cap);
+}
+
 int vaek_train_steps_moment_len(const vaek_ctx* ctx, int64_t* len) {
     if (!ctx || !len) { set_error("null argument"); return VAEK_ERR_INVALID; }
     *len = ctx->lin.NO;

@@ -15,6 +15,24 @@
 //
 // Rows past the batch (the last group's padding) carry zero gradients, so launch 2 sums whole padded rows without a mask.
 // Every sum has a fixed order: bitwise repeatable from run to run.  No bf16, no atomics.
+//
+// THE REPLICA FORM (vaek_train_step_gen_replicas).  Neither launch has a counter, a wait or an atomic, and workgroups of different
+// models share nothing, so N independent models of one shape are the same two launches with gridDim.y = N: blockIdx.y = r runs
+// the very body of the solo kernels (mlp3_chain_body.inc, mlp3_grad_body.inc) on replica r's slices of the caller's stacks.
+//   Defining property: what replica r is left with -- params, m, v, grads, step_dev[r], its ring, its next batch, its counter pair
+//           -- is BITWISE what vaek_train_step_gen (no-draw form: vaek_train_step) leaves when called alone on those slices.
+//   Stride rule: state_stride % 4 == 0.  The VEC form of dX permutes the k-slots of a chunk, so it is not bitwise the dword form,
+//           and the host picks it per layer from the BASE pointer's alignment; with that stride every replica's pointer has the
+//           base's alignment and takes the form a solo call on its slice would take.
+//   Workspace: the call's own buffer, one region of mlp3_replica_region_floats (the solo region rounded up to whole float4s) per
+//           replica; the context's workspace and ring are not used.
+//   Refusals (api.hip, before any launch): n outside 1 .. 256, state_stride < P or % 4 != 0, grads_stride < grad_len, a ring
+//           with cap < 1, a_stride < 0, NULL seeds / counter in the drawing form, some but not all _next pointers NULL,
+//           dd / did > 16, kind outside 0 .. 2 in the drawing form, a missing / misaligned workspace, a wrong struct_size, a
+//           context off the mlp3 path or with world > 1.
+//   The rule of linear_resident.hip, re-read: seeds[r], lrs[r] and counter[2 r + which] are tables or slots this launch does not
+//           write at that address; step_dev[r] is written by the chain launch and read by the NEXT launch; nothing stored inside a
+//           launch is read back inside it through a uniform-address or const __restrict__ load.
 #include "vaek_internal.h"
 #include "rng_dev.h"
 
@@ -182,130 +200,47 @@ __device__ __forceinline__ void m3_store_img(float* __restrict__ dst, const floa
     }
 }
 
+// What the replica form adds to the launch arguments of both kernels (vaek_train_step_gen_replicas): blockIdx.y = r trains replica r.
+// The tables are never written by either launch, so the uniform-address loads of seeds[r] / lrs[r] below are safe from the scalar
+// cache (the rule of linear_resident.hip); step_dev[r] is written by the chain launch and read by the NEXT launch.
+struct Mlp3ReplicaArgs {
+    long long state_stride, grads_stride, a_stride, region_floats;     // floats between two replicas' params / m / v, grads, A, workspace region
+    const unsigned long long* seeds;                                   // [n], or nullptr in the no-draw form
+    const float* lrs;                                                  // [n], or nullptr: Mlp3GradArgs::lr for every replica
+};
+
+// Replica r's view of the chain launch's arguments: Mlp3ChainArgs member for member, with its slices of the caller's buffers in place
+// of the bases.  The layer table stays where it is, in the kernel-argument segment: a private copy indexed by the layer loop would
+// live in scratch memory.  Slices of different replicas are disjoint (the host checks the strides against the lengths), and a
+// workgroup reads and writes only its own.
+struct Mlp3ChainSlice {
+    const float* x; const float* z1; const float* z2; const float* params;
+    float* acts; float* part;
+    int B, D, L, Bs;
+    float inv_bt, eps_cli;
+    int off_epsp, off_eps, e_max;
+    const Mlp3Layers& ly;
+    int32_t* step_dev;
+    unsigned long long* stamps;
+};
+__device__ __forceinline__ Mlp3ChainSlice m3_chain_slice(const Mlp3ChainArgs& a, const Mlp3ReplicaArgs& rp) {
+    const long long r = blockIdx.y;
+    return {a.x + r * a.B * a.D, a.z1 + r * a.B * a.L, a.z2 + r * a.B * a.D, a.params + r * rp.state_stride,
+            a.acts + r * rp.region_floats, a.part + r * rp.region_floats,
+            a.B, a.D, a.L, a.Bs, a.inv_bt, a.eps_cli, a.off_epsp, a.off_eps, a.e_max, a.ly, a.step_dev + r, a.stamps};
+}
+
+// The body of both forms is ONE text, mlp3_chain_body.inc, written in terms of `a`: the solo kernel is that text on its launch
+// arguments as given (the kernel it was before the replica form existed, token for token); the replica kernel is a first statement
+// that slices the arguments, then the same text.  The body has no cross-workgroup state -- no counter, no wait, no atomic -- so
+// replicas share nothing but the code and the launch-wide arguments; blockIdx.x keeps its meaning within a replica.
 __global__ __launch_bounds__(M3_NT) void mlp3_chain_kernel(const Mlp3ChainArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char m3_smem[];
-    Mlp3Lds& s = *reinterpret_cast<Mlp3Lds*>(m3_smem);
-    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int D = a.D, L = a.L, Bs = a.Bs;
-    const int row0 = blockIdx.x * M3_R, valid = min(M3_R, a.B - row0);
-    const float* const P = a.params;
-    if (blockIdx.x == 0 && t == 0 && a.step_dev) a.step_dev[0] += 1;
-    M3_STAMP(0);
-    // ---- inputs as [feature][sample] images, zero-padded; loads unconditional at clamped indices, selects at the LDS store
-    float shl[2];
-    {
-        float xv[2], z1v[2], z2v[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = t + i * M3_NT, c = e >> 4, sm = e & 15;
-            const long long row = row0 + min(sm, valid - 1);
-            xv[i] = a.x[row * D + min(c, D - 1)]; z1v[i] = a.z1[row * L + min(c, L - 1)]; z2v[i] = a.z2[row * D + min(c, D - 1)];
-            shl[i] = P[a.off_epsp + min(c, L - 1)];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int e = t + i * M3_NT, c = e >> 4;
-            (&s.X[0][0])[e] = c < D ? xv[i] : 0.f; (&s.Z1[0][0])[e] = c < L ? z1v[i] : 0.f; (&s.Z2[0][0])[e] = c < D ? z2v[i] : 0.f;
-            shl[i] = expf(0.5f * shl[i]);
-        }
-    }
-    const float eps_ld = P[a.off_eps >= 0 ? a.off_eps : 0];
-    const float eps = a.off_eps >= 0 ? eps_ld * a.eps_cli : a.eps_cli;
-    const float sigma = expf(0.5f * eps), inv_var = expf(-eps);
-    float p_mse = 0.f, p_musq = 0.f, p_deps = 0.f;
-    __syncthreads();
-    M3_STAMP(1);
+#include "mlp3_chain_body.inc"
+}
 
-    // ---- forward: encoder 0 .. 3, reparameterisation, decoder 4 .. 7, ELBO
-    for (int li = 0; li < M3_NL; ++li) {
-        const int n_in = a.ly.n_in[li], n_out = a.ly.n_out[li];
-        const int w_off = a.ly.w_off[li];
-        const M3Img in = m3_in_img(s, li), out = m3_out_img(s, li);
-        m3_store_img(a.acts + a.ly.a_off[li], in, n_in, Bs, row0, t);
-        const bool relu = li != 3 && li != 7;
-        auto epi = [&](int m, int n, float v, float b) { v += b; out[m][n] = relu ? fmaxf(v, 0.f) : v; };
-        const float* const bias = P + w_off + n_in * n_out;
-        if (n_out <= 64) m3_dense<1, false>(P, w_off, bias, n_out, n_in, n_out, true, 0, a.e_max, in, wave, lane, epi);
-        else m3_dense<4, false>(P, w_off, bias, n_out, n_in, n_out, true, 0, a.e_max, in, wave, lane, epi);
-        __syncthreads();
-        if (li == 3) {               // samples = mu + e^{lv/2} z1
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int e = t + i * M3_NT, c = e >> 4, sm = e & 15;
-                if (c < L) {
-                    const float mu = (&s.MU[0][0])[e];
-                    (&s.SMP[0][0])[e] = fmaf(shl[i], (&s.Z1[0][0])[e], mu);
-                    if (sm < valid) p_musq = fmaf(mu, mu, p_musq);
-                }
-            }
-            __syncthreads();
-        }
-        M3_STAMP(2 + li);
-    }
-    // ---- ELBO, elementwise over [feature][sample]: decoder noise, residual, dL/dx_hat (zero for rows past the batch), scalar sums
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int e = t + i * M3_NT, c = e >> 4, sm = e & 15;
-        const bool in = sm < valid && c < D;
-        const float z2v = (&s.Z2[0][0])[e];
-        const float res = (&s.XH[0][0])[e] + z2v * sigma - (&s.X[0][0])[e];
-        (&s.XH[0][0])[e] = in ? res * inv_var * a.inv_bt : 0.f;
-        if (in) {
-            const float q = 0.5f * res * res * inv_var;
-            p_mse += q;
-            p_deps += -q + 0.5f * sigma * z2v * res * inv_var;
-        }
-    }
-    __syncthreads();
-    M3_STAMP(10);
-    m3_store_img(a.acts + a.ly.g_off[7], s.XH, D, Bs, row0, t);
-
-    // ---- backward: dX of layer li from the gradient image of its output, through the relu of the layer below, in place
-    for (int li = M3_NL - 1; li >= 1; --li) {
-        const int n_in = a.ly.n_in[li], n_out = a.ly.n_out[li];
-        const int w_off = a.ly.w_off[li], sh = a.ly.shift[li];
-        const M3Img dy = m3_out_img(s, li);
-        const M3Img dst = li == 4 ? s.DS : m3_out_img(s, li - 1);
-        const bool mask = li != 4;
-        auto epi = [&](int m, int n, float v, float) { dst[m][n] = (!mask || dst[m][n] > 0.f) ? v : 0.f; };
-        if (sh >= 0 && n_in <= 64) m3_dense<1, true>(P, w_off, P, n_in, n_out, n_out, false, sh, a.e_max, dy, wave, lane, epi);
-        else if (sh >= 0) m3_dense<4, true>(P, w_off, P, n_in, n_out, n_out, false, sh, a.e_max, dy, wave, lane, epi);
-        else if (n_in <= 64) m3_dense<1, false>(P, w_off, P, n_in, n_out, n_out, false, 0, a.e_max, dy, wave, lane, epi);
-        else m3_dense<4, false>(P, w_off, P, n_in, n_out, n_out, false, 0, a.e_max, dy, wave, lane, epi);
-        __syncthreads();
-        if (li == 4) {               // d mu = d samples + mu / Bt (zero for rows past the batch); DS becomes d samples * z1
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int e = t + i * M3_NT, c = e >> 4, sm = e & 15;
-                if (c < L) {
-                    const float ds = (&s.DS[0][0])[e];
-                    (&s.MU[0][0])[e] = sm < valid ? fmaf((&s.MU[0][0])[e], a.inv_bt, ds) : 0.f;
-                    (&s.DS[0][0])[e] = sm < valid ? ds * (&s.Z1[0][0])[e] : 0.f;
-                }
-            }
-            __syncthreads();
-        }
-        m3_store_img(a.acts + a.ly.g_off[li - 1], m3_out_img(s, li - 1), a.ly.n_out[li - 1], Bs, row0, t);
-        M3_STAMP(10 + (M3_NL - li));
-    }
-
-    // ---- this workgroup's partial row: the three scalar sums (lanes by xor-shuffle, the four waves in order), epsilon_p's sums
-    float* const row = a.part + (long long)blockIdx.x * M3_PS;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        p_mse += __shfl_xor(p_mse, o, 64); p_musq += __shfl_xor(p_musq, o, 64); p_deps += __shfl_xor(p_deps, o, 64);
-    }
-    if (lane == 0) { s.RED[wave][0] = p_mse; s.RED[wave][1] = p_musq; s.RED[wave][2] = p_deps; }
-    __syncthreads();
-    if (t < 3) row[t] = (s.RED[0][t] + s.RED[1][t]) + (s.RED[2][t] + s.RED[3][t]);
-    if (t == 3) row[3] = 0.f;
-    if (t < L) {
-        float g = 0.f;
-#pragma unroll
-        for (int r = 0; r < M3_R; ++r) g += s.DS[t][r];
-        row[4 + t] = g;
-    }
-    M3_STAMP(18);
+__global__ __launch_bounds__(M3_NT) void mlp3_chain_replicas_kernel(const Mlp3ChainArgs a0, const Mlp3ReplicaArgs rp) {
+    const Mlp3ChainSlice a = m3_chain_slice(a0, rp);
+#include "mlp3_chain_body.inc"
 }
 
 // ---- launch 2 ------------------------------------------------------------------------------------------------------------------
@@ -327,7 +262,8 @@ __device__ __forceinline__ float m3_wsum(float v) {
 
 // epsilon_p, epsilon, the three loss slots: closed-form terms exactly as fused_finalize_block (fused_small.hip) has them.
 // One wave; every load is issued before the first store, so the parameters it updates are read before they are written.
-__device__ __forceinline__ void m3_tail(const Mlp3GradArgs& a) {
+template <typename Args>             // Mlp3GradArgs, or a replica's Mlp3GradSlice
+__device__ __forceinline__ void m3_tail(const Args& a) {
     const int t = threadIdx.x;
     if (t >= 64) return;
     const int P = a.P, L = a.L, G = a.G;
@@ -372,75 +308,44 @@ __device__ __forceinline__ void m3_tail(const Mlp3GradArgs& a) {
     }
 }
 
+// Replica r's view of launch 2's arguments (Mlp3GradArgs member for member, the layer and tile tables left in the kernel-argument
+// segment) and its generator arguments: its slices, its learning rate, seed, dataset matrix and counter pair.
+struct Mlp3GradSlice {
+    const float* acts; const float* part; int G, Bs;
+    const Mlp3Layers& ly; const int (&tile0)[M3_NL + 1];
+    int P, off_epsp, off_eps, L, D;
+    const float* params; float eps_cli, rows_over_bt, inv_bt, rows;
+    float* grads;
+    float* params_rw; float* m; float* v; const int32_t* step_dev; float lr;
+    float* loss_hist; long long loss_hist_cap;
+};
+struct Mlp3GradSlices { Mlp3GradSlice a; BatchArgs b; };
+__device__ __forceinline__ Mlp3GradSlices m3_grad_slice(const Mlp3GradArgs& a, const BatchArgs& b0, const Mlp3ReplicaArgs& rp) {
+    const long long r = blockIdx.y;
+    BatchArgs b = b0;
+    if (b.z1) {                      // the drawing form (the no-draw form launches no generator workgroup: b is all zero, seeds may be NULL)
+        b.x += r * b.rows * b.D; b.z1 += r * b.rows * b.L; b.z2 += r * b.rows * b.D;
+        b.seed = rp.seeds[r];
+        if (b.A) b.A += r * rp.a_stride;
+        b.counter += 2 * r;
+    }
+    return {{a.acts + r * rp.region_floats, a.part + r * rp.region_floats, a.G, a.Bs, a.ly, a.tile0, a.P, a.off_epsp, a.off_eps, a.L, a.D,
+             a.params + r * rp.state_stride, a.eps_cli, a.rows_over_bt, a.inv_bt, a.rows, a.grads + r * rp.grads_stride,
+             a.params_rw + r * rp.state_stride, a.m + r * rp.state_stride, a.v + r * rp.state_stride, a.step_dev + r,
+             rp.lrs ? rp.lrs[r] : a.lr, a.loss_hist ? a.loss_hist + r * a.loss_hist_cap : nullptr, a.loss_hist_cap},
+            b};
+}
+
+// As the chain kernel: one body text (mlp3_grad_body.inc, in terms of `a` and `b`) for the solo kernel, which is the kernel it was,
+// and for the replica kernel behind its slicing statement.  blockIdx.x keeps its meaning within a replica: tiles, the tail, the
+// generator items.
 __global__ __launch_bounds__(M3_NT) void mlp3_grad_kernel(const Mlp3GradArgs a, const BatchArgs b) {
-    __shared__ float As[M3_TK][M3_TB];           // [kernel row | bias][batch row]
-    __shared__ float Gs[M3_TB][M3_TJ + 1];       // [batch row][column]
-    const int t = threadIdx.x, lane = t & 63, kq = __builtin_amdgcn_readfirstlane(t >> 6);
-    const int bid = blockIdx.x, ntiles = a.tile0[M3_NL];
-    if (bid > ntiles) {              // vaek_train_step_gen: the next step's batch does not depend on the weights
-        const unsigned step = make_batch_step(b);
-        make_batch_items(b, step, (long long)(bid - ntiles - 1) * M3_NT + t);
-        make_batch_advance(b, step, bid == ntiles + 1 && t == 0);
-        return;
-    }
-    if (bid == ntiles) { m3_tail(a); return; }
-    int li = 0;
-#pragma unroll
-    for (int i = 1; i < M3_NL; ++i) li = bid >= a.tile0[i] ? i : li;
-    const int n_in = a.ly.n_in[li], n_out = a.ly.n_out[li], Bs = a.Bs;
-    const int tiles_j = (n_out + M3_TJ - 1) / M3_TJ, rel = bid - a.tile0[li];
-    const int k0 = M3_TK * (rel / tiles_j), j0 = M3_TJ * (rel % tiles_j);
-    const float* const ap = a.acts + a.ly.a_off[li];
-    const float* const gp = a.acts + a.ly.g_off[li];
-    // this thread's four outputs: rows k0 + 4 kq + i (row n_in is the bias), column j0 + lane; Adam state loaded up front
-    const int j = j0 + lane;
-    int idx[4]; bool ok[4];
-    float p_old[4], m_old[4], v_old[4];
-    const float* const ps = a.params_rw ? a.params_rw : a.params;
-    const float* const ms = a.m ? a.m : a.params;
-    const float* const vs = a.v ? a.v : a.params;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int k = k0 + 4 * kq + i;
-        ok[i] = k <= n_in && j < n_out;
-        idx[i] = a.ly.w_off[li] + (ok[i] ? k * n_out + j : 0);
-        p_old[i] = ps[idx[i]]; m_old[i] = ms[idx[i]]; v_old[i] = vs[idx[i]];
-    }
-    const int tstep = a.step_dev ? a.step_dev[0] : 0;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int c0 = 0; c0 < Bs; c0 += M3_TB) {
-        const bool in = c0 + lane < Bs;
-        const int bc = min(c0 + lane, Bs - 1);
-        float gv[16], av[4];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) gv[r] = gp[(long long)min(j0 + 16 * kq + r, n_out - 1) * Bs + bc];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) av[r] = ap[(long long)min(k0 + 4 * kq + r, n_in - 1) * Bs + bc];
-        __syncthreads();             // the previous chunk is no longer read
-#pragma unroll
-        for (int r = 0; r < 16; ++r) Gs[lane][16 * kq + r] = in ? gv[r] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) As[4 * kq + r][lane] = !in ? 0.f : (k0 + 4 * kq + r == n_in ? 1.f : av[r]);
-        __syncthreads();
-#pragma unroll 16
-        for (int r = 0; r < M3_TB; ++r) {
-            const float g = Gs[r][lane];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[i] = fmaf(As[4 * kq + i][r], g, acc[i]);
-        }
-    }
-    const float bc1 = -expm1f((float)tstep * -0.10536051565782628f);
-    const float bc2 = -expm1f((float)tstep * -0.0010005003335835335f);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (ok[i]) {
-            a.grads[idx[i]] = acc[i];
-            if (a.params_rw) {
-                adam_apply_f(p_old[i], acc[i], m_old[i], v_old[i], a.lr, bc1, bc2);
-                a.params_rw[idx[i]] = p_old[i]; a.m[idx[i]] = m_old[i]; a.v[idx[i]] = v_old[i];
-            }
-        }
-    }
+#include "mlp3_grad_body.inc"
+}
+
+__global__ __launch_bounds__(M3_NT) void mlp3_grad_replicas_kernel(const Mlp3GradArgs a0, const BatchArgs b0, const Mlp3ReplicaArgs rp) {
+    const auto [a, b] = m3_grad_slice(a0, b0, rp);
+#include "mlp3_grad_body.inc"
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
@@ -475,13 +380,19 @@ size_t mlp3_workspace_bytes(const vaek_ctx* c) {
     return (mlp3_layout(c, nullptr) + (size_t)mlp3_groups(c) * M3_PS) * sizeof(float);
 }
 
-int mlp3_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x, const float* z1,
-                    const float* z2, float lr, bool apply_adam, void* ws, hipStream_t st, const BatchArgs* gen) {
+// Both forms of the step.  rep == nullptr: vaek_train_step* on the context's workspace region and ring (the solo kernels, grid.y = 1).
+// rep != nullptr: n replicas, blockIdx.y = r, on the call's own workspace `ws` (n regions of mlp3_replica_region_floats) and the
+// caller's rings; always a train step.
+struct Mlp3ReplicaHost { int n; Mlp3ReplicaArgs rp; float* loss_hist; long long loss_hist_cap; };
+
+static int mlp3_step_impl(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x, const float* z1,
+                          const float* z2, float lr, bool apply_adam, void* ws, hipStream_t st, const BatchArgs* gen,
+                          const Mlp3ReplicaHost* rep) {
     if (!mlp3_supported(c) || c->enc.layers.size() != 4 || c->dec.layers.size() != 4) {
         set_error("mlp3 path not available for this configuration");
         return VAEK_ERR_INVALID;
     }
-    float* const region = reinterpret_cast<float*>(static_cast<char*>(ws) + c->ws_mlp3);
+    float* const region = rep ? static_cast<float*>(ws) : reinterpret_cast<float*>(static_cast<char*>(ws) + c->ws_mlp3);
     const int G = mlp3_groups(c);
     Mlp3ChainArgs a{};
     const size_t acts_floats = mlp3_layout(c, &a.ly);
@@ -489,21 +400,26 @@ int mlp3_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* v
     a.B = c->B; a.D = c->D; a.L = c->L; a.Bs = G * M3_R;
     a.inv_bt = (float)(1.0 / (double)c->Bt); a.eps_cli = c->cfg.eps_cli;
     a.off_epsp = (int)c->off_epsp; a.off_eps = (int)c->off_eps; a.e_max = (int)((c->P - 4) & ~3ll);
+    // (replicas: state_stride % 4 == 0, so every replica's parameters have the base's alignment and take the form chosen here)
     for (int li = 0; li < M3_NL; ++li)
 #ifdef VAEK_M3_NO_VEC                // diagnostic build (tools/m3_stamps.sh): dX with dword loads, for the A/B in profiles/mlp3_stamps.txt
         a.ly.shift[li] = -1;
 #else
         a.ly.shift[li] = ((reinterpret_cast<uintptr_t>(params) & 15) == 0 && a.ly.n_out[li] % 4 == 0) ? a.ly.w_off[li] % 4 : -1;
 #endif
-    a.step_dev = step_dev; a.stamps = c->dbg_stamps;
-    static thread_local PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)mlp3_chain_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Mlp3Lds)));
-        attr_set.mark();
+    a.step_dev = step_dev; a.stamps = rep ? nullptr : c->dbg_stamps;
+    static thread_local PerDeviceOnce attr_set[2];
+    PerDeviceOnce& once = attr_set[rep ? 1 : 0];
+    if (once.need()) {
+        const void* fn = rep ? (const void*)mlp3_chain_replicas_kernel : (const void*)mlp3_chain_kernel;
+        VAEK_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Mlp3Lds)));
+        once.mark();
     }
+    const unsigned ny = rep ? (unsigned)rep->n : 1u;
     {
-        ProfScope ps("fused_mlp3_chain", st);
-        launch_k(ps, mlp3_chain_kernel, dim3((unsigned)G), dim3(M3_NT), sizeof(Mlp3Lds), st, a);
+        ProfScope ps(rep ? "fused_mlp3_chain_replicas" : "fused_mlp3_chain", st);
+        if (rep) launch_k(ps, mlp3_chain_replicas_kernel, dim3((unsigned)G, ny), dim3(M3_NT), sizeof(Mlp3Lds), st, a, rep->rp);
+        else launch_k(ps, mlp3_chain_kernel, dim3((unsigned)G), dim3(M3_NT), sizeof(Mlp3Lds), st, a);
         VAEK_HIP_CHECK(hipGetLastError());
     }
     Mlp3GradArgs f{};
@@ -520,13 +436,52 @@ int mlp3_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* v
     f.grads = grads;
     f.params_rw = apply_adam ? params : nullptr; f.m = apply_adam ? m : nullptr; f.v = apply_adam ? v : nullptr;
     f.step_dev = step_dev; f.lr = lr;
-    f.loss_hist = (apply_adam && c->cfg.world == 1) ? c->loss_hist : nullptr; f.loss_hist_cap = c->loss_hist_cap;
+    if (rep) {                       // the caller's rings, never the context's
+        f.loss_hist = rep->loss_hist; f.loss_hist_cap = rep->loss_hist ? rep->loss_hist_cap : 0;
+    } else {
+        f.loss_hist = (apply_adam && c->cfg.world == 1) ? c->loss_hist : nullptr; f.loss_hist_cap = c->loss_hist_cap;
+    }
     BatchArgs none{};
     const long long ngen = gen ? (make_batch_item_count(*gen) + M3_NT - 1) / M3_NT : 0;
-    ProfScope ps(gen ? "fused_mlp3_grads_adam_gen" : apply_adam ? "fused_mlp3_grads_adam" : "fused_mlp3_grads", st);
-    launch_k(ps, mlp3_grad_kernel, dim3((unsigned)(ntiles + 1 + ngen)), dim3(M3_NT), 0, st, f, gen ? *gen : none);
+    const unsigned nx = (unsigned)(ntiles + 1 + ngen);
+    if (rep) {
+        ProfScope ps(gen ? "fused_mlp3_grads_adam_gen_replicas" : "fused_mlp3_grads_adam_replicas", st);
+        launch_k(ps, mlp3_grad_replicas_kernel, dim3(nx, ny), dim3(M3_NT), 0, st, f, gen ? *gen : none, rep->rp);
+    } else {
+        ProfScope ps(gen ? "fused_mlp3_grads_adam_gen" : apply_adam ? "fused_mlp3_grads_adam" : "fused_mlp3_grads", st);
+        launch_k(ps, mlp3_grad_kernel, dim3(nx), dim3(M3_NT), 0, st, f, gen ? *gen : none);
+    }
     VAEK_HIP_CHECK(hipGetLastError());
     return VAEK_OK;
+}
+
+int mlp3_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x, const float* z1,
+                    const float* z2, float lr, bool apply_adam, void* ws, hipStream_t st, const BatchArgs* gen) {
+    return mlp3_step_impl(c, params, grads, m, v, step_dev, x, z1, z2, lr, apply_adam, ws, st, gen, nullptr);
+}
+
+// ---- the replica form: vaek_train_step_gen_replicas ---------------------------------------------------------------------------
+// 256 replicas = 1792 chain workgroups at batch 100, seven rounds on the MI355X's 256 CUs: a cap that bounds the length of one launch
+// on a shared machine, not a tuned value.  36 replicas fill the first round; more is legal, the extra workgroups queue.
+constexpr int kMlp3MaxReplicas = 256;
+int mlp3_max_replicas() { return kMlp3MaxReplicas; }
+
+// floats of one replica's region of the call's OWN workspace: the solo region, rounded up to whole float4s so that every replica's
+// region keeps the 16-byte alignment of the base
+size_t mlp3_replica_region_floats(const vaek_ctx* c) { return ((mlp3_workspace_bytes(c) / sizeof(float)) + 3) & ~(size_t)3; }
+size_t mlp3_replicas_workspace_bytes(const vaek_ctx* c, int n) { return (size_t)n * mlp3_replica_region_floats(c) * sizeof(float); }
+
+int mlp3_train_step_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x,
+                             const float* z1, const float* z2, float lr, void* ws, hipStream_t st, const BatchArgs* gen, int n,
+                             long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
+                             long long a_stride, float* loss_hist, long long loss_hist_cap) {
+    Mlp3ReplicaHost rep{};
+    rep.n = n;
+    rep.rp.state_stride = state_stride; rep.rp.grads_stride = grads_stride; rep.rp.a_stride = a_stride;
+    rep.rp.region_floats = (long long)mlp3_replica_region_floats(c);
+    rep.rp.seeds = seeds; rep.rp.lrs = lrs;
+    rep.loss_hist = loss_hist; rep.loss_hist_cap = loss_hist_cap;
+    return mlp3_step_impl(c, params, grads, m, v, step_dev, x, z1, z2, lr, true, ws, st, gen, &rep);
 }
 
 }  // namespace vaek

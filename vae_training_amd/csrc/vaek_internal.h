@@ -418,5 +418,15 @@ size_t mlp3_workspace_bytes(const vaek_ctx* c);   // the region at ws_mlp3: stor
 // two launches (chain; gradients + tail + Adam); gen != nullptr: the second carries workgroups that draw the NEXT step's batch
 int mlp3_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x, const float* z1,
                     const float* z2, float lr, bool apply_adam, void* ws, hipStream_t st, const BatchArgs* gen = nullptr);
+// the same train step for n independent models of the context's shape, blockIdx.y = replica (vaek_train_step_gen_replicas): two
+// launches whatever n is; `ws` is the call's own workspace of mlp3_replicas_workspace_bytes(c, n) bytes, not the context's; x / z1 /
+// z2 and the generator's outputs are [n][B][..] stacks; state_stride % 4 == 0 (every replica then takes the base's dX load form)
+int mlp3_max_replicas();
+size_t mlp3_replica_region_floats(const vaek_ctx* c);
+size_t mlp3_replicas_workspace_bytes(const vaek_ctx* c, int n);
+int mlp3_train_step_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x,
+                             const float* z1, const float* z2, float lr, void* ws, hipStream_t st, const BatchArgs* gen, int n,
+                             long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
+                             long long a_stride, float* loss_hist, long long loss_hist_cap);
 
 }  // namespace vaek

@@ -206,6 +206,52 @@ class Engine:
                                                          int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(row0),
                                                          int(tag), int(n_steps), float(lr), _ptr(workspace), _stream()))
 
+    def supports_train_step_replicas(self):
+        """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_train_step_replicas(self.h, C.byref(f)))
+        return bool(f.value)
+
+    @property
+    def train_step_max_replicas(self):
+        return int(self.lib.vaek_train_step_max_replicas())
+
+    def train_step_replicas_workspace(self, n):
+        """Bytes of the workspace Engine.train_step_gen_replicas needs for n replicas (its own buffer, not self.workspace): n times
+        the mlp3 step's region of stored activations."""
+        b = C.c_size_t()
+        _lib.check(self.lib.vaek_train_step_replicas_workspace_bytes(self.h, int(n), C.byref(b)))
+        return int(b.value)
+
+    def train_step_gen_replicas(self, params, grads, m, v, step_dev, cur, lr, kind, A, dd, did, pad, var_added, nxt, seeds, counter,
+                                which, lrs=None, a_stride=0, loss_hist=None, workspace=None, tag=0, row0=0, n=None, state_stride=None,
+                                grads_stride=None, loss_hist_cap=None):
+        """ONE train step of EACH of n independent three-hidden-layer MLP VAEs of this engine's shape, two launches whatever n is
+        (vaek_train_step_gen_replicas): replica r trains on cur = (x [n, B, D], z1 [n, B, L], z2 [n, B, D])[r] and draws its next
+        batch into nxt[r] (generator step counter[r, which]; counter[r, which ^ 1] = step + 1 is stored; counter: int32 [n, 2]).
+        nxt = None: nothing is drawn (n x train_step; seeds, A and counter may be None).  params / m / v: [n, state_stride] with
+        state_stride a multiple of 4, grads: [n, grads_stride], step_dev: int32 [n], seeds: int64 [n], lrs: float32 [n] or None
+        (then `lr` for all), A: replica r's at A + r * a_stride floats (0: shared), loss_hist: [n, cap] or None, workspace: uint8 of
+        train_step_replicas_workspace(n) bytes -- all device tensors; n, the strides and cap default to the tensors' shapes.
+        Replica r ends bitwise where train_step_gen alone on its slices would.  Asynchronous; capturable."""
+        rep = _lib.VaekReplicas()
+        rep.struct_size = C.sizeof(_lib.VaekReplicas)
+        rep.n = int(params.shape[0] if n is None else n)
+        rep.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        rep.grads_stride = int(grads.shape[1] if grads_stride is None else grads_stride)
+        assert seeds is None or seeds.dtype == torch.int64
+        assert lrs is None or lrs.dtype == torch.float32
+        assert counter is None or (counter.dtype == torch.int32 and counter.is_cuda)
+        rep.seeds, rep.lrs = _ptr(seeds), _ptr(lrs)
+        rep.a_stride = int(a_stride)
+        rep.loss_hist = _ptr(loss_hist)
+        rep.loss_hist_cap = int((0 if loss_hist is None else loss_hist.shape[-1]) if loss_hist_cap is None else loss_hist_cap)
+        nxt = (None, None, None) if nxt is None else nxt
+        _lib.check(self.lib.vaek_train_step_gen_replicas(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep),
+                                                         _ptr(cur[0]), _ptr(cur[1]), _ptr(cur[2]), float(lr), _ptr(workspace), int(kind),
+                                                         _ptr(A), int(dd), int(did), int(pad), float(var_added), _ptr(nxt[0]), _ptr(nxt[1]),
+                                                         _ptr(nxt[2]), int(row0), _ptr(counter), int(which), int(tag), _stream()))
+
     def plan_train_steps(self, params, grads, m, v, step_dev, batches, lr):
         """The same call with its arguments marshalled once: returns a function that issues vaek_train_steps on these buffers
         again (the pointer arrays, not the data, are frozen) -- for loops that repeat a group of steps, where building three

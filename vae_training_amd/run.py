@@ -54,9 +54,11 @@ def build_parser():
     p.add_argument("--no_fast_loop", dest="fast_loop", action="store_false",
                    help="the reference's loop shape: one get_batch + one train_step call per iteration (model.py:221-222)")
     p.add_argument("--sweep_dataset_seeds", dest="sweep_dataset_seeds", type=_int_list, default=None, metavar="S1,S2,...",
-                   help="train one model per dataset seed in ONE launch per run of steps (trainer.ReplicaLoop: workgroup r of "
-                        "vaek_train_loop_gen_replicas trains the model of seed r); output directories NAME_ds<seed>.  Linear VAEs the "
-                        "resident loop covers only, single GPU only")
+                   help="train one model per dataset seed together; output directories NAME_ds<seed>.  Linear VAEs the resident loop covers: "
+                        "ONE launch per run of steps (trainer.ReplicaLoop: workgroup r of vaek_train_loop_gen_replicas trains the model of "
+                        "seed r).  Three-hidden-layer MLP VAEs on the \"mlp3\" train step: a hipGraph loop whose every step trains all "
+                        "models in two launches (trainer.ReplicaGraphLoop, vaek_train_step_gen_replicas).  Other models are refused; "
+                        "single GPU only")
     return p
 
 
@@ -142,14 +144,30 @@ def _get_model_dp(args, dataset, output_dir, dist, world, rank):
     return m
 
 
+def sweep_loop(models):
+    """The loop of --sweep_dataset_seeds: ReplicaLoop where the resident loop covers the models (small-batch linear VAEs), else
+    ReplicaGraphLoop where the engine's step has a replica form (the "mlp3" step), else a refusal that names both."""
+    from .trainer import ReplicaGraphLoop, ReplicaLoop
+    m0 = models[0]
+    eng = m0.model.module.engine(m0.batch_size, m0.optimizer.global_batch)
+    if eng.world > 1 or eng.supports_train_loop_gen(m0.dataset.device_spec()[0]):
+        return ReplicaLoop(models)           # today's behaviour, its own refusals included
+    if eng.supports_train_step_replicas():
+        return ReplicaGraphLoop(models)
+    raise RuntimeError("--sweep_dataset_seeds: neither replica loop covers this model: trainer.ReplicaLoop (vaek_train_loop_gen_replicas) "
+                       "needs a float32 linear VAE with one or two decoders, D, L <= 32 and a batch of at most 256 rows; "
+                       "trainer.ReplicaGraphLoop (vaek_train_step_gen_replicas) needs the \"mlp3\" train step: float32, three hidden "
+                       f"layers of 64 .. 256 units both ways, D, L <= 32, a batch of at most 128 rows (this model's step path: {eng.step_path})")
+
+
 def main_sweep(args):
     """--sweep_dataset_seeds: one dataset and one VAEModel per seed, the reference's schedule (model.py:207-222: stats every n_print
-    steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE ReplicaLoop.run between
-    events for all of them."""
+    steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE loop.run between
+    events for all of them: trainer.ReplicaLoop where the resident loop covers the models, else trainer.ReplicaGraphLoop where the
+    "mlp3" step's replica form does (sweep_loop)."""
     import copy
     import os
 
-    from .trainer import ReplicaLoop
     from .utils import make_output_dir
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise RuntimeError("--sweep_dataset_seeds trains independent models on one GPU: it does not combine with data parallelism")
@@ -165,7 +183,7 @@ def main_sweep(args):
         if ds is None:
             raise ValueError("--dataset must be one of sphere, linear_gaussian, sigmoid")
         models.append(get_model(a, ds, out))
-    loop = ReplicaLoop(models)               # refuses, before any step, what the resident loop does not cover
+    loop = sweep_loop(models)                # refuses, before any step, what neither replica loop covers
     eng = loop.eng
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")

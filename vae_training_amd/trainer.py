@@ -32,7 +32,9 @@ no hipGraph; there is one workgroup, so there is nothing to wait for and check()
 every model that takes it today still does.
 
 ReplicaLoop (below GraphLoop) is the resident loop for a SWEEP: R models of one shape, one workgroup each, in one launch per run of
-steps (vaek_train_loop_gen_replicas); `run.py --sweep_dataset_seeds` drives it."""
+steps (vaek_train_loop_gen_replicas); `run.py --sweep_dataset_seeds` drives it.  ReplicaGraphLoop (below it) is the sweep of the
+models the resident loop does not cover but the whole-network "mlp3" step does: the pipelined hipGraph loop with every step ONE
+vaek_train_step_gen_replicas call for all R models."""
 from __future__ import annotations
 
 import torch
@@ -299,6 +301,171 @@ class ReplicaLoop:
 
     def check(self):
         """Nothing to poll: the launch has no waits."""
+
+    def losses(self, r):
+        """Losses of all steps model r has run so far, in order (device -> host once)."""
+        n = self.ms[r].optimizer.state.step
+        cap = self.rings.shape[1]
+        ring = self.rings[r].cpu()
+        if n <= cap:
+            return ring[:n]
+        k = n % cap
+        return torch.cat([ring[k:], ring[:k]])
+
+    def view(self, r):
+        """Model r's `_graph_loop`: losses() without an argument, as VAEModel.model_save_data calls it."""
+        return _ReplicaLosses(self, r)
+
+
+class ReplicaGraphLoop:
+    """A sweep of three-hidden-layer MLP VAEs (step path "mlp3") as GraphLoop's pipelined hipGraph loop with R models per step: R
+    VAEModels of one shape -- validated as in ReplicaLoop: one batch size, data and latent dimension, architecture, epsilon,
+    dataset kind, -dd, -did, padding and dataset noise -- each with its own dataset matrix, parameters, Adam state and learning
+    rate.  Every step is ONE vaek_train_step_gen_replicas call (csrc/fused_mlp3.hip: two launches, blockIdx.y = model): it trains
+    model r on its slice of one stacked batch buffer and draws model r's next batch into its slice of the other.  Model r's RNG
+    seed is the one GraphLoop derives for it, so model r ends bitwise where GraphLoop(model r, moments=False, resident=False) ends.
+
+    The states live in [R, stride] stacks owned by the loop, stride = P rounded up to a multiple of 4 (the library's stride rule);
+    they are COPIED at the boundaries of run(), in before the steps and out after them, as in ReplicaLoop: between two run() calls
+    every model is an ordinary model.  The stacked batch buffers hold each model's NEXT batch between runs; a model whose step
+    counter was changed between two runs (a loaded checkpoint) has the buffers drawn afresh.
+
+    As in GraphLoop there are two batch buffers and a generator counter pair per model ([R, 2]); a graph of steps_per_graph steps
+    (made even) is captured once, after one eager warm-up step, and replayed on the buffer parity it was captured on.  Single GPU
+    only.  Neither launch waits for anything: check() polls nothing."""
+
+    def __init__(self, vae_models, steps_per_graph=200, loss_capacity=None):
+        ms = list(vae_models)
+        if not ms:
+            raise RuntimeError("ReplicaGraphLoop: no models")
+        from .datasets import DEVICE_DRAW_MAX_DIM
+        self.ms = ms
+        m0 = ms[0]
+        self.B = m0.batch_size
+        self.eng = m0.model.module.engine(self.B, m0.optimizer.global_batch)
+        specs = [m.dataset.device_spec() for m in ms]
+        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
+        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
+            raise RuntimeError(f"ReplicaGraphLoop draws its batches with libvaek's Philox generator, which supports -dd / -did <= "
+                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
+        if self.eng.world > 1:
+            raise RuntimeError("ReplicaGraphLoop: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
+        if not self.eng.supports_train_step_replicas():
+            raise RuntimeError("ReplicaGraphLoop: vaek_train_step_gen_replicas does not cover this model (it needs the \"mlp3\" train step: "
+                               "float32, three hidden layers of 64 .. 256 units in encoder and decoder, D, L <= 32, a batch of at most 128 rows)")
+        R = len(ms)
+        if R > self.eng.train_step_max_replicas:
+            raise RuntimeError(f"ReplicaGraphLoop: {R} models, at most {self.eng.train_step_max_replicas} fit one step "
+                               "(vaek_train_step_max_replicas)")
+        want = ReplicaLoop._signature(m0, specs[0])
+        for r, (m, sp) in enumerate(zip(ms, specs)):
+            got = ReplicaLoop._signature(m, sp)
+            if got != want:
+                raise RuntimeError(f"ReplicaGraphLoop: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
+                                   f"{want}): one step trains replicas of ONE shape")
+        self.R = R
+        self.G = int(steps_per_graph) + int(steps_per_graph) % 2      # two batch buffers: a replay starts on the parity it was captured on
+        dev = self.eng.device
+        D, L = self.eng.D, self.eng.L
+        self.P, GL = m0.model.flat.numel(), m0.optimizer.state.grads.numel()
+        self.stride = (self.P + 3) // 4 * 4
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
+        self.params, self.m, self.v, self.grads = f32(R, self.stride), f32(R, self.stride), f32(R, self.stride), f32(R, GL)
+        self.step_dev = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.seed_list = [(m.dataset.key[0] ^ m.dataset.key[1] ^ m.key[1]) & (2 ** 64 - 1) for m in ms]      # GraphLoop's, model by model
+        self.seeds = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in self.seed_list], dtype=torch.int64, device=dev)
+        self.lrs = torch.tensor([float(m.optimizer.optimizer_def.learning_rate) for m in ms], dtype=torch.float32, device=dev)
+        if specs[0][1] is None:
+            self.A, self.a_stride = None, 0
+        else:
+            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
+            self.a_stride = self.A.shape[1]
+        if loss_capacity is None:             # every step of the longest schedule among the models
+            loss_capacity = max(int(getattr(m, "num_batches", 0) or 0) for m in ms) or (1 << 16)
+        self.rings = f32(R, int(loss_capacity))
+        self.bufs = [(f32(R, self.B, D), f32(R, self.B, L), f32(R, self.B, D)) for _ in range(2)]
+        self.counter = torch.zeros(R, 2, dtype=torch.int32, device=dev)
+        self.workspace = torch.empty(max(self.eng.train_step_replicas_workspace(R), 16), dtype=torch.uint8, device=dev)
+        self.par = 0                          # the buffer that holds the next step's batches
+        self.expect = None                    # the models' step counters at which self.bufs[self.par] is valid
+        self.graph = None
+        self.graph_parity = 0
+
+    def _rows(self, m, r):
+        st = m.optimizer.state
+        P = self.P
+        return ((self.params[r, :P], m.model.flat), (self.grads[r], st.grads), (self.m[r, :P], st.m), (self.v[r, :P], st.v),
+                (self.step_dev[r:r + 1], st.step_dev))
+
+    def _prime(self):
+        """Model r's batch of its next step n_r into self.bufs[self.par][.][r] and its counter pair to (n_r, n_r + 1) in the order
+        the steps alternate in -- GraphLoop's invariant, model by model (vaek_make_batch_next on each model's slices)."""
+        p = self.par
+        steps = [int(m.optimizer.state.step) for m in self.ms]
+        self.counter.copy_(torch.tensor([[n, n] for n in steps], dtype=torch.int32))
+        for r in range(self.R):
+            self.eng.make_batch(self.kind, None if self.A is None else self.A[r], self.dd, self.did, self.pad, self.var, self.B,
+                                self.seed_list[r], tag=0, row0=0, out=tuple(t[r] for t in self.bufs[p]), counter=self.counter[r], which=p)
+        self.expect = steps
+
+    def _one(self):
+        p = self.par
+        self.eng.train_step_gen_replicas(self.params, self.grads, self.m, self.v, self.step_dev, self.bufs[p], 0.0, self.kind, self.A,
+                                         self.dd, self.did, self.pad, self.var, self.bufs[p ^ 1], self.seeds, self.counter, p ^ 1,
+                                         lrs=self.lrs, a_stride=self.a_stride, loss_hist=self.rings, workspace=self.workspace, tag=0,
+                                         row0=0)
+        self.par = p ^ 1
+
+    def _capture(self):
+        self._one()                              # warm-up outside capture (lazy kernel attributes)
+        torch.cuda.synchronize()
+        self.graph_parity = self.par
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                for _ in range(self.G):          # an even number of steps: self.par ends where it began
+                    self._one()
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = g
+        return 1
+
+    def run(self, n_steps):
+        """Exactly n_steps train steps of every model: one library call per step (or per replayed graph node) between the copies
+        in and out."""
+        if n_steps <= 0:
+            return
+        for r, m in enumerate(self.ms):
+            for row, own in self._rows(m, r):
+                row.copy_(own)
+        if self.expect != [int(m.optimizer.state.step) for m in self.ms]:
+            self._prime()
+        done = 0
+        if self.graph is None and n_steps >= self.G + 1:
+            done += self._capture()
+        if self.graph is not None and n_steps - done > self.G and self.par != self.graph_parity:
+            self._one()                          # back onto the buffer parity the graph was captured on
+            done += 1
+        if self.graph is not None and self.par == self.graph_parity:
+            while n_steps - done >= self.G:
+                self.graph.replay()
+                done += self.G
+        for _ in range(n_steps - done):
+            self._one()
+        for r, m in enumerate(self.ms):
+            for row, own in self._rows(m, r):
+                own.copy_(row)
+            m.optimizer.state.step += n_steps
+        self.expect = [int(m.optimizer.state.step) for m in self.ms]
+
+    def describe(self):
+        """One line for run.py."""
+        return (f"hipGraph of {self.G} steps, {self.R} replicas per step (vaek_train_step_gen_replicas), "
+                "next batches drawn inside the step's second launch")
+
+    def check(self):
+        """Nothing to poll: neither launch has a wait."""
 
     def losses(self, r):
         """Losses of all steps model r has run so far, in order (device -> host once)."""
