@@ -346,6 +346,48 @@ int vaek_train_loop_replicas_workspace_bytes(const vaek_ctx* ctx, int32_t n, siz
 int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
                                  const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
                                  float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream);
+/* TRAJECTORY RING of the resident loop: parameter and gradient records written INSIDE the launch (csrc/linear_resident.hip).  The
+ * resident loop keeps params, m and v on chip for up to 1024 steps and stores grads at a launch's last step only; a caller who
+ * studies training dynamics (the reference's params_and_gradients list and its Correlation Ratio, vae.py:143-179, :203-209) had
+ * to cut the loop to see the model.  With a vaek_trajectory the workgroup stores, at every Adam step t with t % every == 0 (t is
+ * 1-based: the value *step_dev takes AFTER the step), one record of vaek_trajectory_record_len = 2 P + 4 floats, BEFORE that step's
+ * Adam update:
+ *   [0, P)         the parameters step t's gradient was evaluated at -- the state after t - 1 steps;
+ *   [P, 2 P + 4)   the gradient buffer of step t exactly as `grads` would hold it if the call ended at step t (vaek_grad_len floats:
+ *                  loss / mean Dkl / mean mse / 0 slots included).
+ * SLOT RULE: the record of step t goes to buf (+ r * replica_stride for replica r) + ((t / every - 1) % cap) * record_stride.  The
+ * slot depends on the global step alone, so placement is the same across the 1024-step launch boundary inside a call, across
+ * calls, after a resume from a checkpoint (*step_dev != 0) and under graph replay (t comes from the device-resident counter).  A
+ * ring of cap records keeps the last cap of them; slots no recorded step of this call maps to keep their contents; floats between
+ * two records or two rings, where a stride exceeds the length, are not touched.  The ring is written with per-lane vector stores
+ * and never read by the launch; no counter, no wait, no atomic is added.
+ * vaek_train_loop_gen_traj / vaek_train_loop_gen_replicas_traj take the arguments of vaek_train_loop_gen /
+ * vaek_train_loop_gen_replicas and a vaek_trajectory; traj == NULL is the plain call.  They cover exactly the contexts and kinds
+ * vaek_supports_train_loop_gen accepts, with the same workspace rules; asynchronous, allocate nothing, do not synchronise,
+ * capturable.  Profile labels linear_resident_traj / linear_resident_replicas_traj (the untraced launches keep theirs).
+ * DEFINING PROPERTY (bitwise, from the same start state and arguments): (a) the traced call leaves in params, m, v, grads,
+ * step_dev and the loss ring exactly what the untraced entry leaves; (b) for every recorded step t, record[0:P] equals the params
+ * an untraced call ending after t - 1 steps leaves and record[P:2P+4] the grads an untraced call ending after t steps leaves;
+ * (c) replica r's ring equals the ring of vaek_train_loop_gen_traj run alone on replica r's slices with seeds[r], lrs[r], its A.
+ * VAEK_ERR_INVALID (with a message, every buffer untouched): every < 1, cap < 1, NULL buf, record_stride < the record length,
+ * replica_stride < cap * record_stride in the replica form, a wrong struct_size, and everything the untraced entry refuses.
+ * n_steps == 0 returns VAEK_OK and touches nothing. */
+typedef struct vaek_trajectory {
+    int32_t struct_size;     /* = sizeof(vaek_trajectory), ABI guard */
+    int32_t every;           /* >= 1: Adam steps t with t % every == 0 are recorded */
+    float*  buf;             /* device; replica r's ring starts at buf + r * replica_stride */
+    int64_t cap;             /* records per ring; step t -> slot (t / every - 1) % cap */
+    int64_t record_stride;   /* floats between two records, >= vaek_trajectory_record_len */
+    int64_t replica_stride;  /* floats between two replicas' rings, >= cap * record_stride; ignored by the solo entry */
+} vaek_trajectory;
+int vaek_trajectory_record_len(const vaek_ctx* ctx, int64_t* floats);
+int vaek_train_loop_gen_traj(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
+                             int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
+                             float lr, void* workspace, void* stream, const vaek_trajectory* traj);
+int vaek_train_loop_gen_replicas_traj(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                      const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                                      float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream,
+                                      const vaek_trajectory* traj);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

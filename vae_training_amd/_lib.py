@@ -37,6 +37,22 @@ class VaekReplicas(C.Structure):
     ]
 
 
+class VaekTrajectory(C.Structure):
+    """vaek_trajectory of include/vaek.h: the trajectory ring of vaek_train_loop_gen_traj and vaek_train_loop_gen_replicas_traj
+    (`buf` is a device pointer; strides and cap count floats and records)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("every", C.c_int32), ("buf", C.c_void_p), ("cap", C.c_int64), ("record_stride", C.c_int64),
+        ("replica_stride", C.c_int64),
+    ]
+
+
+def trajectory_slot(t, every, cap):
+    """The slot rule of vaek_trajectory: the ring slot of the record of Adam step t (1-based), or None where step t is not recorded."""
+    if t < 1 or t % every:
+        return None
+    return (t // every - 1) % cap
+
+
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); exactly the symbols include/vaek.h declares
@@ -95,6 +111,11 @@ SIGNATURES = {
     "vaek_train_loop_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),
     "vaek_train_loop_gen_replicas": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(VaekReplicas), _i32, _vp, _i32, _i32, _i32, _f32,
                                                C.c_int64, C.c_uint32, _i32, _f32, _vp, _vp]),
+    "vaek_trajectory_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "vaek_train_loop_gen_traj": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _f32, C.c_int64, C.c_uint64, C.c_uint32, _i32,
+                                           _f32, _vp, _vp, C.POINTER(VaekTrajectory)]),
+    "vaek_train_loop_gen_replicas_traj": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(VaekReplicas), _i32, _vp, _i32, _i32, _i32, _f32,
+                                                    C.c_int64, C.c_uint32, _i32, _f32, _vp, _vp, C.POINTER(VaekTrajectory)]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

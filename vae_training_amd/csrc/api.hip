@@ -864,43 +864,84 @@ int vaek_train_loop_replicas_workspace_bytes(const vaek_ctx* ctx, int32_t n, siz
     return VAEK_OK;
 }
 
-int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
-                                 const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                                 float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream) {
+// ---- the trajectory ring of the resident loop: vaek_train_loop_gen_traj, vaek_train_loop_gen_replicas_traj ---------------------------
+int vaek_trajectory_record_len(const vaek_ctx* ctx, int64_t* floats) {
+    if (!ctx || !floats) { set_error("vaek_trajectory_record_len: null argument"); return VAEK_ERR_INVALID; }
+    *floats = 2 * (int64_t)ctx->P + kExtra;
+    return VAEK_OK;
+}
+
+// A vaek_trajectory checked against the context (`replicas`: the replica form, where replica_stride counts) and turned into the
+// kernel's TrajArgs: after it every store of the launch lands inside the caller's ring.  Needs a non-null context.
+static int check_trajectory(const char* who, const vaek_ctx* ctx, const vaek_trajectory* traj, bool replicas, TrajArgs* out) {
+    if (traj->struct_size != (int32_t)sizeof(vaek_trajectory)) {
+        set_error("%s: vaek_trajectory.struct_size %d != %d (header / library mismatch)", who, traj->struct_size, (int)sizeof(vaek_trajectory));
+        return VAEK_ERR_INVALID;
+    }
+    const int64_t len = 2 * (int64_t)ctx->P + kExtra;
+    if (traj->every < 1) { set_error("%s: trajectory every = %d, need >= 1", who, traj->every); return VAEK_ERR_INVALID; }
+    if (traj->cap < 1) { set_error("%s: trajectory cap = %lld, need >= 1", who, (long long)traj->cap); return VAEK_ERR_INVALID; }
+    if (!traj->buf) { set_error("%s: trajectory buf is NULL", who); return VAEK_ERR_INVALID; }
+    if (traj->record_stride < len) {
+        set_error("%s: trajectory record_stride %lld < record length %lld (vaek_trajectory_record_len)", who, (long long)traj->record_stride,
+                  (long long)len);
+        return VAEK_ERR_INVALID;
+    }
+    if (traj->cap > INT64_MAX / traj->record_stride) {
+        set_error("%s: trajectory cap %lld * record_stride %lld overflows", who, (long long)traj->cap, (long long)traj->record_stride);
+        return VAEK_ERR_INVALID;
+    }
+    if (replicas && traj->replica_stride < traj->cap * traj->record_stride) {
+        set_error("%s: trajectory replica_stride %lld < cap * record_stride = %lld", who, (long long)traj->replica_stride,
+                  (long long)(traj->cap * traj->record_stride));
+        return VAEK_ERR_INVALID;
+    }
+    out->buf = traj->buf; out->every = traj->every; out->cap = traj->cap; out->record_stride = traj->record_stride;
+    out->replica_stride = replicas ? traj->replica_stride : 0;
+    return VAEK_OK;
+}
+
+// vaek_train_loop_gen_replicas (traj == nullptr) and vaek_train_loop_gen_replicas_traj: one list of checks, in one order
+static int train_loop_gen_replicas_impl(const char* who, vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                        const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                                        float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream,
+                                        const vaek_trajectory* traj) {
     ProfBind pb(ctx);
     if (!ctx || !params || !grads || !m || !v || !step_dev || !rep || n_steps < 0) {
-        set_error("vaek_train_loop_gen_replicas: invalid argument");
+        set_error("%s: invalid argument", who);
         return VAEK_ERR_INVALID;
     }
     if (rep->struct_size != (int32_t)sizeof(vaek_replicas)) {
-        set_error("vaek_train_loop_gen_replicas: vaek_replicas.struct_size %d != %d (header / library mismatch)", rep->struct_size, (int)sizeof(vaek_replicas));
+        set_error("%s: vaek_replicas.struct_size %d != %d (header / library mismatch)", who, rep->struct_size, (int)sizeof(vaek_replicas));
         return VAEK_ERR_INVALID;
     }
     if (!ctx->resident) {
-        set_error("vaek_train_loop_gen_replicas: needs a context vaek_train_loop_gen covers (see vaek_supports_train_loop_gen)");
+        set_error("%s: needs a context vaek_train_loop_gen covers (see vaek_supports_train_loop_gen)", who);
         return VAEK_ERR_INVALID;
     }
     if (rep->n < 1 || rep->n > resident_max_replicas()) {
-        set_error("vaek_train_loop_gen_replicas: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", rep->n, resident_max_replicas());
+        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, rep->n, resident_max_replicas());
         return VAEK_ERR_INVALID;
     }
     if (rep->state_stride < ctx->P || rep->grads_stride < ctx->P + kExtra) {
-        set_error("vaek_train_loop_gen_replicas: state_stride %lld < P = %lld or grads_stride %lld < grad_len = %lld", (long long)rep->state_stride,
+        set_error("%s: state_stride %lld < P = %lld or grads_stride %lld < grad_len = %lld", who, (long long)rep->state_stride,
                   (long long)ctx->P, (long long)rep->grads_stride, (long long)(ctx->P + kExtra));
         return VAEK_ERR_INVALID;
     }
-    if (!rep->seeds) { set_error("vaek_train_loop_gen_replicas: seeds is NULL"); return VAEK_ERR_INVALID; }
-    if (rep->a_stride < 0) { set_error("vaek_train_loop_gen_replicas: a_stride %lld < 0", (long long)rep->a_stride); return VAEK_ERR_INVALID; }
+    if (!rep->seeds) { set_error("%s: seeds is NULL", who); return VAEK_ERR_INVALID; }
+    if (rep->a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)rep->a_stride); return VAEK_ERR_INVALID; }
     if (rep->loss_hist && rep->loss_hist_cap < 1) {
-        set_error("vaek_train_loop_gen_replicas: loss_hist given with loss_hist_cap %lld < 1", (long long)rep->loss_hist_cap);
+        set_error("%s: loss_hist given with loss_hist_cap %lld < 1", who, (long long)rep->loss_hist_cap);
         return VAEK_ERR_INVALID;
     }
     const size_t ws_bytes = resident_replicas_workspace_bytes(ctx, rep->n);
     if (ws_bytes && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15))) {
-        set_error("vaek_train_loop_gen_replicas: this context stages its batches in memory: workspace must be a 16-byte aligned device "
-                  "pointer of vaek_train_loop_replicas_workspace_bytes() = %zu bytes", ws_bytes);
+        set_error("%s: this context stages its batches in memory: workspace must be a 16-byte aligned device "
+                  "pointer of vaek_train_loop_replicas_workspace_bytes() = %zu bytes", who, ws_bytes);
         return VAEK_ERR_INVALID;
     }
+    TrajArgs tj{};
+    if (traj) { const int trc = check_trajectory(who, ctx, traj, true, &tj); if (trc) return trc; }
     BatchArgs gen;
     // (as vaek_train_loop_gen: the kernel points the generator at its own batch image, and puts seeds[r] in place of the seed; the
     // dummy non-null x / z pair passes the argument check, which also fences kind to 0 .. 2 and dd, did to <= 16)
@@ -911,7 +952,46 @@ int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, flo
     if (n_steps == 0) return VAEK_OK;
     return resident_train_loop_replicas(ctx, params, grads, m, v, step_dev, gen, rep->n, rep->state_stride, rep->grads_stride,
                                         reinterpret_cast<const unsigned long long*>(rep->seeds), rep->lrs, rep->a_stride, rep->loss_hist,
-                                        rep->loss_hist_cap, n_steps, lr, workspace, (hipStream_t)stream);
+                                        rep->loss_hist_cap, n_steps, lr, workspace, (hipStream_t)stream, traj ? &tj : nullptr);
+}
+
+int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                 const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                                 float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream) {
+    return train_loop_gen_replicas_impl("vaek_train_loop_gen_replicas", ctx, params, grads, m, v, step_dev, rep, kind, A, dd, did, pad, var_added,
+                                        row0, tag, n_steps, lr, workspace, stream, nullptr);
+}
+
+int vaek_train_loop_gen_replicas_traj(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                      const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                                      float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream,
+                                      const vaek_trajectory* traj) {
+    return train_loop_gen_replicas_impl(traj ? "vaek_train_loop_gen_replicas_traj" : "vaek_train_loop_gen_replicas", ctx, params, grads, m, v,
+                                        step_dev, rep, kind, A, dd, did, pad, var_added, row0, tag, n_steps, lr, workspace, stream, traj);
+}
+
+int vaek_train_loop_gen_traj(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
+                             int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
+                             float lr, void* workspace, void* stream, const vaek_trajectory* traj) {
+    if (!traj) return vaek_train_loop_gen(ctx, params, grads, m, v, step_dev, kind, A, dd, did, pad, var_added, row0, seed, tag, n_steps, lr,
+                                          workspace, stream);
+    ProfBind pb(ctx);
+    if (!ctx || !params || !grads || !m || !v || !step_dev || n_steps < 0) { set_error("vaek_train_loop_gen_traj: invalid argument"); return VAEK_ERR_INVALID; }
+    if (!ctx->resident) {
+        set_error("vaek_train_loop_gen_traj: needs a context vaek_train_loop_gen covers (see vaek_supports_train_loop_gen)");
+        return VAEK_ERR_INVALID;
+    }
+    TrajArgs tj{};
+    int rc = check_trajectory("vaek_train_loop_gen_traj", ctx, traj, false, &tj);
+    if (rc) return rc;
+    if ((rc = check_ws(ctx, workspace))) return rc;
+    BatchArgs gen;
+    // (as vaek_train_loop_gen: a dummy non-null x / z pair passes the generator's argument check)
+    float* dummy = reinterpret_cast<float*>(workspace);
+    if ((rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, dummy, dummy, dummy, ctx->B, row0, seed, step_dev, 0, nullptr, 0, tag, &gen))) return rc;
+    gen.x = gen.z1 = gen.z2 = nullptr;
+    if (n_steps == 0) return VAEK_OK;
+    return resident_train_loop(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream, &tj);
 }
 
 // ---- the replica form of the mlp3 step (fused_mlp3.hip): n models of one shape per step, blockIdx.y = replica ----------------------

@@ -87,12 +87,40 @@ __device__ __forceinline__ ResidentArgs replica_slice(const ResidentArgs& a0, co
     return a;
 }
 
+// THE TRAJECTORY RING (vaek_train_loop_gen_traj / vaek_train_loop_gen_replicas_traj).  A TrajArgs at the end of the pack makes the
+// traced form: at every Adam step t with t % every == 0 the workgroup stores one record of 2 P + 4 floats -- [0, P) the parameters
+// step t's gradient was evaluated at (pk before adam_apply_f), [P, 2 P + 4) the step's gradient buffer exactly as `grads` would
+// hold it (gk, loss slots included) -- to slot (t / every - 1) % cap of its ring.  Both are in this thread's registers at that
+// point: the record is per-lane vector stores and nothing else.  The rule above is kept: the ring is stored only, never read.
+// Without a TrajArgs in the pack TrajOff is what the body sees and `if constexpr` removes every line of it: the untraced kernels
+// are the text they were.
+struct TrajOff { static constexpr bool on = false; };
+struct TrajRing {
+    static constexpr bool on = true;
+    float* buf; int every; long long cap, record_stride;
+    // where step `tstep`'s record goes, or nullptr where the step is not recorded (tstep > 0: a slot is never negative)
+    __device__ __forceinline__ float* record(int tstep) const {
+        if (tstep <= 0 || tstep % every != 0) return nullptr;
+        return buf + (long long)(tstep / every - 1) % cap * record_stride;
+    }
+};
+__device__ __forceinline__ TrajOff traj_ring() { return {}; }
+__device__ __forceinline__ TrajOff traj_ring(const ReplicaArgs&) { return {}; }
+__device__ __forceinline__ TrajRing traj_ring(const TrajArgs& tj) { return {tj.buf, tj.every, tj.cap, tj.record_stride}; }
+__device__ __forceinline__ TrajRing traj_ring(const ReplicaArgs&, const TrajArgs& tj) {
+    return {tj.buf + (long long)blockIdx.x * tj.replica_stride, tj.every, tj.cap, tj.record_stride};
+}
+__device__ __forceinline__ const ResidentArgs& replica_slice(const ResidentArgs& a, const TrajArgs&) { return a; }
+__device__ __forceinline__ ResidentArgs replica_slice(const ResidentArgs& a0, const ReplicaArgs& rp, const TrajArgs&) { return replica_slice(a0, rp); }
+
 // RP is empty (vaek_train_loop_gen: one model, grid 1) or ReplicaArgs (vaek_train_loop_gen_replicas: N independent models of one
-// shape, workgroup r training replica r).  The body has no cross-workgroup state -- no counter, no wait, no atomic -- so the
-// replicas share nothing but the code and the launch-wide arguments.
+// shape, workgroup r training replica r), each with or without a trailing TrajArgs.  The body has no cross-workgroup state -- no
+// counter, no wait, no atomic -- so the replicas share nothing but the code and the launch-wide arguments.
 template <int DP, int LP, bool SIG, bool EXACT, typename... RP>
 __global__ __launch_bounds__(256) void linear_resident_kernel(const ResidentArgs a0, const RP... rp) {
     const ResidentArgs& a = replica_slice(a0, rp...);
+    [[maybe_unused]] const auto traj = traj_ring(rp...);
+    using TR = decltype(traj_ring(rp...));
     using G = MGeom<DP, LP, SIG>;
     using RG = RGeom<DP, LP, SIG>;
     using AD = typename G::AD;
@@ -537,6 +565,17 @@ __global__ __launch_bounds__(256) void linear_resident_kernel(const ResidentArgs
         const float bc1 = -expm1f((float)tstep * -0.10536051565782628f);
         const float bc2 = -expm1f((float)tstep * -0.0010005003335835335f);
         const bool last = it + 1 == a.n_steps;      // only the launch's last gradient is anybody's to read
+        if constexpr (TR::on) {
+            // the trajectory record of this step: theta BEFORE the update and the gradient evaluated at it, from registers
+            if (float* const rec = traj.record(tstep)) {
+#pragma unroll
+                for (int k = 0; k < NOUT; ++k) {
+                    const int idx = t + 256 * k;
+                    if (idx < a.P) rec[idx] = pk[k];
+                    if (idx < a.P + kExtra) rec[a.P + idx] = gk[k];
+                }
+            }
+        }
 #pragma unroll
         for (int k = 0; k < NOUT; ++k) {
             const int idx = t + 256 * k;
@@ -563,10 +602,16 @@ __global__ __launch_bounds__(256) void linear_resident_kernel(const ResidentArgs
 // ---- variant table: the shapes of fused_mfma.hip -----------------------------------------------------
 typedef void (*ResidentKernel)(const ResidentArgs);
 typedef void (*ResidentReplicasKernel)(const ResidentArgs, const ReplicaArgs);
-struct ResidentVariant { int dp, lp, sig, exact; ResidentKernel fn; size_t base_bytes; ResidentReplicasKernel fn_replicas; };
+typedef void (*ResidentTrajKernel)(const ResidentArgs, const TrajArgs);
+typedef void (*ResidentReplicasTrajKernel)(const ResidentArgs, const ReplicaArgs, const TrajArgs);
+struct ResidentVariant {
+    int dp, lp, sig, exact; ResidentKernel fn; size_t base_bytes; ResidentReplicasKernel fn_replicas;
+    ResidentTrajKernel fn_traj; ResidentReplicasTrajKernel fn_replicas_traj;
+};
 #define VAEK_RESIDENT_ROW(DP, LP, SIG, EXACT) \
     {DP, LP, SIG, EXACT, linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0>, sizeof(float) * RGeom<DP, LP, (SIG) != 0>::BASE_FLOATS, \
-     linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0, ReplicaArgs>},
+     linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0, ReplicaArgs>, linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0, TrajArgs>, \
+     linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0, ReplicaArgs, TrajArgs>},
 static const ResidentVariant kResidentVariants[] = {VAEK_MFMA_SHAPES(VAEK_RESIDENT_ROW)};
 #undef VAEK_RESIDENT_ROW
 
@@ -599,16 +644,17 @@ size_t resident_workspace_bytes(const vaek_ctx* c) {
 int resident_steps_per_launch() { return kResidentMaxSteps; }
 
 int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
-                        int n_steps, float lr, void* ws, hipStream_t st) {
+                        int n_steps, float lr, void* ws, hipStream_t st, const TrajArgs* traj) {
     const ResidentVariant* var = c->resident ? pick_resident(c) : nullptr;
     if (!var) { set_error("resident train loop not available for this configuration"); return VAEK_ERR_INVALID; }
     const bool in_lds = stage_in_lds(c, var);
     const size_t lds = var->base_bytes + (in_lds ? stage_bytes(c) : 0);
-    static thread_local PerDeviceOnce attr_set[sizeof(kResidentVariants) / sizeof(kResidentVariants[0])];
-    PerDeviceOnce& once = attr_set[var - kResidentVariants];
+    static thread_local PerDeviceOnce attr_set[2][sizeof(kResidentVariants) / sizeof(kResidentVariants[0])];      // [traced]: two kernels
+    PerDeviceOnce& once = attr_set[traj ? 1 : 0][var - kResidentVariants];
     if (lds > 64 * 1024 && once.need()) {
         // the most this variant ever asks for (the batch image grows with the batch, which another context may have larger)
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)var->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+        VAEK_HIP_CHECK(hipFuncSetAttribute(traj ? (const void*)var->fn_traj : (const void*)var->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)kLdsLimit));
         once.mark();
     }
     ResidentArgs a{};
@@ -622,8 +668,10 @@ int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, floa
     // every launch leaves params / m / v / grads / *step_dev / the ring in HBM: the next one starts from memory alone
     for (int left = n_steps; left > 0; left -= kResidentMaxSteps) {
         a.n_steps = left < kResidentMaxSteps ? left : kResidentMaxSteps;
-        ProfScope ps("linear_resident", st);
-        launch_k(ps, var->fn, dim3(1), dim3(256), lds, st, a);
+        // the traced launch finds the slot of every record from the step counter it reads itself: nothing to carry between launches
+        ProfScope ps(traj ? "linear_resident_traj" : "linear_resident", st);
+        if (traj) launch_k(ps, var->fn_traj, dim3(1), dim3(256), lds, st, a, *traj);
+        else launch_k(ps, var->fn, dim3(1), dim3(256), lds, st, a);
         VAEK_HIP_CHECK(hipGetLastError());
     }
     return VAEK_OK;
@@ -643,15 +691,16 @@ size_t resident_replicas_workspace_bytes(const vaek_ctx* c, int n) { return (siz
 int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
                                  int n, long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
                                  long long a_stride, float* loss_hist, long long loss_hist_cap, int n_steps, float lr, void* ws,
-                                 hipStream_t st) {
+                                 hipStream_t st, const TrajArgs* traj) {
     const ResidentVariant* var = c->resident ? pick_resident(c) : nullptr;
     if (!var) { set_error("resident train loop not available for this configuration"); return VAEK_ERR_INVALID; }
     const bool in_lds = stage_in_lds(c, var);
     const size_t lds = var->base_bytes + (in_lds ? stage_bytes(c) : 0);
-    static thread_local PerDeviceOnce attr_set[sizeof(kResidentVariants) / sizeof(kResidentVariants[0])];
-    PerDeviceOnce& once = attr_set[var - kResidentVariants];
+    static thread_local PerDeviceOnce attr_set[2][sizeof(kResidentVariants) / sizeof(kResidentVariants[0])];      // [traced]: two kernels
+    PerDeviceOnce& once = attr_set[traj ? 1 : 0][var - kResidentVariants];
     if (lds > 64 * 1024 && once.need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)var->fn_replicas, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
+        VAEK_HIP_CHECK(hipFuncSetAttribute(traj ? (const void*)var->fn_replicas_traj : (const void*)var->fn_replicas,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
         once.mark();
     }
     ResidentArgs a{};
@@ -668,8 +717,9 @@ int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float
     rp.seeds = seeds; rp.lrs = lrs;
     for (int left = n_steps; left > 0; left -= kResidentMaxSteps) {
         a.n_steps = left < kResidentMaxSteps ? left : kResidentMaxSteps;
-        ProfScope ps("linear_resident_replicas", st);
-        launch_k(ps, var->fn_replicas, dim3((unsigned)n), dim3(256), lds, st, a, rp);
+        ProfScope ps(traj ? "linear_resident_replicas_traj" : "linear_resident_replicas", st);
+        if (traj) launch_k(ps, var->fn_replicas_traj, dim3((unsigned)n), dim3(256), lds, st, a, rp, *traj);
+        else launch_k(ps, var->fn_replicas, dim3((unsigned)n), dim3(256), lds, st, a, rp);
         VAEK_HIP_CHECK(hipGetLastError());
     }
     return VAEK_OK;

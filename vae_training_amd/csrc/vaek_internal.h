@@ -382,8 +382,15 @@ int lin_train_steps_gen(vaek_ctx* c, float* params, float* grads, float* m, floa
 bool resident_supported(const vaek_ctx* c);       // float32, no hidden layers, D, L <= 32, world 1, 1 <= batch <= 256, not force_generic
 size_t resident_workspace_bytes(const vaek_ctx* c);   // the region at ws_resident: a batch image where LDS has no room for it
 int resident_steps_per_launch();
+// The trajectory ring of vaek_train_loop_gen*_traj (a checked vaek_trajectory): the record of Adam step t, t % every == 0, goes to
+// buf (+ r * replica_stride) + ((t / every - 1) % cap) * record_stride.  `traj` == nullptr below: the untraced kernels, as before.
+struct TrajArgs {
+    float* buf;
+    int every;
+    long long cap, record_stride, replica_stride;
+};
 int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen, int n_steps,
-                        float lr, void* ws, hipStream_t st);
+                        float lr, void* ws, hipStream_t st, const TrajArgs* traj = nullptr);
 // the same loop for n independent models of the context's shape, one workgroup each (vaek_train_loop_gen_replicas); `ws` is the
 // call's own workspace of resident_replicas_workspace_bytes(c, n) bytes, not the context's
 int resident_max_replicas();
@@ -391,7 +398,7 @@ size_t resident_replicas_workspace_bytes(const vaek_ctx* c, int n);
 int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
                                  int n, long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
                                  long long a_stride, float* loss_hist, long long loss_hist_cap, int n_steps, float lr, void* ws,
-                                 hipStream_t st);
+                                 hipStream_t st, const TrajArgs* traj = nullptr);
 
 // ---- rng.hip ------------------------------------------------------------------------------
 // validates the arguments of vaek_make_batch* and fills `out`

@@ -164,10 +164,45 @@ class Engine:
     def train_loop_steps_per_launch(self):
         return int(self.lib.vaek_train_loop_steps_per_launch())
 
-    def train_loop_gen(self, params, grads, m, v, step_dev, n_steps, lr, kind, A, dd, did, pad, var_added, seed, tag=0, row0=0):
+    @property
+    def trajectory_record_len(self):
+        """Floats in one trajectory record (vaek_trajectory_record_len): 2 P + 4 = the parameters, then the gradient buffer."""
+        n = C.c_int64()
+        _lib.check(self.lib.vaek_trajectory_record_len(self.h, C.byref(n)))
+        return int(n.value)
+
+    @staticmethod
+    def _trajectory(trajectory):
+        """vaek_trajectory from `trajectory` = (buf, every) or a dict(buf=, every=, cap=, record_stride=, replica_stride=): buf is a
+        float32 device tensor [cap, record_stride] (solo) or [n, cap, record_stride] (replicas); cap and the strides default to its
+        shape.  The tensor must stay alive until the call has run."""
+        if not isinstance(trajectory, dict):
+            trajectory = dict(buf=trajectory[0], every=trajectory[1])
+        buf = trajectory["buf"]
+        assert buf is None or buf.dtype == torch.float32
+        tj = _lib.VaekTrajectory()
+        tj.struct_size = int(trajectory.get("struct_size", C.sizeof(_lib.VaekTrajectory)))
+        tj.every = int(trajectory["every"])
+        tj.buf = _ptr(buf)
+        shape = (1, 1, 1) if buf is None else tuple(buf.shape)
+        tj.cap = int(trajectory["cap"]) if "cap" in trajectory else shape[-2]
+        tj.record_stride = int(trajectory["record_stride"]) if "record_stride" in trajectory else shape[-1]
+        tj.replica_stride = int(trajectory["replica_stride"]) if "replica_stride" in trajectory else tj.cap * tj.record_stride
+        return tj
+
+    def train_loop_gen(self, params, grads, m, v, step_dev, n_steps, lr, kind, A, dd, did, pad, var_added, seed, tag=0, row0=0,
+                       trajectory=None):
         """n_steps consecutive train steps as a loop INSIDE one workgroup (vaek_train_loop_gen): small-batch linear VAEs with one or
         two decoders, parameters and Adam state on chip between steps, the batch of the step that takes the Adam counter from t
-        to t + 1 bit for bit the one make_batch(..., step = t) would write.  Asynchronous; capturable into a hipGraph."""
+        to t + 1 bit for bit the one make_batch(..., step = t) would write.  Asynchronous; capturable into a hipGraph.
+        `trajectory` (see _trajectory; vaek_train_loop_gen_traj): every Adam step t with t % every == 0 leaves its record -- the
+        parameters before the update, then the gradient buffer -- in slot (t // every - 1) % cap of the ring."""
+        if trajectory is not None:
+            tj = self._trajectory(trajectory)
+            _lib.check(self.lib.vaek_train_loop_gen_traj(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), int(kind), _ptr(A),
+                                                         int(dd), int(did), int(pad), float(var_added), int(row0), int(seed) & (2**64 - 1),
+                                                         int(tag), int(n_steps), float(lr), _ptr(self.workspace), _stream(), C.byref(tj)))
+            return
         _lib.check(self.lib.vaek_train_loop_gen(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), int(kind), _ptr(A),
                                                 int(dd), int(did), int(pad), float(var_added), int(row0), int(seed) & (2**64 - 1), int(tag),
                                                 int(n_steps), float(lr), _ptr(self.workspace), _stream()))
@@ -185,12 +220,13 @@ class Engine:
 
     def train_loop_gen_replicas(self, params, grads, m, v, step_dev, n_steps, lr, kind, A, dd, did, pad, var_added, seeds, lrs=None,
                                 a_stride=0, loss_hist=None, workspace=None, tag=0, row0=0, n=None, state_stride=None, grads_stride=None,
-                                loss_hist_cap=None):
+                                loss_hist_cap=None, trajectory=None):
         """n_steps train steps of EACH of n independent models of this engine's shape in one launch, workgroup r training replica r
         (vaek_train_loop_gen_replicas).  params / m / v: [n, state_stride], grads: [n, grads_stride], step_dev: int32 [n], seeds:
         int64 [n] (the bits of the uint64 seeds), lrs: float32 [n] or None (then `lr` for all), A: replica r's at A + r * a_stride
         floats (0: shared), loss_hist: [n, cap] or None -- all device tensors; n, the strides and cap default to the tensors'
-        shapes.  Replica r ends bitwise where train_loop_gen alone on its slices would.  Asynchronous; capturable."""
+        shapes.  Replica r ends bitwise where train_loop_gen alone on its slices would.  Asynchronous; capturable.
+        `trajectory` (see _trajectory; vaek_train_loop_gen_replicas_traj): replica r's ring is buf[r]."""
         rep = _lib.VaekReplicas()
         rep.struct_size = C.sizeof(_lib.VaekReplicas)
         rep.n = int(params.shape[0] if n is None else n)
@@ -202,9 +238,13 @@ class Engine:
         rep.a_stride = int(a_stride)
         rep.loss_hist = _ptr(loss_hist)
         rep.loss_hist_cap = int((0 if loss_hist is None else loss_hist.shape[-1]) if loss_hist_cap is None else loss_hist_cap)
-        _lib.check(self.lib.vaek_train_loop_gen_replicas(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep),
-                                                         int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(row0),
-                                                         int(tag), int(n_steps), float(lr), _ptr(workspace), _stream()))
+        args = (self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep), int(kind), _ptr(A), int(dd), int(did),
+                int(pad), float(var_added), int(row0), int(tag), int(n_steps), float(lr), _ptr(workspace), _stream())
+        if trajectory is not None:
+            tj = self._trajectory(trajectory)
+            _lib.check(self.lib.vaek_train_loop_gen_replicas_traj(*args, C.byref(tj)))
+            return
+        _lib.check(self.lib.vaek_train_loop_gen_replicas(*args))
 
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""

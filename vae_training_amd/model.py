@@ -210,6 +210,8 @@ class GenerativeModel(Model):
             except ImportError:
                 pass
         fast = getattr(self, "fast_loop", False)
+        if getattr(self, "trajectory_every", None) is not None:
+            fast = True                  # the trajectory ring is written by the resident loop (trainer.GraphLoop)
         if fast is None:                 # auto: the models vaek_train_steps_gen covers (linear VAEs) take the loop built on it
             fast = self._fast_loop_qualifies()
         if fast:
@@ -241,7 +243,9 @@ class GenerativeModel(Model):
         """Same schedule (stats every n_print, plot+save every n_plot and at the last step), but the steps in
         between run from a hipGraph with on-device batch generation (trainer.GraphLoop)."""
         from .trainer import GraphLoop
-        loop = GraphLoop(self)
+        tevery = getattr(self, "trajectory_every", None)
+        # trajectory_every=K (run.py --trajectory_every): the resident loop with its trajectory ring, also where a moments path exists
+        loop = GraphLoop(self) if tevery is None else GraphLoop(self, moments=False, resident=True, trajectory_every=tevery)
         self._graph_loop = loop
         if getattr(self, "rank", 0) == 0:
             print(f"Train loop: {loop.describe()}")

@@ -2,7 +2,7 @@
 --dataset linear_gaussian ...` trains a VAE with the HIP kernels and leaves data/NAME/{args.json,
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
-which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep)."""
+which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every."""
 from __future__ import annotations
 
 import argparse
@@ -59,7 +59,23 @@ def build_parser():
                         "seed r).  Three-hidden-layer MLP VAEs on the \"mlp3\" train step: a hipGraph loop whose every step trains all "
                         "models in two launches (trainer.ReplicaGraphLoop, vaek_train_step_gen_replicas).  Other models are refused; "
                         "single GPU only")
+    p.add_argument("--trajectory_every", dest="trajectory_every", type=_positive_int, default=None, metavar="K",
+                   help="record the model while it trains: every K-th Adam step the resident loop stores the parameters that step's "
+                        "gradient was evaluated at and the gradient itself (trainer.GraphLoop(resident=True, trajectory_every=K); with "
+                        "--sweep_dataset_seeds trainer.ReplicaLoop).  Each output directory gains trajectory.npz (steps, params, grads and "
+                        "the leaf table) and losses.npz a Correlation Ratio per record (vae.py:143-179).  Linear VAEs the resident loop "
+                        "covers only; other models are refused before any step; single GPU only")
     return p
+
+
+def _positive_int(text):
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not an integer")
+    if k < 1:
+        raise argparse.ArgumentTypeError(f"{k} is not >= 1")
+    return k
 
 
 def _int_list(text):
@@ -144,12 +160,45 @@ def _get_model_dp(args, dataset, output_dir, dist, world, rank):
     return m
 
 
-def sweep_loop(models):
+TRAJECTORY_NEEDS = ("a model the resident loop covers (vaek_supports_train_loop_gen): a float32 linear VAE with one or two decoders, "
+                    "D, L <= 32, a batch of at most 256 rows, -dd / -did <= 16, on one GPU")
+
+
+def check_trajectory_model(m):
+    """--trajectory_every: refuse, before any step, a model whose steps would not run in the resident loop."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    kind, _, dd, did, _, _ = m.dataset.device_spec()
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_train_loop_gen(kind):
+        raise RuntimeError(f"--trajectory_every needs {TRAJECTORY_NEEDS} (this model's step path: {getattr(eng, 'step_path', '?')}, "
+                           f"batch {m.batch_size}, world {eng.world})")
+
+
+def write_trajectory(m, loop):
+    """trajectory.npz in the model's output directory: steps [n] (1-based Adam steps), params [n, P] (the parameters each step's
+    gradient was evaluated at), grads [n, P + 4] (loss, mean Dkl, mean mse, 0 behind the P gradients) and the leaf table of
+    vaek_leaf_info (leaf_names, leaf_offsets, leaf_shapes as rows x cols, a vector being 1 x n)."""
+    import os
+
+    import numpy as np
+    steps, th, g = loop.trajectory()
+    leaves = m.model.module.leaves
+    shapes = [(1, sh[0]) if len(sh) == 1 else tuple(sh) for _, sh in leaves.values()]
+    np.savez(os.path.join(m.dirname, "trajectory"), steps=steps.numpy(), params=th.numpy(), grads=g.numpy(),
+             leaf_names=np.array(list(leaves), dtype=np.str_), leaf_offsets=np.array([off for off, _ in leaves.values()], dtype=np.int64),
+             leaf_shapes=np.array(shapes, dtype=np.int64).reshape(-1, 2))
+
+
+def sweep_loop(models, trajectory_every=None):
     """The loop of --sweep_dataset_seeds: ReplicaLoop where the resident loop covers the models (small-batch linear VAEs), else
-    ReplicaGraphLoop where the engine's step has a replica form (the "mlp3" step), else a refusal that names both."""
+    ReplicaGraphLoop where the engine's step has a replica form (the "mlp3" step), else a refusal that names both.  With
+    --trajectory_every only ReplicaLoop will do."""
     from .trainer import ReplicaGraphLoop, ReplicaLoop
     m0 = models[0]
     eng = m0.model.module.engine(m0.batch_size, m0.optimizer.global_batch)
+    if trajectory_every is not None:
+        check_trajectory_model(m0)
+        return ReplicaLoop(models, trajectory_every=trajectory_every)
     if eng.world > 1 or eng.supports_train_loop_gen(m0.dataset.device_spec()[0]):
         return ReplicaLoop(models)           # today's behaviour, its own refusals included
     if eng.supports_train_step_replicas():
@@ -183,7 +232,8 @@ def main_sweep(args):
         if ds is None:
             raise ValueError("--dataset must be one of sphere, linear_gaussian, sigmoid")
         models.append(get_model(a, ds, out))
-    loop = sweep_loop(models)                # refuses, before any step, what neither replica loop covers
+    tevery = getattr(args, "trajectory_every", None)
+    loop = sweep_loop(models, tevery) if tevery is not None else sweep_loop(models)      # refuses, before any step, what no replica loop covers
     eng = loop.eng
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
@@ -208,9 +258,11 @@ def main_sweep(args):
                 m.save()
     loop.run(n - pos)
     loop.check()
-    for m in models:
+    for r, m in enumerate(models):
         m.plot()
         m.save(final=True)
+        if tevery is not None:
+            write_trajectory(m, loop.view(r))
     return 0
 
 
@@ -238,6 +290,12 @@ def main(args):
     if dataset is None:
         raise ValueError("--dataset must be one of sphere, linear_gaussian, sigmoid")
     model = get_model(args, dataset, output_dir, dist)
+    tevery = getattr(args, "trajectory_every", None)
+    if tevery is not None:
+        if world > 1:
+            raise RuntimeError(f"--trajectory_every needs {TRAJECTORY_NEEDS}: it does not combine with data parallelism")
+        check_trajectory_model(model)            # before any step
+        model.trajectory_every = tevery          # train() takes GraphLoop(resident=True, trajectory_every=K) and prints the Train loop: line
     if rank == 0:
         eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
         loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")
@@ -245,6 +303,8 @@ def main(args):
     model.train()
     model.plot()
     model.save(final=True)
+    if tevery is not None:
+        write_trajectory(model, model._graph_loop)
     if dist is not None:
         model.check_replicas()
         dist.barrier()

@@ -34,10 +34,39 @@ every model that takes it today still does.
 ReplicaLoop (below GraphLoop) is the resident loop for a SWEEP: R models of one shape, one workgroup each, in one launch per run of
 steps (vaek_train_loop_gen_replicas); `run.py --sweep_dataset_seeds` drives it.  ReplicaGraphLoop (below it) is the sweep of the
 models the resident loop does not cover but the whole-network "mlp3" step does: the pipelined hipGraph loop with every step ONE
-vaek_train_step_gen_replicas call for all R models."""
+vaek_train_step_gen_replicas call for all R models.
+
+`trajectory_every=K` (GraphLoop with the resident loop, ReplicaLoop; opt-in): the resident kernel records, at every Adam step t with
+t % K == 0, the parameters that step's gradient was evaluated at and the step's gradient buffer, into a device ring the loop owns
+(vaek_train_loop_gen_traj / vaek_train_loop_gen_replicas_traj) -- the reference's `params_and_gradients` list (vae.py:207), which
+the reference never fills.  `trajectory()` / `trajectory(r)` returns them in step order; run() stays one library call."""
 from __future__ import annotations
 
 import torch
+
+
+def _trajectory_capacity(loop_name, models, every, capacity):
+    """Records per ring: every recorded step of the longest schedule among the models, ceil(num_batches / K), unless given."""
+    if int(every) < 1:
+        raise RuntimeError(f"{loop_name}(trajectory_every={every}): need an integer >= 1")
+    if capacity is not None:
+        if int(capacity) < 1:
+            raise RuntimeError(f"{loop_name}(trajectory_capacity={capacity}): need an integer >= 1")
+        return int(capacity)
+    nb = max(int(getattr(m, "num_batches", 0) or 0) for m in models)
+    if nb < 1:
+        raise RuntimeError(f"{loop_name}(trajectory_every={every}): the model has no num_batches to size the ring by; pass trajectory_capacity")
+    return -(-nb // int(every))
+
+
+def _trajectory_view(ring, every, first_step, last_step, P):
+    """(steps, params [n, P], grads [n, P + 4]) of the records a ring [cap, >= 2 P + 4] (already on the host) holds for the Adam steps
+    first_step < t <= last_step with t % every == 0, oldest first: the last `cap` of them, each from slot (t // every - 1) % cap."""
+    cap = ring.shape[0]
+    idx = list(range(first_step // every + 1, last_step // every + 1))[-cap:]
+    slots = torch.tensor([(i - 1) % cap for i in idx], dtype=torch.int64)
+    rec = ring[slots] if idx else ring[:0]
+    return torch.tensor([i * every for i in idx], dtype=torch.int64), rec[:, :P], rec[:, P:2 * P + 4]
 
 
 # What GraphLoop(resident=None) resolves to where the engine supports the resident loop and the model has no moments path.  The gate
@@ -47,7 +76,8 @@ RESIDENT_DEFAULT = False
 
 
 class GraphLoop:
-    def __init__(self, vae_model, steps_per_graph=200, seed=None, loss_capacity=1 << 20, pipeline=True, moments=None, resident=None):
+    def __init__(self, vae_model, steps_per_graph=200, seed=None, loss_capacity=1 << 20, pipeline=True, moments=None, resident=None,
+                 trajectory_every=None, trajectory_capacity=None):
         m = vae_model
         self.m = m
         ds = m.dataset
@@ -73,6 +103,11 @@ class GraphLoop:
         # by default only where there is no moments path to take: a caller who switches an available moments path off
         # (moments=False) has always been asking for the per-sample hipGraph loop, and still gets it
         self.resident = (can_res and not can and RESIDENT_DEFAULT) if resident is None else bool(resident)
+        if trajectory_every is not None and not self.resident:
+            raise RuntimeError(f"GraphLoop(trajectory_every={trajectory_every}): the trajectory ring is written by the resident loop "
+                               "(vaek_train_loop_gen_traj); " + ("pass resident=True" if can_res else
+                                                                  "vaek_train_loop_gen does not cover this model / dataset" if not self.moments
+                                                                  else "the moments path has priority on this model"))
         self.row0 = self.eng.rank * self.B           # ranks draw disjoint rows of the global batch
         self.seed = (ds.key[0] ^ ds.key[1] ^ m.key[1]) if seed is None else seed
         self.pipeline = bool(pipeline) and not self.moments and not self.resident
@@ -91,6 +126,11 @@ class GraphLoop:
         self.graph = None
         self.graph_parity = 0
         self.steps_done_at_attach = m.optimizer.state.step
+        self.trajectory_every = None if trajectory_every is None else int(trajectory_every)
+        self.traj_ring = None
+        if trajectory_every is not None:         # every recorded step of the schedule, sized once
+            cap = _trajectory_capacity("GraphLoop", [m], trajectory_every, trajectory_capacity)
+            self.traj_ring = torch.zeros(cap, self.eng.trajectory_record_len, dtype=torch.float32, device=dev)
         if self.pipeline:
             n = m.optimizer.state.step
             # the generator's own step counter, a pair used alternately (vaek_make_batch_next): the draw of batch k
@@ -141,9 +181,10 @@ class GraphLoop:
             if n_steps > 0:
                 st = self.m.optimizer.state
                 call = self.eng.train_steps_gen if self.moments else self.eng.train_loop_gen
+                kw = {} if self.traj_ring is None else dict(trajectory=dict(buf=self.traj_ring, every=self.trajectory_every))
                 call(self.m.model.flat, st.grads, st.m, st.v, st.step_dev, n_steps,
                      self.m.optimizer.optimizer_def.learning_rate, self.kind, self.A, self.dd, self.did, self.pad,
-                     self.var, self.seed, tag=0, row0=self.row0)
+                     self.var, self.seed, tag=0, row0=self.row0, **kw)
                 st.step += n_steps
             return
         done = 0
@@ -166,7 +207,9 @@ class GraphLoop:
         if self.moments:
             return "persistent moment launches (vaek_train_steps_gen)"
         if self.resident:
-            return f"resident linear kernel, {self.eng.train_loop_steps_per_launch} steps per launch"
+            return (f"resident linear kernel, {self.eng.train_loop_steps_per_launch} steps per launch" +
+                    ("" if self.traj_ring is None else f", trajectory record every {self.trajectory_every} steps "
+                                                       f"(ring of {self.traj_ring.shape[0]})"))
         return f"hipGraph of {self.G} steps" + (", next batch drawn inside the step's launch" if self.pipeline else "")
 
     def check(self):
@@ -188,6 +231,19 @@ class GraphLoop:
         k = n % cap
         return torch.cat([ring[k:], ring[:k]])
 
+    @property
+    def records_trajectory(self):
+        return self.traj_ring is not None
+
+    def trajectory(self):
+        """(steps, params [n, P], grads [n, P + 4]) of the records this loop's steps have left, in step order (one device -> host
+        copy): record i is Adam step steps[i] (1-based), the parameters its gradient was evaluated at (the state after
+        steps[i] - 1 steps) and its gradient buffer (loss, mean Dkl, mean mse, 0 in the last four slots)."""
+        if self.traj_ring is None:
+            raise RuntimeError("GraphLoop.trajectory(): this loop records none (pass trajectory_every=K with resident=True)")
+        return _trajectory_view(self.traj_ring.cpu(), self.trajectory_every, self.steps_done_at_attach, self.m.optimizer.state.step,
+                                self.m.model.flat.numel())
+
 
 class _ReplicaLosses:
     """What VAEModel.model_save_data asks of `model._graph_loop`: the train losses of one replica of a ReplicaLoop."""
@@ -197,6 +253,13 @@ class _ReplicaLosses:
 
     def losses(self):
         return self.loop.losses(self.r)
+
+    @property
+    def records_trajectory(self):
+        return self.loop.traj_ring is not None
+
+    def trajectory(self):
+        return self.loop.trajectory(self.r)
 
 
 class ReplicaLoop:
@@ -216,7 +279,7 @@ class ReplicaLoop:
 
     One workgroup per model and no cross-workgroup state: nothing to wait for, check() polls nothing."""
 
-    def __init__(self, vae_models, loss_capacity=None):
+    def __init__(self, vae_models, loss_capacity=None, trajectory_every=None, trajectory_capacity=None):
         ms = list(vae_models)
         if not ms:
             raise RuntimeError("ReplicaLoop: no models")
@@ -264,6 +327,12 @@ class ReplicaLoop:
         self.rings = f32(R, int(loss_capacity))
         nb = self.eng.train_loop_replicas_workspace(R)
         self.workspace = torch.empty(nb, dtype=torch.uint8, device=dev) if nb else None
+        self.trajectory_every = None if trajectory_every is None else int(trajectory_every)
+        self.traj_ring = None
+        if trajectory_every is not None:         # one ring per model: every recorded step of the longest schedule, sized once
+            cap = _trajectory_capacity("ReplicaLoop", ms, trajectory_every, trajectory_capacity)
+            self.traj_ring = f32(R, cap, self.eng.trajectory_record_len)
+            self.traj_from = [int(m.optimizer.state.step) for m in ms]
 
     @staticmethod
     def _signature(m, spec):
@@ -286,9 +355,10 @@ class ReplicaLoop:
         for r, m in enumerate(self.ms):
             for row, own in self._rows(m, r):
                 row.copy_(own)
+        kw = {} if self.traj_ring is None else dict(trajectory=dict(buf=self.traj_ring, every=self.trajectory_every))
         self.eng.train_loop_gen_replicas(self.params, self.grads, self.m, self.v, self.step_dev, n_steps, 0.0, self.kind, self.A,
                                          self.dd, self.did, self.pad, self.var, self.seeds, lrs=self.lrs, a_stride=self.a_stride,
-                                         loss_hist=self.rings, workspace=self.workspace, tag=0, row0=0)
+                                         loss_hist=self.rings, workspace=self.workspace, tag=0, row0=0, **kw)
         for r, m in enumerate(self.ms):
             for row, own in self._rows(m, r):
                 own.copy_(row)
@@ -297,7 +367,18 @@ class ReplicaLoop:
     def describe(self):
         """One line for run.py."""
         return (f"resident linear kernel, {self.R} replicas in one launch (vaek_train_loop_gen_replicas), "
-                f"{self.eng.train_loop_steps_per_launch} steps per launch")
+                f"{self.eng.train_loop_steps_per_launch} steps per launch" +
+                ("" if self.traj_ring is None else f", trajectory record every {self.trajectory_every} steps "
+                                                   f"(rings of {self.traj_ring.shape[1]})"))
+
+    def trajectory(self, r):
+        """(steps, params [n, P], grads [n, P + 4]) of the records model r's steps in this loop have left, in step order (one device
+        -> host copy of its ring); see GraphLoop.trajectory."""
+        if self.traj_ring is None:
+            raise RuntimeError("ReplicaLoop.trajectory(): this loop records none (pass trajectory_every=K)")
+        m = self.ms[r]
+        return _trajectory_view(self.traj_ring[r].cpu(), self.trajectory_every, self.traj_from[r], m.optimizer.state.step,
+                                m.model.flat.numel())
 
     def check(self):
         """Nothing to poll: the launch has no waits."""

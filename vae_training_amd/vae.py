@@ -2,12 +2,15 @@
 attributes (.model, .optimizer, .key, .vae_losses, .epsilon, .current_epsilon, .latent_dimension)
 and methods (train_one_batch :123-130, compute_model_stats :132-141, sample_batch :191-201,
 model_save_data :203-209), and the warm start of -ws (:62-107: host-side initialisation only, SURVEY.md 8f rank 4's sibling).
-The correlation ratio (:143-179) is out of scope: it iterates an always-empty list."""
+The correlation ratio (:143-179) iterates a list the reference never fills; here `correlation_ratios` below restates it over the
+(parameters, gradient) pairs the resident loop's trajectory ring records (trainer.GraphLoop / ReplicaLoop, trajectory_every=K)."""
 from __future__ import annotations
 
 import math
 
 import torch
+
+import numpy as np
 
 from . import random as vrandom
 from .model import GenerativeModel
@@ -67,6 +70,40 @@ def warm_start_params(params, key, dataset, dataset_name, latent_dimension, data
         var[:A.shape[1] + off] = -3.0
         put(("epsilon_p",), var + 0.1 * normal((L,)))
     return params
+
+
+# the leaves of compute_correlation_ratio (vae.py:149-177) and the sign each one's gradient enters the inner product with
+CORRELATION_LEAVES = (("Decoder/FC0/bias", -1.0), ("Decoder/FC0/kernel", -1.0), ("Encoder/FC0/bias", -1.0), ("Encoder/FC0/kernel", -1.0),
+                      ("epsilon", +1.0), ("epsilon_p", -1.0))
+
+
+def correlation_ratios(params, grads, theta_star, leaves):
+    """The reference's compute_correlation_ratio (vae.py:143-179) for n recorded (parameters, gradient) pairs at once, in float64:
+
+        ratio_i = sum_leaf sign_leaf * <g_i[leaf], theta*[leaf] - theta_i[leaf]>  /  sum_leaf |theta*[leaf] - theta_i[leaf]|^2
+
+    over the leaves the reference names -- Encoder/FC0 and Decoder/FC0 kernel and bias, epsilon_p, epsilon -- with sign -1 for all
+    of them except `epsilon`, which enters with +1, as the reference writes it (vae.py:171).  SigDecoder is not part of it, as in
+    the reference.  Without -tdv the model has no `epsilon` leaf (the reference would raise a KeyError there) and the term is left
+    out of both sums.  params: [n, >= P], grads: [n, >= P] (the loss slots behind P are ignored), theta_star: [P], the model the
+    displacements point at (the reference: the model at the final save); leaves: name -> (offset, shape), the table of
+    vaek_leaf_info / layout.leaves.  Returns float64 [n]; a record AT theta* gives 0 / 0 = nan, as the reference's division would."""
+    to64 = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.float64)
+    th, g, star = to64(params), to64(grads), to64(theta_star)
+    th, g = th.reshape(-1, th.shape[-1]), g.reshape(-1, g.shape[-1])
+    inner, sq = np.zeros(th.shape[0]), np.zeros(th.shape[0])
+    for name, sign in CORRELATION_LEAVES:
+        if name not in leaves:
+            if name == "epsilon":
+                continue
+            raise KeyError(f"correlation_ratios: the model has no leaf {name!r} (the ratio is defined for linear VAEs: vae.py:149-177)")
+        off, shape = leaves[name]
+        n = int(np.prod(shape))
+        d = star[off:off + n][None, :] - th[:, off:off + n]
+        inner += sign * np.einsum("ij,ij->i", g[:, off:off + n], d)
+        sq += np.einsum("ij,ij->i", d, d)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return inner / sq
 
 
 class VAEModel(GenerativeModel):
@@ -141,13 +178,22 @@ class VAEModel(GenerativeModel):
         x_hat, _, _, _ = self.model(None, z1, z2, sampling=True, epsilon=self.current_epsilon)
         return x_hat, z
 
+    def compute_correlation_ratios(self, params, grads):
+        """correlation_ratios of the recorded pairs against THIS model's current parameters (theta* = the model at the final save,
+        vae.py:146)."""
+        return correlation_ratios(params, grads, self.model.flat, self.model.module.leaves)
+
     def model_save_data(self, final=False):
         loop = getattr(self, "_graph_loop", None)
         if loop is not None:                # fast loop: train losses live in the device ring, eval losses in the list
             self.vae_losses_train = loop.losses()
         data = {"VAE Loss": self.vae_losses if loop is None else list(self.vae_losses) + list(self.vae_losses_train), "Decoder Variance": self.var_dec, "Encoder Variance": self.var_enc}
         if final:
-            data["Correlation Ratio"] = self.correlation_ratios       # always empty, as in the reference
+            # empty, as in the reference, unless the loop recorded a trajectory (trajectory_every=K): then one value per record
+            if loop is not None and getattr(loop, "records_trajectory", False):
+                _, th, g = loop.trajectory()
+                self.correlation_ratios = self.compute_correlation_ratios(th, g)
+            data["Correlation Ratio"] = self.correlation_ratios
         return data
 
 
