@@ -235,10 +235,10 @@ int vaek_train_step_gen(vaek_ctx* ctx, float* params, float* grads, float* m, fl
  * the cross-workgroup sum of batch n + 1 and the Adam update of batch n run side by side -- as resident workgroup roles of one
  * persistent launch per 64 steps (arrival counters, bounded waits: vaek_train_steps_status), or where that form does not apply as
  * n_steps + 2 launches ordered by the stream alone.  The launches of one call are chained: each streams its own 64 batches, but
- * leaves its last batch to the next launch's reducers and its last two to the next launch's updater, so a later launch reduces and
+ * leaves its last batch to the next launch's reducers and its last four to the next launch's updater, so a later launch reduces and
  * updates from its first microsecond on and its roles end together; the call's last launch finishes every step, and nothing is
- * carried from one call to the next.  For that the workspace holds 66 batch slots (partial images, moment matrix, arrival
- * counters; batch n of a call uses slot n mod 66): 66 x (tiles x 6 or 10 KB) -- 92.5 MB at batch 65 536, D = 12, L = 20.
+ * carried from one call to the next.  For that the workspace holds 68 batch slots (partial images, moment matrix, arrival
+ * counters; batch n of a call uses slot n mod 68): 68 x (tiles x 6 or 10 KB) -- 95.3 MB at batch 65 536, D = 12, L = 20.
  * The persistent form covers L <= 32 with L + 2 D + 1 <= 48 and D <= 16, or with
  * 49 <= L + 2 D + 1 <= 64 (four 16-feature blocks); data parallelism and vaek_train_steps_gen need it.  Capturable into a hipGraph.  A context recognises a workspace whose arrival
  * counters it has initialised by the workspace's address.  Linear encoder / decoder, one decoder, float32, L + 2 D + 1 <= 64,

@@ -54,9 +54,10 @@ if persist:
     print(f"   streamers 0 / S/2 / S-1 entered the kernel at {(t[50] - t0) / 100.0:.1f} / {(t[51] - t0) / 100.0:.1f} / {(t[52] - t0) / 100.0:.1f} us, streamer 0 signalled its first image at {(t[53] - t0) / 100.0:.1f} us")
     print("   reducer 5, batches 0..2: woke at / done at (us): " + "  ".join(f"{(t[56 + 2 * n] - t0) / 100.0:.1f} / {(t[57 + 2 * n] - t0) / 100.0:.1f}" for n in range(3)))
     # the call's LAST launch (each launch overwrites the stamps): with more than 64 steps per call a chained launch, whose reducers
-    # start one batch and whose updater starts two batches behind its streamers (lin_windows); rows count each role's own batches
+    # start one batch and whose updater starts kLinCarry = 4 batches behind its streamers (lin_windows); rows count each role's own batches
     nl = (nsteps + 63) // 64
-    n_str = nsteps - 64 * (nl - 1); n_red = n_str + (nl > 1); n_upd = n_str + 2 * (nl > 1)
+    carry = 4
+    n_str = nsteps - 64 * (nl - 1); n_red = n_str + (nl > 1); n_upd = n_str + carry * (nl > 1)
     print(f"   last launch of {nl}: streams {n_str}, reduces {n_red}, updates {n_upd} batches; last streamer done at {(t[49] - t0) / 100.0:.1f} us, "
           f"last reduce {(t[136 + n_red - 1] - t0) / 100.0:.1f} us, last update {(t[64 + n_upd - 1] - t0) / 100.0:.1f} us")
     print("   n: the role's n-th batch reduced at | updated at  (us after the updater entered its loop -- STAMPS=2: after the first streamer entered the kernel; last arrival of each role)")

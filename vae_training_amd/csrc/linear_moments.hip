@@ -34,12 +34,13 @@
 // dispatcher does with residency, and every poll is bounded (status word, vaek_train_steps_status).  What it buys on top:
 // no launch boundary and no cold start per step (the updater's instruction stream and parameters stay on one CU).
 // A call of more than 64 steps is several such launches, CHAINED: launch j streams batches [64 j, 64 j + 64), but reduces
-// [64 j - 1, 64 j + 63) and updates [64 j - 2, 64 j + 62) -- the launch-per-step form's shift, across the launch boundary -- and
-// the call's last launch runs every role to the end (lin_windows).  A later launch's reducers and updater so start on batches
-// that are complete (ordered by the stream) while its streamers fill their pipeline, and the three roles end together instead
-// of the streamers idling through the drain.  Batch n of a call lives in slot n % 66 of the workspace (64 + the two carried:
-// partial images, M, arrival counters -- 66 x ntiles x 6 KB of images, 92.5 MB at the metric's 228 tiles); a slot comes round
-// again 66 batches later, when its batch was updated at least a whole launch ago, so still nobody waits for a slot.
+// [64 j - 1, 64 j + 63) and updates [64 j - 4, 64 j + 60) -- the launch-per-step form's shift, widened to kLinCarry = 4 for the
+// updater, across the launch boundary -- and the call's last launch runs every role to the end (lin_windows).  A later launch's
+// reducers and updater so start on batches that are complete (ordered by the stream) while its streamers fill their pipeline,
+// and the three roles end together instead of the streamers idling through the drain.  Batch n of a call lives in slot n % 68 of
+// the workspace (64 + the four carried: partial images, M, arrival counters -- 68 x ntiles x 6 KB of images, 95.3 MB at the
+// metric's 228 tiles); a slot comes round again 68 batches later, when its batch was updated at least a whole launch ago, so
+// still nobody waits for a slot.
 //
 // Numerics: M accumulates exact-f32 products in chains of 72 samples (one multiplying wave's 18 MFMA k-steps at the metric's
 // 288-row tile; 36 in the launch-per-step form), summed further in
@@ -64,18 +65,23 @@ typedef const __attribute__((address_space(1))) void glb_void_t;
 constexpr int LNT = 512, LNW = LNT / 64;          // threads / waves per workgroup, every role
 constexpr int kLinMaxPersist = 64;                // batches a persistent launch streams
 // Launches of ONE call are chained: a launch that is not the call's last leaves its last batch to the next launch's reducers and
-// its last two to the next launch's updater (the shift the launch-per-step form makes per step), so that launch starts reducing
+// its last kLinCarry = 4 to the next launch's updater (the launch-per-step form shifts by one and two), so that launch starts reducing
 // and updating at once, while its streamers fill, and all three roles end together.  Batch n of a call lives in slot n % kLinSlots
-// (partial images, M, arrival counters): a launch's 64 streamed batches and the two carried into it never share a slot.
-constexpr int kLinCarry = 2, kLinSlots = kLinMaxPersist + kLinCarry;
+// (partial images, M, arrival counters): a launch's 64 streamed batches and the kLinCarry carried into it never share a slot.
+// kLinCarry: the batches a launch leaves to the next launch's updater.  All but the last of them are reduced already, so that
+// updater has kLinCarry - 1 steps of ready work (and one more as soon as its own reducers have run once) while its streamers
+// fill their pipeline: the new launch's first own batch is reduced ~13 us after entry, its second ~22 us.  With 2 the updater
+// waited twice in a later launch's first 28 us; with 4 it steps at its own pace from entry (profiles/lin_pace_roles.txt).
+constexpr int kLinCarry = 4, kLinSlots = kLinMaxPersist + kLinCarry;
+static_assert(kLinCarry >= 2 && kLinCarry < kLinMaxPersist, "the updater follows the reducers, which follow the streamers by one batch");
 struct LinWindow { int first, count; };
 struct LinWindows { LinWindow stream, reduce, update; };
 // the batch windows of launch j of a call of K steps
 constexpr LinWindows lin_windows(int K, int j) {
     const int s0 = kLinMaxPersist * j, s1 = s0 + kLinMaxPersist < K ? s0 + kLinMaxPersist : K;
     const bool last = s1 == K;
-    const int r0 = s0 >= 1 ? s0 - 1 : 0, u0 = s0 >= 2 ? s0 - 2 : 0;
-    return LinWindows{{s0, s1 - s0}, {r0, (last ? K : s1 - 1) - r0}, {u0, (last ? K : s1 - 2) - u0}};
+    const int r0 = s0 >= 1 ? s0 - 1 : 0, u0 = s0 >= kLinCarry ? s0 - kLinCarry : 0;
+    return LinWindows{{s0, s1 - s0}, {r0, (last ? K : s1 - 1) - r0}, {u0, (last ? K : s1 - kLinCarry) - u0}};
 }
 constexpr int lin_launches(int K) { return (K + kLinMaxPersist - 1) / kLinMaxPersist; }
 // every role covers [0, K) exactly once, in order; no role takes more batches than it may; a launch's live batches fit the slots
@@ -91,9 +97,10 @@ constexpr bool lin_windows_ok(int K) {
     return s == K && r == K && u == K;
 }
 static_assert(lin_windows_ok(1) && lin_windows_ok(2) && lin_windows_ok(64) && lin_windows_ok(65) && lin_windows_ok(66) && lin_windows_ok(128) &&
-              lin_windows_ok(129) && lin_windows_ok(130) && lin_windows_ok(960), "launch windows of a vaek_train_steps call");
-static_assert(lin_windows(64, 0).update.count == 64 && lin_windows(130, 1).update.first == 62 && lin_windows(130, 1).reduce.first == 63 &&
-              lin_windows(130, 2).update.count == 4, "launch windows of a vaek_train_steps call");
+              lin_windows_ok(129) && lin_windows_ok(130) && lin_windows_ok(132) && lin_windows_ok(960), "launch windows of a vaek_train_steps call");
+static_assert(lin_windows(64, 0).update.count == 64 && lin_windows(130, 1).update.first == 64 - kLinCarry && lin_windows(130, 1).reduce.first == 63 &&
+              lin_windows(130, 2).update.count == 2 + kLinCarry && lin_windows(65, 0).update.count == 64 - kLinCarry &&
+              lin_windows(65, 1).update.count == 1 + kLinCarry, "launch windows of a vaek_train_steps call");
 constexpr int kLinReduceSets = 1;                 // persistent form: reducer sets taking alternate batches (one set of 24 beat two of 12)
 constexpr int kLinReduceWgs = 24;                 // workgroups per set, each summing NO / 32 / 24 slices of 32 outputs (more resident
                                                   // workgroups measurably slow the streamers: 48 per set cost 2 us per step)
@@ -942,7 +949,7 @@ __device__ __forceinline__ int lin_m_index(int NB, int r, int c) {
     return lin_blk(NB, b1, b2) * 256 + (((i >> 2) * 16 + j) << 2) + (i & 3);
 }
 // (LinUpdMG below is the same updater generalised to four feature blocks; a fix to the algebra, the LDS layout or the Adam phase
-// here belongs there too)
+// here belongs there too.  It keeps the plain output map idx = t + 512 k: out_index below is this updater's alone.)
 template <int NB, int DT, int LT>
 struct LinUpdM {
     static constexpr int NFP = 16 * NB;
@@ -955,6 +962,31 @@ struct LinUpdM {
     int mo[NM];                                                                        // chain lanes: image offsets of their M values
 
     static __host__ __device__ constexpr bool shape_ok(int D, int L) { return D <= 16 && L <= 32 && L + 2 * D + 1 <= NFP && NB == 3; }
+    // Which output lives in slot k of thread t (-1: none).  The SPECIAL outputs -- the loss slots P .. P + 3 and epsilon, the ones
+    // behind float64 scalar chains (the four sums; e^{eps/2} and 1 / sigma^2 when the parameters are published) -- are the ONLY output of
+    // the first lanes of the last wave; the plain outputs fill slot 0 of every other thread in order, and those that are left over go
+    // to further slots from thread kOvfTop down (the wave in front of the special one: no chain wave, no special lane), so no wave
+    // runs a plain Adam update and a special lane's chain one behind the other.  load_state, publish_params, step and store_state
+    // all go through this map.
+    static constexpr int kSpecT0 = LNT - 64, kOvfTop = kSpecT0 - 1;
+    static_assert(LNT - (kExtra + 1) - kOvfTop > 32 && kOvfTop + 1 > 32, "publish_params: one exponential per thread needs two slots of a thread more than L <= 32 outputs apart");
+    __device__ __forceinline__ int out_index(int t, int k) const {
+        const int ns = kExtra + (off_eps >= 0 ? 1 : 0), np = P - (off_eps >= 0 ? 1 : 0);        // special lanes; plain outputs
+        int r;
+        if (k == 0) {
+            if (t >= kSpecT0 && t < kSpecT0 + ns) return t - kSpecT0 < kExtra ? P + (t - kSpecT0) : off_eps;
+            r = t < kSpecT0 ? t : t - ns;
+        } else {
+            if (t > kOvfTop) return -1;
+            r = LNT - ns + (kOvfTop + 1) * (k - 1) + (kOvfTop - t);
+        }
+        if (r >= np) return -1;
+        return r + ((off_eps >= 0 && r >= off_eps) ? 1 : 0);
+    }
+    // (uniform) does any thread hold an output in slot k?
+    __device__ __forceinline__ bool slot_used(int k) const {
+        return k == 0 || LNT - (kExtra + (off_eps >= 0 ? 1 : 0)) + (kOvfTop + 1) * (k - 1) < P - (off_eps >= 0 ? 1 : 0);
+    }
     static __host__ size_t lds_bytes(int D, int L, int P) {
         return sizeof(double) * ((size_t)2 * D * L + 4 * L + D + 8 + 16 + 16 * NFP + (size_t)(P + kExtra + 7));
     }
@@ -968,7 +1000,7 @@ struct LinUpdM {
         const int t = threadIdx.x;
 #pragma unroll
         for (int k = 0; k < LKOUT; ++k) {
-            const int idx = min(t + LNT * k, P - 1);
+            const int o = out_index(t, k), idx = o >= 0 && o < P ? o : P - 1;
             p[k] = a.params[idx]; m[k] = a.m[idx]; v[k] = a.v[idx];
         }
         if (off_eps < 0 && t == 0) { const double e = (double)a.eps_cli; scal[0] = e; scal[1] = lin_exp(0.5 * e); scal[2] = lin_exp(-e); }
@@ -992,26 +1024,34 @@ struct LinUpdM {
     // float64 copies of this thread's own parameters into the arrays the products read
     __device__ __forceinline__ void publish_params(const LinArgs& a) {
         const int t = threadIdx.x;
+        int ei = -1;                                                   // the ONE output of this thread behind an exponential, if any
+        double epv = 0.0;
 #pragma unroll
         for (int k = 0; k < LKOUT; ++k) {
-            const int i = t + LNT * k;
+            if (!slot_used(k)) break;
+            const int i = out_index(t, k);
             const double pv = (double)p[k];
+            if (i < 0 || i >= P) continue;
             if (i < off_be) Wed[i] = pv;
             else if (i < off_wd) bed[i - off_be] = pv;
             else if (i < off_bd) Wdd[i - off_wd] = pv;
             else if (i < off_epsp) bdd[i - off_bd] = pv;
-            else if (i < off_epsp + L || i == off_eps) {
-                // e^{lv / 2} and e^{eps / 2}, e^{-eps}: the same instruction stream for the latent lanes and the epsilon lane
-                const bool is_eps = i == off_eps;
-                const double e = is_eps ? pv * (double)a.eps_cli : pv, h = lin_exp(0.5 * e);
-                if (is_eps) {
-                    const double q = h * h;
-                    double r = __builtin_amdgcn_rcp(q);                // 1 / sigma^2: hardware seed, two Newton steps (full double precision)
-                    r = fma(fma(-q, r, 1.0), r, r); r = fma(fma(-q, r, 1.0), r, r);
-                    scal[0] = e; scal[1] = h; scal[2] = r;
-                }
-                else { sd[i - off_epsp] = h; elv[i - off_epsp] = h * h; lvd[i - off_epsp] = pv; }
+            // (at most ONE such output per thread: the latent lanes are L <= 32 consecutive plain outputs, and two slots of one thread
+            // hold plain outputs at least 2 (kOvfTop - t) + LNT - kOvfTop - 5 >= 60 apart -- slot 0 holds rank t, slot 1 rank
+            // LNT - ns + kOvfTop - t with t <= kOvfTop, later slots kOvfTop + 1 further each; the epsilon lane has slot 0 only)
+            else if (i < off_epsp + L || i == off_eps) { ei = i; epv = pv; }
+        }
+        if (ei >= 0) {
+            // e^{lv / 2} and e^{eps / 2}, e^{-eps}: the same instruction stream for the latent lanes and the epsilon lane
+            const bool is_eps = ei == off_eps;
+            const double e = is_eps ? epv * (double)a.eps_cli : epv, h = lin_exp<true>(0.5 * e);      // (coefficients in scalar registers: hoisted into vector registers they push the step loop into scratch)
+            if (is_eps) {
+                const double q = h * h;
+                double r = __builtin_amdgcn_rcp(q);                    // 1 / sigma^2: hardware seed, two Newton steps (full double precision)
+                r = fma(fma(-q, r, 1.0), r, r); r = fma(fma(-q, r, 1.0), r, r);
+                scal[0] = e; scal[1] = h; scal[2] = r;
             }
+            else { sd[ei - off_epsp] = h; elv[ei - off_epsp] = h * h; lvd[ei - off_epsp] = epv; }
         }
     }
     // one step.  In: parameters published and a barrier behind them; mreg = this lane's values of the batch's M (chain waves).
@@ -1233,11 +1273,11 @@ struct LinUpdM {
         const float bc1 = (float)part[13], bc2 = (float)part[14];
 #pragma unroll
         for (int k = 0; k < LKOUT; ++k) {
-            const int idx = t + LNT * k;
-            if (LNT * k >= P + 3) break;                               // (uniform) nothing lives up here
+            if (!slot_used(k)) break;                                  // (uniform) nothing lives up here
+            const int idx = out_index(t, k);
             double gd = 0.0;
-            if (idx < P && idx != off_eps) gd = gq[idx];
-            else if (idx == off_eps || (idx >= P && idx < P + 3)) {
+            if (idx >= 0 && idx < P && idx != off_eps) gd = gq[idx];
+            else if (k == 0 && idx >= 0 && (idx == off_eps || (idx >= P && idx < P + 3))) {      // (special outputs: slot 0 only)
                 const double ssq = part[0] + part[3] + part[6] + part[9], musq = part[1] + part[4] + part[7], z2r = part[2] + part[5] + part[8], klc = part[12];
                 if (idx == off_eps) gd = (double)a.eps_cli * (-0.5 * ssq * inv_var + 0.5 * rows * D + 0.5 * sigma * z2r * inv_var) * inv_bt;
                 else {
@@ -1249,7 +1289,7 @@ struct LinUpdM {
             const float gf = (float)gd;
             gout[k] = gf;
             if (idx == P && a.loss_hist) a.loss_hist[(long long)(tstep - 1) % a.loss_hist_cap] = gf;
-            if (idx < P) adam_apply_f(p[k], gf, m[k], v[k], a.lr, bc1, bc2);
+            if (idx >= 0 && idx < P) adam_apply_f(p[k], gf, m[k], v[k], a.lr, bc1, bc2);
         }
         LIN_STAMP(6);
     }
@@ -1257,9 +1297,9 @@ struct LinUpdM {
         const int t = threadIdx.x;
 #pragma unroll
         for (int k = 0; k < LKOUT; ++k) {
-            const int idx = t + LNT * k;
-            if (idx < P + kExtra) a.grads[idx] = gout[k];
-            if (idx < P) { a.params[idx] = p[k]; a.m[idx] = m[k]; a.v[idx] = v[k]; }
+            const int idx = out_index(t, k);
+            if (idx >= 0 && idx < P + kExtra) a.grads[idx] = gout[k];
+            if (idx >= 0 && idx < P) { a.params[idx] = p[k]; a.m[idx] = m[k]; a.v[idx] = v[k]; }
         }
         if (t == 0) a.step_dev[0] = tstep;
     }
@@ -1787,7 +1827,7 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
             if (rb == 5) { LIN_PUT(40, racc_w); LIN_PUT(41, racc_r); }
             if (rb == 5 && n < 3) { LIN_PUT(56 + 2 * n, r1); LIN_PUT(57 + 2 * n, r2); }
             if (t == 0) __hip_atomic_fetch_add(a.cnt_reduce + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            { [[maybe_unused]] unsigned long long te = 0; LIN_NOW(te); LIN_PUTMAX(136 + n, te); }      // (64 .. 129: the updater's, up to kLinSlots batches)
+            { [[maybe_unused]] unsigned long long te = 0; LIN_NOW(te); LIN_PUTMAX(136 + n, te); }      // (64 .. 131: the updater's, up to kLinSlots batches)
         }
     } else {
         // ---- streamers: workgroup sid takes tiles sid, sid + S, ... of every batch, in batch order, through a ring of THREE LDS
@@ -2078,8 +2118,8 @@ LinPersistGenKernel lin_persist_four_gen(int which);
 #ifndef VAEK_LIN_FOUR_BLOCK_TU
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 constexpr size_t kLinMaxLds = 160 * 1024;
-// workspace: [cnt_stream: kLinSlots (66) batches x 8 shards x 128 B][cnt_reduce: 66 words][status word, init mark][66 M slots][66 partial
-// image slots] -- the metric's shape: 66 x 228 images of 6 KB = 92.5 MB
+// workspace: [cnt_stream: kLinSlots (68) batches x 8 shards x 128 B][cnt_reduce: 68 words][status word, init mark][68 M slots][68 partial
+// image slots] -- the metric's shape: 68 x 228 images of 6 KB = 95.3 MB
 constexpr size_t kLinCntStreamBytes = (size_t)kLinSlots * kLinShards * kLinShardStride * 4, kLinCntBytes = kLinCntStreamBytes + 1024, kLinHeadBytes = kLinCntBytes + 256;
 static_assert(kLinSlots * sizeof(unsigned) <= 1024, "cnt_reduce");
 
