@@ -388,6 +388,61 @@ int vaek_train_loop_gen_replicas_traj(vaek_ctx* ctx, float* params, float* grads
                                       const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
                                       float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream,
                                       const vaek_trajectory* traj);
+/* STATS EVENT of a replica sweep in one launch (csrc/linear_stats.hip): what the reference's compute_stats() does for one model at
+ * every n_print step (model.py:153-168) -- draw `rows` real rows and `rows` latent rows, VAE.loss on them (networks.py:103-113),
+ * sample a fake batch from the SAME latents (networks.py:62-65, vae.py:191-201) and score it (datasets.py score_batch) -- for N
+ * models of the context's shape: workgroup r evaluates model r.  On the host one such event is two vaek_make_batch launches,
+ * vaek_forward, vaek_loss_eval (both layer by layer), a chain of torch ops and several read-backs PER MODEL; here it is one launch
+ * for the sweep, and nothing of a batch ever exists in HBM.  No cross-workgroup state: no counter, no wait, no atomic, no status.
+ * Replica r reads params + r * state_stride (vaek_param_count floats; never written), A + r * a_stride (a_stride == 0: one matrix
+ * shared; A may be NULL for kind 2), x_seeds[r], x_steps[r], z_seeds[r], z_steps[r], sample_eps[r], and
+ *   - draws row i of the real batch exactly as vaek_make_batch(kind, A_r, dd, did, pad, var_added, rows, row0 = 0, x_seeds[r],
+ *     step_host = x_steps[r], x_tag) writes x, and row i of the latents as vaek_make_batch(..., z_seeds[r], z_steps[r], z_tag)
+ *     writes z1 / z2 (the same Philox counters and csrc/rng_dev.h maps, bit for bit);
+ *   - evaluates mu = Encoder(x), samples = mu + exp(epsilon_p / 2) z1, x_hat = Decoder(samples) [+ sigmoid(SigDecoder(samples))]
+ *     + z2 exp(eps / 2) with eps = params[epsilon] * eps_cli under tunable_eps, else eps_cli: loss, mean Dkl, mean mse as plain means
+ *     over `rows` (what vaek_loss_eval returns on those draws);
+ *   - samples fake = Decoder(z1) [+ sigmoid(SigDecoder(z1))] + z2 exp(sample_eps[r] / 2) (vaek_forward(sampling = 1, eps =
+ *     sample_eps[r]) on those latents; the caller's current_epsilon: the PREVIOUS event's eps) and scores it:
+ *       kind 0: mean sum_{c >= dd} fake^2;
+ *       kind 1: mean sum_{c > dd} fake^2, then the manifold error as the reference's broadcast of (B,) against (B, 1) defines it: the
+ *               mean over ALL pairs (i, j) of (fake[j, dd] - fake[i, :dd] . A)^2, from four float64 sums, never a B x B array;
+ *       kind 2: mean (|fake[:, :dd]| - 1)^2, then mean sum_{c >= dd} fake^2.
+ * RECORD of vaek_stats_record_len = 8 + L floats at out + r * out_stride, written with per-lane vector stores:
+ *   [0] loss  [1] mean Dkl  [2] mean mse  [3] eps  [4], [5] the score values in the order above (a kind with one value: [5] = 0)
+ *   [6], [7] 0  [8, 8 + L) epsilon_p, copied.
+ * Floats between two records where out_stride exceeds the length are not touched; nothing but the records is written.
+ * DEFINING PROPERTIES: per-element arithmetic is float32; every sum over rows is accumulated in float64, per thread over its rows
+ * and across the workgroup in a fixed order.  So replica r's record is BITWISE what a call with n = 1 on replica r's slices
+ * leaves, two runs are bitwise equal, and the record agrees with the host path (vaek_make_batch, vaek_loss_eval, vaek_forward,
+ * score_batch) and the float64 oracle within the ELBO contract (1e-5 of |loss|; scores 1e-5 relative).
+ * Independent of ctx.batch: `rows` is the event's own, 1 .. vaek_stats_event_max_rows() = 4096 (a cap that bounds one launch, not
+ * a tuned value); n is 1 .. vaek_train_loop_max_replicas().  No workspace.  Asynchronous on `stream`, allocates nothing, does not
+ * synchronise, capturable into a hipGraph.  Profile label linear_stats_replicas.
+ * vaek_supports_stats_event: exactly the contexts and kinds vaek_supports_train_loop_gen accepts.
+ * VAEK_ERR_INVALID (with a message, nothing touched): a NULL or unsupported context, NULL params or event, a wrong struct_size, n or
+ * rows out of range, a NULL seeds, steps, sample_eps or out array, state_stride < P, out_stride < the record length, a_stride < 0,
+ * NULL A for kind 0 or 1, dd or did > 16, dd + pad (+ 1 for kind 1) != data_dim, kind outside 0 .. 2, a tag >= 2^30. */
+typedef struct vaek_stats_event {
+    int32_t struct_size;                  /* = sizeof(vaek_stats_event), ABI guard                  */
+    int32_t n;                            /* replicas = workgroups of the launch                    */
+    int32_t rows;                         /* rows of the event, 1 .. vaek_stats_event_max_rows()    */
+    int32_t reserved;
+    int64_t state_stride;                 /* floats between two replicas' params, >= P              */
+    const uint64_t* x_seeds;              /* device [n]: seed of the real batch                     */
+    const uint32_t* x_steps;              /* device [n]: its RNG step                               */
+    const uint64_t* z_seeds;              /* device [n]: seed of the latents                        */
+    const uint32_t* z_steps;              /* device [n]: their RNG step                             */
+    const float* sample_eps;              /* device [n]: eps of the sampling pass                   */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared             */
+    float* out;                           /* device: record r at out + r * out_stride               */
+    int64_t out_stride;                   /* >= vaek_stats_record_len                               */
+} vaek_stats_event;
+int vaek_supports_stats_event(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_stats_record_len(const vaek_ctx* ctx, int64_t* floats);
+int vaek_stats_event_max_rows(void);
+int vaek_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_stats_event* ev, int32_t kind, const float* A, int32_t dd,
+                              int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

@@ -46,6 +46,18 @@ class VaekTrajectory(C.Structure):
     ]
 
 
+class VaekStatsEvent(C.Structure):
+    """vaek_stats_event of include/vaek.h: the per-replica description of vaek_stats_event_replicas (device pointers)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32), ("state_stride", C.c_int64),
+        ("x_seeds", C.c_void_p), ("x_steps", C.c_void_p), ("z_seeds", C.c_void_p), ("z_steps", C.c_void_p), ("sample_eps", C.c_void_p),
+        ("a_stride", C.c_int64), ("out", C.c_void_p), ("out_stride", C.c_int64),
+    ]
+
+
+STATS_RECORD_HEAD = 8      # floats of a stats record in front of the epsilon_p copy: loss, Dkl, mse, eps, two score values, 0, 0
+
+
 def trajectory_slot(t, every, cap):
     """The slot rule of vaek_trajectory: the ring slot of the record of Adam step t (1-based), or None where step t is not recorded."""
     if t < 1 or t % every:
@@ -116,6 +128,10 @@ SIGNATURES = {
                                            _f32, _vp, _vp, C.POINTER(VaekTrajectory)]),
     "vaek_train_loop_gen_replicas_traj": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(VaekReplicas), _i32, _vp, _i32, _i32, _i32, _f32,
                                                     C.c_int64, C.c_uint32, _i32, _f32, _vp, _vp, C.POINTER(VaekTrajectory)]),
+    "vaek_supports_stats_event": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_stats_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "vaek_stats_event_max_rows": (C.c_int, []),
+    "vaek_stats_event_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekStatsEvent), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32, _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

@@ -14,6 +14,12 @@ from . import random as vrandom
 
 DEVICE_DRAW_MAX_DIM = 16      # csrc/rng.hip make_batch_args: -dd / -did above this are drawn with torch ops instead
 
+# score_batch's keys by device_spec kind, in the order of each class's dict below: the order vaek_stats_event_replicas writes the score
+# values of a fake batch in (trainer.ReplicaStats)
+SCORE_KEYS = {0: ("Squared Norm of padding dimensions",),
+              1: ("Squared Norm of Padding Dimensions", "Squared Norm of Manifold Dimension"),
+              2: ("Sphere Error", "Padding Error")}
+
 
 def _device():
     return torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")

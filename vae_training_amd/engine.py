@@ -246,6 +246,50 @@ class Engine:
             return
         _lib.check(self.lib.vaek_train_loop_gen_replicas(*args))
 
+    def supports_stats_event(self, kind):
+        """True where stats_event_replicas covers this engine and dataset kind: exactly where supports_train_loop_gen does."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_stats_event(self.h, int(kind), C.byref(f)))
+        return bool(f.value)
+
+    @property
+    def stats_record_len(self):
+        """Floats in one stats record (vaek_stats_record_len): 8 + L = loss, mean Dkl, mean mse, eps, two score values, 0, 0, epsilon_p."""
+        n = C.c_int64()
+        _lib.check(self.lib.vaek_stats_record_len(self.h, C.byref(n)))
+        return int(n.value)
+
+    @property
+    def stats_event_max_rows(self):
+        return int(self.lib.vaek_stats_event_max_rows())
+
+    def stats_event_replicas(self, params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
+                             a_stride=0, x_tag=1, z_tag=2, n=None, state_stride=None, out_stride=None, struct_size=None):
+        """The stats event of EACH of n independent models of this engine's shape in one launch, workgroup r evaluating replica r
+        (vaek_stats_event_replicas): `rows` real rows drawn under (x_seeds[r], x_steps[r], x_tag) and `rows` latent rows under
+        (z_seeds[r], z_steps[r], z_tag) exactly as make_batch draws them, VAE.loss on them, a fake batch sampled from the same
+        latents with eps = sample_eps[r], and its score.  params: [n, state_stride] (read only), x_seeds / z_seeds: int64 [n] (the
+        bits of the uint64 seeds), x_steps / z_steps: int32 [n] (the bits of the uint32 steps), sample_eps: float32 [n], A: replica
+        r's at A + r * a_stride floats (0: shared), out: float32 [n, out_stride >= stats_record_len] -- all device tensors; n and
+        the strides default to the tensors' shapes.  Record r lands in out[r, :stats_record_len]: loss, mean Dkl, mean mse, eps, the
+        score values in score_batch's order, 0, 0, epsilon_p.  Asynchronous; capturable."""
+        ev = _lib.VaekStatsEvent()
+        ev.struct_size = C.sizeof(_lib.VaekStatsEvent) if struct_size is None else int(struct_size)
+        ev.n = int(params.shape[0] if n is None else n)
+        ev.rows = int(rows)
+        ev.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        assert all(s is None or s.dtype == torch.int64 for s in (x_seeds, z_seeds))
+        assert all(s is None or s.dtype == torch.int32 for s in (x_steps, z_steps))
+        assert sample_eps is None or sample_eps.dtype == torch.float32
+        assert out is None or out.dtype == torch.float32
+        ev.x_seeds, ev.x_steps, ev.z_seeds, ev.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
+        ev.sample_eps = _ptr(sample_eps)
+        ev.a_stride = int(a_stride)
+        ev.out = _ptr(out)
+        ev.out_stride = int((0 if out is None else out.shape[-1]) if out_stride is None else out_stride)
+        _lib.check(self.lib.vaek_stats_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                      float(var_added), int(x_tag), int(z_tag), _stream()))
+
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
         f = C.c_int32()

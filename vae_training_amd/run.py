@@ -2,7 +2,8 @@
 --dataset linear_gaussian ...` trains a VAE with the HIP kernels and leaves data/NAME/{args.json,
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
-which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every."""
+which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
+--fused_stats."""
 from __future__ import annotations
 
 import argparse
@@ -65,6 +66,11 @@ def build_parser():
                         "--sweep_dataset_seeds trainer.ReplicaLoop).  Each output directory gains trajectory.npz (steps, params, grads and "
                         "the leaf table) and losses.npz a Correlation Ratio per record (vae.py:143-179).  Linear VAEs the resident loop "
                         "covers only; other models are refused before any step; single GPU only")
+    p.add_argument("--fused_stats", dest="fused_stats", action="store_true",
+                   help="with --sweep_dataset_seeds on models the resident loop covers: the stats event at every n_print step is ONE launch "
+                        "for all models (trainer.ReplicaStats, vaek_stats_event_replicas) instead of one compute_stats() per model.  The "
+                        "same draws, the same host RNG bookkeeping, the same keys in losses.npz.  Refused before any step without "
+                        "--sweep_dataset_seeds and on a sweep of three-hidden-layer MLP VAEs (their events stay per model)")
     return p
 
 
@@ -209,6 +215,16 @@ def sweep_loop(models, trajectory_every=None):
                        f"layers of 64 .. 256 units both ways, D, L <= 32, a batch of at most 128 rows (this model's step path: {eng.step_path})")
 
 
+FUSED_STATS_NEEDS = ("--sweep_dataset_seeds on models the resident loop covers (trainer.ReplicaLoop): the fused event evaluates the "
+                     "models of a sweep in one launch, workgroup r model r")
+
+
+def check_fused_stats_args(args):
+    """--fused_stats without --sweep_dataset_seeds: refused before anything is created."""
+    if getattr(args, "fused_stats", False) and not getattr(args, "sweep_dataset_seeds", None):
+        raise RuntimeError(f"--fused_stats needs {FUSED_STATS_NEEDS}; a single model's stats event is compute_stats()")
+
+
 def main_sweep(args):
     """--sweep_dataset_seeds: one dataset and one VAEModel per seed, the reference's schedule (model.py:207-222: stats every n_print
     steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE loop.run between
@@ -235,8 +251,16 @@ def main_sweep(args):
     tevery = getattr(args, "trajectory_every", None)
     loop = sweep_loop(models, tevery) if tevery is not None else sweep_loop(models)      # refuses, before any step, what no replica loop covers
     eng = loop.eng
+    fused_stats = bool(getattr(args, "fused_stats", False))
+    if fused_stats:                          # before any step
+        from .trainer import ReplicaLoop
+        if not isinstance(loop, ReplicaLoop):
+            raise RuntimeError(f"--fused_stats needs {FUSED_STATS_NEEDS}; this sweep's step path is {eng.step_path!r} "
+                               "(trainer.ReplicaGraphLoop), whose stats events stay one compute_stats() per model")
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
+    if fused_stats:
+        print(f"Stats events: one launch for {len(models)} models (vaek_stats_event_replicas)")
     for r, m in enumerate(models):
         m._graph_loop = loop.view(r)
         score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
@@ -249,10 +273,11 @@ def main_sweep(args):
         loop.run(ev - pos)
         pos = ev
         loop.check()
-        for m in models:
+        fused = loop.stats_event() if fused_stats and ev % n_print == 0 else None      # every model's event in one launch
+        for r, m in enumerate(models):
             m.batchnum = ev
             if ev % n_print == 0:
-                m.write_stats(m.compute_stats())
+                m.write_stats(m.compute_stats() if fused is None else fused[r])
             if ev % n_plot == 0 or ev == n - 1:
                 m.plot_epoch()
                 m.save()
@@ -269,6 +294,7 @@ def main_sweep(args):
 def main(args):
     import os
 
+    check_fused_stats_args(args)
     if getattr(args, "sweep_dataset_seeds", None):
         return main_sweep(args)
     from .utils import get_output_dir, make_output_dir

@@ -380,6 +380,13 @@ class ReplicaLoop:
         return _trajectory_view(self.traj_ring[r].cpu(), self.trajectory_every, self.traj_from[r], m.optimizer.state.step,
                                 m.model.flat.numel())
 
+    def stats_event(self, rows=None):
+        """One stats event of every model in ONE launch (ReplicaStats, vaek_stats_event_replicas): [compute_stats' dict of model 0,
+        ...], with the models' keys, draw counters and lists advanced exactly as compute_stats would advance them."""
+        if getattr(self, "_stats", None) is None or (rows is not None and int(rows) != self._stats.rows):
+            self._stats = ReplicaStats(self.ms, rows=rows)
+        return self._stats.event()
+
     def check(self):
         """Nothing to poll: the launch has no waits."""
 
@@ -396,6 +403,111 @@ class ReplicaLoop:
     def view(self, r):
         """Model r's `_graph_loop`: losses() without an argument, as VAEModel.model_save_data calls it."""
         return _ReplicaLosses(self, r)
+
+
+class ReplicaStats:
+    """The stats event of a sweep as ONE launch: what `compute_stats()` does for one model at every n_print step -- a batch of real
+    rows, a batch of latents, VAE.loss on them, a fake batch sampled from the same latents, its score -- for R VAEModels of one
+    shape (validated as in ReplicaLoop) through vaek_stats_event_replicas (csrc/linear_stats.hip): workgroup r evaluates model r.
+
+    event() copies each model's `model.flat` into its row of an [R, P] stack owned by this object (the rule of ReplicaLoop.run:
+    between two calls the models are ordinary models), makes ONE library call and ONE device -> host copy of the [R, 8 + L] records,
+    and then does for every model exactly the host bookkeeping of compute_stats + compute_model_stats: the model's key is split,
+    `_latent_draws` and the dataset's `_draws` advance, the seeds are the ones `_latent_pair` (tag 2) and `_device_batch` (tag 1)
+    derive, `vae_losses`, `var_enc` and `var_dec` grow by one entry and `current_epsilon` becomes this event's eps.  After it every
+    piece of host RNG state is what the host event would have left, so fused and host events can be mixed freely.  The fake batch
+    is sampled with the model's `current_epsilon` as it was BEFORE the event, as sample_batch does.  Returns one stats dict per
+    model, compute_stats' keys in its order; the values are host tensors (nothing to read back when they are printed)."""
+
+    def __init__(self, vae_models, rows=None):
+        ms = list(vae_models)
+        if not ms:
+            raise RuntimeError("ReplicaStats: no models")
+        from .datasets import DEVICE_DRAW_MAX_DIM, SCORE_KEYS
+        self.ms = ms
+        m0 = ms[0]
+        self.eng = m0.model.module.engine(m0.batch_size, m0.optimizer.global_batch)
+        specs = [m.dataset.device_spec() for m in ms]
+        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
+        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
+            raise RuntimeError(f"ReplicaStats draws its batches with libvaek's Philox generator, which supports -dd / -did <= "
+                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
+        if self.eng.world > 1:
+            raise RuntimeError("ReplicaStats: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
+        if not self.eng.supports_stats_event(self.kind):
+            raise RuntimeError("ReplicaStats: vaek_stats_event_replicas does not cover this model / dataset (it needs what the resident loop "
+                               "needs: a float32 linear VAE with one or two decoders, D, L <= 32 and a train batch of at most 256 rows)")
+        R = len(ms)
+        if R > self.eng.train_loop_max_replicas:
+            raise RuntimeError(f"ReplicaStats: {R} models, at most {self.eng.train_loop_max_replicas} fit one launch "
+                               "(vaek_train_loop_max_replicas)")
+        want = ReplicaLoop._signature(m0, specs[0])
+        for r, (m, sp) in enumerate(zip(ms, specs)):
+            got = ReplicaLoop._signature(m, sp)
+            if got != want:
+                raise RuntimeError(f"ReplicaStats: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
+                                   f"{want}): one launch evaluates replicas of ONE shape")
+        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
+        if not 1 <= self.rows <= self.eng.stats_event_max_rows:
+            raise RuntimeError(f"ReplicaStats: {self.rows} rows per event, need 1 .. {self.eng.stats_event_max_rows} (vaek_stats_event_max_rows)")
+        self.R = R
+        self.score_keys = SCORE_KEYS[self.kind]
+        dev = self.eng.device
+        self.L = self.eng.L
+        self.record_len = self.eng.stats_record_len
+        self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
+        self.out = torch.zeros(R, self.record_len, dtype=torch.float32, device=dev)
+        if specs[0][1] is None:
+            self.A, self.a_stride = None, 0
+        else:
+            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
+            self.a_stride = self.A.shape[1]
+
+    def event(self):
+        """One stats event of every model: [stats dict of model 0, ...]."""
+        from . import random as vrandom
+        dev = self.eng.device
+        i64 = lambda s: s - 2 ** 64 if s >= 2 ** 63 else s
+        i32 = lambda s: s - 2 ** 32 if s >= 2 ** 31 else s
+        x_seeds, x_steps, z_seeds, z_steps, eps_in = [], [], [], [], []
+        for r, m in enumerate(self.ms):
+            self.params[r].copy_(m.model.flat)
+            key, m.key = vrandom.split(m.key)                                    # compute_stats
+            ds = m.dataset
+            ds._draws = getattr(ds, "_draws", 0) + 1                              # _device_batch: seed, step, tag 1
+            x_seeds.append(i64((ds.key[0] ^ ds.key[1]) & (2 ** 64 - 1)))
+            x_steps.append(i32(ds._draws & (2 ** 32 - 1)))
+            m._latent_draws = getattr(m, "_latent_draws", 0) + 1                   # _latent_pair: seed, step, tag 2
+            z_seeds.append(i64((key[0] ^ key[1]) & (2 ** 64 - 1)))
+            z_steps.append(i32(m._latent_draws & (2 ** 32 - 1)))
+            eps_in.append(m.current_epsilon)                                      # sample_batch: the PREVIOUS event's eps
+        t64 = lambda v: torch.tensor(v, dtype=torch.int64).to(dev)
+        t32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)
+        # an eps a host event left is a device tensor: it stays on the device (no read-back); every other one goes up in one copy
+        on_dev = [torch.is_tensor(e) and e.device.type != "cpu" for e in eps_in]
+        sample_eps = torch.tensor([0.0 if d else float(torch.as_tensor(e).reshape(-1)[0]) for e, d in zip(eps_in, on_dev)],
+                                  dtype=torch.float32).to(dev)
+        for r, (e, d) in enumerate(zip(eps_in, on_dev)):
+            if d:
+                sample_eps[r:r + 1].copy_(e.reshape(-1)[:1])
+        self.eng.stats_event_replicas(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, t64(x_seeds),
+                                      t32(x_steps), t64(z_seeds), t32(z_steps), sample_eps, self.out, a_stride=self.a_stride,
+                                      x_tag=1, z_tag=2)
+        rec = self.out.cpu()                                                      # the event's ONE device -> host copy
+        stats = []
+        for r, m in enumerate(self.ms):
+            row = rec[r]
+            tdv = bool(getattr(m.model.module, "tunable_decoder_var", False))
+            eps = row[3:4].clone() if tdv else m.epsilon                          # VAE.loss: a (1,) tensor under -tdv, else the CLI float
+            m.vae_losses.append(row[0].clone())                                   # compute_model_stats
+            m.var_enc.append(row[8:8 + self.L].clone())
+            m.var_dec.append(eps.clone() if torch.is_tensor(eps) else eps)
+            m.current_epsilon = eps.clone() if torch.is_tensor(eps) else eps
+            st = {"VAE Loss": row[0].clone(), "KL divergence": row[1].clone(), "mse": row[2].clone()}
+            for k, name in enumerate(self.score_keys):                            # score_batch's dict, in its order
+                st[name] = row[4 + k].clone()
+            stats.append(st)
+        return stats
 
 
 class ReplicaGraphLoop:
