@@ -443,6 +443,69 @@ int vaek_stats_record_len(const vaek_ctx* ctx, int64_t* floats);
 int vaek_stats_event_max_rows(void);
 int vaek_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_stats_event* ev, int32_t kind, const float* A, int32_t dd,
                               int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream);
+/* IMPORTANCE-WEIGHTED LOG-LIKELIHOOD of N linear VAEs of the context's shape in one call (csrc/linear_loglik.hip): the stat the
+ * reference reserves as `Average Log Likelihood` and never fills.  For replica r, over `rows` data rows x and `samples` = K
+ * importance samples per row (xi_k ~ N(0, I_L)):
+ *   z_k     = mu(x) + exp(epsilon_p / 2) * xi_k                                       mu = Encoder(x)
+ *   log w_k = log p(x | z_k) + log p(z_k) - log q(z_k | x)
+ *           = -1/2 [ |dec(z_k) - x|^2 e^{-eps} + D (eps + log 2 pi) ] + 1/2 sum_l ( xi_kl^2 - z_kl^2 + epsilon_p[l] )
+ * with dec(z) = Decoder(z) [+ sigmoid(SigDecoder(z))] and eps = params[epsilon] * eps_cli under tunable_eps, else eps_cli.  There is
+ * no decoder-noise term: this is the likelihood, not the one-sample loss of vaek_loss_eval (whose expectation is -ELBO + D / 2).
+ * RECORD of vaek_log_likelihood_record_len() = 4 floats at out + r * out_stride, written with per-lane vector stores:
+ *   [0] mean over rows of logsumexp_k(log w_k) - log K      the IWAE-K bound on log p(x): `Average Log Likelihood`
+ *   [1] mean over rows of mean_k log w_k                    the K-sample ELBO estimate
+ *   [2] mean over rows of (sum_k w_k)^2 / (K sum_k w_k^2)   the normalised effective sample size, in (0, 1]
+ *   [3] eps as used.
+ * Floats between two records where out_stride exceeds the length are not touched; nothing but the records and the workspace is
+ * written.  Replica r reads params + r * state_stride (vaek_param_count floats; never written), z_seeds[r], z_steps[r] and
+ *   - EXPLICIT ROWS (x != NULL): its rows from x + r * x_stride as [rows][D] floats (x_stride == 0: one set of rows shared by all
+ *     replicas); kind, A, dd, did, pad, var_added, x_tag, x_seeds, x_steps and a_stride are ignored;
+ *   - DRAWING MODE (x == NULL): row i exactly as vaek_make_batch(kind, A + r * a_stride, dd, did, pad, var_added, rows, row0 = 0,
+ *     x_seeds[r], step_host = x_steps[r], x_tag) writes x (the same Philox counters and csrc/rng_dev.h maps, bit for bit).
+ * BLOCK RULE of the samples: sample k of row i takes its L normals from Philox blocks q = k * ceil(L / 4) + j, j < ceil(L / 4), of
+ * the latent stream vaek_make_batch draws z1 / z2 from under (z_seeds[r], z_steps[r], z_tag) -- normal l of the sample is element
+ * l & 3 of block k * ceil(L / 4) + (l >> 2).  Sample 0 is therefore the z1 vaek_make_batch writes under the same seed, step and tag.
+ * DEFINING PROPERTIES: per-sample arithmetic is float32, with an online log-sum-exp over k in k order; every sum over rows is
+ * float64 in a fixed order (a binary tree per 256-row tile, then the tiles in tile order in a second launch: the partials cross a
+ * launch boundary, nothing stored in a launch is read back in it; no atomic, counter or wait).  So replica r's record is BITWISE
+ * what a call with n = 1 on replica r's slices leaves, two runs are bitwise equal, drawing mode equals explicit mode on the rows
+ * vaek_make_batch writes, and the record does not depend on ctx.batch.  Slots [0], [1] agree with the float64 evaluation on the same
+ * draws within the ELBO contract (1e-5 of |value|), slot [2] within 1e-5 relative.
+ * rows is 1 .. vaek_log_likelihood_max_rows() = 4096 and samples 1 .. vaek_log_likelihood_max_samples() = 1024 (caps that bound the
+ * length of one launch on a shared machine, not tuned values); n is 1 .. vaek_train_loop_max_replicas().  `workspace`: device memory
+ * of vaek_log_likelihood_workspace_bytes(ctx, n, rows) bytes, 8-byte aligned, the call's own (not the context's), no need to clear.
+ * Two launches per call whatever n is (profile labels linear_loglik_replicas, linear_loglik_finalize); asynchronous on `stream`,
+ * allocates nothing, does not synchronise, capturable into a hipGraph.
+ * vaek_supports_log_likelihood: float32, no hidden layers, one or two decoders, D, L <= 32 (D <= 28 with two decoders), kind
+ * 0 .. 2 -- whatever ctx.batch, world and force_generic are: the call reads parameters only.
+ * VAEK_ERR_INVALID (with a message, nothing touched): a NULL or unsupported context (hidden layers, bf16, a larger shape), NULL
+ * params or description, a wrong struct_size, n, rows or samples out of range, a NULL z_seeds, z_steps or out, state_stride < P,
+ * out_stride < 4, a NULL or misaligned workspace, z_tag >= 2^30; explicit rows: x_stride < 0 or 0 < x_stride < rows * D; drawing
+ * mode: NULL x_seeds or x_steps, a_stride < 0, NULL A for kind 0 or 1, dd or did > 16, dd + pad (+ 1 for kind 1) != data_dim, kind
+ * outside 0 .. 2, x_tag >= 2^30. */
+typedef struct vaek_log_likelihood {
+    int32_t struct_size;                  /* = sizeof(vaek_log_likelihood), ABI guard                   */
+    int32_t n;                            /* replicas                                                   */
+    int32_t rows;                         /* data rows, 1 .. vaek_log_likelihood_max_rows()             */
+    int32_t samples;                      /* importance samples per row, 1 .. ..._max_samples()         */
+    int64_t state_stride;                 /* floats between two replicas' params, >= P                  */
+    const uint64_t* x_seeds;              /* device [n]: seed of the rows (drawing mode)                */
+    const uint32_t* x_steps;              /* device [n]: their RNG step (drawing mode)                  */
+    const uint64_t* z_seeds;              /* device [n]: seed of the samples                            */
+    const uint32_t* z_steps;              /* device [n]: their RNG step                                 */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared (drawing mode)  */
+    float* out;                           /* device: record r at out + r * out_stride                   */
+    int64_t out_stride;                   /* >= vaek_log_likelihood_record_len()                        */
+    const float* x;                       /* device [rows][D] per replica: explicit rows; NULL = draw   */
+    int64_t x_stride;                     /* floats between two replicas' rows; 0 = shared              */
+} vaek_log_likelihood;
+int vaek_supports_log_likelihood(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_log_likelihood_record_len(void);
+int vaek_log_likelihood_max_rows(void);
+int vaek_log_likelihood_max_samples(void);
+int vaek_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes);
+int vaek_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, int32_t kind, const float* A, int32_t dd,
+                                 int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* workspace, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

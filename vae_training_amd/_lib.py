@@ -55,6 +55,15 @@ class VaekStatsEvent(C.Structure):
     ]
 
 
+class VaekLogLikelihood(C.Structure):
+    """vaek_log_likelihood of include/vaek.h: the per-replica description of vaek_log_likelihood_replicas (device pointers)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n", C.c_int32), ("rows", C.c_int32), ("samples", C.c_int32), ("state_stride", C.c_int64),
+        ("x_seeds", C.c_void_p), ("x_steps", C.c_void_p), ("z_seeds", C.c_void_p), ("z_steps", C.c_void_p), ("a_stride", C.c_int64),
+        ("out", C.c_void_p), ("out_stride", C.c_int64), ("x", C.c_void_p), ("x_stride", C.c_int64),
+    ]
+
+
 STATS_RECORD_HEAD = 8      # floats of a stats record in front of the epsilon_p copy: loss, Dkl, mse, eps, two score values, 0, 0
 
 
@@ -132,6 +141,13 @@ SIGNATURES = {
     "vaek_stats_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
     "vaek_stats_event_max_rows": (C.c_int, []),
     "vaek_stats_event_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekStatsEvent), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32, _vp]),
+    "vaek_supports_log_likelihood": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_log_likelihood_record_len": (C.c_int, []),
+    "vaek_log_likelihood_max_rows": (C.c_int, []),
+    "vaek_log_likelihood_max_samples": (C.c_int, []),
+    "vaek_log_likelihood_workspace_bytes": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "vaek_log_likelihood_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekLogLikelihood), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32,
+                                               _vp, _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

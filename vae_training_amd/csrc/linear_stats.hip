@@ -45,7 +45,7 @@ struct StatsArgs {
     BatchArgs gen;                 // kind, A, dd, did, pad, noise_std, tag = x_tag, D, L; seed / step / pointers are not used
 };
 
-// floats of the zero-padded parameter image
+// floats of the zero-padded parameter image (linear_loglik.hip restates this layout and the fill below as LGeom: keep the two in step)
 template <int DP, int LP, bool SIG>
 struct SGeom {
     static constexpr int WE = 0, BE = WE + DP * LP, WD = BE + LP, BD = WD + LP * DP, WS = BD + DP, BS = WS + (SIG ? LP * DP : 0),

@@ -290,6 +290,64 @@ class Engine:
         _lib.check(self.lib.vaek_stats_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
                                                       float(var_added), int(x_tag), int(z_tag), _stream()))
 
+    def supports_log_likelihood(self, kind):
+        """True where log_likelihood_replicas covers this engine and dataset kind: a float32 linear VAE with one or two decoders, D, L <= 32
+        (D <= 28 with two decoders), whatever the engine's batch and world are (vaek_supports_log_likelihood)."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_log_likelihood(self.h, int(kind), C.byref(f)))
+        return bool(f.value)
+
+    @property
+    def log_likelihood_record_len(self):
+        """Floats in one log-likelihood record: 4 = IWAE-K bound, K-sample ELBO estimate, normalised effective sample size, eps."""
+        return int(self.lib.vaek_log_likelihood_record_len())
+
+    @property
+    def log_likelihood_max_rows(self):
+        return int(self.lib.vaek_log_likelihood_max_rows())
+
+    @property
+    def log_likelihood_max_samples(self):
+        return int(self.lib.vaek_log_likelihood_max_samples())
+
+    def log_likelihood_workspace(self, n, rows):
+        """Bytes of the workspace log_likelihood_replicas needs for n replicas of `rows` rows (its own buffer, not self.workspace)."""
+        b = C.c_size_t()
+        _lib.check(self.lib.vaek_log_likelihood_workspace_bytes(self.h, int(n), int(rows), C.byref(b)))
+        return int(b.value)
+
+    def log_likelihood_replicas(self, params, rows, samples, z_seeds, z_steps, out, workspace, kind=2, A=None, dd=0, did=0, pad=0,
+                                var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, z_tag=4, n=None,
+                                state_stride=None, out_stride=None, struct_size=None):
+        """The importance-weighted log-likelihood of EACH of n independent models of this engine's shape in one call
+        (vaek_log_likelihood_replicas): over `rows` data rows and `samples` posterior samples per row, record r = [IWAE bound, ELBO
+        estimate, normalised effective sample size, eps] in out[r, :4].  The rows are the caller's (x: float32 [rows, D] shared by all
+        replicas, or [n, rows, D]) or, with x None, drawn under (x_seeds[r], x_steps[r], x_tag) exactly as make_batch draws them from
+        (kind, A, dd, did, pad, var_added); sample k of a row takes blocks k * ceil(L / 4) .. of the latent stream under (z_seeds[r],
+        z_steps[r], z_tag).  params: [n, state_stride] (read only), seeds int64 [n], steps int32 [n], out: float32 [n, out_stride >=
+        4], workspace: uint8 of log_likelihood_workspace(n, rows) bytes -- all device tensors; n and the strides default to the
+        tensors' shapes.  Asynchronous; capturable."""
+        ll = _lib.VaekLogLikelihood()
+        ll.struct_size = C.sizeof(_lib.VaekLogLikelihood) if struct_size is None else int(struct_size)
+        ll.n = int(params.shape[0] if n is None else n)
+        ll.rows, ll.samples = int(rows), int(samples)
+        ll.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        assert all(s is None or s.dtype == torch.int64 for s in (x_seeds, z_seeds))
+        assert all(s is None or s.dtype == torch.int32 for s in (x_steps, z_steps))
+        assert out is None or out.dtype == torch.float32
+        assert x is None or x.dtype == torch.float32
+        ll.x_seeds, ll.x_steps, ll.z_seeds, ll.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
+        ll.a_stride = int(a_stride)
+        ll.out = _ptr(out)
+        ll.out_stride = int((0 if out is None else out.shape[-1]) if out_stride is None else out_stride)
+        ll.x = _ptr(x)
+        if x_stride is None:
+            x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
+        ll.x_stride = int(x_stride)
+        wp = None if workspace is None else C.c_void_p(workspace if isinstance(workspace, int) else workspace.data_ptr())
+        _lib.check(self.lib.vaek_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                         float(var_added), int(x_tag), int(z_tag), wp, _stream()))
+
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
         f = C.c_int32()

@@ -124,6 +124,19 @@ class GenerativeModel(Model):
             stats.update(score)
         return stats
 
+    def _stats_event(self):
+        """The stats of an n_print event: compute_stats(), and with `log_likelihood_samples` = K set (run.py --log_likelihood_samples)
+        the importance-weighted log-likelihood of this model on K samples per row (trainer.ReplicaLogLik, one library call), which
+        neither splits the model's key nor advances a draw counter of the run."""
+        stats = self.compute_stats()
+        K = getattr(self, "log_likelihood_samples", None)
+        if K:
+            from .trainer import ReplicaLogLik
+            if getattr(self, "_loglik", None) is None:
+                self._loglik = ReplicaLogLik([self], K)
+            stats.update(self._loglik.event()[0])
+        return stats
+
     def write_stats(self, stats):
         message = f"Batch | {self.batchnum}"
         for stat, val in stats.items():
@@ -219,7 +232,7 @@ class GenerativeModel(Model):
         for self.batchnum in it:
             if self.batchnum % self.n_print == 0:
                 self._dp_check()
-                self.write_stats(self.compute_stats())
+                self.write_stats(self._stats_event())
             if self.batchnum % self.n_plot == 0 or self.batchnum == self.num_batches - 1:
                 self._dp_check()
                 self.plot_epoch()
@@ -259,7 +272,7 @@ class GenerativeModel(Model):
             loop.check()
             self._dp_check()
             if ev % self.n_print == 0:
-                self.write_stats(self.compute_stats())
+                self.write_stats(self._stats_event())
             if ev % self.n_plot == 0 or ev == self.num_batches - 1:
                 self.plot_epoch()
                 self.save()

@@ -3,7 +3,7 @@
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
---fused_stats."""
+--fused_stats, --log_likelihood_samples."""
 from __future__ import annotations
 
 import argparse
@@ -71,6 +71,13 @@ def build_parser():
                         "for all models (trainer.ReplicaStats, vaek_stats_event_replicas) instead of one compute_stats() per model.  The "
                         "same draws, the same host RNG bookkeeping, the same keys in losses.npz.  Refused before any step without "
                         "--sweep_dataset_seeds and on a sweep of three-hidden-layer MLP VAEs (their events stay per model)")
+    p.add_argument("--log_likelihood_samples", dest="log_likelihood_samples", type=_positive_int, default=None, metavar="K",
+                   help="at every n_print step also evaluate the importance-weighted log-likelihood of the model(s) on K posterior samples "
+                        "per row of a print batch (trainer.ReplicaLogLik, vaek_log_likelihood_replicas): losses.npz gains a non-empty "
+                        "'Average Log Likelihood' (the IWAE-K bound), 'ELBO estimate' and 'Effective Sample Size'.  The evaluation has its "
+                        "own RNG counter and tags, so the training run is bitwise the one without the flag.  Alone or with "
+                        "--sweep_dataset_seeds (one call for all models); float32 linear VAEs with D, L <= 32 only; other models are refused "
+                        "before any step; single GPU only")
     return p
 
 
@@ -225,6 +232,23 @@ def check_fused_stats_args(args):
         raise RuntimeError(f"--fused_stats needs {FUSED_STATS_NEEDS}; a single model's stats event is compute_stats()")
 
 
+LOGLIK_NEEDS = ("a model vaek_log_likelihood_replicas covers (vaek_supports_log_likelihood): a float32 linear VAE -- no hidden layers -- "
+                "with one or two decoders, D, L <= 32 (D <= 28 with two decoders), -dd / -did <= 16, on one GPU")
+
+
+def check_log_likelihood_model(m, samples):
+    """--log_likelihood_samples: refuse, before any step, a model the log-likelihood call does not cover or a K above its cap."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    kind, _, dd, did, _, _ = m.dataset.device_spec()
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_log_likelihood(kind):
+        raise RuntimeError(f"--log_likelihood_samples needs {LOGLIK_NEEDS} (this model's step path: {getattr(eng, 'step_path', '?')}, "
+                           f"world {eng.world})")
+    if samples > eng.log_likelihood_max_samples:
+        raise RuntimeError(f"--log_likelihood_samples {samples}: at most {eng.log_likelihood_max_samples} samples per row fit one call "
+                           "(vaek_log_likelihood_max_samples)")
+
+
 def main_sweep(args):
     """--sweep_dataset_seeds: one dataset and one VAEModel per seed, the reference's schedule (model.py:207-222: stats every n_print
     steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE loop.run between
@@ -257,10 +281,18 @@ def main_sweep(args):
         if not isinstance(loop, ReplicaLoop):
             raise RuntimeError(f"--fused_stats needs {FUSED_STATS_NEEDS}; this sweep's step path is {eng.step_path!r} "
                                "(trainer.ReplicaGraphLoop), whose stats events stay one compute_stats() per model")
+    ll_samples = getattr(args, "log_likelihood_samples", None)
+    loglik = None
+    if ll_samples is not None:               # before any step
+        from .trainer import ReplicaLogLik
+        check_log_likelihood_model(models[0], ll_samples)
+        loglik = ReplicaLogLik(models, ll_samples)
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
     if fused_stats:
         print(f"Stats events: one launch for {len(models)} models (vaek_stats_event_replicas)")
+    if loglik is not None:
+        print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows (vaek_log_likelihood_replicas)")
     for r, m in enumerate(models):
         m._graph_loop = loop.view(r)
         score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
@@ -274,10 +306,14 @@ def main_sweep(args):
         pos = ev
         loop.check()
         fused = loop.stats_event() if fused_stats and ev % n_print == 0 else None      # every model's event in one launch
+        extra = loglik.event() if loglik is not None and ev % n_print == 0 else None     # every model's log-likelihood in one call
         for r, m in enumerate(models):
             m.batchnum = ev
             if ev % n_print == 0:
-                m.write_stats(m.compute_stats() if fused is None else fused[r])
+                stats = m.compute_stats() if fused is None else fused[r]
+                if extra is not None:
+                    stats.update(extra[r])
+                m.write_stats(stats)
             if ev % n_plot == 0 or ev == n - 1:
                 m.plot_epoch()
                 m.save()
@@ -300,6 +336,9 @@ def main(args):
     from .utils import get_output_dir, make_output_dir
     dist = None
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    if world > 1 and getattr(args, "log_likelihood_samples", None) is not None:      # before a process group exists
+        raise RuntimeError(f"--log_likelihood_samples needs {LOGLIK_NEEDS}: it does not combine with data parallelism "
+                           f"(step path of a world of {world}: one shard per rank)")
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -322,6 +361,11 @@ def main(args):
             raise RuntimeError(f"--trajectory_every needs {TRAJECTORY_NEEDS}: it does not combine with data parallelism")
         check_trajectory_model(model)            # before any step
         model.trajectory_every = tevery          # train() takes GraphLoop(resident=True, trajectory_every=K) and prints the Train loop: line
+    ll_samples = getattr(args, "log_likelihood_samples", None)
+    if ll_samples is not None:
+        check_log_likelihood_model(model, ll_samples)      # before any step
+        model.log_likelihood_samples = ll_samples          # the n_print events add trainer.ReplicaLogLik([model], K).event()
+        print(f"Log-likelihood events: {ll_samples} samples × {model.print_batch_size} rows (vaek_log_likelihood_replicas)")
     if rank == 0:
         eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
         loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")

@@ -510,6 +510,106 @@ class ReplicaStats:
         return stats
 
 
+class ReplicaLogLik:
+    """The importance-weighted log-likelihood of R VAEModels of one shape in ONE library call (vaek_log_likelihood_replicas,
+    csrc/linear_loglik.hip): per model, over `rows` data rows drawn from its dataset and `samples` = K posterior samples per row,
+    the IWAE-K bound on log p(x) -- the `Average Log Likelihood` the reference reserves and never fills -- the K-sample ELBO estimate
+    and the normalised effective sample size of the weights.
+
+    The models are validated as in ReplicaLoop (one shape, architecture, epsilon, dataset kind, -dd, -did, padding, noise) but with
+    NO condition on the batch size: the call reads parameters only, so models of any train batch -- and of different ones -- qualify.
+
+    event() copies each model's `model.flat` into its row of an [R, P] stack owned by this object, makes ONE library call and ONE
+    device -> host copy of the [R, 4] records.  It does NOT perturb the run: `m.key`, the dataset's `_draws` and `m._latent_draws` are
+    neither split nor advanced.  Its draws have a counter of their own, `m._loglik_draws` (incremented before use: the first event
+    draws under step 1), the seed dataset.key[0] ^ dataset.key[1] and the tags 3 (rows) and 4 (samples); tags 0, 1 and 2 belong to the
+    train loop, the dataset's batches and the latents.  Returns per model {"Average Log Likelihood", "ELBO estimate", "Effective
+    Sample Size"} (host tensors) and appends the first to `m.average_log_likelihoods`."""
+
+    KEYS = ("Average Log Likelihood", "ELBO estimate", "Effective Sample Size")
+    X_TAG, Z_TAG = 3, 4
+
+    def __init__(self, vae_models, samples, rows=None):
+        ms = list(vae_models)
+        if not ms:
+            raise RuntimeError("ReplicaLogLik: no models")
+        from .datasets import DEVICE_DRAW_MAX_DIM
+        self.ms = ms
+        m0 = ms[0]
+        self.eng = m0.model.module.engine(m0.batch_size, m0.optimizer.global_batch)
+        specs = [m.dataset.device_spec() for m in ms]
+        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
+        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
+            raise RuntimeError(f"ReplicaLogLik draws its rows with libvaek's Philox generator, which supports -dd / -did <= "
+                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
+        if self.eng.world > 1:
+            raise RuntimeError("ReplicaLogLik: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
+        if not self.eng.supports_log_likelihood(self.kind):
+            raise RuntimeError("ReplicaLogLik: vaek_log_likelihood_replicas does not cover this model / dataset (it needs a float32 linear "
+                               "VAE -- no hidden layers -- with one or two decoders and D, L <= 32, D <= 28 with two decoders; this model's "
+                               f"step path: {getattr(self.eng, 'step_path', '?')})")
+        R = len(ms)
+        if R > self.eng.train_loop_max_replicas:
+            raise RuntimeError(f"ReplicaLogLik: {R} models, at most {self.eng.train_loop_max_replicas} fit one call "
+                               "(vaek_train_loop_max_replicas)")
+        want = self._shape(m0, specs[0])
+        for r, (m, sp) in enumerate(zip(ms, specs)):
+            got = self._shape(m, sp)
+            if got != want:
+                raise RuntimeError(f"ReplicaLogLik: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
+                                   f"{want}): one call evaluates replicas of ONE shape")
+        self.samples = int(samples)
+        if not 1 <= self.samples <= self.eng.log_likelihood_max_samples:
+            raise RuntimeError(f"ReplicaLogLik: {self.samples} samples per row, need 1 .. {self.eng.log_likelihood_max_samples} "
+                               "(vaek_log_likelihood_max_samples)")
+        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
+        if not 1 <= self.rows <= self.eng.log_likelihood_max_rows:
+            raise RuntimeError(f"ReplicaLogLik: {self.rows} rows per event, need 1 .. {self.eng.log_likelihood_max_rows} "
+                               "(vaek_log_likelihood_max_rows)")
+        self.R = R
+        dev = self.eng.device
+        self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
+        self.out = torch.zeros(R, self.eng.log_likelihood_record_len, dtype=torch.float32, device=dev)
+        self.workspace = torch.empty(max(self.eng.log_likelihood_workspace(R, self.rows), 8), dtype=torch.uint8, device=dev)
+        if specs[0][1] is None:
+            self.A, self.a_stride = None, 0
+        else:
+            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
+            self.a_stride = self.A.shape[1]
+
+    @staticmethod
+    def _shape(m, spec):
+        """ReplicaLoop._signature without what depends on the batch size (the batch itself and the engine's global batch)."""
+        sig = ReplicaLoop._signature(m, spec)
+        arch = sig[4]
+        return sig[1:4] + (None if arch is None else arch[:-1],) + sig[5:]
+
+    def event(self):
+        """One evaluation of every model: [{"Average Log Likelihood", "ELBO estimate", "Effective Sample Size"} of model 0, ...]."""
+        dev = self.eng.device
+        seeds, steps = [], []
+        for r, m in enumerate(self.ms):
+            self.params[r].copy_(m.model.flat)
+            m._loglik_draws = getattr(m, "_loglik_draws", 0) + 1
+            ds = m.dataset
+            s = (ds.key[0] ^ ds.key[1]) & (2 ** 64 - 1)
+            t = m._loglik_draws & (2 ** 32 - 1)
+            seeds.append(s - 2 ** 64 if s >= 2 ** 63 else s)
+            steps.append(t - 2 ** 32 if t >= 2 ** 31 else t)
+        seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
+        steps = torch.tensor(steps, dtype=torch.int32).to(dev)
+        self.eng.log_likelihood_replicas(self.params, self.rows, self.samples, seeds, steps, self.out, self.workspace, kind=self.kind,
+                                         A=self.A, dd=self.dd, did=self.did, pad=self.pad, var_added=self.var, x_seeds=seeds, x_steps=steps,
+                                         a_stride=self.a_stride, x_tag=self.X_TAG, z_tag=self.Z_TAG)
+        rec = self.out.cpu()                                                      # the event's ONE device -> host copy
+        stats = []
+        for r, m in enumerate(self.ms):
+            st = {name: rec[r, k].clone() for k, name in enumerate(self.KEYS)}
+            m.average_log_likelihoods.append(st[self.KEYS[0]])
+            stats.append(st)
+        return stats
+
+
 class ReplicaGraphLoop:
     """A sweep of three-hidden-layer MLP VAEs (step path "mlp3") as GraphLoop's pipelined hipGraph loop with R models per step: R
     VAEModels of one shape -- validated as in ReplicaLoop: one batch size, data and latent dimension, architecture, epsilon,
