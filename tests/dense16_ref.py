@@ -1,5 +1,6 @@
-"""Float64 references for the bf16 Dense launchers (vaek_debug_dense16, csrc/debug_dense16.hip), rounded where each kernel
-rounds, and the comparison that holds a kernel's output to them.  Needs no GPU: the functions take torch tensors on any device.
+"""Float64 references for the Dense launchers (vaek_debug_dense16, csrc/debug_dense16.hip), rounded where each kernel
+rounds (the all-f32 kernels of gemm_f32.hip, tests/test_gpu_dense32.py: nowhere), and the comparison that holds a kernel's output to
+them.  Needs no GPU: the functions take torch tensors on any device.
 
 Where each kernel rounds (read from the kernel sources; "bf16(.)" = round-to-nearest-even of the float32 value):
 
@@ -30,7 +31,11 @@ launcher offers it and the tests hold it too.
 Bounds (check_f32 / check_bf16): per element |got - ref| <= tol * mag with mag = (|A| . |B| + |bias| + |every epilogue addend|),
 the absolute operands taken after the kernel's bf16 rounding; tol = F32_TOL.  A bf16 output additionally may differ from bf16(ref)
 by at most one bf16 ulp in at most BF16_OFF_FRACTION of its elements (an element whose f32 error bound exceeds one bf16 ulp of
-its value, a cancellation, is held by the first bound alone), and masked elements must be exactly 0."""
+its value, a cancellation, is held by the first bound alone), and masked elements must be exactly 0.
+
+ELBO epilogues also leave one {mse, d eps} pair per output tile; elbo_sums gives the float64 totals over the real rows x columns and
+bounds that carry each element's own bound through the two sums, check_sums holds the tile pairs to them.  guarded / check_guard put
+an output between two bands of one NaN bit pattern and look for a store outside it (or an element nobody stored)."""
 import torch
 
 F32_TOL = 4e-6
@@ -184,3 +189,69 @@ def check_bf16(got, ref, mag, zero=None, tol=F32_TOL, what=""):
     half_ulp = torch.ldexp(torch.ones_like(ref), torch.frexp(ref)[1] - 9).abs()
     excess = (err - half_ulp).clamp(min=0)
     return float((excess / (tol * mag).clamp(min=1e-300)).max()) if got.numel() else 0.0
+
+
+def elbo_sums(y, mag, xdata, z2, eps, tol=F32_TOL):
+    """The two sums of the ELBO epilogue over the real rows x columns, rr = y + exp(eps / 2) z2 - x:
+    mse = sum rr^2 exp(-eps) / 2, deps = sum (-rr^2 exp(-eps) / 2 + exp(eps / 2) z2 rr exp(-eps) / 2).
+    Returns ((mse, deps), (bound_mse, bound_deps)) as float64 numbers.  An element's rr is known to tol * m, m = the magnitude elbo()
+    uses for rr before scaling; d(rr^2 / 2) = |rr| d rr, and the products' own roundings add tol * (their value)."""
+    e = torch.tensor(float(eps), dtype=D64)
+    sig, inv_var = float(torch.exp(0.5 * e)), float(torch.exp(-e))
+    z, x = f64(z2), f64(xdata)
+    sz = sig * z
+    rr = y + sz - x
+    m = mag + sz.abs() + x.abs()
+    q = 0.5 * rr * rr * inv_var
+    mse = q.sum()
+    deps = (-q + 0.5 * sig * z * rr * inv_var).sum()
+    b_q = inv_var * (rr.abs() * m + 0.5 * rr * rr)
+    b_mse = tol * b_q.sum()
+    b_deps = tol * (b_q + 0.5 * float(torch.exp(-0.5 * e)) * z.abs() * (m + rr.abs())).sum()
+    return (float(mse), float(deps)), (float(b_mse), float(b_deps))
+
+
+def check_sums(parts, ref, bound, what=""):
+    """parts: the {mse, d eps} pairs of every tile, flat.  Their float64 totals are within `bound` of `ref`.  Returns the larger
+    error-to-bound ratio."""
+    p = f64(parts).reshape(-1, 2)
+    assert p.numel() > 0, f"{what}: no tile pairs"
+    assert torch.isfinite(p).all(), f"{what}: non-finite tile sums"
+    ratio = 0.0
+    for name, got, r, b in zip(("mse", "d eps"), p.sum(dim=0).tolist(), ref, bound):
+        assert abs(got - r) <= b, f"{what}: {name} sum {got!r} is not within {b!r} of {r!r} ({p.shape[0]} tiles)"
+        ratio = max(ratio, abs(got - r) / max(b, 1e-300))
+    return ratio
+
+
+GUARD = 256                  # floats kept on each side of a guarded output
+GUARD_FILL = 0x7FC5A5A5      # one quiet-NaN bit pattern no kernel here produces
+
+
+def guarded(numel, device, lead=0):
+    """A float32 buffer of GUARD + lead + numel + GUARD elements, every one GUARD_FILL.  Returns (buffer, view): the view is the
+    `numel` floats that start GUARD + lead floats in (lead: 0-3 floats off the buffer's 16-byte alignment)."""
+    buf = torch.full((2 * GUARD + lead + numel,), GUARD_FILL, dtype=torch.int32, device=device).view(torch.float32)
+    return buf, buf[GUARD + lead:GUARD + lead + numel]
+
+
+def check_guard(buf, view, written=None, prefilled=False, what=""):
+    """The GUARD floats before and after `view` (made by guarded()) still hold the fill bit for bit, and no element of the view does.
+    written: only the first `written` elements of the view are to be stored; the rest must still hold the fill.  prefilled: the caller put values into the view before the call (an accumulating op),
+    so only the bands are looked at."""
+    bits = buf.view(torch.int32)
+    n = view.numel()
+    start = view.storage_offset() - buf.storage_offset()
+    assert 0 <= start - GUARD and start + n + GUARD <= bits.numel(), (what, start, n, bits.numel())
+    w = n if written is None else written
+    assert 0 <= w <= n, (what, w, n)
+    before = int((bits[start - GUARD:start] != GUARD_FILL).sum())
+    after = int((bits[start + n:start + n + GUARD] != GUARD_FILL).sum())
+    assert before == 0, f"{what}: {before} floats stored in front of the output"
+    assert after == 0, f"{what}: {after} floats stored behind the output"
+    if prefilled:
+        return
+    left = int((bits[start:start + w] == GUARD_FILL).sum())
+    assert left == 0, f"{what}: {left} of {w} output elements were never stored"
+    stray = int((bits[start + w:start + n] != GUARD_FILL).sum())
+    assert stray == 0, f"{what}: {stray} elements stored past the {w} expected"

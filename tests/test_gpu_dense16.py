@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 OPS = ["dense_fwd_bf16", "dense_fwd_reparam_bf16", "dense_dx_bf16", "dense_dw_bf16",
        "hs_fwd", "hs_dx", "hs_dw",
        "sk_first_fwd", "sk_last_fwd", "sk_last_fwd_reparam", "sk_last_fwd_elbo", "sk_first_dx", "sk_last_bwd", "sk_first_bwd",
-       "fwd_out16", "fwd_in16", "fwd_reparam_in16", "fwd_elbo_in16", "dx_out16", "dx_in16", "dw_x16", "dw_dy16"]
+       "fwd_out16", "fwd_in16", "fwd_reparam_in16", "fwd_elbo_in16", "dx_out16", "dx_in16", "dw_x16", "dw_dy16",
+       "f32_fwd", "f32_fwd_reparam", "f32_fwd_elbo", "f32_dx", "f32_dw"]          # the f32_* ops: tests/test_gpu_dense32.py
 OP = {n: i for i, n in enumerate(OPS)}
 # the profiler label each op's main kernel carries (gemm_f32.hip names its tile shape, not its storage types)
 LABEL = {"dense_fwd_bf16": "gemm_bf16_fwd", "dense_fwd_reparam_bf16": "gemm_bf16_fwd_reparam", "dense_dx_bf16": "gemm_bf16_dx",
@@ -33,7 +34,8 @@ LABEL = {"dense_fwd_bf16": "gemm_bf16_fwd", "dense_fwd_reparam_bf16": "gemm_bf16
 # every kernel label the calls of this file hold to the reference: the main kernels, the weight prep and the slab reductions
 COVERED = set(LABEL.values()) | {"cvt_weights_bf16", "sk16_prep", "sk16_partials_reduce", "sum_slabs"}
 # what else a dtype = bf16 step runs: the elementwise ELBO / reparameterisation passes and the finalisation (whole-model tests,
-# tests/test_gpu_bf16.py), and the exact f32 kernels of f32-storage layers (per call: tests/test_gpu_blocks.py)
+# tests/test_gpu_bf16.py), and the all-f32 kernels of f32-storage layers whose plain label is not already in COVERED (per call
+# and per element: tests/test_gpu_dense32.py)
 NOT_DENSE16 = {"elbo", "elbo_reduce", "reparam_bwd", "finalize", "bulk_finalize", "gemm_f32_fwd_reparam_ts", "gemm_f32_dx_ts",
                "gemm_f32_fwd_128x128", "gemm_f32_dx_128x128", "gemm_f32_dw_128x128"}
 
@@ -50,7 +52,8 @@ class Args(C.Structure):
                 ("out", C.c_void_p), ("out2", C.c_void_p), ("dwb", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
 
 
-RATIOS = {}          # op family -> largest error-to-bound ratio seen (written to $VAEK_DENSE16_RATIOS if set)
+RATIOS = {}          # op family -> largest error-to-bound ratio seen (written to $VAEK_DENSE16_RATIOS if set); the f32 families of
+                     # tests/test_gpu_dense32.py land in the same dictionary and the same file
 
 
 def family(op):
@@ -64,13 +67,44 @@ def note(op, ratio):
     RATIOS[f] = max(RATIOS.get(f, 0.0), ratio)
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _report_ratios():
-    yield
+def dump_ratios():
     path = os.environ.get("VAEK_DENSE16_RATIOS")
     if path:
         with open(path, "w") as f:
             json.dump(RATIOS, f, indent=1, sort_keys=True)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report_ratios():
+    yield
+    dump_ratios()
+
+
+# gemm_f32.hip's launch(): the output tile of an M x N product over K in `splits` batch splits (the 128 x 128 shape exists for the
+# all-f32 instantiations only)
+TILE_DIMS = {"128x32": (128, 32), "32x128": (32, 128), "128x128": (128, 128), "64x64": (64, 64)}
+
+
+def f32_tile(M, N, K, splits=1, all_f32=True):
+    if N <= 32:
+        return "128x32"
+    if M <= 32:
+        return "32x128"
+    if all_f32 and min(M, N, K) >= 128 and ((M + 127) // 128) * ((N + 127) // 128) * splits >= 512:
+        return "128x128"
+    return "64x64"
+
+
+def elbo_parts(rows, n_out):
+    """The caller's buffer for the {mse, d eps} tile pairs of an ELBO op (all NaN), as vaek_dense16_args::out2 sizes it."""
+    return torch.full((2 * ((rows + 31) // 32) * ((n_out + 31) // 32),), float("nan"), device="cuda")
+
+
+def check_parts(parts, tiles, ref, mag, xdata, z2, eps, what):
+    """The first 2 * tiles floats were written, nothing behind them; their totals against the float64 sums."""
+    assert not torch.isnan(parts[:2 * tiles]).any() and torch.isnan(parts[2 * tiles:]).all(), what
+    sums, bounds = R.elbo_sums(ref, mag, xdata, z2, eps)
+    RATIOS["elbo sums bf16 forms"] = max(RATIOS.get("elbo sums bf16 forms", 0.0), R.check_sums(parts[:2 * tiles], sums, bounds, what=what))
 
 
 @pytest.fixture(scope="module")
@@ -296,15 +330,18 @@ def test_sk_last_fwd(eng, rows, d, H):
     note("sk_last_fwd", R.check_f32(mu, ref, mag, what="sk16_last_fwd_reparam mu"))
     rs, ms = R.reparam(ref, mag, z1, lv)
     note("sk_last_fwd", R.check_f32(smp, rs, ms, what="sk16_last_fwd_reparam samples"))
-    # ELBO epilogue: d_out = dL/dx_hat element by element (its {mse, d eps} tile sums feed the loss: whole-model tests)
+    # ELBO epilogue: d_out = dL/dx_hat element by element, and its {mse, d eps} tile sums (they feed the loss)
     xd, z2 = randn(rows, d), randn(rows, d)
     epsp = torch.tensor([0.75], device="cuda")
     eps = float(torch.tensor(0.75, dtype=torch.float32) * torch.tensor(-3.0, dtype=torch.float32))
     inv_bt = float(torch.tensor(1.0 / 3000.0, dtype=torch.float32))
     dout = torch.full((rows, d), float("nan"), device="cuda")
-    run(eng, "sk_last_fwd_elbo", rows, H, d, x=h, w=w, b=b, xdata=xd, z2=z2, eps_param=epsp, eps_cli=-3.0, inv_bt=inv_bt, out=dout)
+    parts = elbo_parts(rows, d)
+    run(eng, "sk_last_fwd_elbo", rows, H, d, x=h, w=w, b=b, xdata=xd, z2=z2, eps_param=epsp, eps_cli=-3.0, inv_bt=inv_bt, out=dout,
+        out2=parts)
     re, me = R.elbo(ref, mag, xd, z2, eps, inv_bt)
     note("sk_last_fwd", R.check_f32(dout, re, me, what="sk16_last_fwd_elbo d_out"))
+    check_parts(parts, (rows + 127) // 128, ref, mag, xd, z2, eps, "sk16_last_fwd_elbo tile sums")      # one pair per 128 rows
 
 
 @pytest.mark.parametrize("rows,d,H", SK_SHAPES)
@@ -395,9 +432,12 @@ def test_f32_out16_in16_forward(eng, rows, d, H):
     xd, z2 = randn(rows, d), randn(rows, d)
     inv_bt = float(torch.tensor(1.0 / 777.0, dtype=torch.float32))
     dout = torch.full((rows, d), float("nan"), device="cuda")
-    run(eng, "fwd_elbo_in16", rows, H, d, x=h, w=w, b=b, xdata=xd, z2=z2, eps_cli=-2.0, inv_bt=inv_bt, out=dout)
+    parts = elbo_parts(rows, d)
+    run(eng, "fwd_elbo_in16", rows, H, d, x=h, w=w, b=b, xdata=xd, z2=z2, eps_cli=-2.0, inv_bt=inv_bt, out=dout, out2=parts)
     re, me = R.elbo(ref, mag, xd, z2, -2.0, inv_bt)
     note("fwd_in16", R.check_f32(dout, re, me, what="dense_fwd_elbo_in16 d_out"))
+    bm, bn = TILE_DIMS[f32_tile(rows, d, H, all_f32=False)]
+    check_parts(parts, ((rows + bm - 1) // bm) * ((d + bn - 1) // bn), ref, mag, xd, z2, -2.0, "dense_fwd_elbo_in16 tile sums")
 
 
 @pytest.mark.parametrize("rows,d,H", F16_SHAPES)

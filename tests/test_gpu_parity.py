@@ -81,6 +81,31 @@ def test_seeded_grads_vs_oracle(name, B, path):
     assert abs(out4[3] - float(np.asarray(ev[4]).reshape(-1)[0])) <= 1e-6
 
 
+@pytest.mark.parametrize("hidden", [(33,), (35, 33)])
+def test_seeded_grads_vs_oracle_odd_parameter_offsets(hidden):
+    """Hidden widths that put later kernels at float offsets of the flat parameter vector that are no multiple of 4 (after the 6 -> 33
+    layer the next kernel starts at float 231): the layer-by-layer kernels fetch those operands on their scalar branch."""
+    cfg = O.Config(6, 5, hidden, hidden, -3.0, True, "sphere")
+    B = 300
+    p, x, z1, z2 = random_problem(cfg, dict(name="sphere", seed=69, dd=3, pad=3), B)
+    loss, g = O.loss_and_grad(cfg, p, x, z1, z2)
+    eng = engine_for(cfg, B, **PATHS["generic"])
+    check_layout(eng, cfg)
+    odd = [n for n, (off, shape) in eng.leaves.items() if n.endswith("kernel") and off % 4]
+    assert odd, dict(eng.leaves)
+    params = dev(O.flatten(cfg, p))
+    grads = eng.new_flat(eng.grad_len)
+    step = torch.zeros(1, dtype=torch.int32, device="cuda")
+    eng.grads_only(params, grads, step, dev(x), dev(z1), dev(z2))
+    got = host(grads)
+    assert abs(got[eng.P] - loss) <= LOSS_RTOL * abs(loss)
+    want = O.flatten(cfg, g)
+    assert rel_err(got[:eng.P], want) <= GRAD_RTOL
+    for n, (off, shape) in eng.leaves.items():
+        k = int(np.prod(shape))
+        assert rel_err(got[off:off + k], want[off:off + k]) <= 1e-4, n
+
+
 @pytest.mark.parametrize("name", ["c1_linear_L20", "c2_sigmoid_mlp", "c3_sphere_mlp"])
 def test_forward_and_sampling(name):
     cfg, dk, _, lr = build(name)

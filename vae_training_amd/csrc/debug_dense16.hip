@@ -1,6 +1,6 @@
-// Diagnostic entry (not part of include/vaek.h; tests/test_gpu_dense16.py): run ONE Dense launcher of dtype = VAEK_BF16 -- the
-// round-1 kernels of gemm_bf16.hip, the bf16-storage kernels of gemm_bf16s.hip and gemm_skinny16.hip, and the bf16-stored forms
-// of gemm_f32.hip -- on caller tensors through the step's own code (api.hip): the op names a layer kind and a launch function
+// Diagnostic entry (not part of include/vaek.h; tests/test_gpu_dense16.py, tests/test_gpu_dense32.py): run ONE Dense launcher --
+// of dtype = VAEK_BF16 the round-1 kernels of gemm_bf16.hip, the bf16-storage kernels of gemm_bf16s.hip and gemm_skinny16.hip and
+// the bf16-stored forms of gemm_f32.hip; of dtype = VAEK_F32 the all-f32 kernels of gemm_f32.hip (the f32_* ops) -- on caller tensors through the step's own code (api.hip): the op names a layer kind and a launch function
 // (dense_fwd / dense_dx / dense_dw), weights are prepared by prep_weights into the caller's scratch, dW|db slabs summed by
 // launch_sum_slabs into the flat-gradient layout [(n_in + 1), n_out].  Every predicate the launcher relies on is checked before
 // the first launch, and so is the step's route: a shape dense_kind gives another kind launches nothing.
@@ -15,12 +15,14 @@ enum {
     VAEK_D16_SK_FIRST_DX, VAEK_D16_SK_LAST_BWD, VAEK_D16_SK_FIRST_BWD,
     VAEK_D16_FWD_OUT16, VAEK_D16_FWD_IN16, VAEK_D16_FWD_REPARAM_IN16, VAEK_D16_FWD_ELBO_IN16,                        // gemm_f32.hip
     VAEK_D16_DX_OUT16, VAEK_D16_DX_IN16, VAEK_D16_DW_X16, VAEK_D16_DW_DY16,
+    VAEK_D16_F32_FWD, VAEK_D16_F32_FWD_REPARAM, VAEK_D16_F32_FWD_ELBO, VAEK_D16_F32_DX, VAEK_D16_F32_DW,             // gemm_f32.hip, all f32
     VAEK_D16_COUNT
 };
 
 // Tensors are row-major and contiguous; "bf16" ones are __bf16.  x: the layer input [rows, n_in]; dy: the gradient of its output
 // [rows, n_out]; w: f32 [n_in, n_out] as the parameters hold it, b: f32 [n_out].  The skinny ops name their layer the same way:
-// first layer n_in = d, n_out = H; last layer n_in = H, n_out = d.
+// first layer n_in = d, n_out = H; last layer n_in = H, n_out = d.  The f32_* ops demand no alignment of any tensor (the public ABI
+// demands none: a layer's kernel sits wherever the layers before it end in the flat parameter vector); scratch stays 256-aligned.
 struct vaek_dense16_args {
     int32_t rows, n_in, n_out;
     int32_t relu, accumulate;            // relu: forward activation / dX mask (ops that have the choice); accumulate: dX ops
@@ -31,7 +33,10 @@ struct vaek_dense16_args {
     const float* z1; const float* lv;    // reparameterisation epilogues: samples = mu + exp(lv / 2) z1
     const float* xdata; const float* z2; const float* eps_param; float eps_cli, inv_bt;      // ELBO epilogues
     void* out;                           // y / mu / dX / dL/dx_hat (sk_last_bwd: dh)
-    float* out2;                         // samples (reparameterisation)
+    float* out2;                         // samples (reparameterisation).  ELBO ops: null, or where the {mse, d eps} pair of every
+                                         // output tile goes instead of scratch, in the kernel's tile order: the caller provides
+                                         // 2 * ceil(rows / 32) * ceil(n_out / 32) floats (tiles are at least 32 x 32; a kernel with
+                                         // larger tiles writes the first 2 * tiles of them)
     float* dwb;                          // summed dW|db [(n_in + 1), n_out]
     void* scratch; int64_t scratch_bytes;     // scratch == null: the bytes needed are written to scratch_bytes
 };
@@ -49,6 +54,7 @@ constexpr Route kRoute[VAEK_D16_COUNT] = {
     {Kind::FIRST_SK, DX}, {Kind::LAST_SK, DW}, {Kind::FIRST_SK, DW},
     {Kind::FIRST16, FWD}, {Kind::LAST16, FWD}, {Kind::LAST16, FWD, Epi::REPARAM}, {Kind::LAST16, FWD, Epi::ELBO},
     {Kind::LAST16, DX}, {Kind::FIRST16, DX}, {Kind::LAST16, DW}, {Kind::FIRST16, DW},
+    {Kind::F32, FWD}, {Kind::F32, FWD, Epi::REPARAM}, {Kind::F32, FWD, Epi::ELBO}, {Kind::F32, DX}, {Kind::F32, DW},
 };
 Pos position(Kind k) {       // the f32-storage kinds' choice does not depend on it
     return k == Kind::FIRST_SK || k == Kind::FIRST16 ? Pos::FIRST : k == Kind::LAST_SK || k == Kind::LAST16 ? Pos::LAST : Pos::HIDDEN;
@@ -100,10 +106,11 @@ int validate(int op, const vaek_dense16_args& a) {
     // the step's route: dense_kind gives this kind to this shape at this position, in a stack that can hold the layer
     const Pos pos = position(r.kind);
     const bool b16 = r.kind != Kind::F32 && r.kind != Kind::BF16;
-    if (dense_kind(VAEK_BF16, b16, pos, a.n_in, a.n_out) != r.kind) return bad("the step runs another kernel on this layer");
+    const int dtype = r.kind == Kind::F32 ? VAEK_F32 : VAEK_BF16;
+    if (dense_kind(dtype, b16, pos, a.n_in, a.n_out) != r.kind) return bad("the step runs another kernel on this layer");
     if (b16 && ((pos != Pos::FIRST && !b16_width(a.n_in)) || (pos != Pos::LAST && !b16_width(a.n_out))))
         return bad("the hidden widths of a bf16-storage stack are multiples of 64");
-    const bool has_relu = (fwd && r.epi == Epi::NONE && pos != Pos::LAST) || (dx && r.kind == Kind::BF16);
+    const bool has_relu = (fwd && r.epi == Epi::NONE && pos != Pos::LAST) || (dx && (r.kind == Kind::BF16 || r.kind == Kind::F32));
     if (a.relu && !has_relu) return bad("this op has no relu switch");
     if (dw) {
         if (a.S < 1) return bad("S must be >= 1");
@@ -148,7 +155,8 @@ extern "C" int vaek_debug_dense16(vaek_ctx* ctx, int32_t op, vaek_dense16_args* 
     if (reads_w16(r) && (rc = prep_weights(a.w, ls, 1, at<__bf16>(a.scratch, s.wb), at<__bf16>(a.scratch, s.skw), st))) return rc;
     const DenseW p{a.w, a.b, at<__bf16>(a.scratch, r.kind == Kind::HIDDEN16 ? s.wb : s.skw)};
     if (r.dir == FWD) {
-        Epilogue e{r.epi, a.out2, a.z1, a.lv, a.xdata, a.z2, a.eps_param, a.eps_cli, a.inv_bt, at<float>(a.scratch, s.epart), 0, 0};
+        float* part = r.epi == Epi::ELBO && a.out2 ? a.out2 : at<float>(a.scratch, s.epart);
+        Epilogue e{r.epi, a.out2, a.z1, a.lv, a.xdata, a.z2, a.eps_param, a.eps_cli, a.inv_bt, part, 0, 0};
         return dense_fwd(l, p, a.x, a.out, a.rows, &e, st);
     }
     if (r.dir == DX) return dense_dx(l, p, a.dy, a.x_post, a.out, a.rows, a.relu != 0, a.accumulate != 0, st);
