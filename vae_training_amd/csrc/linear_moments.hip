@@ -422,22 +422,56 @@ constexpr int lin_scratch_bytes(int NB) { return LNW * (NB * (NB + 1) / 2) * 102
 // three slots over the LDS), three keep the size their plans were made with
 constexpr int lin_ring_scratch_bytes(int NB) { return NB == 3 ? lin_scratch_bytes(NB) : lin_scratch_bytes(NB) / 2; }
 constexpr int kLinCW = 4;      // persistent form: waves 0 .. 3 multiply (one per SIMD), waves 4 .. 7 load
+// Where a lane's feature 16 u + (lane & 15) lives: byte offset of sample 0 and byte stride per sample.  Which tensor a feature
+// belongs to does not change from tile to tile -- only the slot and (for the "1" feature) the validity column do -- so the
+// persistent streamers work the lane's map out ONCE per launch and form a tile's offsets from it with two masked adds per block:
+// per tile the five-way select (D and L are run-time values here) is ~200 instructions with ~20 exec-mask branches on each
+// multiplying wave, between the tile's barrier and its first operand read (profiles/lin_blocks_roles.txt B).  Same addresses:
+// the results are bitwise what they were.  in_slot / is_v: all ones where the feature lies in the tile's slot / is the
+// validity column, else zero.
+template <int NB> struct LinFeatMap {
+    int fb[NB], fs[NB], in_slot[NB], is_v[NB];
+    // v_off, c_off: byte offsets of the validity column of a full tile and of the zero word (neither lies in a slot)
+    __device__ __forceinline__ void init(const LinArgs& a, const LinTile& tl, int v_off, int c_off, int lane) {
+        const int D = a.D, L = a.L;
+#pragma unroll
+        for (int u = 0; u < NB; ++u) {
+            const int f = 16 * u + (lane & 15);
+            in_slot[u] = f < L + 2 * D ? -1 : 0; is_v[u] = f == L + 2 * D ? -1 : 0;
+            if (f < L) { fb[u] = f * 4; fs[u] = L * 4; }
+            else if (f < L + D) { fb[u] = tl.oX + (f - L) * 4; fs[u] = D * 4; }
+            else if (f < L + 2 * D) { fb[u] = tl.oZ2 + (f - L - D) * 4; fs[u] = D * 4; }
+            else if (f == L + 2 * D) { fb[u] = v_off; fs[u] = 4; }
+            else { fb[u] = c_off; fs[u] = 0; }
+        }
+    }
+    // the tile in the slot at slot_off, its validity column v_delta bytes behind v_off
+    __device__ __forceinline__ void at(int slot_off, int v_delta, int (&fb_out)[NB]) const {
+#pragma unroll
+        for (int u = 0; u < NB; ++u) fb_out[u] = fb[u] + (slot_off & in_slot[u]) + (v_delta & is_v[u]);
+    }
+};
+
+template <int NB, int JT, int CW, typename Hook>
+__device__ __forceinline__ void lin_tile_products_at(const LinArgs& a, const char* smem, const int (&fb)[NB], const int (&fs)[NB],
+                                                     f32x4 (&acc)[NB * (NB + 1) / 2], int lane, int wave, Hook&& hook);
+
 template <int NB, int JT, int CW, typename Hook>
 __device__ __forceinline__ void lin_tile_products(const LinArgs& a, const LinTile& tl, const char* smem, int slot_off, int v_off, int c_off,
                                                   f32x4 (&acc)[NB * (NB + 1) / 2], int lane, int wave, Hook&& hook) {
+    LinFeatMap<NB> map;
+    map.init(a, tl, v_off, c_off, lane);
+    int fb[NB];
+    map.at(slot_off, 0, fb);
+    lin_tile_products_at<NB, JT, CW>(a, smem, fb, map.fs, acc, lane, wave, hook);
+}
+
+// the products proper: fb / fs, this lane's byte offset of sample 0 and byte stride per sample of feature 16 u + (lane & 15)
+template <int NB, int JT, int CW, typename Hook>
+__device__ __forceinline__ void lin_tile_products_at(const LinArgs& a, const char* smem, const int (&fb)[NB], const int (&fs)[NB],
+                                                     f32x4 (&acc)[NB * (NB + 1) / 2], int lane, int wave, Hook&& hook) {
     constexpr int NBLK = NB * (NB + 1) / 2;
-    const int g = lane >> 4, D = a.D, L = a.L;
-    // where this lane's feature 16 u + (lane & 15) lives (byte offset of sample 0, byte stride per sample)
-    int fb[NB], fs[NB];
-#pragma unroll
-    for (int u = 0; u < NB; ++u) {
-        const int f = 16 * u + (lane & 15);
-        if (f < L) { fb[u] = slot_off + f * 4; fs[u] = L * 4; }
-        else if (f < L + D) { fb[u] = slot_off + tl.oX + (f - L) * 4; fs[u] = D * 4; }
-        else if (f < L + 2 * D) { fb[u] = slot_off + tl.oZ2 + (f - L - D) * 4; fs[u] = D * 4; }
-        else if (f == L + 2 * D) { fb[u] = v_off; fs[u] = 4; }
-        else { fb[u] = c_off; fs[u] = 0; }
-    }
+    const int g = lane >> 4;
 #pragma unroll
     for (int k = 0; k < NBLK; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
     // Wave w takes samples (T / CW) w .. + T / CW - 1 in J = T / (4 CW) k-steps of 4.  Within a run of 16 samples lane group g takes sample
@@ -2041,6 +2075,8 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
             prepare();
             issue_pieces();
         }
+        LinFeatMap<NB> fmap;                                  // this lane's operand addresses, but for the slot and the validity column
+        fmap.init(a, tl, v_off, c_off, lane);
         [[maybe_unused]] unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, sacc_i = 0, sacc_l = 0, sacc_f = 0, sacc_m = 0, sacc_p = 0, sacc_b = 0;
         for (int i = 0; i < items; ++i) {
             LIN_NOWQ(s0);
@@ -2057,7 +2093,11 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
             }
             LIN_NOWQ(s3);
             f32x4 acc[NB * (NB + 1) / 2];
-            if (!loader) lin_tile_products<NB, JT, kLinCW>(a, tl, lin_smem, slot_off, ragged ? vr_off : v_off, c_off, acc, lane, wave, [](int) {});
+            if (!loader) {
+                int fb[NB];
+                fmap.at(slot_off, ragged ? vr_off - v_off : 0, fb);
+                lin_tile_products_at<NB, JT, kLinCW>(a, lin_smem, fb, fmap.fs, acc, lane, wave, [](int) {});
+            }
             if constexpr (GEN) {
                 gen_share(p_load, p_load, 1);                  // item i + 2: the loading waves at once, the multiplying waves behind their products
                 p_load.advance(per_batch);
