@@ -506,6 +506,37 @@ int vaek_log_likelihood_max_samples(void);
 int vaek_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes);
 int vaek_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, int32_t kind, const float* A, int32_t dd,
                                  int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* workspace, void* stream);
+/* IMPORTANCE-WEIGHTED LOG-LIKELIHOOD of N THREE-HIDDEN-LAYER MLP VAEs of the context's shape in one call (csrc/mlp3_loglik.hip).  The
+ * estimator, the record (vaek_log_likelihood_record_len() = 4 floats, per-lane vector stores), the block rule of the samples, the two
+ * row modes and the description struct are exactly vaek_log_likelihood_replicas'; Encoder and Decoder are the four-Dense relu stacks:
+ *   mu = Encoder(x),  z_k = mu + exp(epsilon_p / 2) * xi_k,
+ *   log w_k = -1/2 [ |Decoder(z_k) - x|^2 e^{-eps} + D (eps + log 2 pi) ] + 1/2 sum_l ( xi_kl^2 - z_kl^2 + epsilon_p[l] ).
+ * FOUR launches per call whatever n is (profile labels mlp3_loglik_encode, mlp3_loglik_sample, mlp3_loglik_rows,
+ * mlp3_loglik_finalize): rows -> mu; the flattened (row, k) pairs of a replica, a tile of contiguous columns per workgroup, -> log w
+ * through matrix-core products (v_mfma_f32_16x16x4_f32, exact f32); per row the online log-sum-exp over k in k order (float32), the
+ * three row values in float64 through a binary tree per 256-row tile; the tiles in tile order.  Nothing stored in a launch is read
+ * back in it; no atomic, counter, wait or status word.  A column's arithmetic does not depend on its place in a tile, so replica r's
+ * record is BITWISE what a call with n = 1 on its slices leaves, two runs are bitwise equal, drawing mode equals explicit mode on the
+ * rows vaek_make_batch writes, and the record does not depend on ctx.batch.  Slots [0], [1] agree with the float64 evaluation on the
+ * same draws within 1e-5 of |value|, slot [2] within 1e-5 relative (1e-4 on a single row), slot [3] within 1e-6.
+ * rows is 1 .. vaek_log_likelihood_max_rows(), samples 1 .. vaek_log_likelihood_max_samples(), n 1 .. vaek_train_loop_max_replicas(),
+ * and n * rows * samples <= vaek_mlp3_log_likelihood_max_columns() = 2^22 (a cap that bounds the workspace and the length of a call on
+ * a shared machine, not a tuned value).  `workspace`: device memory of vaek_mlp3_log_likelihood_workspace_bytes(ctx, n, rows, samples)
+ * bytes, 16-byte aligned, the call's own, no need to clear; it holds the rows, mu, log w and the tile partials.  The weights are read
+ * one dword at a time: state_stride has no alignment rule.  Asynchronous on `stream`, allocates nothing, does not synchronise,
+ * capturable into a hipGraph.
+ * vaek_supports_mlp3_log_likelihood (decided once in vaek_ctx_create): float32, one decoder, exactly three hidden layers of 64 .. 256
+ * units in the encoder and in the decoder (widths may differ between layers and stacks), D, L <= 32, kind 0 .. 2 -- whatever
+ * ctx.batch, world and force_generic are: the call reads parameters only.  vaek_supports_log_likelihood stays false for these contexts.
+ * VAEK_ERR_INVALID (message names vaek_mlp3_log_likelihood_replicas, nothing touched): the list of vaek_log_likelihood_replicas (with
+ * "unsupported context" read as above and a 16-byte workspace alignment), plus n * rows * samples above the column cap.
+ * vaek_mlp3_log_likelihood_workspace_bytes refuses arguments outside those ranges and leaves *bytes alone. */
+int vaek_supports_mlp3_log_likelihood(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_mlp3_log_likelihood_max_columns(void);
+int vaek_mlp3_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, int32_t samples, size_t* bytes);
+int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, int32_t kind, const float* A,
+                                      int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
+                                      void* workspace, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

@@ -504,6 +504,7 @@ int vaek_ctx_create(const vaek_config* cfg, vaek_ctx** out) {
     c->ws_lin = off; off = align_up(off + c->lin.ws_bytes, 256);
     c->ws_lwd = off; off = align_up(off + (c->lwd ? lwd_gpart_bytes(c->B, c->D, c->L) : 0), 256);
     c->resident = resident_supported(c);
+    c->mlp3_loglik = mlp3_loglik_supported(c);
     c->ws_resident = off; off = align_up(off + resident_workspace_bytes(c), 256);
     c->ws_total = off;
     *out = c;

@@ -1,0 +1,542 @@
+// Importance-weighted log-likelihood of N three-hidden-layer MLP VAEs of one shape (vaek_mlp3_log_likelihood_replicas): the
+// estimator, the record, the block rule of the samples and the two row modes of linear_loglik.hip (vaek_log_likelihood_replicas),
+// with Encoder and Decoder the four-Dense relu stacks of networks.py:26-44:
+//   mu      = Encoder(x)
+//   z_k     = mu + exp(epsilon_p / 2) xi_k
+//   log w_k = -1/2 [ |Decoder(z_k) - x|^2 e^{-eps} + D (eps + log 2 pi) ] + 1/2 sum_l ( xi_kl^2 - z_kl^2 + epsilon_p[l] ).
+// A decoder pass per SAMPLE is ~85 000 weights at 200|200|200, so unlike the linear call nothing fits a thread: every product is
+// v_mfma_f32_16x16x4_f32 (exact f32), units on the rows and rows / samples on the columns, the operand scheme of fused_mlp3.hip's
+// m3_dense restated forward-only (that file is the text it was) with TWO changes: a fetched weight operand feeds CB column blocks of
+// 16, so a workgroup streams the weights once per 16 CB columns instead of once per 16; and a k-step wholly past K is skipped.
+//
+// FOUR launches per call whatever n is, ordered by the stream alone; nothing stored in a launch is read back inside it, and there
+// is no atomic, counter, wait or status word:
+//   1. mlp3_loglik_encode   grid (ceil(rows / 16), n): columns are data rows.  Reads the caller's rows or draws them with the functions
+//      of rng_dev.h (the bits vaek_make_batch writes) and stores them in the workspace; runs the encoder; stores mu[n][rows][L].
+//   2. mlp3_loglik_sample   grid (ceil(rows K / NC), n): columns of replica r are the flattened pairs j = row K + k.  A workgroup takes
+//      NC contiguous columns -- many rows at small K, part of one row at large K --, builds z as a [unit][column] LDS image (sample k
+//      of a row from Philox blocks k ceil(L / 4) + q of the row's latent stream), runs the four decoder products between two
+//      ping-pong images, reduces |dec - x|^2 and the sum over l per column and stores log w into lw[n][rows][K].  Columns past rows K
+//      are computed on clamped indices and not stored.  A column's arithmetic does not depend on its place in the tile or on its
+//      neighbours: MFMA columns are independent, and every per-column reduction is one thread walking that column in a fixed order.
+//   3. mlp3_loglik_rows     grid (ceil(rows / 256), n): a thread owns a row; the online log-sum-exp of linear_loglik.hip over k in k
+//      order (float32, branch-free), the three row values to float64, a fixed binary tree over the tile, one 4-double partial.
+//   4. mlp3_loglik_finalize n workgroups: the tiles in tile order, then the record, lane t storing float t.
+//
+// LDS images for NC >= 32.  An operand read is lane (n, kq) -> element (k0 + kq, 16 cb + n), a dword read whose banks are taken
+// modulo 32 within each 32-lane half (kq 0 | 1, 2 | 3); with a row pitch of NC >= 32 floats both k-rows of a half would share 16
+// banks.  The epilogue's store is lane (n, kq) -> element (16 blk + 4 kq + r, 16 cb + n), the same problem.  So element (k, c) lives
+// at k NC + (c ^ 16 s(k)), s(k) = (k ^ (k >> 2)) & 1: a read's two rows differ in bit 0 of k, a store's two rows in bit 2, and s
+// tells both apart, so neither conflicts.  Only the place changes, never the arithmetic.
+//
+// The weights are read one dword per lane and product (16 lanes of a unit block read 64 contiguous bytes), any alignment: there is
+// no stride rule.
+#include "rng_dev.h"
+#include "vaek_internal.h"
+
+namespace vaek {
+
+using ml_f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int kMl3MaxRows = 4096;            // as vaek_log_likelihood_max_rows
+constexpr int kMl3MaxSamples = 1024;         // as vaek_log_likelihood_max_samples
+constexpr int kMl3MaxColumns = 1 << 22;      // n * rows * samples: bounds the workspace and the length of a call -- a cap, not a tuned value
+constexpr int kMl3Record = 4;
+constexpr int kMl3Sums = 3;
+constexpr int ML_NT = 256;                   // threads of the chain kernels
+constexpr int ML_W = 256;                    // widest hidden layer
+constexpr int ML_F = 32;                     // widest D / L
+constexpr int ML_QB = ML_F / 4;              // Philox blocks of one sample, at most
+constexpr int ML_ENC_NC = 16;                // columns of an encode tile
+#ifndef VAEK_ML3_NC
+#define VAEK_ML3_NC 64                       // columns of a sample tile: 64 or 32 (DESIGN 3.14 has the timing of both)
+#endif
+constexpr int ML_NC = VAEK_ML3_NC;
+static_assert(ML_NC == 32 || ML_NC == 64, "a sample tile is two or four 16-column blocks");
+
+struct Ml3Net { int n_in[4], n_out[4], w_off[4]; };        // one stack's Dense layers
+
+struct Ml3Args {
+    const float* params; long long state_stride;
+    const unsigned long long* x_seeds; const unsigned* x_steps;      // [n]: the rows' Philox key and step (drawing mode)
+    const unsigned long long* z_seeds; const unsigned* z_steps;      // [n]: the samples'
+    long long a_stride;
+    const float* x; long long x_stride;      // the rows a launch READS: the caller's, or (sample launch, drawing mode) the workspace's
+    float* x_out;                            // encode launch, drawing mode: where the drawn rows go, [n][rows][D]; else NULL
+    float* mu;                               // [n][rows][L]: written by the encode launch, read by the sample launch
+    float* lw;                               // [n][rows][K]: written by the sample launch
+    int rows, samples, D, L, off_epsp, off_eps;
+    float eps_cli;
+    unsigned z_tag;
+    Ml3Net net;                              // the encoder's layers (encode launch) or the decoder's (sample launch)
+    BatchArgs gen;                           // kind, A, dd, did, pad, noise_std, tag = x_tag, D, L
+};
+
+struct Ml3RowsArgs { const float* lw; double* part; int rows, samples; };
+
+struct Ml3FinalArgs {
+    const float* params; long long state_stride;
+    const double* part;
+    float* out; long long out_stride;
+    int rows, tiles, off_eps;
+    float eps_cli;
+};
+
+// float index of element (k, c) of a [unit][NC] image
+template <int NC>
+__device__ __forceinline__ int ml_at(int k, int c) {
+    return k * NC + (NC >= 32 ? (c ^ (((k ^ (k >> 2)) & 1) << 4)) : c);
+}
+
+// out(m, column) = sum_{k < K} kernel[k][m] * in(k, column), m < M, handed to epi(m, column, sum, bias[m]); kernel = P + w_off, row
+// pitch M, bias behind it.  m3_dense's forward form (fused_mlp3.hip) over CB column blocks: wave w owns the 16-unit blocks w, w + 4,
+// .. (NB of them), the operands of 8 k-steps (a chunk) are fetched while the previous chunk is multiplied, every load is
+// unconditional at a clamped index and k >= K is zeroed on the LDS operand, so a clamped weight meets a zero.  A unit block past M
+// multiplies clamped rows and stores nothing.
+template <int NB, int CB, typename Epi>
+__device__ __forceinline__ void ml_dense(const float* __restrict__ P, int w_off, int M, int K, const float* in, int wave, int lane, Epi&& epi) {
+    constexpr int NC = 16 * CB;
+    const int n = lane & 15, kq = lane >> 4;
+    const float* const bias = P + w_off + K * M;
+    int wrow[NB];
+    float bia[NB][4];
+#pragma unroll
+    for (int bi = 0; bi < NB; ++bi) {
+        wrow[bi] = w_off + min(16 * (wave + 4 * bi) + n, M - 1);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bia[bi][r] = bias[min(16 * (wave + 4 * bi) + 4 * kq + r, M - 1)];
+    }
+    ml_f32x4 acc[NB][CB];
+#pragma unroll
+    for (int bi = 0; bi < NB; ++bi)
+#pragma unroll
+        for (int cb = 0; cb < CB; ++cb) acc[bi][cb] = ml_f32x4{0.f, 0.f, 0.f, 0.f};
+    const int nchunks = (K + 31) / 32;
+    float av0[NB][8], av1[NB][8], bv0[CB][8], bv1[CB][8];
+    auto fetch = [&](float (&av)[NB][8], float (&bv)[CB][8], int c) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int k = min(32 * c + 4 * j + kq, K - 1);
+#pragma unroll
+            for (int cb = 0; cb < CB; ++cb) bv[cb][j] = in[ml_at<NC>(k, 16 * cb + n)];
+#pragma unroll
+            for (int bi = 0; bi < NB; ++bi) av[bi][j] = P[wrow[bi] + k * M];
+        }
+    };
+    auto mult = [&](float (&av)[NB][8], float (&bv)[CB][8], int c) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            if (32 * c + 4 * j < K) {            // wave-uniform: a k-step wholly past K would add zeros (K = 200: 6 of the last chunk's 8)
+                const bool live = 32 * c + 4 * j + kq < K;
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) {
+                    const float b = live ? bv[cb][j] : 0.f;
+#pragma unroll
+                    for (int bi = 0; bi < NB; ++bi) acc[bi][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[bi][j], b, acc[bi][cb], 0, 0, 0);
+                }
+            }
+        }
+    };
+    fetch(av0, bv0, 0);
+    for (int c = 0; c < nchunks; c += 2) {
+        fetch(av1, bv1, c + 1);                  // past the end: clamped loads, never multiplied
+        __builtin_amdgcn_sched_barrier(0);
+        mult(av0, bv0, c);
+        __builtin_amdgcn_sched_barrier(0);
+        fetch(av0, bv0, c + 2);
+        __builtin_amdgcn_sched_barrier(0);
+        if (c + 1 < nchunks) mult(av1, bv1, c + 1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int bi = 0; bi < NB; ++bi)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = 16 * (wave + 4 * bi) + 4 * kq + r;
+            if (m < M) {
+#pragma unroll
+                for (int cb = 0; cb < CB; ++cb) epi(m, 16 * cb + n, acc[bi][cb][r], bia[bi][r]);
+            }
+        }
+}
+
+// the four Dense layers of one stack: img0 -> img1 -> img0 -> img1 -> img0, relu after the first three; ends behind a barrier
+template <int NC>
+__device__ __forceinline__ void ml_stack(const float* __restrict__ P, const Ml3Net& net, float* img0, float* img1, int wave, int lane) {
+    constexpr int CB = NC / 16;
+#pragma unroll 1
+    for (int li = 0; li < 4; ++li) {
+        const float* const in = (li & 1) ? img1 : img0;
+        float* const out = (li & 1) ? img0 : img1;
+        const bool relu = li != 3;
+        auto epi = [&](int m, int c, float v, float b) { v += b; out[ml_at<NC>(m, c)] = relu ? fmaxf(v, 0.f) : v; };
+        const int n_in = net.n_in[li], n_out = net.n_out[li], w_off = net.w_off[li];
+        if (n_out <= 64) ml_dense<1, CB>(P, w_off, n_out, n_in, in, wave, lane, epi);
+        else ml_dense<4, CB>(P, w_off, n_out, n_in, in, wave, lane, epi);
+        __syncthreads();
+    }
+}
+
+// ---- launch 1: rows -> mu ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(ML_NT) void mlp3_loglik_encode_kernel(const Ml3Args a) {
+    constexpr int NC = ML_ENC_NC;
+    extern __shared__ __attribute__((aligned(16))) char ml_smem[];
+    float* const img0 = reinterpret_cast<float*>(ml_smem);
+    float* const img1 = img0 + ML_W * NC;
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const long long r = blockIdx.y;
+    const int row0 = blockIdx.x * NC;
+    const int D = a.D, L = a.L;
+    const float* const P = a.params + r * a.state_stride;
+
+    if (a.x) {                                   // the caller's rows
+        const float* const xr = a.x + r * a.x_stride;
+        for (int e = t; e < D * NC; e += ML_NT) {
+            const int c = e & (NC - 1), d = e / NC;
+            img0[ml_at<NC>(d, c)] = xr[(long long)min(row0 + c, a.rows - 1) * D + d];
+        }
+    } else if (t < NC * ML_QB) {                 // vaek_make_batch's work item for (row, c0): four columns of one row
+        const int c = t & (NC - 1), c0 = 4 * (t / NC);
+        if (c0 < D) {
+            BatchArgs gx = a.gen;
+            if (gx.A) gx.A += r * a.a_stride;
+            const unsigned long long xs = a.x_seeds[r];
+            const uint2 xkey = make_uint2((unsigned)xs, (unsigned)(xs >> 32));
+            const unsigned xstep = a.x_steps[r];
+            const int row = min(row0 + c, a.rows - 1);
+            float nrm[16], o[4];
+            dataset_normals(gx, xstep, row, xkey, nrm);
+            dataset_cols4(gx, xstep, row, xkey, nrm, c0, o);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (c0 + i < D) {
+                    img0[ml_at<NC>(c0 + i, c)] = o[i];
+                    if (row0 + c < a.rows) a.x_out[(r * a.rows + row) * D + c0 + i] = o[i];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    ml_stack<NC>(P, a.net, img0, img1, wave, lane);
+    for (int e = t; e < L * NC; e += ML_NT) {    // mu is img0's rows [0, L)
+        const int c = e / L, l = e - c * L;
+        if (row0 + c < a.rows) a.mu[(r * a.rows + row0 + c) * L + l] = img0[ml_at<NC>(l, c)];
+    }
+}
+
+// ---- launch 2: (row, k) -> log w -----------------------------------------------------------------------------------------------------
+// (32 columns: 64 KB of images, so two workgroups fit a CU if the registers do -- the second bound asks for that)
+__global__ __launch_bounds__(ML_NT, ML_NC == 32 ? 2 : 1) void mlp3_loglik_sample_kernel(const Ml3Args a) {
+    constexpr int NC = ML_NC;
+    extern __shared__ __attribute__((aligned(16))) char ml_smem[];
+    float* const img0 = reinterpret_cast<float*>(ml_smem);
+    float* const img1 = img0 + ML_W * NC;
+    __shared__ float qsp[ML_QB][NC];             // per Philox block of a column: sum of xi^2 - z^2 over its (up to) four elements
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const long long r = blockIdx.y;
+    const int D = a.D, L = a.L, K = a.samples;
+    const int total = a.rows * K;                // <= 2^22
+    const int col0 = blockIdx.x * NC;
+    const float* const P = a.params + r * a.state_stride;
+    const int nlb = (L + 3) >> 2;
+
+    // ---- z = mu + e^{lv/2} xi as rows [0, L) of img0; thread (column c, block q) draws one Philox block -----------------------------
+    {
+        BatchArgs gz = a.gen;
+        gz.tag = a.z_tag;
+        const unsigned long long zs = a.z_seeds[r];
+        const uint2 zkey = make_uint2((unsigned)zs, (unsigned)(zs >> 32));
+        const unsigned zstep = a.z_steps[r];
+        const float* const mu = a.mu + r * a.rows * L;
+        for (int e = t; e < NC * nlb; e += ML_NT) {
+            const int c = e & (NC - 1), q = e / NC;
+            const int j = min(col0 + c, total - 1);
+            const int row = j / K, k = j - row * K;
+            float n4[4];
+            latent_block(gz, zstep, row, zkey, k * nlb + q, n4);
+            float qs = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int l = 4 * q + i;
+                if (l < L) {                     // elements >= L of the last block are not part of the sample
+                    const float z = fmaf(expf(0.5f * P[a.off_epsp + l]), n4[i], mu[(long long)row * L + l]);      // e^{lv/2}, networks.py:73
+                    qs = fmaf(n4[i], n4[i], qs);
+                    qs = fmaf(-z, z, qs);
+                    img0[ml_at<NC>(l, c)] = z;
+                }
+            }
+            qsp[q][c] = qs;
+        }
+    }
+    __syncthreads();
+    ml_stack<NC>(P, a.net, img0, img1, wave, lane);      // Decoder(z) is img0's rows [0, D)
+
+    // ---- log w: thread c walks its column, d and q in order ---------------------------------------------------------------------------
+    if (t < NC) {
+        const int c = t;
+        const int j = min(col0 + c, total - 1);
+        const int row = j / K;
+        const float* const xr = a.x + r * a.x_stride + (long long)row * D;
+        const float eps = a.off_eps >= 0 ? P[a.off_eps] * a.eps_cli : a.eps_cli;
+        float rsq = 0.f, qs = 0.f, lvsum = 0.f;
+        for (int d = 0; d < D; ++d) {
+            const float rr = img0[ml_at<NC>(d, c)] - xr[d];
+            rsq = fmaf(rr, rr, rsq);
+        }
+        for (int q = 0; q < nlb; ++q) qs += qsp[q][c];
+        for (int l = 0; l < L; ++l) lvsum += P[a.off_epsp + l];
+        const float c0 = 0.5f * lvsum - 0.5f * (float)D * (eps + kLog2Pi);
+        const float lw = c0 + 0.5f * (qs - rsq * expf(-eps));
+        if (col0 + c < total) a.lw[r * total + j] = lw;
+    }
+}
+
+// ---- launch 3: per row the online log-sum-exp over k, per tile of 256 rows the float64 sums -----------------------------------------
+__global__ __launch_bounds__(256) void mlp3_loglik_rows_kernel(const Ml3RowsArgs a) {
+    __shared__ double red[kMl3Sums][256];
+    const int t = threadIdx.x;
+    const int tile = blockIdx.x;
+    const long long r = blockIdx.y;
+    const int row = tile * 256 + t;
+    const int K = a.samples;
+    float res[kMl3Sums] = {0.f, 0.f, 0.f};
+    if (row < a.rows) {
+        const float* const lwr = a.lw + (r * a.rows + row) * K;
+        float m = -INFINITY, s1 = 0.f, s2 = 0.f, sl = 0.f;                 // running max, sum e^{lw - m}, sum e^{2 (lw - m)}, sum lw
+        for (int k0 = 0; k0 < K; k0 += 8) {
+            float v[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] = lwr[min(k0 + i, K - 1)];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (k0 + i < K) {
+                    const float lw = v[i];
+                    const float mn = fmaxf(m, lw);
+                    const float c = expf(m - mn), e = expf(lw - mn);       // first sample: c = e^{-inf} = 0, e = 1
+                    s1 = fmaf(s1, c, e);
+                    s2 = fmaf(s2, c * c, e * e);
+                    sl += lw;
+                    m = mn;
+                }
+            }
+        }
+        const float kf = (float)K;
+        res[0] = m + logf(s1) - logf(kf);
+        res[1] = sl / kf;
+        res[2] = (s1 * s1) / (kf * s2);
+    }
+#pragma unroll
+    for (int j = 0; j < kMl3Sums; ++j) red[j][t] = (double)res[j];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) {
+#pragma unroll
+            for (int j = 0; j < kMl3Sums; ++j) red[j][t] += red[j][t + s];
+        }
+        __syncthreads();
+    }
+    if (t < 4) {                                 // lane t stores double t; the finalize launch reads it
+        double v = 0.0;
+        if (t < kMl3Sums) v = red[t][0];
+        a.part[(r * gridDim.x + tile) * 4 + t] = v;
+    }
+}
+
+// ---- launch 4: one workgroup per replica: the tiles' partials in tile order, then the record, lane t storing float t ----------------
+__global__ __launch_bounds__(64) void mlp3_loglik_finalize_kernel(const Ml3FinalArgs a) {
+    const int t = threadIdx.x;
+    const long long r = blockIdx.x;
+    if (t >= kMl3Record) return;
+    float v;
+    if (t < kMl3Sums) {
+        double s = 0.0;
+        for (int tile = 0; tile < a.tiles; ++tile) s += a.part[(r * a.tiles + tile) * 4 + t];
+        v = (float)(s / (double)a.rows);
+    } else {
+        v = a.off_eps >= 0 ? a.params[r * a.state_stride + a.off_eps] * a.eps_cli : a.eps_cli;
+    }
+    a.out[r * a.out_stride + t] = v;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------
+// float32, one decoder, exactly three hidden layers of 64 .. 256 units both ways (any mix of widths), D, L <= 32.  Nothing about the
+// batch, the world or force_generic: the call reads parameters only
+bool mlp3_loglik_supported(const vaek_ctx* c) {
+    const vaek_config& f = c->cfg;
+    if (f.dtype != VAEK_F32 || f.sigmoid_decoder || f.n_enc_hidden != 3 || f.n_dec_hidden != 3) return false;
+    for (int i = 0; i < 3; ++i)
+        if (f.enc_hidden[i] < 64 || f.enc_hidden[i] > ML_W || f.dec_hidden[i] < 64 || f.dec_hidden[i] > ML_W) return false;
+    return c->D <= ML_F && c->L <= ML_F && c->enc.layers.size() == 4 && c->dec.layers.size() == 4;
+}
+
+static int ml3_tiles(int rows) { return (rows + 255) / 256; }
+static size_t ml3_up16(size_t b) { return (b + 15) & ~(size_t)15; }
+// the workspace: tile partials [n][tiles][4] doubles, then x [n][rows][D], mu [n][rows][L], lw [n][rows][K] floats, each 16-byte aligned
+struct Ml3Ws { size_t x, mu, lw, total; };
+static Ml3Ws ml3_workspace(const vaek_ctx* c, int n, int rows, int samples) {
+    Ml3Ws w;
+    w.x = ml3_up16(sizeof(double) * 4 * (size_t)n * ml3_tiles(rows));
+    w.mu = w.x + ml3_up16(sizeof(float) * (size_t)n * rows * c->D);
+    w.lw = w.mu + ml3_up16(sizeof(float) * (size_t)n * rows * c->L);
+    w.total = w.lw + ml3_up16(sizeof(float) * (size_t)n * rows * samples);
+    return w;
+}
+
+static void ml3_net(const Net& net, Ml3Net* out) {
+    for (int i = 0; i < 4; ++i) { out->n_in[i] = net.layers[i].n_in; out->n_out[i] = net.layers[i].n_out; out->w_off[i] = (int)net.layers[i].w_off; }
+}
+
+}  // namespace vaek
+
+using namespace vaek;
+
+extern "C" {
+
+int vaek_supports_mlp3_log_likelihood(const vaek_ctx* ctx, int32_t kind, int32_t* yes) {
+    if (!ctx || !yes) { set_error("vaek_supports_mlp3_log_likelihood: null argument"); return VAEK_ERR_INVALID; }
+    *yes = kind >= 0 && kind <= 2 && ctx->mlp3_loglik ? 1 : 0;
+    return VAEK_OK;
+}
+
+int vaek_mlp3_log_likelihood_max_columns(void) { return kMl3MaxColumns; }
+
+int vaek_mlp3_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, int32_t samples, size_t* bytes) {
+    const char* who = "vaek_mlp3_log_likelihood_workspace_bytes";
+    if (!ctx || !bytes) { set_error("%s: null argument", who); return VAEK_ERR_INVALID; }
+    if (n < 1 || n > resident_max_replicas() || rows < 1 || rows > kMl3MaxRows || samples < 1 || samples > kMl3MaxSamples ||
+        (long long)n * rows * samples > kMl3MaxColumns) {
+        set_error("%s: %d replicas of %d rows x %d samples, need 1 .. %d replicas, 1 .. %d rows, 1 .. %d samples and at most %d columns in all", who,
+                  n, rows, samples, resident_max_replicas(), kMl3MaxRows, kMl3MaxSamples, kMl3MaxColumns);
+        return VAEK_ERR_INVALID;
+    }
+    *bytes = ml3_workspace(ctx, n, rows, samples).total;
+    return VAEK_OK;
+}
+
+int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, int32_t kind, const float* A, int32_t dd,
+                                      int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* workspace, void* stream) {
+    const char* who = "vaek_mlp3_log_likelihood_replicas";
+    ProfBind pb(ctx);
+    if (!ctx || !params || !ll) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
+    if (ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)) {
+        set_error("%s: vaek_log_likelihood.struct_size %d != %d (header / library mismatch)", who, ll->struct_size, (int)sizeof(vaek_log_likelihood));
+        return VAEK_ERR_INVALID;
+    }
+    if (!ctx->mlp3_loglik) {
+        set_error("%s: needs a float32 VAE with one decoder and three hidden layers of 64 .. %d units both ways, D, L <= %d (see "
+                  "vaek_supports_mlp3_log_likelihood)", who, ML_W, ML_F);
+        return VAEK_ERR_INVALID;
+    }
+    if (ll->n < 1 || ll->n > resident_max_replicas()) {
+        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ll->n, resident_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    if (ll->rows < 1 || ll->rows > kMl3MaxRows) {
+        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kMl3MaxRows);
+        return VAEK_ERR_INVALID;
+    }
+    if (ll->samples < 1 || ll->samples > kMl3MaxSamples) {
+        set_error("%s: %d samples, need 1 .. %d (vaek_log_likelihood_max_samples)", who, ll->samples, kMl3MaxSamples);
+        return VAEK_ERR_INVALID;
+    }
+    if ((long long)ll->n * ll->rows * ll->samples > kMl3MaxColumns) {
+        set_error("%s: %d replicas x %d rows x %d samples = %lld columns, at most %d (vaek_mlp3_log_likelihood_max_columns)", who, ll->n, ll->rows,
+                  ll->samples, (long long)ll->n * ll->rows * ll->samples, kMl3MaxColumns);
+        return VAEK_ERR_INVALID;
+    }
+    const bool explicit_rows = ll->x != nullptr;
+    if (!ll->z_seeds || !ll->z_steps || !ll->out || (!explicit_rows && (!ll->x_seeds || !ll->x_steps))) {
+        set_error("%s: x_seeds, x_steps (drawing mode), z_seeds, z_steps or out is NULL", who);
+        return VAEK_ERR_INVALID;
+    }
+    if (ll->state_stride < ctx->P || ll->out_stride < kMl3Record) {
+        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %d (vaek_log_likelihood_record_len)", who,
+                  (long long)ll->state_stride, (long long)ctx->P, (long long)ll->out_stride, kMl3Record);
+        return VAEK_ERR_INVALID;
+    }
+    if (!workspace || ((uintptr_t)workspace & 15) != 0) {
+        set_error("%s: workspace is NULL or not 16-byte aligned (vaek_mlp3_log_likelihood_workspace_bytes)", who);
+        return VAEK_ERR_INVALID;
+    }
+    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    if (explicit_rows) {
+        if (ll->x_stride < 0 || (ll->x_stride > 0 && ll->x_stride < (int64_t)ll->rows * ctx->D)) {
+            set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)ll->x_stride, (long long)ll->rows * ctx->D);
+            return VAEK_ERR_INVALID;
+        }
+    } else {
+        if (ll->a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)ll->a_stride); return VAEK_ERR_INVALID; }
+        if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
+        if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
+        if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
+            set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
+            return VAEK_ERR_INVALID;
+        }
+        if (dd + pad + (kind == 1 ? 1 : 0) != ctx->D) {
+            set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
+            return VAEK_ERR_INVALID;
+        }
+        if (x_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    }
+    const int n = ll->n, rows = ll->rows, K = ll->samples, tiles = ml3_tiles(rows);
+    const Ml3Ws w = ml3_workspace(ctx, n, rows, K);
+    char* const ws = static_cast<char*>(workspace);
+    Ml3Args a{};
+    a.params = params; a.state_stride = ll->state_stride;
+    a.x_seeds = reinterpret_cast<const unsigned long long*>(ll->x_seeds); a.x_steps = ll->x_steps;
+    a.z_seeds = reinterpret_cast<const unsigned long long*>(ll->z_seeds); a.z_steps = ll->z_steps;
+    a.x = ll->x; a.x_stride = ll->x_stride;
+    a.x_out = explicit_rows ? nullptr : reinterpret_cast<float*>(ws + w.x);
+    a.mu = reinterpret_cast<float*>(ws + w.mu);
+    a.lw = reinterpret_cast<float*>(ws + w.lw);
+    a.rows = rows; a.samples = K; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
+    a.eps_cli = ctx->cfg.eps_cli; a.z_tag = z_tag;
+    a.gen.kind = 2; a.gen.D = ctx->D; a.gen.L = ctx->L; a.gen.rows = rows; a.gen.row0 = 0;
+    if (!explicit_rows) {
+        a.a_stride = ll->a_stride;
+        a.gen.kind = kind; a.gen.A = kind == 2 ? nullptr : A; a.gen.dd = dd; a.gen.did = did; a.gen.pad = pad;
+        a.gen.noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
+        a.gen.tag = x_tag;
+    }
+    ml3_net(ctx->enc, &a.net);
+    Ml3Args s = a;                               // the sample launch reads the rows the encode launch read or drew
+    if (!explicit_rows) { s.x = a.x_out; s.x_stride = (long long)rows * ctx->D; }
+    s.x_out = nullptr;
+    ml3_net(ctx->dec, &s.net);
+    Ml3RowsArgs ra{};
+    ra.lw = a.lw; ra.part = reinterpret_cast<double*>(ws); ra.rows = rows; ra.samples = K;
+    Ml3FinalArgs f{};
+    f.params = params; f.state_stride = ll->state_stride; f.part = ra.part; f.out = ll->out; f.out_stride = ll->out_stride;
+    f.rows = rows; f.tiles = tiles; f.off_eps = (int)ctx->off_eps; f.eps_cli = ctx->cfg.eps_cli;
+
+    constexpr size_t lds_enc = sizeof(float) * 2 * ML_W * ML_ENC_NC, lds_smp = sizeof(float) * 2 * ML_W * ML_NC;
+    static thread_local PerDeviceOnce attr_set;
+    if (attr_set.need()) {
+        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)mlp3_loglik_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_smp));
+        attr_set.mark();
+    }
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps("mlp3_loglik_encode", st);
+        launch_k(ps, mlp3_loglik_encode_kernel, dim3((unsigned)((rows + ML_ENC_NC - 1) / ML_ENC_NC), (unsigned)n), dim3(ML_NT), lds_enc, st, a);
+    }
+    VAEK_HIP_CHECK(hipGetLastError());
+    {
+        ProfScope ps("mlp3_loglik_sample", st);
+        launch_k(ps, mlp3_loglik_sample_kernel, dim3((unsigned)((rows * K + ML_NC - 1) / ML_NC), (unsigned)n), dim3(ML_NT), lds_smp, st, s);
+    }
+    VAEK_HIP_CHECK(hipGetLastError());
+    {
+        ProfScope ps("mlp3_loglik_rows", st);
+        launch_k(ps, mlp3_loglik_rows_kernel, dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, st, ra);
+    }
+    VAEK_HIP_CHECK(hipGetLastError());
+    {
+        ProfScope ps("mlp3_loglik_finalize", st);
+        launch_k(ps, mlp3_loglik_finalize_kernel, dim3((unsigned)n), dim3(64), 0, st, f);
+    }
+    VAEK_HIP_CHECK(hipGetLastError());
+    return VAEK_OK;
+}
+
+}  // extern "C"

@@ -127,6 +127,7 @@ struct vaek_ctx {
     bool fused;                      // a whole-network path is available and selected (fused_small / fused_mfma / fused_mlp1 / fused_mlp3)
     bool mlp3 = false;               // ... and it is fused_mlp3.hip's (three hidden layers both ways, small batch)
     bool resident = false;           // vaek_train_loop_gen covers this context (linear_resident.hip: resident_supported)
+    bool mlp3_loglik = false;        // vaek_mlp3_log_likelihood_replicas covers this context (mlp3_loglik.hip: mlp3_loglik_supported)
     // workspace layout (bytes)
     size_t ws_samples, ws_dsamp, ws_gbuf0, ws_gbuf1, ws_slabs, ws_epart, ws_epart_blk, ws_rpart, ws_eblk, ws_fused, ws_mlp3, ws_wb16, ws_sk16, ws_skpart, ws_lin, ws_lwd, ws_resident, ws_total;
     bool lwd = false; int lwd_rb = 0;           // wide linear decoder: fused forward / ELBO / backward (linear_wide.hip), rows per row block
@@ -435,5 +436,8 @@ int mlp3_train_step_replicas(vaek_ctx* c, float* params, float* grads, float* m,
                              const float* z1, const float* z2, float lr, void* ws, hipStream_t st, const BatchArgs* gen, int n,
                              long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
                              long long a_stride, float* loss_hist, long long loss_hist_cap);
+
+// ---- mlp3_loglik.hip: importance-weighted log-likelihood of three-hidden-layer MLP VAEs; whatever the batch, world or force_generic
+bool mlp3_loglik_supported(const vaek_ctx* c);
 
 }  // namespace vaek

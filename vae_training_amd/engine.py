@@ -316,17 +316,10 @@ class Engine:
         _lib.check(self.lib.vaek_log_likelihood_workspace_bytes(self.h, int(n), int(rows), C.byref(b)))
         return int(b.value)
 
-    def log_likelihood_replicas(self, params, rows, samples, z_seeds, z_steps, out, workspace, kind=2, A=None, dd=0, did=0, pad=0,
-                                var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, z_tag=4, n=None,
-                                state_stride=None, out_stride=None, struct_size=None):
-        """The importance-weighted log-likelihood of EACH of n independent models of this engine's shape in one call
-        (vaek_log_likelihood_replicas): over `rows` data rows and `samples` posterior samples per row, record r = [IWAE bound, ELBO
-        estimate, normalised effective sample size, eps] in out[r, :4].  The rows are the caller's (x: float32 [rows, D] shared by all
-        replicas, or [n, rows, D]) or, with x None, drawn under (x_seeds[r], x_steps[r], x_tag) exactly as make_batch draws them from
-        (kind, A, dd, did, pad, var_added); sample k of a row takes blocks k * ceil(L / 4) .. of the latent stream under (z_seeds[r],
-        z_steps[r], z_tag).  params: [n, state_stride] (read only), seeds int64 [n], steps int32 [n], out: float32 [n, out_stride >=
-        4], workspace: uint8 of log_likelihood_workspace(n, rows) bytes -- all device tensors; n and the strides default to the
-        tensors' shapes.  Asynchronous; capturable."""
+    @staticmethod
+    def _log_likelihood_desc(params, rows, samples, z_seeds, z_steps, out, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride, out_stride,
+                             struct_size):
+        """The vaek_log_likelihood description both log-likelihood calls take, from tensors; strides default to the tensors' shapes."""
         ll = _lib.VaekLogLikelihood()
         ll.struct_size = C.sizeof(_lib.VaekLogLikelihood) if struct_size is None else int(struct_size)
         ll.n = int(params.shape[0] if n is None else n)
@@ -344,9 +337,55 @@ class Engine:
         if x_stride is None:
             x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
         ll.x_stride = int(x_stride)
+        return ll
+
+    def log_likelihood_replicas(self, params, rows, samples, z_seeds, z_steps, out, workspace, kind=2, A=None, dd=0, did=0, pad=0,
+                                var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, z_tag=4, n=None,
+                                state_stride=None, out_stride=None, struct_size=None):
+        """The importance-weighted log-likelihood of EACH of n independent models of this engine's shape in one call
+        (vaek_log_likelihood_replicas): over `rows` data rows and `samples` posterior samples per row, record r = [IWAE bound, ELBO
+        estimate, normalised effective sample size, eps] in out[r, :4].  The rows are the caller's (x: float32 [rows, D] shared by all
+        replicas, or [n, rows, D]) or, with x None, drawn under (x_seeds[r], x_steps[r], x_tag) exactly as make_batch draws them from
+        (kind, A, dd, did, pad, var_added); sample k of a row takes blocks k * ceil(L / 4) .. of the latent stream under (z_seeds[r],
+        z_steps[r], z_tag).  params: [n, state_stride] (read only), seeds int64 [n], steps int32 [n], out: float32 [n, out_stride >=
+        4], workspace: uint8 of log_likelihood_workspace(n, rows) bytes -- all device tensors; n and the strides default to the
+        tensors' shapes.  Asynchronous; capturable."""
+        ll = self._log_likelihood_desc(params, rows, samples, z_seeds, z_steps, out, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride,
+                                       out_stride, struct_size)
         wp = None if workspace is None else C.c_void_p(workspace if isinstance(workspace, int) else workspace.data_ptr())
         _lib.check(self.lib.vaek_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did), int(pad),
                                                          float(var_added), int(x_tag), int(z_tag), wp, _stream()))
+
+    def supports_mlp3_log_likelihood(self, kind):
+        """True where mlp3_log_likelihood_replicas covers this engine and dataset kind: float32, one decoder, exactly three hidden layers
+        of 64 .. 256 units in the encoder and in the decoder, D, L <= 32 -- whatever the engine's batch, world and force_generic are
+        (vaek_supports_mlp3_log_likelihood)."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_mlp3_log_likelihood(self.h, int(kind), C.byref(f)))
+        return bool(f.value)
+
+    @property
+    def mlp3_log_likelihood_max_columns(self):
+        """The cap on n * rows * samples of one mlp3_log_likelihood_replicas call (vaek_mlp3_log_likelihood_max_columns)."""
+        return int(self.lib.vaek_mlp3_log_likelihood_max_columns())
+
+    def mlp3_log_likelihood_workspace(self, n, rows, samples):
+        """Bytes of the workspace mlp3_log_likelihood_replicas needs (its own buffer, 16-byte aligned, not self.workspace)."""
+        b = C.c_size_t()
+        _lib.check(self.lib.vaek_mlp3_log_likelihood_workspace_bytes(self.h, int(n), int(rows), int(samples), C.byref(b)))
+        return int(b.value)
+
+    def mlp3_log_likelihood_replicas(self, params, rows, samples, z_seeds, z_steps, out, workspace, kind=2, A=None, dd=0, did=0, pad=0,
+                                     var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, z_tag=4, n=None,
+                                     state_stride=None, out_stride=None, struct_size=None):
+        """log_likelihood_replicas for three-hidden-layer MLP VAEs (vaek_mlp3_log_likelihood_replicas): the same estimator, record, block
+        rule, row modes and arguments, with the relu stacks as Encoder and Decoder; workspace: uint8 of
+        mlp3_log_likelihood_workspace(n, rows, samples) bytes.  Four launches whatever n is.  Asynchronous; capturable."""
+        ll = self._log_likelihood_desc(params, rows, samples, z_seeds, z_steps, out, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride,
+                                       out_stride, struct_size)
+        wp = None if workspace is None else C.c_void_p(workspace if isinstance(workspace, int) else workspace.data_ptr())
+        _lib.check(self.lib.vaek_mlp3_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                              float(var_added), int(x_tag), int(z_tag), wp, _stream()))
 
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""

@@ -127,7 +127,8 @@ class GenerativeModel(Model):
     def _stats_event(self):
         """The stats of an n_print event: compute_stats(), and with `log_likelihood_samples` = K set (run.py --log_likelihood_samples)
         the importance-weighted log-likelihood of this model on K samples per row (trainer.ReplicaLogLik, one library call), which
-        neither splits the model's key nor advances a draw counter of the run."""
+        neither splits the model's key nor advances a draw counter of the run; `mlp_log_likelihood_samples` does the same for a
+        three-hidden-layer MLP model (trainer.ReplicaLogLikMlp3)."""
         stats = self.compute_stats()
         K = getattr(self, "log_likelihood_samples", None)
         if K:
@@ -135,6 +136,12 @@ class GenerativeModel(Model):
             if getattr(self, "_loglik", None) is None:
                 self._loglik = ReplicaLogLik([self], K)
             stats.update(self._loglik.event()[0])
+        K = getattr(self, "mlp_log_likelihood_samples", None)      # run.py --mlp_log_likelihood_samples: the same event for an mlp3 model
+        if K:
+            from .trainer import ReplicaLogLikMlp3
+            if getattr(self, "_loglik_mlp3", None) is None:
+                self._loglik_mlp3 = ReplicaLogLikMlp3([self], K)
+            stats.update(self._loglik_mlp3.event()[0])
         return stats
 
     def write_stats(self, stats):

@@ -3,7 +3,7 @@
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
---fused_stats, --log_likelihood_samples."""
+--fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples."""
 from __future__ import annotations
 
 import argparse
@@ -78,6 +78,12 @@ def build_parser():
                         "own RNG counter and tags, so the training run is bitwise the one without the flag.  Alone or with "
                         "--sweep_dataset_seeds (one call for all models); float32 linear VAEs with D, L <= 32 only; other models are refused "
                         "before any step; single GPU only")
+    p.add_argument("--mlp_log_likelihood_samples", dest="mlp_log_likelihood_samples", type=_positive_int, default=None, metavar="K",
+                   help="--log_likelihood_samples for three-hidden-layer MLP VAEs (trainer.ReplicaLogLikMlp3, "
+                        "vaek_mlp3_log_likelihood_replicas): the same three stats from the same draws, the training run bitwise the one "
+                        "without the flag.  Alone or with --sweep_dataset_seeds (one call for all models); float32, one decoder, three "
+                        "hidden layers of 64 .. 256 units both ways, D, L <= 32, models x 1000 rows x K at most 2^22; linear models (use "
+                        "--log_likelihood_samples), other models and both flags together are refused before any step; single GPU only")
     return p
 
 
@@ -249,6 +255,40 @@ def check_log_likelihood_model(m, samples):
                            "(vaek_log_likelihood_max_samples)")
 
 
+MLP_LOGLIK_NEEDS = ("a model vaek_mlp3_log_likelihood_replicas covers (vaek_supports_mlp3_log_likelihood): float32, one decoder, exactly "
+                    "three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32, -dd / -did <= 16, on one GPU")
+
+
+def check_log_likelihood_flags(args):
+    """--log_likelihood_samples and --mlp_log_likelihood_samples cover disjoint models: both together are refused before anything is
+    created."""
+    if getattr(args, "log_likelihood_samples", None) is not None and getattr(args, "mlp_log_likelihood_samples", None) is not None:
+        raise RuntimeError("--log_likelihood_samples (linear VAEs) and --mlp_log_likelihood_samples (three-hidden-layer MLP VAEs) cover "
+                           "disjoint models: give the one that matches the model's step path")
+
+
+def check_mlp_log_likelihood_model(m, samples, n_models=1):
+    """--mlp_log_likelihood_samples: refuse, before any step, a model the call does not cover, a K above its cap or more columns
+    (models x print rows x K) than one call takes."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    kind, _, dd, did, _, _ = m.dataset.device_spec()
+    path = getattr(eng, "step_path", "?")
+    if eng.world == 1 and eng.supports_log_likelihood(kind):
+        raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS}; this is a linear VAE: use --log_likelihood_samples "
+                           f"(this model's step path: {path})")
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_mlp3_log_likelihood(kind):
+        raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS} (this model's step path: {path}, world {eng.world})")
+    if samples > eng.log_likelihood_max_samples:
+        raise RuntimeError(f"--mlp_log_likelihood_samples {samples}: at most {eng.log_likelihood_max_samples} samples per row fit one call "
+                           f"(vaek_log_likelihood_max_samples; this model's step path: {path})")
+    cols = n_models * m.print_batch_size * samples
+    if cols > eng.mlp3_log_likelihood_max_columns:
+        raise RuntimeError(f"--mlp_log_likelihood_samples {samples}: {n_models} models x {m.print_batch_size} rows x {samples} samples = {cols} "
+                           f"columns, at most {eng.mlp3_log_likelihood_max_columns} fit one call (vaek_mlp3_log_likelihood_max_columns; this "
+                           f"model's step path: {path})")
+
+
 def main_sweep(args):
     """--sweep_dataset_seeds: one dataset and one VAEModel per seed, the reference's schedule (model.py:207-222: stats every n_print
     steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE loop.run between
@@ -287,12 +327,18 @@ def main_sweep(args):
         from .trainer import ReplicaLogLik
         check_log_likelihood_model(models[0], ll_samples)
         loglik = ReplicaLogLik(models, ll_samples)
+    mlp_samples = getattr(args, "mlp_log_likelihood_samples", None)
+    if mlp_samples is not None:              # before any step
+        from .trainer import ReplicaLogLikMlp3
+        check_mlp_log_likelihood_model(models[0], mlp_samples, len(models))
+        loglik = ReplicaLogLikMlp3(models, mlp_samples)
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
     if fused_stats:
         print(f"Stats events: one launch for {len(models)} models (vaek_stats_event_replicas)")
     if loglik is not None:
-        print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows (vaek_log_likelihood_replicas)")
+        entry = "vaek_log_likelihood_replicas" if mlp_samples is None else "vaek_mlp3_log_likelihood_replicas"
+        print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows ({entry})")
     for r, m in enumerate(models):
         m._graph_loop = loop.view(r)
         score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
@@ -331,6 +377,7 @@ def main(args):
     import os
 
     check_fused_stats_args(args)
+    check_log_likelihood_flags(args)
     if getattr(args, "sweep_dataset_seeds", None):
         return main_sweep(args)
     from .utils import get_output_dir, make_output_dir
@@ -338,6 +385,9 @@ def main(args):
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     if world > 1 and getattr(args, "log_likelihood_samples", None) is not None:      # before a process group exists
         raise RuntimeError(f"--log_likelihood_samples needs {LOGLIK_NEEDS}: it does not combine with data parallelism "
+                           f"(step path of a world of {world}: one shard per rank)")
+    if world > 1 and getattr(args, "mlp_log_likelihood_samples", None) is not None:
+        raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS}: it does not combine with data parallelism "
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1:
         import torch
@@ -366,6 +416,11 @@ def main(args):
         check_log_likelihood_model(model, ll_samples)      # before any step
         model.log_likelihood_samples = ll_samples          # the n_print events add trainer.ReplicaLogLik([model], K).event()
         print(f"Log-likelihood events: {ll_samples} samples × {model.print_batch_size} rows (vaek_log_likelihood_replicas)")
+    mlp_samples = getattr(args, "mlp_log_likelihood_samples", None)
+    if mlp_samples is not None:
+        check_mlp_log_likelihood_model(model, mlp_samples)      # before any step
+        model.mlp_log_likelihood_samples = mlp_samples          # the n_print events add trainer.ReplicaLogLikMlp3([model], K).event()
+        print(f"Log-likelihood events: {mlp_samples} samples × {model.print_batch_size} rows (vaek_mlp3_log_likelihood_replicas)")
     if rank == 0:
         eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
         loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")

@@ -528,11 +528,12 @@ class ReplicaLogLik:
 
     KEYS = ("Average Log Likelihood", "ELBO estimate", "Effective Sample Size")
     X_TAG, Z_TAG = 3, 4
+    NAME = "ReplicaLogLik"             # ReplicaLogLikMlp3 overrides the name and the four methods below __init__
 
     def __init__(self, vae_models, samples, rows=None):
         ms = list(vae_models)
         if not ms:
-            raise RuntimeError("ReplicaLogLik: no models")
+            raise RuntimeError(f"{self.NAME}: no models")
         from .datasets import DEVICE_DRAW_MAX_DIM
         self.ms = ms
         m0 = ms[0]
@@ -540,42 +541,55 @@ class ReplicaLogLik:
         specs = [m.dataset.device_spec() for m in ms]
         self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
         if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
-            raise RuntimeError(f"ReplicaLogLik draws its rows with libvaek's Philox generator, which supports -dd / -did <= "
+            raise RuntimeError(f"{self.NAME} draws its rows with libvaek's Philox generator, which supports -dd / -did <= "
                                f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
         if self.eng.world > 1:
-            raise RuntimeError("ReplicaLogLik: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
-        if not self.eng.supports_log_likelihood(self.kind):
-            raise RuntimeError("ReplicaLogLik: vaek_log_likelihood_replicas does not cover this model / dataset (it needs a float32 linear "
-                               "VAE -- no hidden layers -- with one or two decoders and D, L <= 32, D <= 28 with two decoders; this model's "
-                               f"step path: {getattr(self.eng, 'step_path', '?')})")
+            raise RuntimeError(f"{self.NAME}: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
+        self._check_covered()
         R = len(ms)
         if R > self.eng.train_loop_max_replicas:
-            raise RuntimeError(f"ReplicaLogLik: {R} models, at most {self.eng.train_loop_max_replicas} fit one call "
+            raise RuntimeError(f"{self.NAME}: {R} models, at most {self.eng.train_loop_max_replicas} fit one call "
                                "(vaek_train_loop_max_replicas)")
         want = self._shape(m0, specs[0])
         for r, (m, sp) in enumerate(zip(ms, specs)):
             got = self._shape(m, sp)
             if got != want:
-                raise RuntimeError(f"ReplicaLogLik: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
+                raise RuntimeError(f"{self.NAME}: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
                                    f"{want}): one call evaluates replicas of ONE shape")
         self.samples = int(samples)
         if not 1 <= self.samples <= self.eng.log_likelihood_max_samples:
-            raise RuntimeError(f"ReplicaLogLik: {self.samples} samples per row, need 1 .. {self.eng.log_likelihood_max_samples} "
+            raise RuntimeError(f"{self.NAME}: {self.samples} samples per row, need 1 .. {self.eng.log_likelihood_max_samples} "
                                "(vaek_log_likelihood_max_samples)")
         self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
         if not 1 <= self.rows <= self.eng.log_likelihood_max_rows:
-            raise RuntimeError(f"ReplicaLogLik: {self.rows} rows per event, need 1 .. {self.eng.log_likelihood_max_rows} "
+            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 1 .. {self.eng.log_likelihood_max_rows} "
                                "(vaek_log_likelihood_max_rows)")
         self.R = R
+        self._check_size()
         dev = self.eng.device
         self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
         self.out = torch.zeros(R, self.eng.log_likelihood_record_len, dtype=torch.float32, device=dev)
-        self.workspace = torch.empty(max(self.eng.log_likelihood_workspace(R, self.rows), 8), dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty(max(self._workspace_bytes(), 8), dtype=torch.uint8, device=dev)
         if specs[0][1] is None:
             self.A, self.a_stride = None, 0
         else:
             self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
             self.a_stride = self.A.shape[1]
+
+    def _check_covered(self):
+        if not self.eng.supports_log_likelihood(self.kind):
+            raise RuntimeError("ReplicaLogLik: vaek_log_likelihood_replicas does not cover this model / dataset (it needs a float32 linear "
+                               "VAE -- no hidden layers -- with one or two decoders and D, L <= 32, D <= 28 with two decoders; this model's "
+                               f"step path: {getattr(self.eng, 'step_path', '?')})")
+
+    def _check_size(self):
+        pass                           # rows and samples are the linear call's only caps
+
+    def _workspace_bytes(self):
+        return self.eng.log_likelihood_workspace(self.R, self.rows)
+
+    def _call(self, *args, **kw):
+        self.eng.log_likelihood_replicas(*args, **kw)
 
     @staticmethod
     def _shape(m, spec):
@@ -598,9 +612,9 @@ class ReplicaLogLik:
             steps.append(t - 2 ** 32 if t >= 2 ** 31 else t)
         seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
         steps = torch.tensor(steps, dtype=torch.int32).to(dev)
-        self.eng.log_likelihood_replicas(self.params, self.rows, self.samples, seeds, steps, self.out, self.workspace, kind=self.kind,
-                                         A=self.A, dd=self.dd, did=self.did, pad=self.pad, var_added=self.var, x_seeds=seeds, x_steps=steps,
-                                         a_stride=self.a_stride, x_tag=self.X_TAG, z_tag=self.Z_TAG)
+        self._call(self.params, self.rows, self.samples, seeds, steps, self.out, self.workspace, kind=self.kind,
+                   A=self.A, dd=self.dd, did=self.did, pad=self.pad, var_added=self.var, x_seeds=seeds, x_steps=steps,
+                   a_stride=self.a_stride, x_tag=self.X_TAG, z_tag=self.Z_TAG)
         rec = self.out.cpu()                                                      # the event's ONE device -> host copy
         stats = []
         for r, m in enumerate(self.ms):
@@ -608,6 +622,34 @@ class ReplicaLogLik:
             m.average_log_likelihoods.append(st[self.KEYS[0]])
             stats.append(st)
         return stats
+
+
+class ReplicaLogLikMlp3(ReplicaLogLik):
+    """ReplicaLogLik for three-hidden-layer MLP VAEs (vaek_mlp3_log_likelihood_replicas, csrc/mlp3_loglik.hip): the same contract --
+    one shape, any batch size, ONE library call and ONE device -> host copy per event, the same three keys, the counter
+    `m._loglik_draws`, the seed dataset.key[0] ^ dataset.key[1], tags 3 and 4, nothing of the run touched, the first key appended to
+    `m.average_log_likelihoods` -- on models Engine.supports_mlp3_log_likelihood covers, with one more cap: R * rows * samples at most
+    Engine.mlp3_log_likelihood_max_columns."""
+
+    NAME = "ReplicaLogLikMlp3"
+
+    def _check_covered(self):
+        if not self.eng.supports_mlp3_log_likelihood(self.kind):
+            raise RuntimeError("ReplicaLogLikMlp3: vaek_mlp3_log_likelihood_replicas does not cover this model / dataset (it needs a float32 "
+                               "VAE with one decoder and exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, "
+                               f"D, L <= 32; a linear VAE is ReplicaLogLik's; this model's step path: {getattr(self.eng, 'step_path', '?')})")
+
+    def _check_size(self):
+        cols, cap = self.R * self.rows * self.samples, self.eng.mlp3_log_likelihood_max_columns
+        if cols > cap:
+            raise RuntimeError(f"ReplicaLogLikMlp3: {self.R} models x {self.rows} rows x {self.samples} samples = {cols} columns, at most "
+                               f"{cap} fit one call (vaek_mlp3_log_likelihood_max_columns)")
+
+    def _workspace_bytes(self):
+        return self.eng.mlp3_log_likelihood_workspace(self.R, self.rows, self.samples)
+
+    def _call(self, *args, **kw):
+        self.eng.mlp3_log_likelihood_replicas(*args, **kw)
 
 
 class ReplicaGraphLoop:
