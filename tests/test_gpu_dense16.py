@@ -33,8 +33,8 @@ LABEL = {"dense_fwd_bf16": "gemm_bf16_fwd", "dense_fwd_reparam_bf16": "gemm_bf16
          "dx_in16": "gemm_f32_dx", "dw_x16": "gemm_f32_dw", "dw_dy16": "gemm_f32_dw"}
 # every kernel label the calls of this file hold to the reference: the main kernels, the weight prep and the slab reductions
 COVERED = set(LABEL.values()) | {"cvt_weights_bf16", "sk16_prep", "sk16_partials_reduce", "sum_slabs"}
-# what else a dtype = bf16 step runs: the elementwise ELBO / reparameterisation passes and the finalisation (whole-model tests,
-# tests/test_gpu_bf16.py), and the all-f32 kernels of f32-storage layers whose plain label is not already in COVERED (per call
+# what else a dtype = bf16 step runs: the elementwise ELBO / reparameterisation passes and the finalisation (per call and per output:
+# tests/test_gpu_elbo_tail.py; whole models: tests/test_gpu_bf16.py), and the all-f32 kernels of f32-storage layers whose plain label is not already in COVERED (per call
 # and per element: tests/test_gpu_dense32.py)
 NOT_DENSE16 = {"elbo", "elbo_reduce", "reparam_bwd", "finalize", "bulk_finalize", "gemm_f32_fwd_reparam_ts", "gemm_f32_dx_ts",
                "gemm_f32_fwd_128x128", "gemm_f32_dx_128x128", "gemm_f32_dw_128x128"}

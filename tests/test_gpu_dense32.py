@@ -30,7 +30,8 @@ f32_tile, TILE_DIMS = T16.f32_tile, T16.TILE_DIMS
 # every label the calls of this file hold to the reference
 DENSE32 = {"gemm_f32_fwd", "gemm_f32_fwd_128x128", "gemm_f32_fwd_reparam", "gemm_f32_fwd_reparam_ts", "gemm_f32_fwd_elbo",
            "gemm_f32_dx", "gemm_f32_dx_128x128", "gemm_f32_dx_ts", "gemm_f32_dw", "gemm_f32_dw_128x128", "sum_slabs"}
-# what else a layer-by-layer f32 step runs: the elementwise ELBO / reparameterisation passes and the finalisation
+# what else a layer-by-layer f32 step runs: the elementwise ELBO / reparameterisation passes and the finalisation (per call and per
+# output: tests/test_gpu_elbo_tail.py, which also runs these models with Adam, in eval and in forward)
 NOT_DENSE32 = {"elbo", "elbo_reduce", "reparam_bwd", "finalize", "bulk_finalize"}
 
 

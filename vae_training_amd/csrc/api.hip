@@ -346,8 +346,27 @@ static int whole_step(vaek_ctx* c, float* params, float* grads, float* m, float*
 
 constexpr int64_t kBulkFinalizeMin = 65536;      // parameters below which the 64-output finalize alone is faster
 
-static int generic_finalize(vaek_ctx* c, const float* params, float* grads, float* params_rw, float* m, float* v,
-                            const int32_t* step_dev, float lr, void* ws, hipStream_t st, int64_t lo = 0) {
+// The launch sequence of the finalisation on filled-in arguments (the step below; vaek_debug_tail, debug_tail.hip): the outputs
+// [0, hi) as a streaming pass with Adam (hi = 0: none) and the 64-output finalize above them, else the 64-output finalize from
+// f.lo; Adam (f.params_rw) inside the finalize kernel when `fuse`, else a separate launch over what the bulk pass left.
+int finalize_launches(const FinalizeArgs& args, int64_t hi, bool fuse, hipStream_t st) {
+    FinalizeArgs f = args;
+    float* const params_rw = f.params_rw;
+    int rc;
+    int64_t adam_from = 0;
+    if (hi > 0) {
+        // big models: weights and biases as a streaming pass (with Adam), the 64-output finalize only for the tail
+        if ((rc = launch_bulk_finalize(f, hi, st))) return rc;
+        f.lo = adam_from = hi;
+    }
+    if (!fuse) f.params_rw = nullptr;
+    if ((rc = launch_finalize(f, st)) || params_rw == nullptr || fuse) return rc;
+    return launch_adam(params_rw + adam_from, f.grads + adam_from, f.m + adam_from, f.v + adam_from, f.P - adam_from, f.lr, 0, f.step_dev, 1.f, st);
+}
+
+// the finalisation's arguments as the context and its workspace give them
+static FinalizeArgs finalize_args(vaek_ctx* c, const float* params, float* grads, float* params_rw, float* m, float* v,
+                                  const int32_t* step_dev, float lr, void* ws, int64_t lo) {
     FinalizeArgs f{};
     f.lo = lo;
     f.slabs = at<float>(ws, c->ws_slabs); f.slab_stride = slab_stride(c); f.S = c->S;
@@ -363,22 +382,20 @@ static int generic_finalize(vaek_ctx* c, const float* params, float* grads, floa
     f.rows_over_bt = (float)((double)c->B / (double)c->Bt); f.inv_bt = (float)(1.0 / (double)c->Bt);
     f.rows = (float)c->B;
     f.grads = grads; f.params_rw = params_rw; f.m = m; f.v = v; f.step_dev = step_dev; f.lr = lr;
+    f.loss_hist = c->cfg.world == 1 ? c->loss_hist : nullptr; f.loss_hist_cap = c->loss_hist_cap;
+    if (!f.step_dev) f.loss_hist = nullptr;
+    return f;
+}
+
+static int generic_finalize(vaek_ctx* c, const float* params, float* grads, float* params_rw, float* m, float* v,
+                            const int32_t* step_dev, float lr, void* ws, hipStream_t st, int64_t lo = 0) {
+    const FinalizeArgs f = finalize_args(c, params, grads, params_rw, m, v, step_dev, lr, ws, lo);
     // Adam is fused into the finalize kernel only while epsilon_p, epsilon and the scalar sums all sit
     // in its block 0 (64 outputs): the loss lanes read epsilon_p, so its Adam writers must be behind the
     // same block-local barrier.  Wider latents take a separate Adam launch.
-    f.loss_hist = c->cfg.world == 1 ? c->loss_hist : nullptr; f.loss_hist_cap = c->loss_hist_cap;
-    if (!f.step_dev) f.loss_hist = nullptr;
     const bool fuse = params_rw != nullptr && c->L + 5 <= 64;
-    int rc;
-    int64_t adam_from = 0;
-    if (lo == 0 && c->off_epsp >= kBulkFinalizeMin) {
-        // big models: weights and biases as a streaming pass (with Adam), the 64-output finalize only for the tail
-        if ((rc = launch_bulk_finalize(f, c->off_epsp, st))) return rc;
-        f.lo = adam_from = c->off_epsp;
-    }
-    if (!fuse) f.params_rw = nullptr;
-    if ((rc = launch_finalize(f, st)) || params_rw == nullptr || fuse) return rc;
-    return launch_adam(params_rw + adam_from, grads + adam_from, m + adam_from, v + adam_from, c->P - adam_from, lr, 0, step_dev, 1.f, st);
+    const int64_t hi = lo == 0 && c->off_epsp >= kBulkFinalizeMin ? c->off_epsp : 0;
+    return finalize_launches(f, hi, fuse, st);
 }
 
 }  // namespace vaek

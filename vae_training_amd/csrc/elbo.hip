@@ -308,7 +308,8 @@ __global__ __launch_bounds__(256) void bulk_finalize_kernel(const FinalizeArgs a
     float bc1 = 1.f, bc2 = 1.f;
     if (a.params_rw) adam_bias_corrections(a.step_dev[0], bc1, bc2);
     const int S0 = slabs_of(i0);
-    const bool vec = i0 + 3 < hi && slabs_of(i0 + 3) == S0 && a.slab_stride % 4 == 0 &&
+    // all four lanes, not the two ends: a two-element layer (1 -> 1) can sit in the middle of a unit between equal neighbours
+    const bool vec = i0 + 3 < hi && slabs_of(i0 + 1) == S0 && slabs_of(i0 + 2) == S0 && slabs_of(i0 + 3) == S0 && a.slab_stride % 4 == 0 &&
                      (((uintptr_t)a.slabs | (uintptr_t)a.grads | (uintptr_t)a.params_rw | (uintptr_t)a.m | (uintptr_t)a.v) & 15) == 0;
     if (vec) {
         // Adam state first: it does not depend on the sum, and issued here its latency hides under the slab loads

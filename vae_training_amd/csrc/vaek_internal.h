@@ -284,6 +284,8 @@ struct FinalizeArgs {
 int launch_finalize(const FinalizeArgs& a, hipStream_t st);
 // streaming slab sum (+ Adam) of the outputs [0, hi); pair with launch_finalize(lo = hi) for the tail
 int launch_bulk_finalize(const FinalizeArgs& a, int64_t hi, hipStream_t st);
+// api.hip: bulk_finalize over [0, hi) (hi = 0: none), finalize above it (else from a.lo), Adam fused or as its own launch
+int finalize_launches(const FinalizeArgs& a, int64_t hi, bool fuse, hipStream_t st);
 int launch_adam(float* params, const float* grads, float* m, float* v, int64_t n, float lr, int step,
                 const int32_t* step_dev, float grad_scale, hipStream_t st);
 // x_hat = y_lin (+ sigmoid(y_sig)) + z2 * exp(eps/2)
