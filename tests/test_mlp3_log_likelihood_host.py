@@ -36,8 +36,10 @@ def test_abi_surface_of_the_mlp3_log_likelihood():
     assert _lib.SIGNATURES["vaek_mlp3_log_likelihood_replicas"] == _lib.SIGNATURES["vaek_log_likelihood_replicas"]      # one description
     assert _c_args(hdr, "vaek_mlp3_log_likelihood_workspace_bytes") == 5
     assert lib.vaek_mlp3_log_likelihood_max_columns() == 4194304 == 2 ** 22
-    src = open(os.path.join(ROOT, "vae_training_amd", "csrc", "mlp3_loglik.hip")).read()
-    assert "ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)" in src
+    # the description's checks are one text for both calls: linear_loglik.hip's check_log_likelihood, which this entry point goes through
+    csrc = os.path.join(ROOT, "vae_training_amd", "csrc")
+    assert "ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)" in open(os.path.join(csrc, "linear_loglik.hip")).read()
+    assert "check_log_likelihood(who, ctx, params, ll," in open(os.path.join(csrc, "mlp3_loglik.hip")).read()
     assert "mlp3_loglik.hip" in open(os.path.join(ROOT, "vae_training_amd", "csrc", "Makefile")).read()
     # a NULL context is refused before anything is touched, and the message names the entry point
     yes = C.c_int32(7)

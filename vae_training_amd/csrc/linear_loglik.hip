@@ -12,25 +12,19 @@
 //     takes its L normals from Philox blocks k ceil(L / 4) + j of the row's latent stream, so sample 0 is vaek_make_batch's z1.  An
 //     online log-sum-exp carries a running max, sum e^{lw - m}, sum e^{2 (lw - m)} and sum lw in float32, in k order.  Nothing of a
 //     row, a sample or a weight ever exists in HBM;
-//   - the parameters live in the zero-padded LDS image of linear_stats.hip (the same layout, filled the same way; that file's header
-//     says why: broadcast reads, 16 bytes at a time, static register indices, a padded row or column adds 0).  The products are VALU
-//     fmas: with a row per thread the chain stays in registers;
+//   - the parameters live in the zero-padded LDS image of linear_stats.hip (ParamImage of eval_dev.h, one text for both; that file's
+//     header says why: broadcast reads, 16 bytes at a time, static register indices, a padded row or column adds 0).  The products
+//     are VALU fmas: with a row per thread the chain stays in registers;
 //   - the image is loop-invariant, and a compiler that knows it lifts the weights out of the sample loop and spills them: the
 //     compiler barrier at the top of the loop makes every sample read them again;
 //   - the three row sums are float64: a fixed binary tree across the workgroup, then one 4-double partial per (replica, tile) in
 //     the call's workspace.  A SECOND launch of n workgroups adds the tiles in tile order and stores the 4-float record with per-lane
 //     vector stores.  The partials cross a launch boundary: nothing stored in a launch is read back in it, and there is no atomic,
 //     counter or wait.  A record therefore depends on neither n, nor the replica index, nor the run.
+#include "eval_dev.h"
 #include "mfma_geom.h"
-#include "rng_dev.h"
-#include "vaek_internal.h"
 
 namespace vaek {
-
-constexpr int kLogLikMaxRows = 4096;         // rows per call and ...
-constexpr int kLogLikMaxSamples = 1024;      // ... samples per row: they bound one launch on a shared machine -- caps, not tuned values
-constexpr int kLogLikRecord = 4;             // IWAE-K bound, ELBO estimate, effective sample size, eps
-constexpr int kLogLikSums = 3;               // float64 row sums
 
 struct LogLikArgs {
     const float* params; long long state_stride;
@@ -45,6 +39,7 @@ struct LogLikArgs {
     BatchArgs gen;                 // kind, A, dd, did, pad, noise_std, tag = x_tag, D, L; seed / step / pointers are not used
 };
 
+// the finalize launch of this call and of vaek_mlp3_log_likelihood_replicas (loglik_finalize)
 struct LogLikFinalArgs {
     const float* params; long long state_stride;
     const double* part;
@@ -53,17 +48,9 @@ struct LogLikFinalArgs {
     float eps_cli;
 };
 
-// floats of the zero-padded parameter image: linear_stats.hip's SGeom and its fill, restated here (keep the two in step)
-template <int DP, int LP, bool SIG>
-struct LGeom {
-    static constexpr int WE = 0, BE = WE + DP * LP, WD = BE + LP, BD = WD + LP * DP, WS = BD + DP, BS = WS + (SIG ? LP * DP : 0),
-                         SD = BS + (SIG ? DP : 0), LV = SD + LP, N = LV + LP;      // SD: exp(epsilon_p / 2), LV: epsilon_p itself
-};
-
 template <int DP, int LP, bool SIG>
 __global__ __launch_bounds__(256) void linear_loglik_kernel(const LogLikArgs a) {
-    using G = LGeom<DP, LP, SIG>;
-    static_assert(DP % 4 == 0 && LP % 4 == 0, "the image is read 16 bytes at a time");
+    using G = ParamImage<DP, LP, SIG>;
     __shared__ __attribute__((aligned(16))) float W[G::N];
     __shared__ double red[kLogLikSums][256];
     const int t = threadIdx.x;
@@ -72,28 +59,7 @@ __global__ __launch_bounds__(256) void linear_loglik_kernel(const LogLikArgs a) 
     const int D = a.D, L = a.L;
     const float* const p = a.params + r * a.state_stride;
 
-    // ---- the parameter image: zero outside [D] x [L] --------------------------------------------------------------
-    {
-        const int off_be = D * L, off_wd = off_be + L, off_bd = off_wd + L * D, off_ws = off_bd + D, off_bs = off_ws + L * D;
-        for (int i = t; i < DP * LP; i += 256) {
-            const int d = i / LP, l = i % LP;
-            W[G::WE + i] = (d < D && l < L) ? p[d * L + l] : 0.f;
-            const int l2 = i / DP, d2 = i % DP;
-            const bool in = l2 < L && d2 < D;
-            W[G::WD + i] = in ? p[off_wd + l2 * D + d2] : 0.f;
-            if (SIG) W[G::WS + i] = in ? p[off_ws + l2 * D + d2] : 0.f;
-        }
-        for (int i = t; i < LP; i += 256) {
-            const float lv = i < L ? p[a.off_epsp + i] : 0.f;
-            W[G::BE + i] = i < L ? p[off_be + i] : 0.f;
-            W[G::LV + i] = lv;
-            W[G::SD + i] = i < L ? expf(0.5f * lv) : 0.f;                 // e^{lv/2}, networks.py:73
-        }
-        for (int i = t; i < DP; i += 256) {
-            W[G::BD + i] = i < D ? p[off_bd + i] : 0.f;
-            if (SIG) W[G::BS + i] = i < D ? p[off_bs + i] : 0.f;
-        }
-    }
+    G::fill(W, p, D, L, a.off_epsp, t);                                 // the parameter image: zero outside [D] x [L]
     __syncthreads();
 
     const float eps = a.off_eps >= 0 ? p[a.off_eps] * a.eps_cli : a.eps_cli;
@@ -102,7 +68,8 @@ __global__ __launch_bounds__(256) void linear_loglik_kernel(const LogLikArgs a) 
     float res[kLogLikSums] = {0.f, 0.f, 0.f};
 
     if (row < a.rows) {
-        // ---- the row: the caller's, or vaek_make_batch's work item for (row, c0), all c0 ------------------------------------
+        // ---- the row: the caller's, or vaek_make_batch's work item for (row, c0), all c0.  The draw and the encoder product below are
+        // linear_stats.hip's text too: keep the two in step (eval_dev.h says why they are not shared) -------------------------------
         float x[DP];
         if (a.x) {
             const float* const xr = a.x + r * a.x_stride + (long long)row * D;
@@ -111,8 +78,7 @@ __global__ __launch_bounds__(256) void linear_loglik_kernel(const LogLikArgs a) 
         } else {
             BatchArgs gx = a.gen;
             if (gx.A) gx.A += r * a.a_stride;
-            const unsigned long long xs = a.x_seeds[r];
-            const uint2 xkey = make_uint2((unsigned)xs, (unsigned)(xs >> 32));
+            const uint2 xkey = philox_key(a.x_seeds[r]);
             const unsigned xstep = a.x_steps[r];
             float nrm[16];
             dataset_normals(gx, xstep, row, xkey, nrm);
@@ -140,12 +106,11 @@ __global__ __launch_bounds__(256) void linear_loglik_kernel(const LogLikArgs a) 
 
         BatchArgs gz = a.gen;
         gz.tag = a.z_tag;
-        const unsigned long long zs = a.z_seeds[r];
-        const uint2 zkey = make_uint2((unsigned)zs, (unsigned)(zs >> 32));
+        const uint2 zkey = philox_key(a.z_seeds[r]);
         const unsigned zstep = a.z_steps[r];
         const int nlb = (L + 3) >> 2;                                      // Philox blocks of one sample
 
-        float m = -INFINITY, s1 = 0.f, s2 = 0.f, sl = 0.f;                 // running max, sum e^{lw - m}, sum e^{2 (lw - m)}, sum lw
+        OnlineLogSumExp lse;                                               // in k order
         for (int k = 0; k < a.samples; ++k) {
             // the image is loop-invariant, and a compiler that knows it lifts thousands of weights out of the loop and spills them:
             // every sample reads them again (broadcast LDS reads, 16 bytes each)
@@ -191,42 +156,20 @@ __global__ __launch_bounds__(256) void linear_loglik_kernel(const LogLikArgs a) 
                 const float rr = d < D ? xh - x[d] : 0.f;
                 rsq = fmaf(rr, rr, rsq);
             }
-            const float lw = c0 + 0.5f * (qs - rsq * inv_var);
-            // ---- online log-sum-exp, in k order -------------------------------------------------------------------------------------
-            const float mn = fmaxf(m, lw);
-            const float c = expf(m - mn), e = expf(lw - mn);               // first sample: c = e^{-inf} = 0, e = 1
-            s1 = fmaf(s1, c, e);
-            s2 = fmaf(s2, c * c, e * e);
-            sl += lw;
-            m = mn;
+            lse.push(c0 + 0.5f * (qs - rsq * inv_var));
         }
-        const float kf = (float)a.samples;
-        res[0] = m + logf(s1) - logf(kf);
-        res[1] = sl / kf;
-        res[2] = (s1 * s1) / (kf * s2);
+        lse.finish(a.samples, res);
     }
 
     // ---- the tile's sums: a fixed binary tree over the 256 threads, float64 ------------------------------------------
 #pragma unroll
     for (int j = 0; j < kLogLikSums; ++j) red[j][t] = (double)res[j];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int j = 0; j < kLogLikSums; ++j) red[j][t] += red[j][t + s];
-        }
-        __syncthreads();
-    }
-    // ---- the partial: lane t stores double t; the finalize launch reads it ----------------------------------------------
-    if (t < 4) {
-        double v = 0.0;
-        if (t < kLogLikSums) v = red[t][0];
-        a.part[(r * gridDim.x + tile) * 4 + t] = v;
-    }
+    tree_sum256(red, t);
+    store_tile_partial(a.part, r, tile, t, red);
 }
 
 // one workgroup per replica: the tiles' partials in tile order, then the record, lane t storing float t
-__global__ __launch_bounds__(64) void linear_loglik_finalize_kernel(const LogLikFinalArgs a) {
+__global__ __launch_bounds__(64) void loglik_finalize_kernel(const LogLikFinalArgs a) {
     const int t = threadIdx.x;
     const long long r = blockIdx.x;
     if (t >= kLogLikRecord) return;
@@ -245,8 +188,7 @@ __global__ __launch_bounds__(64) void linear_loglik_finalize_kernel(const LogLik
 // takes the smallest that holds it (an EXACT shape of that table is one more padded shape here) ---------------------------------
 typedef void (*LogLikKernel)(const LogLikArgs);
 struct LogLikVariant { int dp, lp, sig; LogLikKernel fn; };
-constexpr int ll_up4(int n) { return (n + 3) & ~3; }
-#define VAEK_LOGLIK_ROW(DP, LP, SIG, EXACT) {ll_up4(DP), ll_up4(LP), SIG, linear_loglik_kernel<ll_up4(DP), ll_up4(LP), (SIG) != 0>},
+#define VAEK_LOGLIK_ROW(DP, LP, SIG, EXACT) {up4(DP), up4(LP), SIG, linear_loglik_kernel<up4(DP), up4(LP), (SIG) != 0>},
 static const LogLikVariant kLogLikVariants[] = {VAEK_MFMA_SHAPES(VAEK_LOGLIK_ROW)};
 #undef VAEK_LOGLIK_ROW
 
@@ -256,15 +198,66 @@ static const LogLikVariant* pick_loglik(const vaek_ctx* c) {
     const vaek_config& cfg = c->cfg;
     if (cfg.dtype != VAEK_F32 || cfg.n_enc_hidden != 0 || cfg.n_dec_hidden != 0) return nullptr;
     if (cfg.sigmoid_decoder && c->D > 28) return nullptr;
-    const LogLikVariant* best = nullptr;
-    for (const auto& v : kLogLikVariants) {
-        if (v.sig != (cfg.sigmoid_decoder ? 1 : 0) || v.dp < c->D || v.lp < c->L) continue;
-        if (!best || v.dp * v.lp < best->dp * best->lp) best = &v;
-    }
-    return best;
+    return pick_smallest_shape(kLogLikVariants, c->D, c->L, cfg.sigmoid_decoder != 0);
 }
 
 static size_t loglik_workspace_bytes(int n, int rows) { return sizeof(double) * 4 * (size_t)n * (size_t)((rows + 255) / 256); }
+
+int check_log_likelihood(const char* who, const vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, bool covered,
+                         const char* needs, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, uint32_t x_tag, uint32_t z_tag,
+                         const void* workspace, int ws_align, const char* ws_bytes_fn) {
+    if (!ctx || !params || !ll) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
+    if (ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)) {
+        set_error("%s: vaek_log_likelihood.struct_size %d != %d (header / library mismatch)", who, ll->struct_size, (int)sizeof(vaek_log_likelihood));
+        return VAEK_ERR_INVALID;
+    }
+    if (!covered) { set_error("%s: %s", who, needs); return VAEK_ERR_INVALID; }
+    if (ll->n < 1 || ll->n > resident_max_replicas()) {
+        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ll->n, resident_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    if (ll->rows < 1 || ll->rows > kLogLikMaxRows) {
+        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kLogLikMaxRows);
+        return VAEK_ERR_INVALID;
+    }
+    if (ll->samples < 1 || ll->samples > kLogLikMaxSamples) {
+        set_error("%s: %d samples, need 1 .. %d (vaek_log_likelihood_max_samples)", who, ll->samples, kLogLikMaxSamples);
+        return VAEK_ERR_INVALID;
+    }
+    const bool explicit_rows = ll->x != nullptr;
+    if (!ll->z_seeds || !ll->z_steps || !ll->out || (!explicit_rows && (!ll->x_seeds || !ll->x_steps))) {
+        set_error("%s: x_seeds, x_steps (drawing mode), z_seeds, z_steps or out is NULL", who);
+        return VAEK_ERR_INVALID;
+    }
+    if (ll->state_stride < ctx->P || ll->out_stride < kLogLikRecord) {
+        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %d (vaek_log_likelihood_record_len)", who,
+                  (long long)ll->state_stride, (long long)ctx->P, (long long)ll->out_stride, kLogLikRecord);
+        return VAEK_ERR_INVALID;
+    }
+    if (!workspace || ((uintptr_t)workspace & (uintptr_t)(ws_align - 1)) != 0) {
+        set_error("%s: workspace is NULL or not %d-byte aligned (%s)", who, ws_align, ws_bytes_fn);
+        return VAEK_ERR_INVALID;
+    }
+    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    if (!explicit_rows) return check_dataset_draw(who, ctx, kind, A, dd, did, pad, ll->a_stride, x_tag);
+    if (ll->x_stride < 0 || (ll->x_stride > 0 && ll->x_stride < (int64_t)ll->rows * ctx->D)) {
+        set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)ll->x_stride, (long long)ll->rows * ctx->D);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int loglik_finalize(const char* label, const vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, const double* part, hipStream_t st) {
+    LogLikFinalArgs f{};
+    f.params = params; f.state_stride = ll->state_stride; f.part = part; f.out = ll->out; f.out_stride = ll->out_stride;
+    f.rows = ll->rows; f.tiles = (ll->rows + 255) / 256; f.off_eps = (int)ctx->off_eps; f.eps_cli = ctx->cfg.eps_cli;
+    {
+        ProfScope ps(label, st);
+        launch_k(ps, loglik_finalize_kernel, dim3((unsigned)ll->n), dim3(64), 0, st, f);
+    }
+    VAEK_HIP_CHECK(hipGetLastError());
+    return VAEK_OK;
+}
 
 }  // namespace vaek
 
@@ -297,62 +290,13 @@ int vaek_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_
                                  int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* workspace, void* stream) {
     const char* who = "vaek_log_likelihood_replicas";
     ProfBind pb(ctx);
-    if (!ctx || !params || !ll) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
-    if (ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)) {
-        set_error("%s: vaek_log_likelihood.struct_size %d != %d (header / library mismatch)", who, ll->struct_size, (int)sizeof(vaek_log_likelihood));
-        return VAEK_ERR_INVALID;
-    }
-    const LogLikVariant* var = pick_loglik(ctx);
-    if (!var) {
-        set_error("%s: needs a float32 linear VAE (no hidden layers) with D, L <= 32, D <= 28 with two decoders (see vaek_supports_log_likelihood)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->n < 1 || ll->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ll->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->rows < 1 || ll->rows > kLogLikMaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kLogLikMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->samples < 1 || ll->samples > kLogLikMaxSamples) {
-        set_error("%s: %d samples, need 1 .. %d (vaek_log_likelihood_max_samples)", who, ll->samples, kLogLikMaxSamples);
-        return VAEK_ERR_INVALID;
-    }
+    const LogLikVariant* var = ctx ? pick_loglik(ctx) : nullptr;
+    if (int rc = check_log_likelihood(who, ctx, params, ll, var != nullptr,
+                                      "needs a float32 linear VAE (no hidden layers) with D, L <= 32, D <= 28 with two decoders (see "
+                                      "vaek_supports_log_likelihood)",
+                                      kind, A, dd, did, pad, x_tag, z_tag, workspace, 8, "vaek_log_likelihood_workspace_bytes"))
+        return rc;
     const bool explicit_rows = ll->x != nullptr;
-    if (!ll->z_seeds || !ll->z_steps || !ll->out || (!explicit_rows && (!ll->x_seeds || !ll->x_steps))) {
-        set_error("%s: x_seeds, x_steps (drawing mode), z_seeds, z_steps or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->state_stride < ctx->P || ll->out_stride < kLogLikRecord) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %d (vaek_log_likelihood_record_len)", who,
-                  (long long)ll->state_stride, (long long)ctx->P, (long long)ll->out_stride, kLogLikRecord);
-        return VAEK_ERR_INVALID;
-    }
-    if (!workspace || ((uintptr_t)workspace & 7) != 0) {
-        set_error("%s: workspace is NULL or not 8-byte aligned (vaek_log_likelihood_workspace_bytes)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
-    if (explicit_rows) {
-        if (ll->x_stride < 0 || (ll->x_stride > 0 && ll->x_stride < (int64_t)ll->rows * ctx->D)) {
-            set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)ll->x_stride, (long long)ll->rows * ctx->D);
-            return VAEK_ERR_INVALID;
-        }
-    } else {
-        if (ll->a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)ll->a_stride); return VAEK_ERR_INVALID; }
-        if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
-        if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
-        if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
-            set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
-            return VAEK_ERR_INVALID;
-        }
-        if (dd + pad + (kind == 1 ? 1 : 0) != ctx->D) {
-            set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
-            return VAEK_ERR_INVALID;
-        }
-        if (x_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
-    }
     const int tiles = (ll->rows + 255) / 256;
     LogLikArgs a{};
     a.params = params; a.state_stride = ll->state_stride;
@@ -362,28 +306,19 @@ int vaek_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_
     a.part = static_cast<double*>(workspace);
     a.rows = ll->rows; a.samples = ll->samples; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
     a.eps_cli = ctx->cfg.eps_cli; a.z_tag = z_tag;
-    a.gen.kind = 2; a.gen.D = ctx->D; a.gen.L = ctx->L; a.gen.rows = ll->rows; a.gen.row0 = 0;
-    if (!explicit_rows) {
+    if (explicit_rows) {
+        fill_draw_args(&a.gen, ctx, ll->rows, 2, nullptr, 0, 0, 0, 0.f, 0);      // nothing is drawn: the sphere's kind, which has no matrix
+    } else {
         a.a_stride = ll->a_stride;
-        a.gen.kind = kind; a.gen.A = kind == 2 ? nullptr : A; a.gen.dd = dd; a.gen.did = did; a.gen.pad = pad;
-        a.gen.noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
-        a.gen.tag = x_tag;
+        fill_draw_args(&a.gen, ctx, ll->rows, kind, A, dd, did, pad, var_added, x_tag);
     }
-    LogLikFinalArgs f{};
-    f.params = params; f.state_stride = ll->state_stride; f.part = a.part; f.out = ll->out; f.out_stride = ll->out_stride;
-    f.rows = ll->rows; f.tiles = tiles; f.off_eps = (int)ctx->off_eps; f.eps_cli = ctx->cfg.eps_cli;
     hipStream_t st = (hipStream_t)stream;
     {
         ProfScope ps("linear_loglik_replicas", st);
         launch_k(ps, var->fn, dim3((unsigned)tiles, (unsigned)ll->n), dim3(256), 0, st, a);
     }
     VAEK_HIP_CHECK(hipGetLastError());
-    {
-        ProfScope ps("linear_loglik_finalize", st);
-        launch_k(ps, linear_loglik_finalize_kernel, dim3((unsigned)ll->n), dim3(64), 0, st, f);
-    }
-    VAEK_HIP_CHECK(hipGetLastError());
-    return VAEK_OK;
+    return loglik_finalize("linear_loglik_finalize", ctx, params, ll, a.part, st);
 }
 
 }  // extern "C"

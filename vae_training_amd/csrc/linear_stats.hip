@@ -22,9 +22,8 @@
 //
 // The kernel reads params, A and the per-replica tables and stores only the records, with per-lane vector stores; it reads nothing
 // back.
+#include "eval_dev.h"
 #include "mfma_geom.h"
-#include "rng_dev.h"
-#include "vaek_internal.h"
 
 namespace vaek {
 
@@ -45,17 +44,9 @@ struct StatsArgs {
     BatchArgs gen;                 // kind, A, dd, did, pad, noise_std, tag = x_tag, D, L; seed / step / pointers are not used
 };
 
-// floats of the zero-padded parameter image (linear_loglik.hip restates this layout and the fill below as LGeom: keep the two in step)
-template <int DP, int LP, bool SIG>
-struct SGeom {
-    static constexpr int WE = 0, BE = WE + DP * LP, WD = BE + LP, BD = WD + LP * DP, WS = BD + DP, BS = WS + (SIG ? LP * DP : 0),
-                         SD = BS + (SIG ? DP : 0), LV = SD + LP, N = LV + LP;      // SD: exp(epsilon_p / 2), LV: epsilon_p itself
-};
-
 template <int DP, int LP, bool SIG>
 __global__ __launch_bounds__(256) void linear_stats_kernel(const StatsArgs a) {
-    using G = SGeom<DP, LP, SIG>;
-    static_assert(DP % 4 == 0 && LP % 4 == 0, "the image is read 16 bytes at a time");
+    using G = ParamImage<DP, LP, SIG>;
     __shared__ __attribute__((aligned(16))) float W[G::N];
     __shared__ double red[kStatsSums][256];
     const int t = threadIdx.x;
@@ -63,36 +54,14 @@ __global__ __launch_bounds__(256) void linear_stats_kernel(const StatsArgs a) {
     const int D = a.D, L = a.L;
     const float* const p = a.params + r * a.state_stride;
 
-    // ---- the parameter image: zero outside [D] x [L] --------------------------------------------------------------
-    {
-        const int off_be = D * L, off_wd = off_be + L, off_bd = off_wd + L * D, off_ws = off_bd + D, off_bs = off_ws + L * D;
-        for (int i = t; i < DP * LP; i += 256) {
-            const int d = i / LP, l = i % LP;
-            W[G::WE + i] = (d < D && l < L) ? p[d * L + l] : 0.f;
-            const int l2 = i / DP, d2 = i % DP;
-            const bool in = l2 < L && d2 < D;
-            W[G::WD + i] = in ? p[off_wd + l2 * D + d2] : 0.f;
-            if (SIG) W[G::WS + i] = in ? p[off_ws + l2 * D + d2] : 0.f;
-        }
-        for (int i = t; i < LP; i += 256) {
-            const float lv = i < L ? p[a.off_epsp + i] : 0.f;
-            W[G::BE + i] = i < L ? p[off_be + i] : 0.f;
-            W[G::LV + i] = lv;
-            W[G::SD + i] = i < L ? expf(0.5f * lv) : 0.f;                 // e^{lv/2}, networks.py:73
-        }
-        for (int i = t; i < DP; i += 256) {
-            W[G::BD + i] = i < D ? p[off_bd + i] : 0.f;
-            if (SIG) W[G::BS + i] = i < D ? p[off_bs + i] : 0.f;
-        }
-    }
+    G::fill(W, p, D, L, a.off_epsp, t);                                 // the parameter image: zero outside [D] x [L]
     __syncthreads();
 
     BatchArgs gx = a.gen;
     if (gx.A) gx.A += r * a.a_stride;
     BatchArgs gz = gx;
     gz.tag = a.z_tag;
-    const unsigned long long xs = a.x_seeds[r], zs = a.z_seeds[r];
-    const uint2 xkey = make_uint2((unsigned)xs, (unsigned)(xs >> 32)), zkey = make_uint2((unsigned)zs, (unsigned)(zs >> 32));
+    const uint2 xkey = philox_key(a.x_seeds[r]), zkey = philox_key(a.z_seeds[r]);
     const unsigned xstep = a.x_steps[r], zstep = a.z_steps[r];
     const float eps = a.off_eps >= 0 ? p[a.off_eps] * a.eps_cli : a.eps_cli;
     const float inv_var = expf(-eps), sigma = expf(0.5f * eps), ssigma = expf(0.5f * a.sample_eps[r]);
@@ -134,7 +103,8 @@ __global__ __launch_bounds__(256) void linear_stats_kernel(const StatsArgs a) {
         // the image is loop-invariant, and a compiler that knows it lifts thousands of weights out of the loop and spills them: every
         // row reads them again (broadcast LDS reads, 16 bytes each)
         asm volatile("" ::: "memory");
-        // ---- the real row: vaek_make_batch's work item for (row, c0), all c0 (columns >= D of the last piece are not part of it) ----
+        // ---- the real row: vaek_make_batch's work item for (row, c0), all c0 (columns >= D of the last piece are not part of it).  This
+        // and the encoder product below are linear_loglik.hip's text too: keep the two in step (eval_dev.h says why they are not shared)
         float x[DP];
         {
             float nrm[16];
@@ -241,14 +211,7 @@ __global__ __launch_bounds__(256) void linear_stats_kernel(const StatsArgs a) {
     // ---- the workgroup's sums: a fixed binary tree over the 256 threads ---------------------------------------------
 #pragma unroll
     for (int k = 0; k < kStatsSums; ++k) red[k][t] = acc[k];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int k = 0; k < kStatsSums; ++k) red[k][t] += red[k][t + s];
-        }
-        __syncthreads();
-    }
+    tree_sum256(red, t);
 
     // ---- the record: lane t stores float t ------------------------------------------------------------------
     if (t < kStatsHead + L) {
@@ -283,19 +246,11 @@ __global__ __launch_bounds__(256) void linear_stats_kernel(const StatsArgs a) {
 // takes the smallest that holds it (an EXACT shape of that table is one more padded shape here) ---------------------------------
 typedef void (*StatsKernel)(const StatsArgs);
 struct StatsVariant { int dp, lp, sig; StatsKernel fn; };
-constexpr int up4(int n) { return (n + 3) & ~3; }
 #define VAEK_STATS_ROW(DP, LP, SIG, EXACT) {up4(DP), up4(LP), SIG, linear_stats_kernel<up4(DP), up4(LP), (SIG) != 0>},
 static const StatsVariant kStatsVariants[] = {VAEK_MFMA_SHAPES(VAEK_STATS_ROW)};
 #undef VAEK_STATS_ROW
 
-static const StatsVariant* pick_stats(const vaek_ctx* c) {
-    const StatsVariant* best = nullptr;
-    for (const auto& v : kStatsVariants) {
-        if (v.sig != (c->cfg.sigmoid_decoder ? 1 : 0) || v.dp < c->D || v.lp < c->L) continue;
-        if (!best || v.dp * v.lp < best->dp * best->lp) best = &v;
-    }
-    return best;
-}
+static const StatsVariant* pick_stats(const vaek_ctx* c) { return pick_smallest_shape(kStatsVariants, c->D, c->L, c->cfg.sigmoid_decoder != 0); }
 
 }  // namespace vaek
 
@@ -346,18 +301,8 @@ int vaek_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_sta
                   (long long)ev->state_stride, (long long)ctx->P, (long long)ev->out_stride, (long long)len);
         return VAEK_ERR_INVALID;
     }
-    if (ev->a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)ev->a_stride); return VAEK_ERR_INVALID; }
-    if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
-    if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
-    if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
-        set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
-        return VAEK_ERR_INVALID;
-    }
-    if (dd + pad + (kind == 1 ? 1 : 0) != ctx->D) {
-        set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
-        return VAEK_ERR_INVALID;
-    }
-    if (x_tag >= 0x40000000u || z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ev->a_stride, x_tag)) return rc;
+    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
     StatsArgs a{};
     a.params = params; a.state_stride = ev->state_stride;
     a.x_seeds = reinterpret_cast<const unsigned long long*>(ev->x_seeds); a.x_steps = ev->x_steps;
@@ -366,9 +311,7 @@ int vaek_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_sta
     a.out = ev->out; a.out_stride = ev->out_stride;
     a.rows = ev->rows; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
     a.eps_cli = ctx->cfg.eps_cli; a.z_tag = z_tag;
-    a.gen.kind = kind; a.gen.A = kind == 2 ? nullptr : A; a.gen.dd = dd; a.gen.did = did; a.gen.pad = pad;
-    a.gen.noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
-    a.gen.rows = ev->rows; a.gen.row0 = 0; a.gen.D = ctx->D; a.gen.L = ctx->L; a.gen.tag = x_tag;
+    fill_draw_args(&a.gen, ctx, ev->rows, kind, A, dd, did, pad, var_added, x_tag);
     hipStream_t st = (hipStream_t)stream;
     {
         ProfScope ps("linear_stats_replicas", st);

@@ -19,9 +19,11 @@
 //      ping-pong images, reduces |dec - x|^2 and the sum over l per column and stores log w into lw[n][rows][K].  Columns past rows K
 //      are computed on clamped indices and not stored.  A column's arithmetic does not depend on its place in the tile or on its
 //      neighbours: MFMA columns are independent, and every per-column reduction is one thread walking that column in a fixed order.
-//   3. mlp3_loglik_rows     grid (ceil(rows / 256), n): a thread owns a row; the online log-sum-exp of linear_loglik.hip over k in k
-//      order (float32, branch-free), the three row values to float64, a fixed binary tree over the tile, one 4-double partial.
-//   4. mlp3_loglik_finalize n workgroups: the tiles in tile order, then the record, lane t storing float t.
+//   3. mlp3_loglik_rows     grid (ceil(rows / 256), n): a thread owns a row; the online log-sum-exp of linear_loglik.hip (eval_dev.h:
+//      one text) over k in k order (float32, branch-free), the three row values to float64, a fixed binary tree over the tile, one
+//      4-double partial.
+//   4. mlp3_loglik_finalize n workgroups: the tiles in tile order, then the record, lane t storing float t (linear_loglik.hip's
+//      loglik_finalize: one kernel for both calls).
 //
 // LDS images for NC >= 32.  An operand read is lane (n, kq) -> element (k0 + kq, 16 cb + n), a dword read whose banks are taken
 // modulo 32 within each 32-lane half (kq 0 | 1, 2 | 3); with a row pitch of NC >= 32 floats both k-rows of a half would share 16
@@ -31,18 +33,13 @@
 //
 // The weights are read one dword per lane and product (16 lanes of a unit block read 64 contiguous bytes), any alignment: there is
 // no stride rule.
-#include "rng_dev.h"
-#include "vaek_internal.h"
+#include "eval_dev.h"
 
 namespace vaek {
 
 using ml_f32x4 = __attribute__((ext_vector_type(4))) float;
 
-constexpr int kMl3MaxRows = 4096;            // as vaek_log_likelihood_max_rows
-constexpr int kMl3MaxSamples = 1024;         // as vaek_log_likelihood_max_samples
 constexpr int kMl3MaxColumns = 1 << 22;      // n * rows * samples: bounds the workspace and the length of a call -- a cap, not a tuned value
-constexpr int kMl3Record = 4;
-constexpr int kMl3Sums = 3;
 constexpr int ML_NT = 256;                   // threads of the chain kernels
 constexpr int ML_W = 256;                    // widest hidden layer
 constexpr int ML_F = 32;                     // widest D / L
@@ -73,14 +70,6 @@ struct Ml3Args {
 };
 
 struct Ml3RowsArgs { const float* lw; double* part; int rows, samples; };
-
-struct Ml3FinalArgs {
-    const float* params; long long state_stride;
-    const double* part;
-    float* out; long long out_stride;
-    int rows, tiles, off_eps;
-    float eps_cli;
-};
 
 // float index of element (k, c) of a [unit][NC] image
 template <int NC>
@@ -200,8 +189,7 @@ __global__ __launch_bounds__(ML_NT) void mlp3_loglik_encode_kernel(const Ml3Args
         if (c0 < D) {
             BatchArgs gx = a.gen;
             if (gx.A) gx.A += r * a.a_stride;
-            const unsigned long long xs = a.x_seeds[r];
-            const uint2 xkey = make_uint2((unsigned)xs, (unsigned)(xs >> 32));
+            const uint2 xkey = philox_key(a.x_seeds[r]);
             const unsigned xstep = a.x_steps[r];
             const int row = min(row0 + c, a.rows - 1);
             float nrm[16], o[4];
@@ -244,8 +232,7 @@ __global__ __launch_bounds__(ML_NT, ML_NC == 32 ? 2 : 1) void mlp3_loglik_sample
     {
         BatchArgs gz = a.gen;
         gz.tag = a.z_tag;
-        const unsigned long long zs = a.z_seeds[r];
-        const uint2 zkey = make_uint2((unsigned)zs, (unsigned)(zs >> 32));
+        const uint2 zkey = philox_key(a.z_seeds[r]);
         const unsigned zstep = a.z_steps[r];
         const float* const mu = a.mu + r * a.rows * L;
         for (int e = t; e < NC * nlb; e += ML_NT) {
@@ -293,69 +280,31 @@ __global__ __launch_bounds__(ML_NT, ML_NC == 32 ? 2 : 1) void mlp3_loglik_sample
 
 // ---- launch 3: per row the online log-sum-exp over k, per tile of 256 rows the float64 sums -----------------------------------------
 __global__ __launch_bounds__(256) void mlp3_loglik_rows_kernel(const Ml3RowsArgs a) {
-    __shared__ double red[kMl3Sums][256];
+    __shared__ double red[kLogLikSums][256];
     const int t = threadIdx.x;
     const int tile = blockIdx.x;
     const long long r = blockIdx.y;
     const int row = tile * 256 + t;
     const int K = a.samples;
-    float res[kMl3Sums] = {0.f, 0.f, 0.f};
+    float res[kLogLikSums] = {0.f, 0.f, 0.f};
     if (row < a.rows) {
         const float* const lwr = a.lw + (r * a.rows + row) * K;
-        float m = -INFINITY, s1 = 0.f, s2 = 0.f, sl = 0.f;                 // running max, sum e^{lw - m}, sum e^{2 (lw - m)}, sum lw
+        OnlineLogSumExp lse;
         for (int k0 = 0; k0 < K; k0 += 8) {
             float v[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) v[i] = lwr[min(k0 + i, K - 1)];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                if (k0 + i < K) {
-                    const float lw = v[i];
-                    const float mn = fmaxf(m, lw);
-                    const float c = expf(m - mn), e = expf(lw - mn);       // first sample: c = e^{-inf} = 0, e = 1
-                    s1 = fmaf(s1, c, e);
-                    s2 = fmaf(s2, c * c, e * e);
-                    sl += lw;
-                    m = mn;
-                }
+                if (k0 + i < K) lse.push(v[i]);
             }
         }
-        const float kf = (float)K;
-        res[0] = m + logf(s1) - logf(kf);
-        res[1] = sl / kf;
-        res[2] = (s1 * s1) / (kf * s2);
+        lse.finish(K, res);
     }
 #pragma unroll
-    for (int j = 0; j < kMl3Sums; ++j) red[j][t] = (double)res[j];
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) {
-#pragma unroll
-            for (int j = 0; j < kMl3Sums; ++j) red[j][t] += red[j][t + s];
-        }
-        __syncthreads();
-    }
-    if (t < 4) {                                 // lane t stores double t; the finalize launch reads it
-        double v = 0.0;
-        if (t < kMl3Sums) v = red[t][0];
-        a.part[(r * gridDim.x + tile) * 4 + t] = v;
-    }
-}
-
-// ---- launch 4: one workgroup per replica: the tiles' partials in tile order, then the record, lane t storing float t ----------------
-__global__ __launch_bounds__(64) void mlp3_loglik_finalize_kernel(const Ml3FinalArgs a) {
-    const int t = threadIdx.x;
-    const long long r = blockIdx.x;
-    if (t >= kMl3Record) return;
-    float v;
-    if (t < kMl3Sums) {
-        double s = 0.0;
-        for (int tile = 0; tile < a.tiles; ++tile) s += a.part[(r * a.tiles + tile) * 4 + t];
-        v = (float)(s / (double)a.rows);
-    } else {
-        v = a.off_eps >= 0 ? a.params[r * a.state_stride + a.off_eps] * a.eps_cli : a.eps_cli;
-    }
-    a.out[r * a.out_stride + t] = v;
+    for (int j = 0; j < kLogLikSums; ++j) red[j][t] = (double)res[j];
+    tree_sum256(red, t);
+    store_tile_partial(a.part, r, tile, t, red);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------
@@ -403,10 +352,10 @@ int vaek_mlp3_log_likelihood_max_columns(void) { return kMl3MaxColumns; }
 int vaek_mlp3_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, int32_t samples, size_t* bytes) {
     const char* who = "vaek_mlp3_log_likelihood_workspace_bytes";
     if (!ctx || !bytes) { set_error("%s: null argument", who); return VAEK_ERR_INVALID; }
-    if (n < 1 || n > resident_max_replicas() || rows < 1 || rows > kMl3MaxRows || samples < 1 || samples > kMl3MaxSamples ||
+    if (n < 1 || n > resident_max_replicas() || rows < 1 || rows > kLogLikMaxRows || samples < 1 || samples > kLogLikMaxSamples ||
         (long long)n * rows * samples > kMl3MaxColumns) {
         set_error("%s: %d replicas of %d rows x %d samples, need 1 .. %d replicas, 1 .. %d rows, 1 .. %d samples and at most %d columns in all", who,
-                  n, rows, samples, resident_max_replicas(), kMl3MaxRows, kMl3MaxSamples, kMl3MaxColumns);
+                  n, rows, samples, resident_max_replicas(), kLogLikMaxRows, kLogLikMaxSamples, kMl3MaxColumns);
         return VAEK_ERR_INVALID;
     }
     *bytes = ml3_workspace(ctx, n, rows, samples).total;
@@ -417,67 +366,18 @@ int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const 
                                       int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* workspace, void* stream) {
     const char* who = "vaek_mlp3_log_likelihood_replicas";
     ProfBind pb(ctx);
-    if (!ctx || !params || !ll) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
-    if (ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)) {
-        set_error("%s: vaek_log_likelihood.struct_size %d != %d (header / library mismatch)", who, ll->struct_size, (int)sizeof(vaek_log_likelihood));
-        return VAEK_ERR_INVALID;
-    }
-    if (!ctx->mlp3_loglik) {
-        set_error("%s: needs a float32 VAE with one decoder and three hidden layers of 64 .. %d units both ways, D, L <= %d (see "
-                  "vaek_supports_mlp3_log_likelihood)", who, ML_W, ML_F);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->n < 1 || ll->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ll->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->rows < 1 || ll->rows > kMl3MaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kMl3MaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->samples < 1 || ll->samples > kMl3MaxSamples) {
-        set_error("%s: %d samples, need 1 .. %d (vaek_log_likelihood_max_samples)", who, ll->samples, kMl3MaxSamples);
-        return VAEK_ERR_INVALID;
-    }
+    char needs[256];
+    snprintf(needs, sizeof(needs), "needs a float32 VAE with one decoder and three hidden layers of 64 .. %d units both ways, D, L <= %d (see "
+             "vaek_supports_mlp3_log_likelihood)", ML_W, ML_F);
+    if (int rc = check_log_likelihood(who, ctx, params, ll, ctx && ctx->mlp3_loglik, needs, kind, A, dd, did, pad, x_tag, z_tag, workspace, 16,
+                                      "vaek_mlp3_log_likelihood_workspace_bytes"))
+        return rc;
     if ((long long)ll->n * ll->rows * ll->samples > kMl3MaxColumns) {
         set_error("%s: %d replicas x %d rows x %d samples = %lld columns, at most %d (vaek_mlp3_log_likelihood_max_columns)", who, ll->n, ll->rows,
                   ll->samples, (long long)ll->n * ll->rows * ll->samples, kMl3MaxColumns);
         return VAEK_ERR_INVALID;
     }
     const bool explicit_rows = ll->x != nullptr;
-    if (!ll->z_seeds || !ll->z_steps || !ll->out || (!explicit_rows && (!ll->x_seeds || !ll->x_steps))) {
-        set_error("%s: x_seeds, x_steps (drawing mode), z_seeds, z_steps or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->state_stride < ctx->P || ll->out_stride < kMl3Record) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %d (vaek_log_likelihood_record_len)", who,
-                  (long long)ll->state_stride, (long long)ctx->P, (long long)ll->out_stride, kMl3Record);
-        return VAEK_ERR_INVALID;
-    }
-    if (!workspace || ((uintptr_t)workspace & 15) != 0) {
-        set_error("%s: workspace is NULL or not 16-byte aligned (vaek_mlp3_log_likelihood_workspace_bytes)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
-    if (explicit_rows) {
-        if (ll->x_stride < 0 || (ll->x_stride > 0 && ll->x_stride < (int64_t)ll->rows * ctx->D)) {
-            set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)ll->x_stride, (long long)ll->rows * ctx->D);
-            return VAEK_ERR_INVALID;
-        }
-    } else {
-        if (ll->a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)ll->a_stride); return VAEK_ERR_INVALID; }
-        if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
-        if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
-        if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
-            set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
-            return VAEK_ERR_INVALID;
-        }
-        if (dd + pad + (kind == 1 ? 1 : 0) != ctx->D) {
-            set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
-            return VAEK_ERR_INVALID;
-        }
-        if (x_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
-    }
     const int n = ll->n, rows = ll->rows, K = ll->samples, tiles = ml3_tiles(rows);
     const Ml3Ws w = ml3_workspace(ctx, n, rows, K);
     char* const ws = static_cast<char*>(workspace);
@@ -491,12 +391,11 @@ int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const 
     a.lw = reinterpret_cast<float*>(ws + w.lw);
     a.rows = rows; a.samples = K; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
     a.eps_cli = ctx->cfg.eps_cli; a.z_tag = z_tag;
-    a.gen.kind = 2; a.gen.D = ctx->D; a.gen.L = ctx->L; a.gen.rows = rows; a.gen.row0 = 0;
-    if (!explicit_rows) {
+    if (explicit_rows) {
+        fill_draw_args(&a.gen, ctx, rows, 2, nullptr, 0, 0, 0, 0.f, 0);          // nothing is drawn: the sphere's kind, which has no matrix
+    } else {
         a.a_stride = ll->a_stride;
-        a.gen.kind = kind; a.gen.A = kind == 2 ? nullptr : A; a.gen.dd = dd; a.gen.did = did; a.gen.pad = pad;
-        a.gen.noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
-        a.gen.tag = x_tag;
+        fill_draw_args(&a.gen, ctx, rows, kind, A, dd, did, pad, var_added, x_tag);
     }
     ml3_net(ctx->enc, &a.net);
     Ml3Args s = a;                               // the sample launch reads the rows the encode launch read or drew
@@ -505,9 +404,6 @@ int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const 
     ml3_net(ctx->dec, &s.net);
     Ml3RowsArgs ra{};
     ra.lw = a.lw; ra.part = reinterpret_cast<double*>(ws); ra.rows = rows; ra.samples = K;
-    Ml3FinalArgs f{};
-    f.params = params; f.state_stride = ll->state_stride; f.part = ra.part; f.out = ll->out; f.out_stride = ll->out_stride;
-    f.rows = rows; f.tiles = tiles; f.off_eps = (int)ctx->off_eps; f.eps_cli = ctx->cfg.eps_cli;
 
     constexpr size_t lds_enc = sizeof(float) * 2 * ML_W * ML_ENC_NC, lds_smp = sizeof(float) * 2 * ML_W * ML_NC;
     static thread_local PerDeviceOnce attr_set;
@@ -531,12 +427,7 @@ int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const 
         launch_k(ps, mlp3_loglik_rows_kernel, dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, st, ra);
     }
     VAEK_HIP_CHECK(hipGetLastError());
-    {
-        ProfScope ps("mlp3_loglik_finalize", st);
-        launch_k(ps, mlp3_loglik_finalize_kernel, dim3((unsigned)n), dim3(64), 0, st, f);
-    }
-    VAEK_HIP_CHECK(hipGetLastError());
-    return VAEK_OK;
+    return loglik_finalize("mlp3_loglik_finalize", ctx, params, ll, ra.part, st);
 }
 
 }  // extern "C"

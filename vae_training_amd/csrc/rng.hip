@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void rng_fill_kernel(float* out_n, unsigned* o
                                                       unsigned step, unsigned tag) {
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;     // one Philox block = 4 outputs
     if (4 * b >= n) return;
-    const uint4 r = philox4x32_10(make_uint4((unsigned)b, (unsigned)(b >> 32), step, tag), make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
+    const uint4 r = philox4x32_10(make_uint4((unsigned)b, (unsigned)(b >> 32), step, tag), philox_key(seed));
     float nv[4];
     normals4(r, nv);
     const unsigned uv[4] = {r.x, r.y, r.z, r.w};
@@ -55,6 +55,31 @@ int make_batch_args(vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int
     a.seed = seed; a.step_dev = step_dev; a.step_host = step_host; a.tag = tag; a.counter = counter; a.which = which;
     *out = a;
     return VAEK_OK;
+}
+
+// ---- the in-kernel draw of the evaluation calls (vaek_stats_event_replicas and the two log-likelihood calls) -------------------
+int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                       int64_t a_stride, uint32_t x_tag) {
+    if (a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)a_stride); return VAEK_ERR_INVALID; }
+    if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
+    if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
+    if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
+        set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
+        return VAEK_ERR_INVALID;
+    }
+    if (dd + pad + (kind == 1 ? 1 : 0) != ctx->D) {
+        set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
+        return VAEK_ERR_INVALID;
+    }
+    if (x_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    return VAEK_OK;
+}
+
+void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                    float var_added, uint32_t x_tag) {
+    g->kind = kind; g->A = kind == 2 ? nullptr : A; g->dd = dd; g->did = did; g->pad = pad;
+    g->noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
+    g->rows = rows; g->row0 = 0; g->D = ctx->D; g->L = ctx->L; g->tag = x_tag;
 }
 
 int make_batch_launch(vaek_ctx* ctx, const BatchArgs& a, hipStream_t st) {

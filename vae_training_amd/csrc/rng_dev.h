@@ -32,6 +32,9 @@ __device__ __forceinline__ void normals4(uint4 b, float (&n)[4]) {
     n[2] = rb * __builtin_amdgcn_cosf(tb); n[3] = rb * __builtin_amdgcn_sinf(tb);
 }
 
+// a 64-bit seed as the Philox key
+__device__ __forceinline__ uint2 philox_key(unsigned long long seed) { return make_uint2((unsigned)seed, (unsigned)(seed >> 32)); }
+
 struct NormalStream {           // sequential normals of one row
     uint2 key; unsigned row, step, tag, q; int have; float buf[4];
     __device__ __forceinline__ float next() {
@@ -102,7 +105,7 @@ __device__ __forceinline__ void latent_block(const BatchArgs& a, unsigned step, 
 // consecutive lanes store consecutive 16-byte pieces of z1 / z2 -- the 11.5 MB of a 65 536-row batch
 // leave as coalesced stores instead of 44 scattered dwords per thread.
 __device__ __forceinline__ void make_batch_items(const BatchArgs& a, unsigned step, long long item) {
-    const uint2 key = make_uint2((unsigned)a.seed, (unsigned)(a.seed >> 32));
+    const uint2 key = philox_key(a.seed);
     const int nxb = (a.D + 3) / 4;
     const long long nx = a.x ? (long long)a.rows * nxb : 0;
     if (item < nx) {

@@ -69,6 +69,51 @@ def _trajectory_view(ring, every, first_step, last_step, P):
     return torch.tensor([i * every for i in idx], dtype=torch.int64), rec[:, :P], rec[:, P:2 * P + 4]
 
 
+def _wrap_signed(value, bits):
+    """`value` modulo 2^bits as the signed integer of that width: how a seed (64) or an RNG step (32) goes into an int64 / int32 tensor."""
+    value &= (1 << bits) - 1
+    return value - (1 << bits) if value >> (bits - 1) else value
+
+
+def _replica_setup(self, vae_models, name, noun, draws, verb, cap, signature, covered):
+    """What the constructors of the replica classes share.  Sets on `self`: ms, eng, specs (device_spec() of every model), kind, dd,
+    did, pad, var, A ([R, a_stride] stack of the dataset matrices, or None), a_stride and R, after refusing -- in this order -- no
+    models, a -dd / -did the device draw does not support, world > 1, what `covered()` refuses (called with eng and kind set), more
+    than `cap` models (an attribute of the engine; "vaek_" + cap is its ABI name) and a model whose `signature(m, spec)` differs
+    from model 0's.  `name` is the class in the messages, one `noun` ("launch", "call", "step") `verb`s ("trains", "evaluates") the
+    replicas, and `draws` ("batches", "rows") is what the generator draws for it."""
+    ms = list(vae_models)
+    if not ms:
+        raise RuntimeError(f"{name}: no models")
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    self.ms = ms
+    m0 = ms[0]
+    self.eng = m0.model.module.engine(m0.batch_size, m0.optimizer.global_batch)
+    self.specs = specs = [m.dataset.device_spec() for m in ms]
+    self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
+    if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
+        raise RuntimeError(f"{name} draws its {draws} with libvaek's Philox generator, which supports -dd / -did <= "
+                           f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
+    if self.eng.world > 1:
+        raise RuntimeError(f"{name}: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
+    covered()
+    R = len(ms)
+    if R > getattr(self.eng, cap):
+        raise RuntimeError(f"{name}: {R} models, at most {getattr(self.eng, cap)} fit one {noun} (vaek_{cap})")
+    want = signature(m0, specs[0])
+    for r, (m, sp) in enumerate(zip(ms, specs)):
+        got = signature(m, sp)
+        if got != want:
+            raise RuntimeError(f"{name}: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
+                               f"{want}): one {noun} {verb} replicas of ONE shape")
+    self.R = R
+    if specs[0][1] is None:
+        self.A, self.a_stride = None, 0
+    else:
+        self.A = torch.stack([sp[1].reshape(-1).to(device=self.eng.device, dtype=torch.float32) for sp in specs]).contiguous()
+        self.a_stride = self.A.shape[1]
+
+
 # What GraphLoop(resident=None) resolves to where the engine supports the resident loop and the model has no moments path.  The gate
 # is tools/time_resident.py: True only once the resident loop's slowest repeat has beaten the hipGraph loop's fastest on all seven
 # shapes.  That table has NOT been measured yet (DESIGN 3.8), so the default is off: resident=True asks for the loop explicitly.
@@ -280,48 +325,21 @@ class ReplicaLoop:
     One workgroup per model and no cross-workgroup state: nothing to wait for, check() polls nothing."""
 
     def __init__(self, vae_models, loss_capacity=None, trajectory_every=None, trajectory_capacity=None):
-        ms = list(vae_models)
-        if not ms:
-            raise RuntimeError("ReplicaLoop: no models")
-        from .datasets import DEVICE_DRAW_MAX_DIM
-        self.ms = ms
-        m0 = ms[0]
+        def covered():
+            if not self.eng.supports_train_loop_gen(self.kind):
+                raise RuntimeError("ReplicaLoop: vaek_train_loop_gen does not cover this model / dataset (it needs a float32 linear VAE with "
+                                   "one or two decoders, D, L <= 32 and a batch of at most 256 rows)")
+        _replica_setup(self, vae_models, "ReplicaLoop", "launch", "batches", "trains", "train_loop_max_replicas", self._signature, covered)
+        ms, R, m0 = self.ms, self.R, self.ms[0]
         self.B = m0.batch_size
-        self.eng = m0.model.module.engine(self.B, m0.optimizer.global_batch)
-        specs = [m.dataset.device_spec() for m in ms]
-        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
-        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
-            raise RuntimeError(f"ReplicaLoop draws its batches with libvaek's Philox generator, which supports -dd / -did <= "
-                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
-        if self.eng.world > 1:
-            raise RuntimeError("ReplicaLoop: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
-        if not self.eng.supports_train_loop_gen(self.kind):
-            raise RuntimeError("ReplicaLoop: vaek_train_loop_gen does not cover this model / dataset (it needs a float32 linear VAE with "
-                               "one or two decoders, D, L <= 32 and a batch of at most 256 rows)")
-        R = len(ms)
-        if R > self.eng.train_loop_max_replicas:
-            raise RuntimeError(f"ReplicaLoop: {R} models, at most {self.eng.train_loop_max_replicas} fit one launch "
-                               "(vaek_train_loop_max_replicas)")
-        want = self._signature(m0, specs[0])
-        for r, (m, sp) in enumerate(zip(ms, specs)):
-            got = self._signature(m, sp)
-            if got != want:
-                raise RuntimeError(f"ReplicaLoop: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
-                                   f"{want}): one launch trains replicas of ONE shape")
-        self.R = R
         dev = self.eng.device
         P, GL = m0.model.flat.numel(), m0.optimizer.state.grads.numel()
         f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)
         self.params, self.m, self.v, self.grads = f32(R, P), f32(R, P), f32(R, P), f32(R, GL)
         self.step_dev = torch.zeros(R, dtype=torch.int32, device=dev)
         seeds = [(m.dataset.key[0] ^ m.dataset.key[1] ^ m.key[1]) & (2 ** 64 - 1) for m in ms]       # GraphLoop's, model by model
-        self.seeds = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device=dev)
+        self.seeds = torch.tensor([_wrap_signed(s, 64) for s in seeds], dtype=torch.int64, device=dev)
         self.lrs = torch.tensor([float(m.optimizer.optimizer_def.learning_rate) for m in ms], dtype=torch.float32, device=dev)
-        if specs[0][1] is None:
-            self.A, self.a_stride = None, 0
-        else:
-            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
-            self.a_stride = self.A.shape[1]
         if loss_capacity is None:             # every step of the longest schedule among the models
             loss_capacity = max(int(getattr(m, "num_batches", 0) or 0) for m in ms) or (1 << 16)
         self.rings = f32(R, int(loss_capacity))
@@ -420,66 +438,40 @@ class ReplicaStats:
     model, compute_stats' keys in its order; the values are host tensors (nothing to read back when they are printed)."""
 
     def __init__(self, vae_models, rows=None):
-        ms = list(vae_models)
-        if not ms:
-            raise RuntimeError("ReplicaStats: no models")
-        from .datasets import DEVICE_DRAW_MAX_DIM, SCORE_KEYS
-        self.ms = ms
-        m0 = ms[0]
-        self.eng = m0.model.module.engine(m0.batch_size, m0.optimizer.global_batch)
-        specs = [m.dataset.device_spec() for m in ms]
-        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
-        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
-            raise RuntimeError(f"ReplicaStats draws its batches with libvaek's Philox generator, which supports -dd / -did <= "
-                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
-        if self.eng.world > 1:
-            raise RuntimeError("ReplicaStats: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
-        if not self.eng.supports_stats_event(self.kind):
-            raise RuntimeError("ReplicaStats: vaek_stats_event_replicas does not cover this model / dataset (it needs what the resident loop "
-                               "needs: a float32 linear VAE with one or two decoders, D, L <= 32 and a train batch of at most 256 rows)")
-        R = len(ms)
-        if R > self.eng.train_loop_max_replicas:
-            raise RuntimeError(f"ReplicaStats: {R} models, at most {self.eng.train_loop_max_replicas} fit one launch "
-                               "(vaek_train_loop_max_replicas)")
-        want = ReplicaLoop._signature(m0, specs[0])
-        for r, (m, sp) in enumerate(zip(ms, specs)):
-            got = ReplicaLoop._signature(m, sp)
-            if got != want:
-                raise RuntimeError(f"ReplicaStats: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
-                                   f"{want}): one launch evaluates replicas of ONE shape")
+        from .datasets import SCORE_KEYS
+
+        def covered():
+            if not self.eng.supports_stats_event(self.kind):
+                raise RuntimeError("ReplicaStats: vaek_stats_event_replicas does not cover this model / dataset (it needs what the resident "
+                                   "loop needs: a float32 linear VAE with one or two decoders, D, L <= 32 and a train batch of at most 256 rows)")
+        _replica_setup(self, vae_models, "ReplicaStats", "launch", "batches", "evaluates", "train_loop_max_replicas", ReplicaLoop._signature,
+                       covered)
+        R, m0 = self.R, self.ms[0]
         self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
         if not 1 <= self.rows <= self.eng.stats_event_max_rows:
             raise RuntimeError(f"ReplicaStats: {self.rows} rows per event, need 1 .. {self.eng.stats_event_max_rows} (vaek_stats_event_max_rows)")
-        self.R = R
         self.score_keys = SCORE_KEYS[self.kind]
         dev = self.eng.device
         self.L = self.eng.L
         self.record_len = self.eng.stats_record_len
         self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
         self.out = torch.zeros(R, self.record_len, dtype=torch.float32, device=dev)
-        if specs[0][1] is None:
-            self.A, self.a_stride = None, 0
-        else:
-            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
-            self.a_stride = self.A.shape[1]
 
     def event(self):
         """One stats event of every model: [stats dict of model 0, ...]."""
         from . import random as vrandom
         dev = self.eng.device
-        i64 = lambda s: s - 2 ** 64 if s >= 2 ** 63 else s
-        i32 = lambda s: s - 2 ** 32 if s >= 2 ** 31 else s
         x_seeds, x_steps, z_seeds, z_steps, eps_in = [], [], [], [], []
         for r, m in enumerate(self.ms):
             self.params[r].copy_(m.model.flat)
             key, m.key = vrandom.split(m.key)                                    # compute_stats
             ds = m.dataset
             ds._draws = getattr(ds, "_draws", 0) + 1                              # _device_batch: seed, step, tag 1
-            x_seeds.append(i64((ds.key[0] ^ ds.key[1]) & (2 ** 64 - 1)))
-            x_steps.append(i32(ds._draws & (2 ** 32 - 1)))
+            x_seeds.append(_wrap_signed(ds.key[0] ^ ds.key[1], 64))
+            x_steps.append(_wrap_signed(ds._draws, 32))
             m._latent_draws = getattr(m, "_latent_draws", 0) + 1                   # _latent_pair: seed, step, tag 2
-            z_seeds.append(i64((key[0] ^ key[1]) & (2 ** 64 - 1)))
-            z_steps.append(i32(m._latent_draws & (2 ** 32 - 1)))
+            z_seeds.append(_wrap_signed(key[0] ^ key[1], 64))
+            z_steps.append(_wrap_signed(m._latent_draws, 32))
             eps_in.append(m.current_epsilon)                                      # sample_batch: the PREVIOUS event's eps
         t64 = lambda v: torch.tensor(v, dtype=torch.int64).to(dev)
         t32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)
@@ -531,31 +523,8 @@ class ReplicaLogLik:
     NAME = "ReplicaLogLik"             # ReplicaLogLikMlp3 overrides the name and the four methods below __init__
 
     def __init__(self, vae_models, samples, rows=None):
-        ms = list(vae_models)
-        if not ms:
-            raise RuntimeError(f"{self.NAME}: no models")
-        from .datasets import DEVICE_DRAW_MAX_DIM
-        self.ms = ms
-        m0 = ms[0]
-        self.eng = m0.model.module.engine(m0.batch_size, m0.optimizer.global_batch)
-        specs = [m.dataset.device_spec() for m in ms]
-        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
-        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
-            raise RuntimeError(f"{self.NAME} draws its rows with libvaek's Philox generator, which supports -dd / -did <= "
-                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
-        if self.eng.world > 1:
-            raise RuntimeError(f"{self.NAME}: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
-        self._check_covered()
-        R = len(ms)
-        if R > self.eng.train_loop_max_replicas:
-            raise RuntimeError(f"{self.NAME}: {R} models, at most {self.eng.train_loop_max_replicas} fit one call "
-                               "(vaek_train_loop_max_replicas)")
-        want = self._shape(m0, specs[0])
-        for r, (m, sp) in enumerate(zip(ms, specs)):
-            got = self._shape(m, sp)
-            if got != want:
-                raise RuntimeError(f"{self.NAME}: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
-                                   f"{want}): one call evaluates replicas of ONE shape")
+        _replica_setup(self, vae_models, self.NAME, "call", "rows", "evaluates", "train_loop_max_replicas", self._shape, self._check_covered)
+        R, m0 = self.R, self.ms[0]
         self.samples = int(samples)
         if not 1 <= self.samples <= self.eng.log_likelihood_max_samples:
             raise RuntimeError(f"{self.NAME}: {self.samples} samples per row, need 1 .. {self.eng.log_likelihood_max_samples} "
@@ -564,17 +533,11 @@ class ReplicaLogLik:
         if not 1 <= self.rows <= self.eng.log_likelihood_max_rows:
             raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 1 .. {self.eng.log_likelihood_max_rows} "
                                "(vaek_log_likelihood_max_rows)")
-        self.R = R
         self._check_size()
         dev = self.eng.device
         self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
         self.out = torch.zeros(R, self.eng.log_likelihood_record_len, dtype=torch.float32, device=dev)
         self.workspace = torch.empty(max(self._workspace_bytes(), 8), dtype=torch.uint8, device=dev)
-        if specs[0][1] is None:
-            self.A, self.a_stride = None, 0
-        else:
-            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
-            self.a_stride = self.A.shape[1]
 
     def _check_covered(self):
         if not self.eng.supports_log_likelihood(self.kind):
@@ -606,10 +569,8 @@ class ReplicaLogLik:
             self.params[r].copy_(m.model.flat)
             m._loglik_draws = getattr(m, "_loglik_draws", 0) + 1
             ds = m.dataset
-            s = (ds.key[0] ^ ds.key[1]) & (2 ** 64 - 1)
-            t = m._loglik_draws & (2 ** 32 - 1)
-            seeds.append(s - 2 ** 64 if s >= 2 ** 63 else s)
-            steps.append(t - 2 ** 32 if t >= 2 ** 31 else t)
+            seeds.append(_wrap_signed(ds.key[0] ^ ds.key[1], 64))
+            steps.append(_wrap_signed(m._loglik_draws, 32))
         seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
         steps = torch.tensor(steps, dtype=torch.int32).to(dev)
         self._call(self.params, self.rows, self.samples, seeds, steps, self.out, self.workspace, kind=self.kind,
@@ -670,35 +631,14 @@ class ReplicaGraphLoop:
     only.  Neither launch waits for anything: check() polls nothing."""
 
     def __init__(self, vae_models, steps_per_graph=200, loss_capacity=None):
-        ms = list(vae_models)
-        if not ms:
-            raise RuntimeError("ReplicaGraphLoop: no models")
-        from .datasets import DEVICE_DRAW_MAX_DIM
-        self.ms = ms
-        m0 = ms[0]
+        def covered():
+            if not self.eng.supports_train_step_replicas():
+                raise RuntimeError("ReplicaGraphLoop: vaek_train_step_gen_replicas does not cover this model (it needs the \"mlp3\" train step: "
+                                   "float32, three hidden layers of 64 .. 256 units in encoder and decoder, D, L <= 32, a batch of at most 128 rows)")
+        _replica_setup(self, vae_models, "ReplicaGraphLoop", "step", "batches", "trains", "train_step_max_replicas", ReplicaLoop._signature,
+                       covered)
+        ms, R, m0 = self.ms, self.R, self.ms[0]
         self.B = m0.batch_size
-        self.eng = m0.model.module.engine(self.B, m0.optimizer.global_batch)
-        specs = [m.dataset.device_spec() for m in ms]
-        self.kind, _, self.dd, self.did, self.pad, self.var = specs[0]
-        if self.dd > DEVICE_DRAW_MAX_DIM or self.did > DEVICE_DRAW_MAX_DIM:
-            raise RuntimeError(f"ReplicaGraphLoop draws its batches with libvaek's Philox generator, which supports -dd / -did <= "
-                               f"{DEVICE_DRAW_MAX_DIM} (got {self.dd} / {self.did})")
-        if self.eng.world > 1:
-            raise RuntimeError("ReplicaGraphLoop: data parallelism (world > 1) is not supported: the replicas are independent models on one GPU")
-        if not self.eng.supports_train_step_replicas():
-            raise RuntimeError("ReplicaGraphLoop: vaek_train_step_gen_replicas does not cover this model (it needs the \"mlp3\" train step: "
-                               "float32, three hidden layers of 64 .. 256 units in encoder and decoder, D, L <= 32, a batch of at most 128 rows)")
-        R = len(ms)
-        if R > self.eng.train_step_max_replicas:
-            raise RuntimeError(f"ReplicaGraphLoop: {R} models, at most {self.eng.train_step_max_replicas} fit one step "
-                               "(vaek_train_step_max_replicas)")
-        want = ReplicaLoop._signature(m0, specs[0])
-        for r, (m, sp) in enumerate(zip(ms, specs)):
-            got = ReplicaLoop._signature(m, sp)
-            if got != want:
-                raise RuntimeError(f"ReplicaGraphLoop: model {r} differs from model 0 in shape, architecture or dataset kind ({got} against "
-                                   f"{want}): one step trains replicas of ONE shape")
-        self.R = R
         self.G = int(steps_per_graph) + int(steps_per_graph) % 2      # two batch buffers: a replay starts on the parity it was captured on
         dev = self.eng.device
         D, L = self.eng.D, self.eng.L
@@ -708,13 +648,8 @@ class ReplicaGraphLoop:
         self.params, self.m, self.v, self.grads = f32(R, self.stride), f32(R, self.stride), f32(R, self.stride), f32(R, GL)
         self.step_dev = torch.zeros(R, dtype=torch.int32, device=dev)
         self.seed_list = [(m.dataset.key[0] ^ m.dataset.key[1] ^ m.key[1]) & (2 ** 64 - 1) for m in ms]      # GraphLoop's, model by model
-        self.seeds = torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in self.seed_list], dtype=torch.int64, device=dev)
+        self.seeds = torch.tensor([_wrap_signed(s, 64) for s in self.seed_list], dtype=torch.int64, device=dev)
         self.lrs = torch.tensor([float(m.optimizer.optimizer_def.learning_rate) for m in ms], dtype=torch.float32, device=dev)
-        if specs[0][1] is None:
-            self.A, self.a_stride = None, 0
-        else:
-            self.A = torch.stack([sp[1].reshape(-1).to(device=dev, dtype=torch.float32) for sp in specs]).contiguous()
-            self.a_stride = self.A.shape[1]
         if loss_capacity is None:             # every step of the longest schedule among the models
             loss_capacity = max(int(getattr(m, "num_batches", 0) or 0) for m in ms) or (1 << 16)
         self.rings = f32(R, int(loss_capacity))
