@@ -537,6 +537,38 @@ int vaek_mlp3_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int
 int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, int32_t kind, const float* A,
                                       int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
                                       void* workspace, void* stream);
+/* The STATS EVENT of N THREE-HIDDEN-LAYER MLP VAEs of the context's shape in one call (csrc/mlp3_stats.hip): vaek_stats_event_replicas
+ * for the models of vaek_supports_mlp3_log_likelihood.  The description struct (vaek_stats_event), the draws, what is evaluated, the
+ * score terms and the RECORD of vaek_stats_record_len = 8 + L floats (per-lane vector stores; floats between two records are not
+ * touched) are exactly that call's; Encoder and Decoder are the four-Dense relu stacks:
+ *   mu = Encoder(x),  samples = mu + exp(epsilon_p / 2) z1,  x_hat = Decoder(samples) + z2 exp(eps / 2),
+ *   fake = Decoder(z1) + z2 exp(sample_eps[r] / 2).
+ * TWO launches per call whatever n is (profile labels mlp3_stats_tile, mlp3_stats_finalize): a workgroup per tile of 32 rows of a
+ * replica draws the rows and latents (the bits vaek_make_batch writes under (x_seeds[r], x_steps[r], x_tag) and (z_seeds[r],
+ * z_steps[r], z_tag), row0 = 0), runs the encoder and then the decoder ONCE on 64 columns (samples | z1) through matrix-core products
+ * (v_mfma_f32_16x16x4_f32, exact f32), evaluates each row in float32 and adds the seven row values in float64 through a binary tree
+ * over the tile; the second launch adds the tiles in tile order and stores the records.  Nothing stored in a launch is read back in
+ * it; no atomic, counter, wait or status word.  A row's arithmetic does not depend on its place in a tile, so replica r's record is
+ * BITWISE what a call with n = 1 on its slices leaves, two runs are bitwise equal, and the record does not depend on ctx.batch or
+ * state_stride.  It agrees with the float64 evaluation on the same draws and with the host path (vaek_make_batch, vaek_loss_eval,
+ * vaek_forward(sampling), score_batch) within the ELBO contract: [0] .. [2] within 1e-5 of |loss|, [3] within 1e-6, a score within
+ * 1e-5 of its own value, epsilon_p bitwise.
+ * rows is 1 .. vaek_stats_event_max_rows() = 4096, n 1 .. vaek_train_loop_max_replicas().  `workspace`: device memory of
+ * vaek_mlp3_stats_event_workspace_bytes(ctx, n, rows) bytes, 16-byte aligned, the call's own, no need to clear; it holds the tile
+ * partials only.  The weights are read one dword at a time: state_stride has no alignment rule.  Asynchronous on `stream`, allocates
+ * nothing, does not synchronise, capturable into a hipGraph.
+ * vaek_supports_mlp3_stats_event: vaek_supports_mlp3_log_likelihood's predicate (decided once in vaek_ctx_create): float32, one
+ * decoder, exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32, kind 0 .. 2 -- whatever
+ * ctx.batch, world and force_generic are: the call reads parameters only.  vaek_supports_stats_event and vaek_stats_event_replicas keep
+ * refusing these contexts.
+ * VAEK_ERR_INVALID (message names vaek_mlp3_stats_event_replicas, nothing touched): the list of vaek_stats_event_replicas (with
+ * "unsupported context" read as above), plus a NULL or misaligned workspace.  vaek_mlp3_stats_event_workspace_bytes refuses n or rows
+ * outside those ranges (checked before the context: they are no context's) and leaves *bytes alone. */
+int vaek_supports_mlp3_stats_event(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_mlp3_stats_event_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes);
+int vaek_mlp3_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_stats_event* ev, int32_t kind, const float* A,
+                                   int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
+                                   void* workspace, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

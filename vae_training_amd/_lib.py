@@ -153,6 +153,10 @@ SIGNATURES = {
     "vaek_mlp3_log_likelihood_workspace_bytes": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(C.c_size_t)]),
     "vaek_mlp3_log_likelihood_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekLogLikelihood), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
                                                     C.c_uint32, _vp, _vp]),
+    "vaek_supports_mlp3_stats_event": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_mlp3_stats_event_workspace_bytes": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "vaek_mlp3_stats_event_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekStatsEvent), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32,
+                                                 _vp, _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

@@ -273,6 +273,14 @@ class Engine:
         r's at A + r * a_stride floats (0: shared), out: float32 [n, out_stride >= stats_record_len] -- all device tensors; n and
         the strides default to the tensors' shapes.  Record r lands in out[r, :stats_record_len]: loss, mean Dkl, mean mse, eps, the
         score values in score_batch's order, 0, 0, epsilon_p.  Asynchronous; capturable."""
+        ev = self._stats_event_desc(params, rows, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out, a_stride, n, state_stride, out_stride,
+                                    struct_size)
+        _lib.check(self.lib.vaek_stats_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                      float(var_added), int(x_tag), int(z_tag), _stream()))
+
+    @staticmethod
+    def _stats_event_desc(params, rows, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out, a_stride, n, state_stride, out_stride, struct_size):
+        """The vaek_stats_event description both stats-event calls take, from tensors; strides default to the tensors' shapes."""
         ev = _lib.VaekStatsEvent()
         ev.struct_size = C.sizeof(_lib.VaekStatsEvent) if struct_size is None else int(struct_size)
         ev.n = int(params.shape[0] if n is None else n)
@@ -287,8 +295,32 @@ class Engine:
         ev.a_stride = int(a_stride)
         ev.out = _ptr(out)
         ev.out_stride = int((0 if out is None else out.shape[-1]) if out_stride is None else out_stride)
-        _lib.check(self.lib.vaek_stats_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
-                                                      float(var_added), int(x_tag), int(z_tag), _stream()))
+        return ev
+
+    def supports_mlp3_stats_event(self, kind):
+        """True where mlp3_stats_event_replicas covers this engine and dataset kind: exactly where supports_mlp3_log_likelihood does --
+        float32, one decoder, exactly three hidden layers of 64 .. 256 units both ways, D, L <= 32, whatever the engine's batch, world
+        and force_generic are (vaek_supports_mlp3_stats_event)."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_mlp3_stats_event(self.h, int(kind), C.byref(f)))
+        return bool(f.value)
+
+    def mlp3_stats_event_workspace(self, n, rows):
+        """Bytes of the workspace mlp3_stats_event_replicas needs (its own buffer, 16-byte aligned, not self.workspace)."""
+        b = C.c_size_t()
+        _lib.check(self.lib.vaek_mlp3_stats_event_workspace_bytes(self.h, int(n), int(rows), C.byref(b)))
+        return int(b.value)
+
+    def mlp3_stats_event_replicas(self, params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
+                                  workspace, a_stride=0, x_tag=1, z_tag=2, n=None, state_stride=None, out_stride=None, struct_size=None):
+        """stats_event_replicas for three-hidden-layer MLP VAEs (vaek_mlp3_stats_event_replicas): the same draws, record and arguments,
+        with the relu stacks as Encoder and Decoder; workspace: uint8 of mlp3_stats_event_workspace(n, rows) bytes.  Two launches
+        whatever n is.  Asynchronous; capturable."""
+        ev = self._stats_event_desc(params, rows, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out, a_stride, n, state_stride, out_stride,
+                                    struct_size)
+        wp = None if workspace is None else C.c_void_p(workspace if isinstance(workspace, int) else workspace.data_ptr())
+        _lib.check(self.lib.vaek_mlp3_stats_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                           float(var_added), int(x_tag), int(z_tag), wp, _stream()))
 
     def supports_log_likelihood(self, kind):
         """True where log_likelihood_replicas covers this engine and dataset kind: a float32 linear VAE with one or two decoders, D, L <= 32

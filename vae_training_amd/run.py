@@ -70,7 +70,14 @@ def build_parser():
                    help="with --sweep_dataset_seeds on models the resident loop covers: the stats event at every n_print step is ONE launch "
                         "for all models (trainer.ReplicaStats, vaek_stats_event_replicas) instead of one compute_stats() per model.  The "
                         "same draws, the same host RNG bookkeeping, the same keys in losses.npz.  Refused before any step without "
-                        "--sweep_dataset_seeds and on a sweep of three-hidden-layer MLP VAEs (their events stay per model)")
+                        "--sweep_dataset_seeds and on a sweep of three-hidden-layer MLP VAEs (their fused event is --mlp_fused_stats)")
+    p.add_argument("--mlp_fused_stats", dest="mlp_fused_stats", action="store_true",
+                   help="--fused_stats for a sweep of three-hidden-layer MLP VAEs (trainer.ReplicaStatsMlp3, "
+                        "vaek_mlp3_stats_event_replicas): with --sweep_dataset_seeds on models the \"mlp3\" train step covers, the stats "
+                        "event at every n_print step is ONE call (two launches) for all models instead of one compute_stats() per model.  "
+                        "The same draws, the same host RNG bookkeeping, the same keys in losses.npz; combines with "
+                        "--mlp_log_likelihood_samples.  Refused before any step, with the step path, without --sweep_dataset_seeds, "
+                        "on a sweep the resident loop takes (use --fused_stats) and with --fused_stats")
     p.add_argument("--log_likelihood_samples", dest="log_likelihood_samples", type=_positive_int, default=None, metavar="K",
                    help="at every n_print step also evaluate the importance-weighted log-likelihood of the model(s) on K posterior samples "
                         "per row of a print batch (trainer.ReplicaLogLik, vaek_log_likelihood_replicas): losses.npz gains a non-empty "
@@ -238,6 +245,33 @@ def check_fused_stats_args(args):
         raise RuntimeError(f"--fused_stats needs {FUSED_STATS_NEEDS}; a single model's stats event is compute_stats()")
 
 
+MLP_FUSED_STATS_NEEDS = ("--sweep_dataset_seeds on three-hidden-layer MLP VAEs (trainer.ReplicaGraphLoop, the \"mlp3\" train step): the "
+                         "fused event evaluates the models of a sweep in one call (vaek_mlp3_stats_event_replicas)")
+
+
+def refuse_mlp_fused_stats_single(step_path):
+    """--mlp_fused_stats without --sweep_dataset_seeds: refused before any step (main() calls it once the model's engine exists)."""
+    raise RuntimeError(f"--mlp_fused_stats needs {MLP_FUSED_STATS_NEEDS}; a single model's stats event is compute_stats() (this model's "
+                       f"step path: {step_path})")
+
+
+def check_mlp_fused_stats_loop(loop, fused_stats=False):
+    """--mlp_fused_stats on a sweep: refuse, before any step, both stats flags together, a sweep whose loop is ReplicaLoop (that is
+    --fused_stats' sweep) and models the call does not cover."""
+    from .trainer import ReplicaLoop
+    eng = loop.eng
+    path = getattr(eng, "step_path", "?")
+    if fused_stats:
+        raise RuntimeError("--fused_stats (sweeps the resident loop takes: linear VAEs) and --mlp_fused_stats (sweeps of three-hidden-layer "
+                           f"MLP VAEs) cover disjoint sweeps: give the one that matches the sweep's step path ({path!r})")
+    if isinstance(loop, ReplicaLoop):
+        raise RuntimeError(f"--mlp_fused_stats needs {MLP_FUSED_STATS_NEEDS}; this sweep's step path is {path!r} "
+                           "(trainer.ReplicaLoop): use --fused_stats")
+    if not eng.supports_mlp3_stats_event(loop.kind):
+        raise RuntimeError(f"--mlp_fused_stats needs {MLP_FUSED_STATS_NEEDS}; this sweep's step path is {path!r}, which "
+                           "vaek_supports_mlp3_stats_event does not cover")
+
+
 LOGLIK_NEEDS = ("a model vaek_log_likelihood_replicas covers (vaek_supports_log_likelihood): a float32 linear VAE -- no hidden layers -- "
                 "with one or two decoders, D, L <= 32 (D <= 28 with two decoders), -dd / -did <= 16, on one GPU")
 
@@ -316,11 +350,14 @@ def main_sweep(args):
     loop = sweep_loop(models, tevery) if tevery is not None else sweep_loop(models)      # refuses, before any step, what no replica loop covers
     eng = loop.eng
     fused_stats = bool(getattr(args, "fused_stats", False))
+    mlp_fused_stats = bool(getattr(args, "mlp_fused_stats", False))
+    if mlp_fused_stats:                      # before any step
+        check_mlp_fused_stats_loop(loop, fused_stats)
     if fused_stats:                          # before any step
         from .trainer import ReplicaLoop
         if not isinstance(loop, ReplicaLoop):
             raise RuntimeError(f"--fused_stats needs {FUSED_STATS_NEEDS}; this sweep's step path is {eng.step_path!r} "
-                               "(trainer.ReplicaGraphLoop), whose stats events stay one compute_stats() per model")
+                               "(trainer.ReplicaGraphLoop), whose fused stats event is --mlp_fused_stats")
     ll_samples = getattr(args, "log_likelihood_samples", None)
     loglik = None
     if ll_samples is not None:               # before any step
@@ -336,6 +373,8 @@ def main_sweep(args):
     print(f"Train loop: {loop.describe()}")
     if fused_stats:
         print(f"Stats events: one launch for {len(models)} models (vaek_stats_event_replicas)")
+    if mlp_fused_stats:
+        print(f"Stats events: one call for {len(models)} models (vaek_mlp3_stats_event_replicas)")
     if loglik is not None:
         entry = "vaek_log_likelihood_replicas" if mlp_samples is None else "vaek_mlp3_log_likelihood_replicas"
         print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows ({entry})")
@@ -351,7 +390,7 @@ def main_sweep(args):
         loop.run(ev - pos)
         pos = ev
         loop.check()
-        fused = loop.stats_event() if fused_stats and ev % n_print == 0 else None      # every model's event in one launch
+        fused = loop.stats_event() if (fused_stats or mlp_fused_stats) and ev % n_print == 0 else None      # every model's event in one call
         extra = loglik.event() if loglik is not None and ev % n_print == 0 else None     # every model's log-likelihood in one call
         for r, m in enumerate(models):
             m.batchnum = ev
@@ -405,6 +444,8 @@ def main(args):
     if dataset is None:
         raise ValueError("--dataset must be one of sphere, linear_gaussian, sigmoid")
     model = get_model(args, dataset, output_dir, dist)
+    if getattr(args, "mlp_fused_stats", False):      # before any step
+        refuse_mlp_fused_stats_single(getattr(model.model.module.engine(model.batch_size, model.optimizer.global_batch), "step_path", "?"))
     tevery = getattr(args, "trajectory_every", None)
     if tevery is not None:
         if world > 1:

@@ -437,25 +437,34 @@ class ReplicaStats:
     is sampled with the model's `current_epsilon` as it was BEFORE the event, as sample_batch does.  Returns one stats dict per
     model, compute_stats' keys in its order; the values are host tensors (nothing to read back when they are printed)."""
 
+    NAME = "ReplicaStats"              # ReplicaStatsMlp3 overrides the name and the three methods below __init__
+
     def __init__(self, vae_models, rows=None):
         from .datasets import SCORE_KEYS
-
-        def covered():
-            if not self.eng.supports_stats_event(self.kind):
-                raise RuntimeError("ReplicaStats: vaek_stats_event_replicas does not cover this model / dataset (it needs what the resident "
-                                   "loop needs: a float32 linear VAE with one or two decoders, D, L <= 32 and a train batch of at most 256 rows)")
-        _replica_setup(self, vae_models, "ReplicaStats", "launch", "batches", "evaluates", "train_loop_max_replicas", ReplicaLoop._signature,
-                       covered)
+        _replica_setup(self, vae_models, self.NAME, "launch", "batches", "evaluates", "train_loop_max_replicas", ReplicaLoop._signature,
+                       self._check_covered)
         R, m0 = self.R, self.ms[0]
         self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
         if not 1 <= self.rows <= self.eng.stats_event_max_rows:
-            raise RuntimeError(f"ReplicaStats: {self.rows} rows per event, need 1 .. {self.eng.stats_event_max_rows} (vaek_stats_event_max_rows)")
+            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 1 .. {self.eng.stats_event_max_rows} (vaek_stats_event_max_rows)")
         self.score_keys = SCORE_KEYS[self.kind]
         dev = self.eng.device
         self.L = self.eng.L
         self.record_len = self.eng.stats_record_len
         self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
         self.out = torch.zeros(R, self.record_len, dtype=torch.float32, device=dev)
+        self._make_workspace()
+
+    def _check_covered(self):
+        if not self.eng.supports_stats_event(self.kind):
+            raise RuntimeError("ReplicaStats: vaek_stats_event_replicas does not cover this model / dataset (it needs what the resident "
+                               "loop needs: a float32 linear VAE with one or two decoders, D, L <= 32 and a train batch of at most 256 rows)")
+
+    def _make_workspace(self):
+        pass                           # the linear launch needs none
+
+    def _call(self, *args, **kw):
+        self.eng.stats_event_replicas(*args, **kw)
 
     def event(self):
         """One stats event of every model: [stats dict of model 0, ...]."""
@@ -482,9 +491,8 @@ class ReplicaStats:
         for r, (e, d) in enumerate(zip(eps_in, on_dev)):
             if d:
                 sample_eps[r:r + 1].copy_(e.reshape(-1)[:1])
-        self.eng.stats_event_replicas(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, t64(x_seeds),
-                                      t32(x_steps), t64(z_seeds), t32(z_steps), sample_eps, self.out, a_stride=self.a_stride,
-                                      x_tag=1, z_tag=2)
+        self._call(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, t64(x_seeds), t32(x_steps),
+                   t64(z_seeds), t32(z_steps), sample_eps, self.out, a_stride=self.a_stride, x_tag=1, z_tag=2)
         rec = self.out.cpu()                                                      # the event's ONE device -> host copy
         stats = []
         for r, m in enumerate(self.ms):
@@ -500,6 +508,29 @@ class ReplicaStats:
                 st[name] = row[4 + k].clone()
             stats.append(st)
         return stats
+
+
+class ReplicaStatsMlp3(ReplicaStats):
+    """ReplicaStats for three-hidden-layer MLP VAEs (vaek_mlp3_stats_event_replicas, csrc/mlp3_stats.hip): the same contract -- one
+    parameter stack, ONE library call (two launches whatever R is) and ONE device -> host copy per event, the key split,
+    `_latent_draws`, the dataset's `_draws`, tags 1 and 2, `vae_losses` / `var_enc` / `var_dec`, `current_epsilon`, compute_stats' keys
+    in its order, fused and host events mixed freely -- on models Engine.supports_mlp3_stats_event covers, with the call's own
+    workspace for the tile partials."""
+
+    NAME = "ReplicaStatsMlp3"
+
+    def _check_covered(self):
+        if not self.eng.supports_mlp3_stats_event(self.kind):
+            raise RuntimeError("ReplicaStatsMlp3: vaek_mlp3_stats_event_replicas does not cover this model / dataset (it needs a float32 VAE "
+                               "with one decoder and exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, "
+                               f"D, L <= 32; a linear VAE is ReplicaStats'; this model's step path: {getattr(self.eng, 'step_path', '?')})")
+
+    def _make_workspace(self):
+        nb = self.eng.mlp3_stats_event_workspace(self.R, self.rows)
+        self.workspace = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.eng.device)
+
+    def _call(self, *args, **kw):
+        self.eng.mlp3_stats_event_replicas(*args, workspace=self.workspace, **kw)
 
 
 class ReplicaLogLik:
@@ -733,6 +764,13 @@ class ReplicaGraphLoop:
         """One line for run.py."""
         return (f"hipGraph of {self.G} steps, {self.R} replicas per step (vaek_train_step_gen_replicas), "
                 "next batches drawn inside the step's second launch")
+
+    def stats_event(self, rows=None):
+        """One stats event of every model in ONE call (ReplicaStatsMlp3, vaek_mlp3_stats_event_replicas): [compute_stats' dict of model
+        0, ...], with the models' keys, draw counters and lists advanced exactly as compute_stats would advance them."""
+        if getattr(self, "_stats", None) is None or (rows is not None and int(rows) != self._stats.rows):
+            self._stats = ReplicaStatsMlp3(self.ms, rows=rows)
+        return self._stats.event()
 
     def check(self):
         """Nothing to poll: neither launch has a wait."""
