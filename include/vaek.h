@@ -569,6 +569,75 @@ int vaek_mlp3_stats_event_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_
 int vaek_mlp3_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_stats_event* ev, int32_t kind, const float* A,
                                    int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
                                    void* workspace, void* stream);
+/* COVARIANCE SPECTRA of generated and real rows (csrc/cov_spectrum.hip): the stat the reference reserves as `EigenValues` and never
+ * fills -- cov_hat = jnp.cov(batch.T) of a batch and eigh of it, the "learnt eigenvalue" on generated rows and the "ground truth
+ * eigenvalue" on real ones (datasets.py:113-125).  ONE workgroup of 256 threads turns one set of `rows` float32 rows of D = data_dim
+ * <= 32 columns into one RECORD of vaek_cov_spectrum_record_len = D^2 + 2 D + 4 doubles, written with per-lane vector stores:
+ *   [0, D) the eigenvalues of C, ascending (eigh's order)      [D, 2 D) the column means m
+ *   [2 D, 2 D + D^2) C, row-major, exactly symmetric           then: sweeps run, final off_F, |C|_F, rows.
+ * Doubles between two records where a stride exceeds the length are not touched; nothing but the records is written.
+ * SUMMATION RULE: the column sums S1 and the D x D second-moment matrix S2 of ALL rows are accumulated in float64 on the matrix cores
+ * (v_mfma_f64_16x16x4_f64, k over the rows, four per instruction, 256 rows staged in LDS at a time, the accumulators kept across the
+ * tiles, the column sums from a ones operand, rows past `rows` zero rows).  A product x_i x_j is the exact float64 product of two
+ * float32 values and every matrix element is ONE accumulation chain over the rows in row order: no tile partials, no workspace, no
+ * second launch, no atomic, counter or wait.  m = S1 / rows, C = (S2 - rows m m^T) / (rows - 1) (ddof = 1), the upper triangle
+ * computed and mirrored.
+ * SOLVE RULE: cyclic Jacobi in float64 on C, D padded to even, round-robin ordering (D / 2 disjoint rotations per round, D - 1
+ * rounds per sweep; a round takes its angles from the current matrix and then forms A <- J^T A J, each new element from its four
+ * sources, for i <= j, mirrored).  A rotation with a_pq == 0 is skipped; t = 1 / (2 theta) where theta = (a_qq - a_pp) / (2 a_pq) is
+ * too large to square.  off_F is the root of the sum of the off-diagonal squares themselves.  The solve stops when off_F <= 2^-43
+ * |C|_F or after vaek_cov_spectrum_max_sweeps() = 32 sweeps (a cap that bounds one launch, not a tuned value; a caller checks the
+ * reported off_F).  Ranks come from counting, ties break by index.  Nothing is clamped: a tiny negative eigenvalue of a
+ * rank-deficient set is reported as it is.
+ * vaek_cov_spectrum_rows: EXPLICIT rows.  Set s of n reads x + s * x_stride as [rows][D] floats (x_stride == 0: one set shared) and
+ * stores its record at out + s * out_stride; one launch of n workgroups, profile label cov_spectrum_rows; n is 1 ..
+ * vaek_cov_spectrum_max_sets() = 2 * vaek_train_loop_max_replicas().  vaek_supports_cov_spectrum: any context with data_dim <= 32,
+ * whatever its architecture, dtype, batch or world are: the call reads rows only.
+ * vaek_spectrum_event_replicas: the FUSED EVENT of N linear VAEs of the context's shape, one launch with grid (n, 2), profile label
+ * spectrum_event_replicas.  `ev` has the fields of vaek_stats_event with a double* out.  Replica r's two records go to out + r *
+ * out_stride (FAKE side) and + record_len (REAL side), out_stride >= 2 * record_len.  The real side draws row i exactly as
+ * vaek_make_batch(kind, A + r * a_stride, dd, did, pad, var_added, rows, row0 = 0, x_seeds[r], step_host = x_steps[r], x_tag) writes
+ * x; the fake side draws latent row i exactly as vaek_make_batch(..., z_seeds[r], z_steps[r], z_tag) writes z1 / z2 and forms
+ * fake = Decoder(z1) [+ sigmoid(SigDecoder(z1))] + z2 exp(sample_eps[r] / 2) in float32 (vaek_forward(sampling = 1, eps =
+ * sample_eps[r]) on those latents) from params + r * state_stride (never written).  Nothing of a row ever exists in HBM.
+ * vaek_supports_spectrum_event: exactly vaek_supports_log_likelihood's predicate (float32, no hidden layers, one or two decoders,
+ * D, L <= 32, D <= 28 with two decoders, kind 0 .. 2, any batch and world).
+ * DEFINING PROPERTIES: the three row sources feed one accumulate and solve text through the same row -> tile-slot assignment, so a
+ * record depends on the rows' bits only.  (i) Replica or set r's record is BITWISE what a call with n = 1 on its slices leaves;
+ * (ii) two runs are bitwise equal; (iii) the fused event's REAL record is bitwise what vaek_cov_spectrum_rows leaves on the x that
+ * vaek_make_batch writes under the same seed, step and tag; (iv) the fused event does not depend on ctx.batch.  C and m agree with
+ * the float64 covariance of the identical rows within 1e-11 of max_k(C_kk + m_k^2) (its root for m); the eigenvalues agree with a
+ * LAPACK solve of the stored C within off_F + 64 D 2^-53 |C|_F.
+ * Both calls: rows is 2 .. vaek_stats_event_max_rows() = 4096 (one row has no ddof = 1 covariance); `out` is 8-byte aligned; no
+ * workspace; asynchronous on `stream`, allocate nothing, do not synchronise, capturable into a hipGraph.
+ * VAEK_ERR_INVALID (message names the function, nothing touched): NULL arguments, a wrong struct_size, n or rows out of range,
+ * 0 < x_stride < rows * D or a negative stride, out_stride below the record length (two records for the event), a misaligned out, an
+ * unsupported context, state_stride < P, a NULL seeds, steps or sample_eps array, a_stride < 0, NULL A for kind 0 or 1, dd or did
+ * > 16, dd + pad (+ 1 for kind 1) != data_dim, kind outside 0 .. 2, a tag >= 2^30. */
+typedef struct vaek_spectrum_event {
+    int32_t struct_size;                  /* = sizeof(vaek_spectrum_event), ABI guard               */
+    int32_t n;                            /* replicas: the launch has 2 n workgroups                */
+    int32_t rows;                         /* rows of each side, 2 .. vaek_stats_event_max_rows()    */
+    int32_t reserved;
+    int64_t state_stride;                 /* floats between two replicas' params, >= P              */
+    const uint64_t* x_seeds;              /* device [n]: seed of the real rows                      */
+    const uint32_t* x_steps;              /* device [n]: their RNG step                             */
+    const uint64_t* z_seeds;              /* device [n]: seed of the latents                        */
+    const uint32_t* z_steps;              /* device [n]: their RNG step                             */
+    const float* sample_eps;              /* device [n]: eps of the sampling pass                   */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared             */
+    double* out;                          /* device: fake record r at out + r * out_stride, real one behind it */
+    int64_t out_stride;                   /* doubles, >= 2 * vaek_cov_spectrum_record_len           */
+} vaek_spectrum_event;
+int vaek_supports_cov_spectrum(const vaek_ctx* ctx, int32_t* yes);
+int vaek_cov_spectrum_record_len(const vaek_ctx* ctx, int64_t* doubles);
+int vaek_cov_spectrum_max_sets(void);
+int vaek_cov_spectrum_max_sweeps(void);
+int vaek_cov_spectrum_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t rows, int64_t x_stride, double* out, int64_t out_stride,
+                           void* stream);
+int vaek_supports_spectrum_event(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_spectrum_event_replicas(vaek_ctx* ctx, const float* params, const vaek_spectrum_event* ev, int32_t kind, const float* A, int32_t dd,
+                                 int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

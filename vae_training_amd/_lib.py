@@ -64,6 +64,11 @@ class VaekLogLikelihood(C.Structure):
     ]
 
 
+class VaekSpectrumEvent(C.Structure):
+    """vaek_spectrum_event of include/vaek.h: vaek_stats_event's fields with a double* out (device pointers)."""
+    _fields_ = list(VaekStatsEvent._fields_)
+
+
 STATS_RECORD_HEAD = 8      # floats of a stats record in front of the epsilon_p copy: loss, Dkl, mse, eps, two score values, 0, 0
 
 
@@ -157,6 +162,14 @@ SIGNATURES = {
     "vaek_mlp3_stats_event_workspace_bytes": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_size_t)]),
     "vaek_mlp3_stats_event_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekStatsEvent), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32,
                                                  _vp, _vp]),
+    "vaek_supports_cov_spectrum": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "vaek_cov_spectrum_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "vaek_cov_spectrum_max_sets": (C.c_int, []),
+    "vaek_cov_spectrum_max_sweeps": (C.c_int, []),
+    "vaek_cov_spectrum_rows": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp]),
+    "vaek_supports_spectrum_event": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_spectrum_event_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSpectrumEvent), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32,
+                                               _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

@@ -419,6 +419,74 @@ class Engine:
         _lib.check(self.lib.vaek_mlp3_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did), int(pad),
                                                               float(var_added), int(x_tag), int(z_tag), wp, _stream()))
 
+    def supports_cov_spectrum(self):
+        """True where cov_spectrum_rows covers this engine: data_dim <= 32, whatever its architecture, dtype, batch and world are
+        (vaek_supports_cov_spectrum)."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_cov_spectrum(self.h, C.byref(f)))
+        return bool(f.value)
+
+    @property
+    def cov_spectrum_record_len(self):
+        """Doubles in one spectrum record (vaek_cov_spectrum_record_len): D^2 + 2 D + 4 = D eigenvalues ascending, D column means, the
+        covariance matrix row-major, then sweeps run, final off_F, |C|_F and rows."""
+        n = C.c_int64()
+        _lib.check(self.lib.vaek_cov_spectrum_record_len(self.h, C.byref(n)))
+        return int(n.value)
+
+    @property
+    def cov_spectrum_max_sets(self):
+        return int(self.lib.vaek_cov_spectrum_max_sets())
+
+    @property
+    def cov_spectrum_max_sweeps(self):
+        return int(self.lib.vaek_cov_spectrum_max_sweeps())
+
+    def cov_spectrum_rows(self, x, rows, out, n=None, x_stride=None, out_stride=None):
+        """The covariance spectrum of EACH of n sets of `rows` float32 rows of D columns in one launch, workgroup s turning set s into
+        record s (vaek_cov_spectrum_rows).  x: float32 [n, rows, D] (or [rows, D]: one set), out: float64 [n, out_stride >=
+        cov_spectrum_record_len] (or a raw device address) -- device tensors; n and the strides default to the tensors' shapes.  Asynchronous; capturable."""
+        assert x is None or x.dtype == torch.float32
+        assert out is None or isinstance(out, int) or out.dtype == torch.float64
+        if n is None:
+            n = 1 if x is None or x.dim() < 3 else x.shape[0]
+        if x_stride is None:
+            x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
+        if out_stride is None:
+            out_stride = 0 if out is None or isinstance(out, int) else out.shape[-1]
+        op = None if out is None else C.c_void_p(out if isinstance(out, int) else out.data_ptr())
+        _lib.check(self.lib.vaek_cov_spectrum_rows(self.h, _ptr(x), int(n), int(rows), int(x_stride), op, int(out_stride), _stream()))
+
+    def supports_spectrum_event(self, kind):
+        """True where spectrum_event_replicas covers this engine and dataset kind: exactly where supports_log_likelihood does."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_spectrum_event(self.h, int(kind), C.byref(f)))
+        return bool(f.value)
+
+    def spectrum_event_replicas(self, params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
+                                a_stride=0, x_tag=5, z_tag=6, n=None, state_stride=None, out_stride=None, struct_size=None):
+        """The covariance spectra of a generated and of a real batch of EACH of n linear VAEs of this engine's shape in one launch of
+        (n, 2) workgroups (vaek_spectrum_event_replicas): `rows` real rows drawn under (x_seeds[r], x_steps[r], x_tag) and `rows`
+        latent rows under (z_seeds[r], z_steps[r], z_tag) exactly as make_batch draws them, the fake batch sampled from the latents
+        with eps = sample_eps[r].  out: float64 [n, out_stride >= 2 * cov_spectrum_record_len]: the fake record, then the real one.
+        The other arguments are stats_event_replicas'.  Asynchronous; capturable."""
+        ev = _lib.VaekSpectrumEvent()
+        ev.struct_size = C.sizeof(_lib.VaekSpectrumEvent) if struct_size is None else int(struct_size)
+        ev.n = int(params.shape[0] if n is None else n)
+        ev.rows = int(rows)
+        ev.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        assert all(s is None or s.dtype == torch.int64 for s in (x_seeds, z_seeds))
+        assert all(s is None or s.dtype == torch.int32 for s in (x_steps, z_steps))
+        assert sample_eps is None or sample_eps.dtype == torch.float32
+        assert out is None or isinstance(out, int) or out.dtype == torch.float64
+        ev.x_seeds, ev.x_steps, ev.z_seeds, ev.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
+        ev.sample_eps = _ptr(sample_eps)
+        ev.a_stride = int(a_stride)
+        ev.out = None if out is None else (out if isinstance(out, int) else out.data_ptr())
+        ev.out_stride = int((0 if out is None or isinstance(out, int) else out.shape[-1]) if out_stride is None else out_stride)
+        _lib.check(self.lib.vaek_spectrum_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                         float(var_added), int(x_tag), int(z_tag), _stream()))
+
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
         f = C.c_int32()

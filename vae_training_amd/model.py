@@ -128,7 +128,8 @@ class GenerativeModel(Model):
         """The stats of an n_print event: compute_stats(), and with `log_likelihood_samples` = K set (run.py --log_likelihood_samples)
         the importance-weighted log-likelihood of this model on K samples per row (trainer.ReplicaLogLik, one library call), which
         neither splits the model's key nor advances a draw counter of the run; `mlp_log_likelihood_samples` does the same for a
-        three-hidden-layer MLP model (trainer.ReplicaLogLikMlp3)."""
+        three-hidden-layer MLP model (trainer.ReplicaLogLikMlp3); `eigenvalues` (run.py --eigenvalues) adds the covariance spectra of
+        a generated and a real batch (trainer.ReplicaSpectrum), which leaves the run alone in the same way."""
         stats = self.compute_stats()
         K = getattr(self, "log_likelihood_samples", None)
         if K:
@@ -142,6 +143,11 @@ class GenerativeModel(Model):
             if getattr(self, "_loglik_mlp3", None) is None:
                 self._loglik_mlp3 = ReplicaLogLikMlp3([self], K)
             stats.update(self._loglik_mlp3.event()[0])
+        if getattr(self, "eigenvalues", False):                    # run.py --eigenvalues: the covariance spectra of a fake and a real batch
+            from .trainer import ReplicaSpectrum
+            if getattr(self, "_spectrum", None) is None:
+                self._spectrum = ReplicaSpectrum([self])
+            stats.update(self._spectrum.event()[0])
         return stats
 
     def write_stats(self, stats):

@@ -3,7 +3,7 @@
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
---fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples."""
+--fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples, --eigenvalues."""
 from __future__ import annotations
 
 import argparse
@@ -91,6 +91,14 @@ def build_parser():
                         "without the flag.  Alone or with --sweep_dataset_seeds (one call for all models); float32, one decoder, three "
                         "hidden layers of 64 .. 256 units both ways, D, L <= 32, models x 1000 rows x K at most 2^22; linear models (use "
                         "--log_likelihood_samples), other models and both flags together are refused before any step; single GPU only")
+    p.add_argument("--eigenvalues", dest="eigenvalues", action="store_true",
+                   help="at every n_print step also evaluate the covariance spectrum of a generated print batch and of a real one "
+                        "(trainer.ReplicaSpectrum, csrc/cov_spectrum.hip): losses.npz gains 'learnt eigenvalue' and 'ground truth "
+                        "eigenvalue' per event and 'EigenValues' = (learnt, ground truth), the key the reference saves empty.  Linear "
+                        "VAEs: one fused launch (vaek_spectrum_event_replicas); other models: make_batch + forward per model and one "
+                        "vaek_cov_spectrum_rows call.  The evaluation has its own RNG counter and tags, so the training run is bitwise "
+                        "the one without the flag.  Alone or with --sweep_dataset_seeds; combines with the stats and log-likelihood "
+                        "flags; data_dim <= 32; single GPU only")
     return p
 
 
@@ -323,6 +331,18 @@ def check_mlp_log_likelihood_model(m, samples, n_models=1):
                            f"model's step path: {path})")
 
 
+EIGEN_NEEDS = "data_dim <= 32 (vaek_supports_cov_spectrum), -dd / -did <= 16, on one GPU"
+
+
+def check_eigenvalues_model(m):
+    """--eigenvalues: refuse, before any step, a model the spectrum calls do not cover."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    _, _, dd, did, _, _ = m.dataset.device_spec()
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_cov_spectrum():
+        raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS} (this model's data_dim: {getattr(eng, 'D', '?')}, world {eng.world})")
+
+
 def main_sweep(args):
     """--sweep_dataset_seeds: one dataset and one VAEModel per seed, the reference's schedule (model.py:207-222: stats every n_print
     steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE loop.run between
@@ -369,6 +389,13 @@ def main_sweep(args):
         from .trainer import ReplicaLogLikMlp3
         check_mlp_log_likelihood_model(models[0], mlp_samples, len(models))
         loglik = ReplicaLogLikMlp3(models, mlp_samples)
+    spectrum = None
+    if getattr(args, "eigenvalues", False):  # before any step
+        from .trainer import ReplicaSpectrum
+        check_eigenvalues_model(models[0])
+        spectrum = ReplicaSpectrum(models)
+        for m in models:
+            m.eigenvalues = True             # model_save_data writes "EigenValues"
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
     if fused_stats:
@@ -378,6 +405,9 @@ def main_sweep(args):
     if loglik is not None:
         entry = "vaek_log_likelihood_replicas" if mlp_samples is None else "vaek_mlp3_log_likelihood_replicas"
         print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows ({entry})")
+    if spectrum is not None:
+        entry = "vaek_spectrum_event_replicas" if spectrum.fused else "vaek_cov_spectrum_rows"
+        print(f"Eigenvalue events: {spectrum.rows} generated and {spectrum.rows} real rows per model ({entry})")
     for r, m in enumerate(models):
         m._graph_loop = loop.view(r)
         score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
@@ -392,12 +422,15 @@ def main_sweep(args):
         loop.check()
         fused = loop.stats_event() if (fused_stats or mlp_fused_stats) and ev % n_print == 0 else None      # every model's event in one call
         extra = loglik.event() if loglik is not None and ev % n_print == 0 else None     # every model's log-likelihood in one call
+        spectra = spectrum.event() if spectrum is not None and ev % n_print == 0 else None     # every model's two spectra in one call
         for r, m in enumerate(models):
             m.batchnum = ev
             if ev % n_print == 0:
                 stats = m.compute_stats() if fused is None else fused[r]
                 if extra is not None:
                     stats.update(extra[r])
+                if spectra is not None:
+                    stats.update(spectra[r])
                 m.write_stats(stats)
             if ev % n_plot == 0 or ev == n - 1:
                 m.plot_epoch()
@@ -427,6 +460,9 @@ def main(args):
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1 and getattr(args, "mlp_log_likelihood_samples", None) is not None:
         raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS}: it does not combine with data parallelism "
+                           f"(step path of a world of {world}: one shard per rank)")
+    if world > 1 and getattr(args, "eigenvalues", False):
+        raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS}: it does not combine with data parallelism "
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1:
         import torch
@@ -462,6 +498,10 @@ def main(args):
         check_mlp_log_likelihood_model(model, mlp_samples)      # before any step
         model.mlp_log_likelihood_samples = mlp_samples          # the n_print events add trainer.ReplicaLogLikMlp3([model], K).event()
         print(f"Log-likelihood events: {mlp_samples} samples × {model.print_batch_size} rows (vaek_mlp3_log_likelihood_replicas)")
+    if getattr(args, "eigenvalues", False):
+        check_eigenvalues_model(model)                     # before any step
+        model.eigenvalues = True                           # the n_print events add trainer.ReplicaSpectrum([model]).event()
+        print(f"Eigenvalue events: {model.print_batch_size} generated and {model.print_batch_size} real rows (csrc/cov_spectrum.hip)")
     if rank == 0:
         eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
         loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")

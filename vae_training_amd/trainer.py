@@ -644,6 +644,99 @@ class ReplicaLogLikMlp3(ReplicaLogLik):
         self.eng.mlp3_log_likelihood_replicas(*args, **kw)
 
 
+class ReplicaSpectrum:
+    """The covariance spectra of a generated and of a real batch of R VAEModels of one shape: per model the eigenvalues of
+    cov(fake batch) -- the reference's "learnt eigenvalue" -- and of cov(real batch) -- its "ground truth eigenvalue"
+    (datasets.py:113-125), the `EigenValues` the reference saves and never fills (csrc/cov_spectrum.hip).
+
+    The models are validated as in ReplicaLogLik (one shape, any batch size; data_dim <= 32).  Where the engine's
+    supports_spectrum_event holds (linear VAEs) event() is one parameter stack, ONE fused call (vaek_spectrum_event_replicas: nothing
+    of a row exists in HBM) and one device -> host copy.  Every other model -- the mlp3 sweep included -- takes the host route: per
+    model make_batch and forward(sampling) under the same seeds, steps and tags into a [2R, rows, D] stack, then ONE
+    vaek_cov_spectrum_rows call with n = 2R and one device -> host copy.
+
+    event() does NOT perturb the run: `m.key`, the dataset's `_draws` and `m._latent_draws` are neither split nor advanced.  Its draws
+    have a counter of their own, `m._spectrum_draws` (incremented before use), the seed dataset.key[0] ^ dataset.key[1] and the tags 5
+    (rows) and 6 (latents); tags 0 .. 4 belong to the train loop, the dataset's batches, the latents and the log-likelihood.  The fake
+    batch is sampled with the model's `current_epsilon`.  Returns per model {"learnt eigenvalue", "ground truth eigenvalue"} (float64
+    arrays, ascending) and appends them to `m.ht_eigen` and `m.gt_eigen`.  Raises RuntimeError naming the model where a solve hit the
+    sweep cap without converging (off_F > 2^-40 |C|_F)."""
+
+    KEYS = ("learnt eigenvalue", "ground truth eigenvalue")
+    X_TAG, Z_TAG = 5, 6
+    NAME = "ReplicaSpectrum"
+    OFF_BOUND = 2.0 ** -40
+
+    def __init__(self, vae_models, rows=None):
+        _replica_setup(self, vae_models, self.NAME, "call", "rows", "evaluates", "train_loop_max_replicas", ReplicaLogLik._shape,
+                       self._check_covered)
+        R, m0 = self.R, self.ms[0]
+        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
+        if not 2 <= self.rows <= self.eng.stats_event_max_rows:
+            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 2 .. {self.eng.stats_event_max_rows} (vaek_stats_event_max_rows; "
+                               "one row has no covariance)")
+        dev = self.eng.device
+        self.D = self.eng.D
+        self.record_len = self.eng.cov_spectrum_record_len
+        self.fused = bool(self.eng.supports_spectrum_event(self.kind))
+        self.out = torch.zeros(2 * R, self.record_len, dtype=torch.float64, device=dev)      # [R, 2 records] on the fused route
+        if self.fused:
+            self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
+        else:
+            self.stack = torch.zeros(2 * R, self.rows, self.D, dtype=torch.float32, device=dev)
+
+    def _check_covered(self):
+        if not self.eng.supports_cov_spectrum():
+            raise RuntimeError(f"ReplicaSpectrum: vaek_cov_spectrum_rows does not cover this model (it needs data_dim <= 32; this model's "
+                               f"data_dim: {getattr(self.eng, 'D', '?')})")
+
+    def event(self):
+        """One evaluation of every model: [{"learnt eigenvalue", "ground truth eigenvalue"} of model 0, ...]."""
+        dev = self.eng.device
+        R, D = self.R, self.D
+        seeds, steps, eps_in = [], [], []
+        for m in self.ms:
+            m._spectrum_draws = getattr(m, "_spectrum_draws", 0) + 1
+            ds = m.dataset
+            seeds.append(ds.key[0] ^ ds.key[1])
+            steps.append(m._spectrum_draws)
+            eps_in.append(float(torch.as_tensor(m.current_epsilon).reshape(-1)[0]))       # sample_batch: the model's current eps
+        if self.fused:
+            for r, m in enumerate(self.ms):
+                self.params[r].copy_(m.model.flat)
+            sd = torch.tensor([_wrap_signed(s, 64) for s in seeds], dtype=torch.int64).to(dev)
+            st = torch.tensor([_wrap_signed(s, 32) for s in steps], dtype=torch.int32).to(dev)
+            self.eng.spectrum_event_replicas(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, sd, st, sd, st,
+                                             torch.tensor(eps_in, dtype=torch.float32).to(dev), self.out.view(R, 2 * self.record_len),
+                                             a_stride=self.a_stride, x_tag=self.X_TAG, z_tag=self.Z_TAG)
+        else:
+            for r, m in enumerate(self.ms):
+                eng = m.model.module.engine(self.rows)                                 # forward takes at most its context's batch
+                Ar = None if self.A is None else self.A[r]
+                eng.make_batch(self.kind, Ar, self.dd, self.did, self.pad, self.var, self.rows, seeds[r], step=steps[r], tag=self.X_TAG,
+                               out=(self.stack[2 * r + 1], None, None))
+                _, z1, z2 = eng.make_batch(self.kind, Ar, self.dd, self.did, self.pad, self.var, self.rows, seeds[r], step=steps[r],
+                                           tag=self.Z_TAG, want_x=False)
+                fake, _ = eng.forward(m.model.flat, None, z1, z2, sampling=True, eps=eps_in[r], want_mu=False)
+                self.stack[2 * r].copy_(fake)
+            self.eng.cov_spectrum_rows(self.stack, self.rows, self.out)
+        rec = self.out.cpu().numpy()                                                  # the event's ONE device -> host copy
+        stats = []
+        for r, m in enumerate(self.ms):
+            st = {}
+            for side, name in enumerate(self.KEYS):                                   # record 2 r: the fake side, 2 r + 1: the real side
+                row = rec[2 * r + side]
+                off, norm = row[2 * D + D * D + 1], row[2 * D + D * D + 2]
+                if not off <= self.OFF_BOUND * norm:
+                    raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the {name} solve stopped at the cap of "
+                                       f"{int(row[2 * D + D * D])} sweeps with off_F = {off:.3e} > 2^-40 |C|_F = {self.OFF_BOUND * norm:.3e}")
+                st[name] = row[:D].copy()
+            m.ht_eigen.append(st[self.KEYS[0]])
+            m.gt_eigen.append(st[self.KEYS[1]])
+            stats.append(st)
+        return stats
+
+
 class ReplicaGraphLoop:
     """A sweep of three-hidden-layer MLP VAEs (step path "mlp3") as GraphLoop's pipelined hipGraph loop with R models per step: R
     VAEModels of one shape -- validated as in ReplicaLoop: one batch size, data and latent dimension, architecture, epsilon,

@@ -188,6 +188,8 @@ class VAEModel(GenerativeModel):
         if loop is not None:                # fast loop: train losses live in the device ring, eval losses in the list
             self.vae_losses_train = loop.losses()
         data = {"VAE Loss": self.vae_losses if loop is None else list(self.vae_losses) + list(self.vae_losses_train), "Decoder Variance": self.var_dec, "Encoder Variance": self.var_enc}
+        if getattr(self, "eigenvalues", False):      # run.py --eigenvalues, and only it: the reference's key (vae.py:205), filled
+            data["EigenValues"] = (self.ht_eigen, self.gt_eigen)
         if final:
             # empty, as in the reference, unless the loop recorded a trajectory (trajectory_every=K): then one value per record
             if loop is not None and getattr(loop, "records_trajectory", False):
