@@ -2078,57 +2078,70 @@ __global__ __launch_bounds__(LNT, 2) void lin_persist_kernel(const LinArgs a, co
         LinFeatMap<NB> fmap;                                  // this lane's operand addresses, but for the slot and the validity column
         fmap.init(a, tl, v_off, c_off, lane);
         [[maybe_unused]] unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0, s5 = 0, s6 = 0, sacc_i = 0, sacc_l = 0, sacc_f = 0, sacc_m = 0, sacc_p = 0, sacc_b = 0;
-        for (int i = 0; i < items; ++i) {
-            LIN_NOWQ(s0);
-            lin_wait_vmcnt_upto((i + 1 < items ? npw : 0) + (i >= 1 ? sw : 0));       // tile i has landed, this wave's share of image i - 2 is out
-            LIN_NOWQ(s1);
-            lin_barrier();                                     // ... for every wave; and everybody is done with slot (i + 2) % 3 (the scratch of i - 1)
-            LIN_NOWQ(s2);
-            if (i >= 3) signal();                              // image i - 2 (image 0 left at the end of iteration 0)
-            const int n = p_cur.n, tile = pos_tile(p_cur), slot_off = p_cur.slot * stride;
-            char* slot = lin_smem + slot_off;
-            const bool ragged = tile == a.ntiles - 1 && valid_last < a.T;
-            if constexpr (!GEN) {
-                if (ragged) lin_fix_ragged(a, tl, tab[n], tab[kLinMaxPersist + n], tab[2 * kLinMaxPersist + n], tile, slot, t);
-            }
-            LIN_NOWQ(s3);
-            f32x4 acc[NB * (NB + 1) / 2];
-            if (!loader) {
-                int fb[NB];
-                fmap.at(slot_off, ragged ? vr_off - v_off : 0, fb);
-                lin_tile_products_at<NB, JT, kLinCW>(a, lin_smem, fb, fmap.fs, acc, lane, wave, [](int) {});
-            }
-            if constexpr (GEN) {
-                gen_share(p_load, p_load, 1);                  // item i + 2: the loading waves at once, the multiplying waves behind their products
-                p_load.advance(per_batch);
-            } else if (loader && i > 0) {
-                // (iteration 0 issues the pieces of tile 2 only behind its early signal: the drain in front of that signal would
-                // otherwise wait for them to land)
-                prepare();
-                issue_pieces();
-            }
-            LIN_NOWQ(s5);
-            lin_barrier();                                     // every wave has read its last operand: the slot turns into scratch
-            if constexpr (GEN) { if (t == 0) *ticket = 0u; }   // (nobody takes a ticket before the next iteration's first barrier)
-            LIN_NOWQ(s6);
-            lin_tile_combine<NB, true, kLinCW>(acc, slot, a.partial_base + ((long long)p_cur.bs * a.ntiles + tile) * NO, t, wave, lane);
-            if (i == 0) {                                      // the launch's first image: out at once (pipeline fill), not two tiles later
-                lin_wait_vmcnt<0>();
-                lin_barrier();
-                signal();
-                if (sid == 0) { [[maybe_unused]] unsigned long long te = 0; LIN_NOWQ(te); LIN_PUT(53, te); }
+        // ONE LOOP PER ROLE in the three-block kernels, the same barriers in both: the multiplying waves carry no piece cursors, no
+        // LinTileSrc and no pointer tables through their loop, the loading waves no accumulators and no feature map, and neither
+        // walks through the other's code as skipped branches (streamers alone 3.31 -> 3.20 us per step at the metric's shape:
+        // profiles/lin_trim_roles.txt).  The four-block kernels keep one loop for both roles: their streamers are not the pace, and
+        // the launch got SLOWER when they ran faster (profiles/lin_trim_bench.txt, M20).
+        auto items_loop = [&](auto role) __attribute__((always_inline)) {
+            constexpr int kRole = decltype(role)::value;          // 0 multiplying, 1 loading, 2 either (one loop for both)
+            const bool is_loader = kRole == 2 ? loader : kRole == 1;
+            for (int i = 0; i < items; ++i) {
+                LIN_NOWQ(s0);
+                lin_wait_vmcnt_upto((i + 1 < items ? npw : 0) + (i >= 1 ? sw : 0));       // tile i has landed, this wave's share of image i - 2 is out
+                LIN_NOWQ(s1);
+                lin_barrier();                                     // ... for every wave; and everybody is done with slot (i + 2) % 3 (the scratch of i - 1)
+                LIN_NOWQ(s2);
+                if (i >= 3) signal();                              // image i - 2 (image 0 left at the end of iteration 0)
+                const int n = p_cur.n, tile = pos_tile(p_cur), slot_off = p_cur.slot * stride;
+                char* slot = lin_smem + slot_off;
+                const bool ragged = tile == a.ntiles - 1 && valid_last < a.T;
                 if constexpr (!GEN) {
-                    if (loader) {
-                        prepare();
-                        issue_pieces();
+                    if (ragged) lin_fix_ragged(a, tl, tab[n], tab[kLinMaxPersist + n], tab[2 * kLinMaxPersist + n], tile, slot, t);
+                }
+                LIN_NOWQ(s3);
+                f32x4 acc[NB * (NB + 1) / 2];
+                if (!is_loader) {
+                    int fb[NB];
+                    fmap.at(slot_off, ragged ? vr_off - v_off : 0, fb);
+                    lin_tile_products_at<NB, JT, kLinCW>(a, lin_smem, fb, fmap.fs, acc, lane, wave, [](int) {});
+                }
+                if constexpr (GEN) {
+                    gen_share(p_load, p_load, 1);                  // item i + 2: the loading waves at once, the multiplying waves behind their products
+                    p_load.advance(per_batch);
+                } else if (is_loader && i > 0) {
+                    // (iteration 0 issues the pieces of tile 2 only behind its early signal: the drain in front of that signal would
+                    // otherwise wait for them to land)
+                    prepare();
+                    issue_pieces();
+                }
+                LIN_NOWQ(s5);
+                float* const out = a.partial_base + ((long long)p_cur.bs * a.ntiles + tile) * NO;
+                lin_barrier();                                     // every wave has read its last operand: the slot turns into scratch
+                if constexpr (GEN) { if (t == 0) *ticket = 0u; }   // (nobody takes a ticket before the next iteration's first barrier)
+                LIN_NOWQ(s6);
+                lin_tile_combine<NB, true, kLinCW>(acc, slot, out, t, wave, lane);
+                if (i == 0) {                                      // the launch's first image: out at once (pipeline fill), not two tiles later
+                    lin_wait_vmcnt<0>();
+                    lin_barrier();
+                    signal();
+                    if (sid == 0) { [[maybe_unused]] unsigned long long te = 0; LIN_NOWQ(te); LIN_PUT(53, te); }
+                    if constexpr (!GEN) {
+                        if (is_loader) {
+                            prepare();
+                            issue_pieces();
+                        }
                     }
                 }
+                LIN_NOWQ(s4);
+                if (i + 1 < items) { sacc_i += s1 - s0; sacc_l += s2 - s1; sacc_f += s3 - s2; sacc_m += s4 - s3; sacc_p += s5 - s3; sacc_b += s6 - s5; }
+                if (sid == 7) { LIN_PUT(42, sacc_i); LIN_PUT(43, sacc_l); LIN_PUT(44, sacc_f); LIN_PUT(45, sacc_m); LIN_PUT(46, (unsigned long long)items); LIN_PUT(47, sacc_p); LIN_PUT(48, sacc_b); }
+                p_cur.advance(per_batch);
             }
-            LIN_NOWQ(s4);
-            if (i + 1 < items) { sacc_i += s1 - s0; sacc_l += s2 - s1; sacc_f += s3 - s2; sacc_m += s4 - s3; sacc_p += s5 - s3; sacc_b += s6 - s5; }
-            if (sid == 7) { LIN_PUT(42, sacc_i); LIN_PUT(43, sacc_l); LIN_PUT(44, sacc_f); LIN_PUT(45, sacc_m); LIN_PUT(46, (unsigned long long)items); LIN_PUT(47, sacc_p); LIN_PUT(48, sacc_b); }
-            p_cur.advance(per_batch);
-        }
+        };
+        if constexpr (NB != 3) items_loop(std::integral_constant<int, 2>{});
+        else if (loader) items_loop(std::integral_constant<int, 1>{});
+        else items_loop(std::integral_constant<int, 0>{});
         lin_wait_vmcnt<0>();
         lin_barrier();
         if (items - 2 >= 1) signal();
