@@ -638,6 +638,35 @@ int vaek_cov_spectrum_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t row
 int vaek_supports_spectrum_event(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
 int vaek_spectrum_event_replicas(vaek_ctx* ctx, const float* params, const vaek_spectrum_event* ev, int32_t kind, const float* A, int32_t dd,
                                  int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream);
+/* EIGENVECTORS of those covariances and PRINCIPAL ANGLES between two of their eigenbases (csrc/cov_spectrum.hip): which directions
+ * carry the variance, not only how many -- whether a generator's mass lies in the subspace the data lives in.
+ * vaek_cov_eigen_rows and vaek_eigen_event_replicas are vaek_cov_spectrum_rows and vaek_spectrum_event_replicas with a longer RECORD
+ * of vaek_cov_eigen_record_len = 2 D^2 + 2 D + 4 doubles: the spectrum record above, BITWISE and in its layout, then V row-major,
+ * V[i * D + k] = component i of the eigenvector of eigenvalue k (the eigenvalues' ascending order, the same counting ranks, ties by
+ * index).  SIGN: every eigenvector's component of largest magnitude is positive; a tie goes to the lowest row index.  Each Jacobi
+ * round also forms V <- V J from the (c, s, mate) it publishes (V starts as I; V never feeds back into the matrix, so eigenvalues,
+ * sweeps and off_F are those of the spectrum calls).  The event's records go to out + r * out_stride (fake) and + the eigen record
+ * length (real), out_stride >= 2 * that length.  Same predicates (vaek_supports_cov_spectrum, vaek_supports_spectrum_event), same
+ * ranges, same refusal lists, same properties (i) .. (iv); profile labels cov_eigen_rows and eigen_event_replicas.  C V = V diag(lambda)
+ * holds within off_F + 256 D 2^-53 |C|_F in the Frobenius norm and max |V^T V - I| <= 4 D (sweeps + 1) 2^-53.
+ * vaek_subspace_angles: pair p of n (1 .. vaek_cov_spectrum_max_sets(), one workgroup of 256 threads each) reads the EIGEN records at
+ * a + p * a_stride and b + p * b_stride, written by an earlier launch.  U = the ka eigenvectors of a's largest eigenvalues, W = the kb
+ * of b's, 1 <= kb <= ka <= D.  In float64: M = U^T W, R = W - U M formed explicitly, G = R^T R (i <= j, mirrored), and G's eigenvalues
+ * by the SOLVE RULE above (the same device routine).  RECORD of vaek_subspace_record_len(kb) = kb + 4 doubles at out + p * out_stride:
+ *   [0, kb) sin^2 of the principal angles, ascending, unclamped      [kb] |sin Theta|_F^2 = the sum of the squares of R's elements
+ *   [kb + 1] sweeps run      [kb + 2] final off_F of G      [kb + 3] max(max |U^T U - I|, max |W^T W - I|).
+ * No workspace, atomics, counters or waits; per-lane vector stores of the records only; pair p's record is bitwise the n = 1 call's.
+ * Asynchronous, allocates nothing, capturable; profile label subspace_angles.  VAEK_ERR_INVALID (message, nothing touched): NULL
+ * pointers, data_dim > 32, n, ka or kb out of range, a_stride or b_stride below the eigen record length, out_stride < kb + 4, an a, b
+ * or out that is not 8-byte aligned. */
+int vaek_cov_eigen_record_len(const vaek_ctx* ctx, int64_t* doubles);
+int vaek_cov_eigen_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t rows, int64_t x_stride, double* out, int64_t out_stride,
+                        void* stream);
+int vaek_eigen_event_replicas(vaek_ctx* ctx, const float* params, const vaek_spectrum_event* ev, int32_t kind, const float* A, int32_t dd,
+                              int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream);
+int vaek_subspace_record_len(int32_t kb);
+int vaek_subspace_angles(vaek_ctx* ctx, const double* a, int64_t a_stride, const double* b, int64_t b_stride, int32_t n, int32_t ka,
+                         int32_t kb, double* out, int64_t out_stride, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

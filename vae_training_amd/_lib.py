@@ -170,6 +170,12 @@ SIGNATURES = {
     "vaek_supports_spectrum_event": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
     "vaek_spectrum_event_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSpectrumEvent), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32,
                                                _vp]),
+    "vaek_cov_eigen_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "vaek_cov_eigen_rows": (C.c_int, [_vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp]),
+    "vaek_eigen_event_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSpectrumEvent), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, C.c_uint32,
+                                            _vp]),
+    "vaek_subspace_record_len": (C.c_int, [_i32]),
+    "vaek_subspace_angles": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

@@ -19,6 +19,12 @@
 //     columns of real rows).  The off-diagonal norm is the sum of the off-diagonal squares themselves (never |A|^2 - sum a_ii^2,
 //     which stalls at 1e-8 |C|_F); the solve stops when off_F <= 2^-43 |C|_F or after kSpectrumMaxSweeps sweeps, a decision every
 //     thread reads from LDS.  Ranks come from counting, ties break by index; nothing is clamped.
+//   EIGENVECTORS (vaek_cov_eigen_rows, vaek_eigen_event_replicas: the VEC instantiations).  The solve is one routine, jacobi_solve;
+//     with VEC a round also forms V <- V J between its two barriers into two more buffers of the dead tile, and the record gains V
+//     behind the spectrum record, columns in the eigenvalues' order, the largest component of each positive.  V never feeds back, so
+//     the spectrum part is bitwise the VEC = false record.
+//   PRINCIPAL ANGLES (vaek_subspace_angles): a second kernel reads two eigen records an earlier launch stored, forms M = U^T W,
+//     R = W - U M and G = R^T R in LDS and solves G with the same jacobi_solve: sin^2 of the principal angles between the two spans.
 //
 // Three row sources feed that one text through the same row -> tile-slot assignment, so a record depends on the rows' bits only:
 // SRC_EXPLICIT reads [rows][D] from HBM, SRC_REAL draws row i as vaek_make_batch writes x, SRC_FAKE draws latent row i as
@@ -164,15 +170,104 @@ __device__ __forceinline__ double block_sum256(double v, double* red, int t) {
     return r;
 }
 
-// The whole record of one set.  `smem`: the tile while the rows are summed, then the two Jacobi buffers.  src is uniform over the
-// workgroup; an EVENT kernel carries the two drawing sources, the rows kernel the explicit one.
-template <bool EVENT, int DP, int LP, bool SIG>
+// the largest v over the 256 threads, the same value in every thread (v >= 0)
+__device__ __forceinline__ double block_max256(double v, double* red, int t) {
+    red[t] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (t < s) red[t] = fmax(red[t], red[t + s]);
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+constexpr int kMatDoubles = kSpectrumMaxDim * kMatStride;     // one Jacobi buffer
+
+// Cyclic Jacobi, round-robin, on the symmetric De x De matrix in buffer 0 of `mat` (two buffers of kMatDoubles; De even, index
+// De - 1 stays, the others turn), published by a barrier before the call.  Leaves the diagonalised matrix in buffer `cur` and returns
+// (cur, sweeps, off_F), the same in every thread.  VEC: buffer 0 of `vec` (two more buffers) starts as I, also published, and every
+// round forms V <- V J between the round's own two barriers: new column i = c_i V[:, i] + s_i V[:, mate(i)]; V ends in buffer `cur`
+// of `vec` with C V = V diag(A).
+template <bool VEC>
+__device__ __forceinline__ void jacobi_solve(double* const mat, double* const vec, const int De, const double norm_c, double* const red,
+                                             double* const rot_c, double* const rot_s, int* const rot_mate, const int t, int& cur_out,
+                                             int& sweeps_out, double& off_out) {
+    int cur = 0, sweeps = 0;
+    double off_f;
+    for (;;) {
+        const double* const A = mat + cur * kMatDoubles;
+        double osq = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+            if (i < j && j < De) { const double v = A[i * kMatStride + j]; osq += 2.0 * v * v; }
+        }
+        off_f = sqrt(block_sum256(osq, red, t));                     // the same value in every thread: the decision is uniform
+        if (off_f <= kSpectrumTol * norm_c || sweeps == kSpectrumMaxSweeps) break;
+        const int n1 = De - 1;
+        for (int round = 0; round < n1; ++round) {
+            const double* const Ac = mat + cur * kMatDoubles;
+            double* const An = mat + (cur ^ 1) * kMatDoubles;
+            if (t < De / 2) {
+                const int p = t == 0 ? round : (round + t) % n1;
+                const int q = t == 0 ? n1 : (round - t + n1) % n1;
+                const double apq = Ac[p * kMatStride + q];
+                double cs = 1.0, sn = 0.0;
+                if (apq != 0.0) {
+                    const double theta = (Ac[q * kMatStride + q] - Ac[p * kMatStride + p]) / (2.0 * apq);
+                    const double ath = fabs(theta);
+                    const double tt = ath > 1e150 ? 0.5 / theta : copysign(1.0, theta) / (ath + sqrt(theta * theta + 1.0));
+                    cs = 1.0 / sqrt(tt * tt + 1.0);
+                    sn = tt * cs;
+                }
+                rot_c[p] = cs; rot_c[q] = cs;
+                rot_s[p] = -sn; rot_s[q] = sn;                       // new column i = c col_i + s_i col_mate(i)
+                rot_mate[p] = q; rot_mate[q] = p;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+                if (i <= j && j < De) {
+                    const int mi = rot_mate[i], mj = rot_mate[j];
+                    const double ci = rot_c[i], si = rot_s[i], cj = rot_c[j], sj = rot_s[j];
+                    const double v = ci * (cj * Ac[i * kMatStride + j] + sj * Ac[i * kMatStride + mj]) +
+                                     si * (cj * Ac[mi * kMatStride + j] + sj * Ac[mi * kMatStride + mj]);
+                    An[i * kMatStride + j] = v;
+                    An[j * kMatStride + i] = v;
+                }
+            }
+            if constexpr (VEC) {
+                const double* const Vc = vec + cur * kMatDoubles;
+                double* const Vn = vec + (cur ^ 1) * kMatDoubles;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+                    if (i < De && j < De) Vn[i * kMatStride + j] = rot_c[j] * Vc[i * kMatStride + j] + rot_s[j] * Vc[i * kMatStride + rot_mate[j]];
+                }
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        ++sweeps;
+    }
+    cur_out = cur; sweeps_out = sweeps; off_out = off_f;
+}
+
+// The whole record of one set.  `smem`: the tile while the rows are summed, then the two Jacobi buffers and, with VEC, the two
+// eigenvector buffers behind them.  src is uniform over the workgroup; an EVENT kernel carries the two drawing sources, the rows
+// kernel the explicit one.  VEC appends V (row-major, column k the eigenvector of eigenvalue k, its largest component positive) to
+// the record; what comes before it is the VEC = false record, bit for bit (V never feeds back into A).
+template <bool EVENT, int DP, int LP, bool SIG, bool VEC>
 __device__ __forceinline__ void cov_spectrum_set(const RowCtx& rc, const int src, const int rows, const int D, double* const out) {
     __shared__ __attribute__((aligned(16))) float smem[256 * kTileStride];
     __shared__ double red[256];
     __shared__ double S1[kSpectrumMaxDim], rot_c[kSpectrumMaxDim], rot_s[kSpectrumMaxDim], eig[kSpectrumMaxDim];
     __shared__ int rot_mate[kSpectrumMaxDim];
-    static_assert(sizeof(float) * 256 * kTileStride >= sizeof(double) * 2 * kSpectrumMaxDim * kMatStride, "the Jacobi buffers reuse the tile");
+    static_assert(sizeof(float) * 256 * kTileStride >= sizeof(double) * 2 * kMatDoubles, "the Jacobi buffers reuse the tile");
+    static_assert(!VEC || sizeof(float) * 256 * kTileStride >= sizeof(double) * 4 * kMatDoubles, "and so do the two eigenvector buffers");
 
     const int t = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -253,62 +348,23 @@ __device__ __forceinline__ void cov_spectrum_set(const RowCtx& rc, const int src
         }
     }
     if (t < D) out[D + t] = S1[t] / n;
-    const double norm_c = sqrt(block_sum256(sq, red, t));           // its barriers also publish the first buffer
-
-    // ---- cyclic Jacobi, round-robin: index De - 1 stays, the others turn ------------------------------------------------------------
-    int cur = 0, sweeps = 0;
-    double off_f;
-    for (;;) {
-        const double* const A = mat + cur * kSpectrumMaxDim * kMatStride;
-        double osq = 0.0;
+    double* const vec = mat + 2 * kMatDoubles;                     // behind S2: V starts as I
+    if constexpr (VEC) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
-            if (i < j && j < De) { const double v = A[i * kMatStride + j]; osq += 2.0 * v * v; }
+            vec[i * kMatStride + j] = i == j ? 1.0 : 0.0;
         }
-        off_f = sqrt(block_sum256(osq, red, t));                     // the same value in every thread: the decision is uniform
-        if (off_f <= kSpectrumTol * norm_c || sweeps == kSpectrumMaxSweeps) break;
-        const int n1 = De - 1;
-        for (int round = 0; round < n1; ++round) {
-            const double* const Ac = mat + cur * kSpectrumMaxDim * kMatStride;
-            double* const An = mat + (cur ^ 1) * kSpectrumMaxDim * kMatStride;
-            if (t < De / 2) {
-                const int p = t == 0 ? round : (round + t) % n1;
-                const int q = t == 0 ? n1 : (round - t + n1) % n1;
-                const double apq = Ac[p * kMatStride + q];
-                double cs = 1.0, sn = 0.0;
-                if (apq != 0.0) {
-                    const double theta = (Ac[q * kMatStride + q] - Ac[p * kMatStride + p]) / (2.0 * apq);
-                    const double ath = fabs(theta);
-                    const double tt = ath > 1e150 ? 0.5 / theta : copysign(1.0, theta) / (ath + sqrt(theta * theta + 1.0));
-                    cs = 1.0 / sqrt(tt * tt + 1.0);
-                    sn = tt * cs;
-                }
-                rot_c[p] = cs; rot_c[q] = cs;
-                rot_s[p] = -sn; rot_s[q] = sn;                       // new column i = c col_i + s_i col_mate(i)
-                rot_mate[p] = q; rot_mate[q] = p;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
-                if (i <= j && j < De) {
-                    const int mi = rot_mate[i], mj = rot_mate[j];
-                    const double ci = rot_c[i], si = rot_s[i], cj = rot_c[j], sj = rot_s[j];
-                    const double v = ci * (cj * Ac[i * kMatStride + j] + sj * Ac[i * kMatStride + mj]) +
-                                     si * (cj * Ac[mi * kMatStride + j] + sj * Ac[mi * kMatStride + mj]);
-                    An[i * kMatStride + j] = v;
-                    An[j * kMatStride + i] = v;
-                }
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
-        ++sweeps;
     }
+    const double norm_c = sqrt(block_sum256(sq, red, t));           // its barriers also publish the first buffer (and V)
+
+    // ---- cyclic Jacobi, round-robin: index De - 1 stays, the others turn ------------------------------------------------------------
+    int cur, sweeps;
+    double off_f;
+    jacobi_solve<VEC>(mat, vec, De, norm_c, red, rot_c, rot_s, rot_mate, t, cur, sweeps, off_f);
 
     // ---- eigenvalues ascending: the rank of a diagonal element is the count of those before it, ties by index ---------------------
-    const double* const A = mat + cur * kSpectrumMaxDim * kMatStride;
+    const double* const A = mat + cur * kMatDoubles;
     if (t < kSpectrumMaxDim) eig[t] = t < D ? A[t * kMatStride + t] : 0.0;
     __syncthreads();
     if (t < D) {
@@ -319,23 +375,49 @@ __device__ __forceinline__ void cov_spectrum_set(const RowCtx& rc, const int src
             rank += (o < e || (o == e && j < t)) ? 1 : 0;
         }
         out[rank] = e;
+        if constexpr (VEC) {
+            // column t goes to column `rank` with its component of largest magnitude positive (a tie: the lowest row).  The rotation
+            // tables are dead: they carry the rank and the sign to the stores below.
+            const double* const V = vec + cur * kMatDoubles;
+            double big = 0.0, at = 1.0;
+            for (int i = 0; i < D; ++i) {
+                const double v = V[i * kMatStride + t];
+                if (fabs(v) > big) { big = fabs(v); at = v; }
+            }
+            rot_mate[t] = rank;
+            rot_s[t] = at < 0.0 ? -1.0 : 1.0;
+        }
     }
     if (t < 4) {
         const double tail = t == 0 ? (double)sweeps : (t == 1 ? off_f : (t == 2 ? norm_c : n));
         out[2 * D + D * D + t] = tail;
     }
+    if constexpr (VEC) {
+        __syncthreads();
+        const double* const V = vec + cur * kMatDoubles;
+        double* const vout = out + 2 * D + D * D + 4;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+            if (i < D && j < D) vout[i * D + rot_mate[j]] = rot_s[j] * V[i * kMatStride + j];
+        }
+    }
 }
 
-__global__ __launch_bounds__(256) void cov_spectrum_rows_kernel(const SpectrumArgs a) {
+template <bool VEC>
+__device__ __forceinline__ void rows_kernel_body(const SpectrumArgs& a) {
     const long long s = blockIdx.x;
     RowCtx rc{};
     rc.xr = a.x + s * a.x_stride;
     rc.D = a.D;
-    cov_spectrum_set<false, kSpectrumMaxDim, 4, false>(rc, SRC_EXPLICIT, a.rows, a.D, a.out + s * a.out_stride);
+    cov_spectrum_set<false, kSpectrumMaxDim, 4, false, VEC>(rc, SRC_EXPLICIT, a.rows, a.D, a.out + s * a.out_stride);
 }
 
+__global__ __launch_bounds__(256) void cov_spectrum_rows_kernel(const SpectrumArgs a) { rows_kernel_body<false>(a); }
+__global__ __launch_bounds__(256) void cov_eigen_rows_kernel(const SpectrumArgs a) { rows_kernel_body<true>(a); }
+
 // grid (n, 2): blockIdx.y = 0 the fake side, 1 the real side of replica blockIdx.x
-template <int DP, int LP, bool SIG>
+template <int DP, int LP, bool SIG, bool VEC = false>
 __global__ __launch_bounds__(256) void spectrum_event_kernel(const SpectrumArgs a) {
     using G = ParamImage<DP, LP, SIG>;
     __shared__ __attribute__((aligned(16))) float W[G::N];
@@ -358,14 +440,15 @@ __global__ __launch_bounds__(256) void spectrum_event_kernel(const SpectrumArgs 
         rc.ssigma = expf(0.5f * a.sample_eps[r]);
     }
     __syncthreads();
-    const long long len = (long long)D * D + 2 * D + 4;
-    cov_spectrum_set<true, DP, LP, SIG>(rc, real ? SRC_REAL : SRC_FAKE, a.rows, D, a.out + r * a.out_stride + (real ? len : 0));
+    const long long len = (long long)D * D * (VEC ? 2 : 1) + 2 * D + 4;
+    cov_spectrum_set<true, DP, LP, SIG, VEC>(rc, real ? SRC_REAL : SRC_FAKE, a.rows, D, a.out + r * a.out_stride + (real ? len : 0));
 }
 
 // ---- variant table of the fused event: linear_stats.hip's (the padded shapes of mfma_geom.h, each side rounded up to 4) ----------
 typedef void (*SpectrumKernel)(const SpectrumArgs);
-struct SpectrumVariant { int dp, lp, sig; SpectrumKernel fn; };
-#define VAEK_SPECTRUM_ROW(DP, LP, SIG, EXACT) {up4(DP), up4(LP), SIG, spectrum_event_kernel<up4(DP), up4(LP), (SIG) != 0>},
+struct SpectrumVariant { int dp, lp, sig; SpectrumKernel fn, fn_vec; };
+#define VAEK_SPECTRUM_ROW(DP, LP, SIG, EXACT) \
+    {up4(DP), up4(LP), SIG, spectrum_event_kernel<up4(DP), up4(LP), (SIG) != 0>, spectrum_event_kernel<up4(DP), up4(LP), (SIG) != 0, true>},
 static const SpectrumVariant kSpectrumVariants[] = {VAEK_MFMA_SHAPES(VAEK_SPECTRUM_ROW)};
 #undef VAEK_SPECTRUM_ROW
 
@@ -378,7 +461,119 @@ static const SpectrumVariant* pick_spectrum(const vaek_ctx* c) {
 }
 
 static int64_t spectrum_record_len(const vaek_ctx* c) { return (int64_t)c->D * c->D + 2 * (int64_t)c->D + 4; }
+static int64_t eigen_record_len(const vaek_ctx* c) { return spectrum_record_len(c) + (int64_t)c->D * c->D; }
 static int spectrum_max_sets() { return 2 * resident_max_replicas(); }
+
+// ---- principal angles between two eigenbases (vaek_subspace_angles) ----------------------------------------------------------------
+// Pair p: U = the ka eigenvectors of record a's largest eigenvalues, W = the kb of record b's (the last columns of the V blocks an
+// EARLIER launch stored).  M = U^T W, R = W - U M formed explicitly (never I - M^T M, which loses small angles), G = R^T R for i <= j,
+// mirrored, and G's eigenvalues -- sin^2 of the principal angles -- by jacobi_solve, the covariance solve's own text.  All float64 in LDS.
+struct SubspaceArgs {
+    const double* a; long long a_stride;
+    const double* b; long long b_stride;
+    double* out; long long out_stride;
+    int D, ka, kb;
+};
+
+__global__ __launch_bounds__(256) void subspace_angles_kernel(const SubspaceArgs s) {
+    __shared__ double mat[2 * kMatDoubles];
+    __shared__ double U[kMatDoubles], W[kMatDoubles], M[kMatDoubles], R[kMatDoubles];
+    __shared__ double red[256];
+    __shared__ double rot_c[kSpectrumMaxDim], rot_s[kSpectrumMaxDim], eig[kSpectrumMaxDim];
+    __shared__ int rot_mate[kSpectrumMaxDim];
+
+    const int t = threadIdx.x;
+    const long long p = blockIdx.x;
+    const int D = s.D, ka = s.ka, kb = s.kb;
+    const long long v0 = (long long)D * D + 2 * D + 4;               // V behind the spectrum record
+    const double* const va = s.a + p * s.a_stride + v0;
+    const double* const vb = s.b + p * s.b_stride + v0;
+    double* const out = s.out + p * s.out_stride;
+
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+        U[i * kMatStride + j] = (i < D && j < ka) ? va[i * D + D - ka + j] : 0.0;
+        W[i * kMatStride + j] = (i < D && j < kb) ? vb[i * D + D - kb + j] : 0.0;
+    }
+    __syncthreads();
+
+    // ---- how far the two bases are from orthonormal, M = U^T W ---------------------------------------------------------------------
+    double dev = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+        if (i <= j && j < ka) {
+            double uu = 0.0, ww = 0.0;
+            for (int r = 0; r < D; ++r) {
+                uu = fma(U[r * kMatStride + i], U[r * kMatStride + j], uu);
+                ww = fma(W[r * kMatStride + i], W[r * kMatStride + j], ww);
+            }
+            const double id = i == j ? 1.0 : 0.0;
+            dev = fmax(dev, fabs(uu - id));
+            if (j < kb) dev = fmax(dev, fabs(ww - id));
+        }
+        double m = 0.0;
+        if (i < ka && j < kb)
+            for (int r = 0; r < D; ++r) m = fma(U[r * kMatStride + i], W[r * kMatStride + j], m);
+        M[i * kMatStride + j] = m;
+    }
+    const double orth = block_max256(dev, red, t);                   // its barriers also publish M
+
+    // ---- R = W - U M and the sum of its squares ----------------------------------------------------------------------------------------
+    double rsq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+        double r = 0.0;
+        if (i < D && j < kb) {
+            double um = 0.0;
+            for (int u = 0; u < ka; ++u) um = fma(U[i * kMatStride + u], M[u * kMatStride + j], um);
+            r = W[i * kMatStride + j] - um;
+        }
+        R[i * kMatStride + j] = r;
+        rsq += r * r;
+    }
+    const double frob2 = block_sum256(rsq, red, t);                  // its barriers also publish R
+
+    // ---- G = R^T R (i <= j, mirrored), zero outside kb x kb ----------------------------------------------------------------------------
+    double sq = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
+        if (i <= j) {
+            double v = 0.0;
+            if (j < kb)
+                for (int r = 0; r < D; ++r) v = fma(R[r * kMatStride + i], R[r * kMatStride + j], v);
+            mat[i * kMatStride + j] = v;
+            mat[j * kMatStride + i] = v;
+            sq += i == j ? v * v : 2.0 * v * v;
+        }
+    }
+    const double norm_g = sqrt(block_sum256(sq, red, t));            // its barriers also publish G
+
+    int cur, sweeps;
+    double off_f;
+    jacobi_solve<false>(mat, nullptr, kb + (kb & 1), norm_g, red, rot_c, rot_s, rot_mate, t, cur, sweeps, off_f);
+
+    // ---- sin^2 ascending: counting ranks, ties by index; nothing is clamped --------------------------------------------------------------
+    const double* const A = mat + cur * kMatDoubles;
+    if (t < kSpectrumMaxDim) eig[t] = t < kb ? A[t * kMatStride + t] : 0.0;
+    __syncthreads();
+    if (t < kb) {
+        const double e = eig[t];
+        int rank = 0;
+        for (int j = 0; j < kb; ++j) {
+            const double o = eig[j];
+            rank += (o < e || (o == e && j < t)) ? 1 : 0;
+        }
+        out[rank] = e;
+    }
+    if (t < 4) {
+        const double tail = t == 0 ? frob2 : (t == 1 ? (double)sweeps : (t == 2 ? off_f : orth));
+        out[kb + t] = tail;
+    }
+}
 
 }  // namespace vaek
 
@@ -401,9 +596,9 @@ int vaek_cov_spectrum_record_len(const vaek_ctx* ctx, int64_t* doubles) {
 int vaek_cov_spectrum_max_sets(void) { return spectrum_max_sets(); }
 int vaek_cov_spectrum_max_sweeps(void) { return kSpectrumMaxSweeps; }
 
-int vaek_cov_spectrum_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t rows, int64_t x_stride, double* out, int64_t out_stride,
-                           void* stream) {
-    const char* who = "vaek_cov_spectrum_rows";
+// vaek_cov_spectrum_rows and, with `vec`, vaek_cov_eigen_rows: one refusal list, one launch
+static int spectrum_rows_call(const char* who, bool vec, vaek_ctx* ctx, const float* x, int32_t n, int32_t rows, int64_t x_stride, double* out,
+                              int64_t out_stride, void* stream) {
     ProfBind pb(ctx);
     if (!ctx || !x || !out) { set_error("%s: null context, x or out", who); return VAEK_ERR_INVALID; }
     if (ctx->D > kSpectrumMaxDim) {
@@ -422,9 +617,10 @@ int vaek_cov_spectrum_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t row
         set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)x_stride, (long long)rows * ctx->D);
         return VAEK_ERR_INVALID;
     }
-    const int64_t len = spectrum_record_len(ctx);
+    const int64_t len = vec ? eigen_record_len(ctx) : spectrum_record_len(ctx);
     if (out_stride < len) {
-        set_error("%s: out_stride %lld < record length %lld (vaek_cov_spectrum_record_len)", who, (long long)out_stride, (long long)len);
+        set_error("%s: out_stride %lld < record length %lld (%s)", who, (long long)out_stride, (long long)len,
+                  vec ? "vaek_cov_eigen_record_len" : "vaek_cov_spectrum_record_len");
         return VAEK_ERR_INVALID;
     }
     if (((uintptr_t)out & 7u) != 0) { set_error("%s: out is not 8-byte aligned", who); return VAEK_ERR_INVALID; }
@@ -432,10 +628,26 @@ int vaek_cov_spectrum_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t row
     a.x = x; a.x_stride = x_stride; a.out = out; a.out_stride = out_stride; a.rows = rows; a.D = ctx->D;
     hipStream_t st = (hipStream_t)stream;
     {
-        ProfScope ps("cov_spectrum_rows", st);
-        launch_k(ps, cov_spectrum_rows_kernel, dim3((unsigned)n), dim3(256), 0, st, a);
+        ProfScope ps(vec ? "cov_eigen_rows" : "cov_spectrum_rows", st);
+        launch_k(ps, vec ? cov_eigen_rows_kernel : cov_spectrum_rows_kernel, dim3((unsigned)n), dim3(256), 0, st, a);
     }
     VAEK_HIP_CHECK(hipGetLastError());
+    return VAEK_OK;
+}
+
+int vaek_cov_spectrum_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t rows, int64_t x_stride, double* out, int64_t out_stride,
+                           void* stream) {
+    return spectrum_rows_call("vaek_cov_spectrum_rows", false, ctx, x, n, rows, x_stride, out, out_stride, stream);
+}
+
+int vaek_cov_eigen_rows(vaek_ctx* ctx, const float* x, int32_t n, int32_t rows, int64_t x_stride, double* out, int64_t out_stride,
+                        void* stream) {
+    return spectrum_rows_call("vaek_cov_eigen_rows", true, ctx, x, n, rows, x_stride, out, out_stride, stream);
+}
+
+int vaek_cov_eigen_record_len(const vaek_ctx* ctx, int64_t* doubles) {
+    if (!ctx || !doubles) { set_error("vaek_cov_eigen_record_len: null argument"); return VAEK_ERR_INVALID; }
+    *doubles = eigen_record_len(ctx);
     return VAEK_OK;
 }
 
@@ -445,9 +657,10 @@ int vaek_supports_spectrum_event(const vaek_ctx* ctx, int32_t kind, int32_t* yes
     return VAEK_OK;
 }
 
-int vaek_spectrum_event_replicas(vaek_ctx* ctx, const float* params, const vaek_spectrum_event* ev, int32_t kind, const float* A, int32_t dd,
-                                 int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream) {
-    const char* who = "vaek_spectrum_event_replicas";
+// vaek_spectrum_event_replicas and, with `vec`, vaek_eigen_event_replicas: one refusal list, one launch
+static int spectrum_event_call(const char* who, bool vec, vaek_ctx* ctx, const float* params, const vaek_spectrum_event* ev, int32_t kind,
+                               const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
+                               void* stream) {
     ProfBind pb(ctx);
     if (!ctx || !params || !ev) { set_error("%s: null context, params or event", who); return VAEK_ERR_INVALID; }
     if (ev->struct_size != (int32_t)sizeof(vaek_spectrum_event)) {
@@ -472,10 +685,10 @@ int vaek_spectrum_event_replicas(vaek_ctx* ctx, const float* params, const vaek_
         set_error("%s: x_seeds, x_steps, z_seeds, z_steps, sample_eps or out is NULL", who);
         return VAEK_ERR_INVALID;
     }
-    const int64_t len = spectrum_record_len(ctx);
+    const int64_t len = vec ? eigen_record_len(ctx) : spectrum_record_len(ctx);
     if (ev->state_stride < ctx->P || ev->out_stride < 2 * len) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < two records of %lld (vaek_cov_spectrum_record_len)", who,
-                  (long long)ev->state_stride, (long long)ctx->P, (long long)ev->out_stride, (long long)len);
+        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < two records of %lld (%s)", who, (long long)ev->state_stride,
+                  (long long)ctx->P, (long long)ev->out_stride, (long long)len, vec ? "vaek_cov_eigen_record_len" : "vaek_cov_spectrum_record_len");
         return VAEK_ERR_INVALID;
     }
     if (((uintptr_t)ev->out & 7u) != 0) { set_error("%s: out is not 8-byte aligned", who); return VAEK_ERR_INVALID; }
@@ -491,11 +704,62 @@ int vaek_spectrum_event_replicas(vaek_ctx* ctx, const float* params, const vaek_
     fill_draw_args(&a.gen, ctx, ev->rows, kind, A, dd, did, pad, var_added, x_tag);
     hipStream_t st = (hipStream_t)stream;
     {
-        ProfScope ps("spectrum_event_replicas", st);
-        launch_k(ps, var->fn, dim3((unsigned)ev->n, 2u), dim3(256), 0, st, a);
+        ProfScope ps(vec ? "eigen_event_replicas" : "spectrum_event_replicas", st);
+        launch_k(ps, vec ? var->fn_vec : var->fn, dim3((unsigned)ev->n, 2u), dim3(256), 0, st, a);
     }
     VAEK_HIP_CHECK(hipGetLastError());
     return VAEK_OK;
 }
 
+int vaek_spectrum_event_replicas(vaek_ctx* ctx, const float* params, const vaek_spectrum_event* ev, int32_t kind, const float* A, int32_t dd,
+                                 int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream) {
+    return spectrum_event_call("vaek_spectrum_event_replicas", false, ctx, params, ev, kind, A, dd, did, pad, var_added, x_tag, z_tag, stream);
+}
+
+int vaek_eigen_event_replicas(vaek_ctx* ctx, const float* params, const vaek_spectrum_event* ev, int32_t kind, const float* A, int32_t dd,
+                              int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream) {
+    return spectrum_event_call("vaek_eigen_event_replicas", true, ctx, params, ev, kind, A, dd, did, pad, var_added, x_tag, z_tag, stream);
+}
+
+int vaek_subspace_record_len(int32_t kb) { return kb + 4; }
+
+int vaek_subspace_angles(vaek_ctx* ctx, const double* a, int64_t a_stride, const double* b, int64_t b_stride, int32_t n, int32_t ka,
+                         int32_t kb, double* out, int64_t out_stride, void* stream) {
+    const char* who = "vaek_subspace_angles";
+    ProfBind pb(ctx);
+    if (!ctx || !a || !b || !out) { set_error("%s: null context, a, b or out", who); return VAEK_ERR_INVALID; }
+    if (ctx->D > kSpectrumMaxDim) {
+        set_error("%s: data_dim %d, need <= %d (see vaek_supports_cov_spectrum)", who, ctx->D, kSpectrumMaxDim);
+        return VAEK_ERR_INVALID;
+    }
+    if (n < 1 || n > spectrum_max_sets()) {
+        set_error("%s: %d pairs, need 1 .. %d (vaek_cov_spectrum_max_sets)", who, n, spectrum_max_sets());
+        return VAEK_ERR_INVALID;
+    }
+    if (kb < 1 || kb > ka || ka > ctx->D) {
+        set_error("%s: ka %d, kb %d: need 1 <= kb <= ka <= data_dim = %d", who, ka, kb, ctx->D);
+        return VAEK_ERR_INVALID;
+    }
+    const int64_t len = eigen_record_len(ctx);
+    if (a_stride < len || b_stride < len) {
+        set_error("%s: a_stride %lld or b_stride %lld < record length %lld (vaek_cov_eigen_record_len)", who, (long long)a_stride,
+                  (long long)b_stride, (long long)len);
+        return VAEK_ERR_INVALID;
+    }
+    if (out_stride < kb + 4) {
+        set_error("%s: out_stride %lld < record length %d (vaek_subspace_record_len)", who, (long long)out_stride, kb + 4);
+        return VAEK_ERR_INVALID;
+    }
+    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 7u) != 0) { set_error("%s: a, b or out is not 8-byte aligned", who); return VAEK_ERR_INVALID; }
+    SubspaceArgs s{};
+    s.a = a; s.a_stride = a_stride; s.b = b; s.b_stride = b_stride; s.out = out; s.out_stride = out_stride;
+    s.D = ctx->D; s.ka = ka; s.kb = kb;
+    hipStream_t st = (hipStream_t)stream;
+    {
+        ProfScope ps("subspace_angles", st);
+        launch_k(ps, subspace_angles_kernel, dim3((unsigned)n), dim3(256), 0, st, s);
+    }
+    VAEK_HIP_CHECK(hipGetLastError());
+    return VAEK_OK;
+}
 }  // extern "C"

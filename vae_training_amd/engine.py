@@ -442,7 +442,7 @@ class Engine:
     def cov_spectrum_max_sweeps(self):
         return int(self.lib.vaek_cov_spectrum_max_sweeps())
 
-    def cov_spectrum_rows(self, x, rows, out, n=None, x_stride=None, out_stride=None):
+    def cov_spectrum_rows(self, x, rows, out, n=None, x_stride=None, out_stride=None, _vec=False):
         """The covariance spectrum of EACH of n sets of `rows` float32 rows of D columns in one launch, workgroup s turning set s into
         record s (vaek_cov_spectrum_rows).  x: float32 [n, rows, D] (or [rows, D]: one set), out: float64 [n, out_stride >=
         cov_spectrum_record_len] (or a raw device address) -- device tensors; n and the strides default to the tensors' shapes.  Asynchronous; capturable."""
@@ -455,7 +455,42 @@ class Engine:
         if out_stride is None:
             out_stride = 0 if out is None or isinstance(out, int) else out.shape[-1]
         op = None if out is None else C.c_void_p(out if isinstance(out, int) else out.data_ptr())
-        _lib.check(self.lib.vaek_cov_spectrum_rows(self.h, _ptr(x), int(n), int(rows), int(x_stride), op, int(out_stride), _stream()))
+        fn = self.lib.vaek_cov_eigen_rows if _vec else self.lib.vaek_cov_spectrum_rows
+        _lib.check(fn(self.h, _ptr(x), int(n), int(rows), int(x_stride), op, int(out_stride), _stream()))
+
+    @property
+    def cov_eigen_record_len(self):
+        """Doubles in one eigen record (vaek_cov_eigen_record_len): 2 D^2 + 2 D + 4 = the spectrum record, then V row-major (column k
+        the eigenvector of eigenvalue k, its component of largest magnitude positive)."""
+        n = C.c_int64()
+        _lib.check(self.lib.vaek_cov_eigen_record_len(self.h, C.byref(n)))
+        return int(n.value)
+
+    def cov_eigen_rows(self, x, rows, out, n=None, x_stride=None, out_stride=None):
+        """cov_spectrum_rows with eigenvectors (vaek_cov_eigen_rows): out is float64 [n, out_stride >= cov_eigen_record_len]; the first
+        cov_spectrum_record_len doubles of a record are bitwise cov_spectrum_rows' record.  Asynchronous; capturable."""
+        self.cov_spectrum_rows(x, rows, out, n=n, x_stride=x_stride, out_stride=out_stride, _vec=True)
+
+    def subspace_record_len(self, kb):
+        """Doubles in one record of subspace_angles (vaek_subspace_record_len): kb + 4."""
+        return int(self.lib.vaek_subspace_record_len(int(kb)))
+
+    def subspace_angles(self, a, b, ka, kb, out, n=None, a_stride=None, b_stride=None, out_stride=None):
+        """The principal angles between the span of the ka leading eigenvectors of eigen record a[p] and the kb leading ones of b[p],
+        1 <= kb <= ka <= D, for each of n pairs in one launch (vaek_subspace_angles).  a, b: float64 [n, stride >=
+        cov_eigen_record_len] written by an EARLIER call (or raw device addresses); out: float64 [n, out_stride >= kb + 4]: sin^2
+        ascending, |sin Theta|_F^2, sweeps, off_F, the bases' distance from orthonormal.  Asynchronous; capturable."""
+        def addr(v):
+            assert v is None or isinstance(v, int) or v.dtype == torch.float64
+            return None if v is None else C.c_void_p(v if isinstance(v, int) else v.data_ptr())
+
+        def stride(v, given):
+            return int((0 if v is None or isinstance(v, int) else v.shape[-1]) if given is None else given)
+
+        if n is None:
+            n = 1 if a is None or isinstance(a, int) or a.dim() < 2 else a.shape[0]
+        _lib.check(self.lib.vaek_subspace_angles(self.h, addr(a), stride(a, a_stride), addr(b), stride(b, b_stride), int(n), int(ka), int(kb),
+                                                 addr(out), stride(out, out_stride), _stream()))
 
     def supports_spectrum_event(self, kind):
         """True where spectrum_event_replicas covers this engine and dataset kind: exactly where supports_log_likelihood does."""
@@ -464,7 +499,7 @@ class Engine:
         return bool(f.value)
 
     def spectrum_event_replicas(self, params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
-                                a_stride=0, x_tag=5, z_tag=6, n=None, state_stride=None, out_stride=None, struct_size=None):
+                                a_stride=0, x_tag=5, z_tag=6, n=None, state_stride=None, out_stride=None, struct_size=None, _vec=False):
         """The covariance spectra of a generated and of a real batch of EACH of n linear VAEs of this engine's shape in one launch of
         (n, 2) workgroups (vaek_spectrum_event_replicas): `rows` real rows drawn under (x_seeds[r], x_steps[r], x_tag) and `rows`
         latent rows under (z_seeds[r], z_steps[r], z_tag) exactly as make_batch draws them, the fake batch sampled from the latents
@@ -484,8 +519,15 @@ class Engine:
         ev.a_stride = int(a_stride)
         ev.out = None if out is None else (out if isinstance(out, int) else out.data_ptr())
         ev.out_stride = int((0 if out is None or isinstance(out, int) else out.shape[-1]) if out_stride is None else out_stride)
-        _lib.check(self.lib.vaek_spectrum_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
-                                                         float(var_added), int(x_tag), int(z_tag), _stream()))
+        fn = self.lib.vaek_eigen_event_replicas if _vec else self.lib.vaek_spectrum_event_replicas
+        _lib.check(fn(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(x_tag),
+                      int(z_tag), _stream()))
+
+    def eigen_event_replicas(self, params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out, **kw):
+        """spectrum_event_replicas with eigenvectors (vaek_eigen_event_replicas): out is float64 [n, out_stride >= 2 *
+        cov_eigen_record_len]: the fake eigen record, then the real one.  Asynchronous; capturable."""
+        self.spectrum_event_replicas(params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
+                                     _vec=True, **kw)
 
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""

@@ -129,7 +129,8 @@ class GenerativeModel(Model):
         the importance-weighted log-likelihood of this model on K samples per row (trainer.ReplicaLogLik, one library call), which
         neither splits the model's key nor advances a draw counter of the run; `mlp_log_likelihood_samples` does the same for a
         three-hidden-layer MLP model (trainer.ReplicaLogLikMlp3); `eigenvalues` (run.py --eigenvalues) adds the covariance spectra of
-        a generated and a real batch (trainer.ReplicaSpectrum), which leaves the run alone in the same way."""
+        a generated and a real batch (trainer.ReplicaSpectrum), which leaves the run alone in the same way; `subspace` (run.py
+        --subspace) adds the principal angles between their leading eigenspaces (trainer.ReplicaSubspace) under the same counter."""
         stats = self.compute_stats()
         K = getattr(self, "log_likelihood_samples", None)
         if K:
@@ -143,7 +144,13 @@ class GenerativeModel(Model):
             if getattr(self, "_loglik_mlp3", None) is None:
                 self._loglik_mlp3 = ReplicaLogLikMlp3([self], K)
             stats.update(self._loglik_mlp3.event()[0])
-        if getattr(self, "eigenvalues", False):                    # run.py --eigenvalues: the covariance spectra of a fake and a real batch
+        if getattr(self, "subspace", False):                       # run.py --subspace: eigenvectors too, and the principal angles between
+            from .trainer import ReplicaSubspace                   # the two leading eigenspaces; one device call serves --eigenvalues as well
+            if getattr(self, "_subspace", None) is None:
+                self._subspace = ReplicaSubspace([self], k=getattr(self, "subspace_k", None))
+            st = self._subspace.event()[0]
+            stats.update(st if getattr(self, "eigenvalues", False) else {k: v for k, v in st.items() if k not in ReplicaSubspace.KEYS})
+        elif getattr(self, "eigenvalues", False):                  # run.py --eigenvalues: the covariance spectra of a fake and a real batch
             from .trainer import ReplicaSpectrum
             if getattr(self, "_spectrum", None) is None:
                 self._spectrum = ReplicaSpectrum([self])

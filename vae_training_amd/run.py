@@ -3,7 +3,7 @@
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
---fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples, --eigenvalues."""
+--fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples, --eigenvalues, --subspace."""
 from __future__ import annotations
 
 import argparse
@@ -91,6 +91,13 @@ def build_parser():
                         "without the flag.  Alone or with --sweep_dataset_seeds (one call for all models); float32, one decoder, three "
                         "hidden layers of 64 .. 256 units both ways, D, L <= 32, models x 1000 rows x K at most 2^22; linear models (use "
                         "--log_likelihood_samples), other models and both flags together are refused before any step; single GPU only")
+    p.add_argument("--subspace", dest="subspace", default=None, type=subspace_arg, metavar="auto|K",
+                   help="at every n_print step also evaluate the principal angles between the span of the K leading eigenvectors of "
+                        "cov(generated print batch) and that of cov(real print batch) (trainer.ReplicaSubspace, csrc/cov_spectrum.hip): "
+                        "losses.npz gains 'Subspace Distance' (|sin Theta|_F) and 'Principal Angles' (radians, ascending) per event.  "
+                        "auto: the dimension of the dataset's linear span (linear_gaussian min(dd, did), sigmoid dd + 1, sphere dd).  "
+                        "With --eigenvalues one device call serves both and EigenValues is bitwise what --eigenvalues alone writes.  "
+                        "Needs data_dim <= 32, K in 1 .. data_dim and one GPU; the training run is bitwise the run without the flag")
     p.add_argument("--eigenvalues", dest="eigenvalues", action="store_true",
                    help="at every n_print step also evaluate the covariance spectrum of a generated print batch and of a real one "
                         "(trainer.ReplicaSpectrum, csrc/cov_spectrum.hip): losses.npz gains 'learnt eigenvalue' and 'ground truth "
@@ -120,6 +127,20 @@ def _int_list(text):
     if not vals:
         raise argparse.ArgumentTypeError("an empty list of seeds")
     return vals
+
+
+def subspace_arg(v):
+    """--subspace: "auto" or a positive integer K."""
+    if v == "auto":
+        return v
+    try:
+        k = int(v)
+    except ValueError:
+        k = 0
+    if k < 1:
+        import argparse
+        raise argparse.ArgumentTypeError(f"--subspace takes auto or an integer K >= 1, got {v!r}")
+    return k
 
 
 def parse_arguments(argv=None):
@@ -343,6 +364,23 @@ def check_eigenvalues_model(m):
         raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS} (this model's data_dim: {getattr(eng, 'D', '?')}, world {eng.world})")
 
 
+SUBSPACE_NEEDS = "data_dim <= 32 (vaek_supports_cov_spectrum), K in 1 .. data_dim, -dd / -did <= 16, on one GPU"
+
+
+def check_subspace_model(m, k):
+    """--subspace: refuse, before any step, a model the eigen calls do not cover or a K outside 1 .. data_dim.  Returns K (None: auto)."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    _, _, dd, did, _, _ = m.dataset.device_spec()
+    D = getattr(eng, "D", None)
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_cov_spectrum():
+        raise RuntimeError(f"--subspace needs {SUBSPACE_NEEDS} (this model's data_dim: {D if D is not None else '?'}, world {eng.world})")
+    k = None if k == "auto" else int(k)
+    if k is not None and not 1 <= k <= D:
+        raise RuntimeError(f"--subspace {k} needs {SUBSPACE_NEEDS} (this model's data_dim: {D})")
+    return k
+
+
 def main_sweep(args):
     """--sweep_dataset_seeds: one dataset and one VAEModel per seed, the reference's schedule (model.py:207-222: stats every n_print
     steps, plot + save every n_plot steps and at the last step) for each model at each event, and ONE loop.run between
@@ -393,9 +431,15 @@ def main_sweep(args):
     if getattr(args, "eigenvalues", False):  # before any step
         from .trainer import ReplicaSpectrum
         check_eigenvalues_model(models[0])
-        spectrum = ReplicaSpectrum(models)
+        if getattr(args, "subspace", None) is None:
+            spectrum = ReplicaSpectrum(models)
         for m in models:
             m.eigenvalues = True             # model_save_data writes "EigenValues"
+    if getattr(args, "subspace", None) is not None:      # before any step; with --eigenvalues its one device call serves both
+        from .trainer import ReplicaSubspace
+        spectrum = ReplicaSubspace(models, k=check_subspace_model(models[0], args.subspace))
+        for m in models:
+            m.subspace = True                # model_save_data writes "Subspace Distance" and "Principal Angles"
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
     if fused_stats:
@@ -405,9 +449,14 @@ def main_sweep(args):
     if loglik is not None:
         entry = "vaek_log_likelihood_replicas" if mlp_samples is None else "vaek_mlp3_log_likelihood_replicas"
         print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows ({entry})")
-    if spectrum is not None:
-        entry = "vaek_spectrum_event_replicas" if spectrum.fused else "vaek_cov_spectrum_rows"
+    if spectrum is not None and getattr(args, "eigenvalues", False):
+        entry = ("vaek_eigen_event_replicas" if spectrum.fused else "vaek_cov_eigen_rows") if spectrum.VEC else \
+                ("vaek_spectrum_event_replicas" if spectrum.fused else "vaek_cov_spectrum_rows")
         print(f"Eigenvalue events: {spectrum.rows} generated and {spectrum.rows} real rows per model ({entry})")
+    if spectrum is not None and spectrum.VEC:
+        entry = "vaek_eigen_event_replicas" if spectrum.fused else "vaek_cov_eigen_rows"
+        print(f"Subspace events: the {spectrum.k} leading eigenvectors of {spectrum.rows} generated and {spectrum.rows} real rows per model "
+              f"({entry}, vaek_subspace_angles)")
     for r, m in enumerate(models):
         m._graph_loop = loop.view(r)
         score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
@@ -430,7 +479,8 @@ def main_sweep(args):
                 if extra is not None:
                     stats.update(extra[r])
                 if spectra is not None:
-                    stats.update(spectra[r])
+                    stats.update(spectra[r] if getattr(args, "eigenvalues", False) else
+                                 {k: v for k, v in spectra[r].items() if k not in spectrum.KEYS})
                 m.write_stats(stats)
             if ev % n_plot == 0 or ev == n - 1:
                 m.plot_epoch()
@@ -463,6 +513,9 @@ def main(args):
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1 and getattr(args, "eigenvalues", False):
         raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS}: it does not combine with data parallelism "
+                           f"(step path of a world of {world}: one shard per rank)")
+    if world > 1 and getattr(args, "subspace", None) is not None:
+        raise RuntimeError(f"--subspace needs {SUBSPACE_NEEDS}: it does not combine with data parallelism "
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1:
         import torch
@@ -502,6 +555,10 @@ def main(args):
         check_eigenvalues_model(model)                     # before any step
         model.eigenvalues = True                           # the n_print events add trainer.ReplicaSpectrum([model]).event()
         print(f"Eigenvalue events: {model.print_batch_size} generated and {model.print_batch_size} real rows (csrc/cov_spectrum.hip)")
+    if getattr(args, "subspace", None) is not None:
+        model.subspace_k = check_subspace_model(model, args.subspace)      # before any step
+        model.subspace = True                              # the n_print events add trainer.ReplicaSubspace([model], k).event()
+        print(f"Subspace events: {model.print_batch_size} generated and {model.print_batch_size} real rows (csrc/cov_spectrum.hip)")
     if rank == 0:
         eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
         loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")

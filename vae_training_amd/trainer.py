@@ -42,6 +42,7 @@ t % K == 0, the parameters that step's gradient was evaluated at and the step's 
 the reference never fills.  `trajectory()` / `trajectory(r)` returns them in step order; run() stays one library call."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 
@@ -666,6 +667,7 @@ class ReplicaSpectrum:
     X_TAG, Z_TAG = 5, 6
     NAME = "ReplicaSpectrum"
     OFF_BOUND = 2.0 ** -40
+    VEC = False                        # ReplicaSubspace: the eigen records and entry points
 
     def __init__(self, vae_models, rows=None):
         _replica_setup(self, vae_models, self.NAME, "call", "rows", "evaluates", "train_loop_max_replicas", ReplicaLogLik._shape,
@@ -677,13 +679,20 @@ class ReplicaSpectrum:
                                "one row has no covariance)")
         dev = self.eng.device
         self.D = self.eng.D
-        self.record_len = self.eng.cov_spectrum_record_len
+        self.record_len = self.eng.cov_eigen_record_len if self.VEC else self.eng.cov_spectrum_record_len
         self.fused = bool(self.eng.supports_spectrum_event(self.kind))
-        self.out = torch.zeros(2 * R, self.record_len, dtype=torch.float64, device=dev)      # [R, 2 records] on the fused route
+        self.buf = torch.zeros(2 * R * self.record_len + self._extra_doubles(), dtype=torch.float64, device=dev)
+        self.out = self.buf[:2 * R * self.record_len].view(2 * R, self.record_len)          # [R, 2 records] on the fused route
         if self.fused:
             self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
         else:
             self.stack = torch.zeros(2 * R, self.rows, self.D, dtype=torch.float32, device=dev)
+
+    def _extra_doubles(self):
+        return 0                       # doubles behind the records in the one buffer event() copies to the host
+
+    def _after_solve(self):
+        pass                           # device work between the solve and the copy
 
     def _check_covered(self):
         if not self.eng.supports_cov_spectrum():
@@ -706,9 +715,10 @@ class ReplicaSpectrum:
                 self.params[r].copy_(m.model.flat)
             sd = torch.tensor([_wrap_signed(s, 64) for s in seeds], dtype=torch.int64).to(dev)
             st = torch.tensor([_wrap_signed(s, 32) for s in steps], dtype=torch.int32).to(dev)
-            self.eng.spectrum_event_replicas(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, sd, st, sd, st,
-                                             torch.tensor(eps_in, dtype=torch.float32).to(dev), self.out.view(R, 2 * self.record_len),
-                                             a_stride=self.a_stride, x_tag=self.X_TAG, z_tag=self.Z_TAG)
+            call = self.eng.eigen_event_replicas if self.VEC else self.eng.spectrum_event_replicas
+            call(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, sd, st, sd, st,
+                 torch.tensor(eps_in, dtype=torch.float32).to(dev), self.out.view(R, 2 * self.record_len), a_stride=self.a_stride,
+                 x_tag=self.X_TAG, z_tag=self.Z_TAG)
         else:
             for r, m in enumerate(self.ms):
                 eng = m.model.module.engine(self.rows)                                 # forward takes at most its context's batch
@@ -719,22 +729,88 @@ class ReplicaSpectrum:
                                            tag=self.Z_TAG, want_x=False)
                 fake, _ = eng.forward(m.model.flat, None, z1, z2, sampling=True, eps=eps_in[r], want_mu=False)
                 self.stack[2 * r].copy_(fake)
-            self.eng.cov_spectrum_rows(self.stack, self.rows, self.out)
-        rec = self.out.cpu().numpy()                                                  # the event's ONE device -> host copy
+            (self.eng.cov_eigen_rows if self.VEC else self.eng.cov_spectrum_rows)(self.stack, self.rows, self.out)
+        self._after_solve()
+        host = self.buf.cpu().numpy()                                                 # the event's ONE device -> host copy
+        rec = host[:2 * R * self.record_len].reshape(2 * R, self.record_len)
         stats = []
         for r, m in enumerate(self.ms):
-            st = {}
-            for side, name in enumerate(self.KEYS):                                   # record 2 r: the fake side, 2 r + 1: the real side
-                row = rec[2 * r + side]
-                off, norm = row[2 * D + D * D + 1], row[2 * D + D * D + 2]
-                if not off <= self.OFF_BOUND * norm:
-                    raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the {name} solve stopped at the cap of "
-                                       f"{int(row[2 * D + D * D])} sweeps with off_F = {off:.3e} > 2^-40 |C|_F = {self.OFF_BOUND * norm:.3e}")
-                st[name] = row[:D].copy()
+            st = self._model_stats(r, m, rec, host)
             m.ht_eigen.append(st[self.KEYS[0]])
             m.gt_eigen.append(st[self.KEYS[1]])
             stats.append(st)
         return stats
+
+    def _model_stats(self, r, m, rec, host):
+        D = self.D
+        st = {}
+        for side, name in enumerate(self.KEYS):                                   # record 2 r: the fake side, 2 r + 1: the real side
+            row = rec[2 * r + side]
+            off, norm = row[2 * D + D * D + 1], row[2 * D + D * D + 2]
+            if not off <= self.OFF_BOUND * norm:
+                raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the {name} solve stopped at the cap of "
+                                   f"{int(row[2 * D + D * D])} sweeps with off_F = {off:.3e} > 2^-40 |C|_F = {self.OFF_BOUND * norm:.3e}")
+            st[name] = row[:D].copy()
+        return st
+
+
+class ReplicaSubspace(ReplicaSpectrum):
+    """ReplicaSpectrum with eigenvectors: per model also the principal angles between the span of the k leading eigenvectors of
+    cov(fake batch) and that of cov(real batch) -- whether the generator's mass lies in the subspace the data lives in -- and their
+    distance |sin Theta|_F, the well-defined form of the reference's unused sin_theta_distance (utils.py:317-325).
+
+    Validation, the counter `m._spectrum_draws`, the seed and the tags 5 / 6 are ReplicaSpectrum's, so event() perturbs nothing of the
+    run and its eigenvalues are bitwise ReplicaSpectrum's under the same counter.  k defaults to the dimension of the dataset's linear
+    span: linear_gaussian min(dd, did), sigmoid dd + 1, sphere dd.  Linear models: ONE vaek_eigen_event_replicas call, ONE
+    vaek_subspace_angles call (a = fake, b = real, ka = kb = k) and one device -> host copy; every other model takes the host route
+    (rows into one vaek_cov_eigen_rows call with n = 2R), then the same angles call.  Returns per model "learnt eigenvalue", "ground
+    truth eigenvalue", "Principal Angles" (radians, ascending: arcsin sqrt clip(sin^2, 0, 1)) and "Subspace Distance" (the root of the
+    record's direct sum of squares), and appends the last two to `m.principal_angles` and `m.subspace_distances`.  Raises RuntimeError
+    naming the model where a solve -- of either covariance or of the angles -- ended above 2^-40 of its norm."""
+
+    NAME = "ReplicaSubspace"
+    VEC = True
+    ANGLES, DISTANCE = "Principal Angles", "Subspace Distance"
+
+    def __init__(self, vae_models, k=None, rows=None):
+        self._k_arg = k
+        super().__init__(vae_models, rows=rows)
+
+    @staticmethod
+    def default_k(kind, dd, did):
+        """The dimension of the dataset's linear span: linear_gaussian min(dd, did), sigmoid dd + 1, sphere dd."""
+        return {0: min(dd, did), 1: dd + 1, 2: dd}[int(kind)]
+
+    def _extra_doubles(self):
+        k = self.default_k(self.kind, self.dd, self.did) if self._k_arg is None else int(self._k_arg)
+        if not 1 <= k <= self.D:
+            raise RuntimeError(f"{self.NAME}: k = {k}, need 1 .. data_dim = {self.D}")
+        self.k = k
+        self.angle_len = self.eng.subspace_record_len(k)
+        return self.R * self.angle_len
+
+    def _after_solve(self):
+        R, ln = self.R, self.record_len
+        self.angles = self.buf[2 * R * ln:].view(R, self.angle_len)
+        pairs = self.out.view(R, 2 * ln)                                               # pair r: a = the fake record, b = the real one
+        self.eng.subspace_angles(pairs, pairs[:, ln:], self.k, self.k, self.angles, n=R, a_stride=2 * ln, b_stride=2 * ln)
+
+    def _model_stats(self, r, m, rec, host):
+        st = super()._model_stats(r, m, rec, host)
+        k = self.k
+        row = host[2 * self.R * self.record_len:].reshape(self.R, self.angle_len)[r]
+        sin2, off = row[:k], row[k + 2]
+        norm = float(np.sqrt(np.sum(sin2 * sin2) + off * off))
+        if not off <= self.OFF_BOUND * norm:
+            raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the principal-angle solve stopped at the cap of "
+                               f"{int(row[k + 1])} sweeps with off_F = {off:.3e} > 2^-40 |G|_F = {self.OFF_BOUND * norm:.3e}")
+        st[self.ANGLES] = np.arcsin(np.sqrt(np.clip(sin2, 0.0, 1.0)))
+        st[self.DISTANCE] = float(np.sqrt(row[k]))
+        for name, key in (("principal_angles", self.ANGLES), ("subspace_distances", self.DISTANCE)):
+            if not hasattr(m, name):
+                setattr(m, name, [])
+            getattr(m, name).append(st[key])
+        return st
 
 
 class ReplicaGraphLoop:
