@@ -667,6 +667,66 @@ int vaek_eigen_event_replicas(vaek_ctx* ctx, const float* params, const vaek_spe
 int vaek_subspace_record_len(int32_t kb);
 int vaek_subspace_angles(vaek_ctx* ctx, const double* a, int64_t a_stride, const double* b, int64_t b_stride, int32_t n, int32_t ka,
                          int32_t kb, double* out, int64_t out_stride, void* stream);
+/* EXACT LOG-LIKELIHOOD, EXACT ELBO and POSTERIOR GAP of N one-decoder linear VAEs of the context's shape in one launch
+ * (csrc/cov_spectrum.hip).  Such a model is a linear-Gaussian latent-variable model, so nothing has to be estimated:
+ *   p(x) = N(b_d, K^T K + e^{eps} I)      K = the Decoder kernel [L][D], b_d its bias, eps as in vaek_log_likelihood_replicas
+ * and the ELBO of the diagonal-Gaussian encoder (kernel E [D][L], bias b_e, epsilon_p [L]) is closed form too; their difference is
+ * KL(q(z | x) || p(z | x)) >= 0.  Parameters are float32; every quantity below is float64.  Per model r (ONE workgroup of 256 threads):
+ *   G = K^T K (D x D; element (i, j) one chain over l in l order of exact float64 products of two float32 values, the upper triangle
+ *   computed and mirrored), |G|_F, G = V diag(lambda) V^T by the SOLVE RULE of vaek_cov_spectrum_rows with eigenvectors (the same
+ *   device routine, its ordering, 2^-43 stop and 32-sweep cap; G = 0 ends with 0 sweeps), s_i = max(lambda_i, 0) + e^{eps} (the one
+ *   place that uses G being PSD), logdet = sum_i log s_i, T = sum_l e^{epsilon_p[l]} |K_l|^2.
+ * Per row x (float32, widened):
+ *   c = x - b_d, y = V^T c, quad = sum_i y_i^2 / s_i,          log p(x) = -1/2 (quad + logdet + D log 2 pi)
+ *   mu = x E + b_e, r = mu K + b_d - x,
+ *   ELBO(x) = -1/2 [ e^{-eps} (|r|^2 + T) + D (eps + log 2 pi) ] - 1/2 sum_l ( e^{epsilon_p[l]} + mu_l^2 - 1 - epsilon_p[l] )
+ *   gap(x) = log p(x) - ELBO(x).
+ * The D x D eigenvector form is used because trained decoders are rank-deficient (collapsed latent rows) and e^{eps} is small: V
+ * from Jacobi is orthonormal whatever the rank, where the L x L (Woodbury) form subtracts nearly equal numbers and divides by e^{eps}.
+ * RECORD of vaek_exact_log_likelihood_record_len = 10 + D doubles at out + r * out_stride, written with per-lane vector stores:
+ *   [0] mean log p(x)      [1] mean ELBO      [2] mean gap      [3] eps as used      [4] logdet      [5] sweeps run
+ *   [6] final off_F        [7] |G|_F          [8] (off_F + 64 D 2^-53 |G|_F) e^{-eps}: the bound on the relative error of the
+ *   smallest s_i -- the conditioning of the evaluation, reported, not hidden                          [9] rows
+ *   [10, 10 + D) the eigenvalues of K^T K, ascending, unclamped (counting ranks, ties by index).
+ * row_out (optional; NULL: none): [rows][2] doubles per model at row_out + r * row_stride: log p(x_i), ELBO(x_i).  Doubles between
+ * two records or two row blocks where a stride exceeds the length are not touched; nothing else is written.
+ * Thread t takes rows 256 j + t in j order and keeps three private running sums (log p, ELBO, gap); one fixed binary tree per sum
+ * adds the 256 threads'; a mean is a sum divided by rows.  No workspace, no second launch, no atomic, counter or wait.  So replica
+ * r's record is BITWISE what a call with n = 1 on its slices leaves, two runs are bitwise equal, drawing mode equals explicit mode
+ * on the rows vaek_make_batch writes, the record depends on neither ctx.batch nor row_out.
+ * The two row modes are vaek_log_likelihood_replicas': EXPLICIT ROWS (x != NULL: x + r * x_stride as [rows][D] floats, x_stride == 0
+ * shared) and DRAWING MODE (x == NULL: row i exactly as vaek_make_batch(kind, A + r * a_stride, dd, did, pad, var_added, rows,
+ * row0 = 0, x_seeds[r], step_host = x_steps[r], x_tag) writes x).  rows is 1 .. vaek_log_likelihood_max_rows(), n 1 ..
+ * vaek_train_loop_max_replicas().  Asynchronous on `stream`, allocates nothing, does not synchronise, capturable into a hipGraph;
+ * profile label exact_loglik_replicas.
+ * vaek_supports_exact_log_likelihood: vaek_supports_log_likelihood AND one decoder (the sigmoid second decoder has no closed form)
+ * -- whatever ctx.batch, world and force_generic are.
+ * VAEK_ERR_INVALID (message names vaek_exact_log_likelihood_replicas, nothing touched): a NULL or unsupported context (hidden
+ * layers, bf16, a larger shape, two decoders), NULL params or description, a wrong struct_size, n or rows out of range, a NULL out,
+ * state_stride < P, out_stride below the record length, an out or row_out that is not 8-byte aligned, row_stride < 2 * rows with a
+ * row_out (0 included, unless n == 1); explicit rows: x_stride < 0 or 0 < x_stride < rows * D; drawing mode: NULL x_seeds or x_steps,
+ * a_stride < 0, NULL A for kind 0 or 1, dd or did > 16, dd + pad (+ 1 for kind 1) != data_dim, kind outside 0 .. 2, x_tag >= 2^30. */
+typedef struct vaek_exact_log_likelihood {
+    int32_t struct_size;                  /* = sizeof(vaek_exact_log_likelihood), ABI guard             */
+    int32_t n;                            /* replicas: the launch has n workgroups                      */
+    int32_t rows;                         /* data rows, 1 .. vaek_log_likelihood_max_rows()             */
+    int32_t reserved;
+    int64_t state_stride;                 /* floats between two replicas' params, >= P                  */
+    const uint64_t* x_seeds;              /* device [n]: seed of the rows (drawing mode)                */
+    const uint32_t* x_steps;              /* device [n]: their RNG step (drawing mode)                  */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared (drawing mode)  */
+    double* out;                          /* device: record r at out + r * out_stride                   */
+    int64_t out_stride;                   /* doubles, >= vaek_exact_log_likelihood_record_len           */
+    const float* x;                       /* device [rows][D] per replica: explicit rows; NULL = draw   */
+    int64_t x_stride;                     /* floats between two replicas' rows; 0 = shared              */
+    double* row_out;                      /* device [rows][2] per replica, or NULL                      */
+    int64_t row_stride;                   /* doubles between two replicas' row blocks, >= 2 * rows      */
+} vaek_exact_log_likelihood;
+int vaek_supports_exact_log_likelihood(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_exact_log_likelihood_record_len(const vaek_ctx* ctx, int64_t* doubles);
+int vaek_exact_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_exact_log_likelihood* ll, int32_t kind,
+                                       const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
+                                       void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

@@ -69,7 +69,17 @@ class VaekSpectrumEvent(C.Structure):
     _fields_ = list(VaekStatsEvent._fields_)
 
 
-STATS_RECORD_HEAD = 8      # floats of a stats record in front of the epsilon_p copy: loss, Dkl, mse, eps, two score values, 0, 0
+class VaekExactLogLikelihood(C.Structure):
+    """vaek_exact_log_likelihood of include/vaek.h: the per-replica description of vaek_exact_log_likelihood_replicas (device pointers)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32), ("state_stride", C.c_int64),
+        ("x_seeds", C.c_void_p), ("x_steps", C.c_void_p), ("a_stride", C.c_int64), ("out", C.c_void_p), ("out_stride", C.c_int64),
+        ("x", C.c_void_p), ("x_stride", C.c_int64), ("row_out", C.c_void_p), ("row_stride", C.c_int64),
+    ]
+
+
+EXACT_LOGLIK_RECORD_HEAD = 10      # doubles of an exact log-likelihood record in front of the D eigenvalues of K^T K
+STATS_RECORD_HEAD = 8     # floats of a stats record in front of the epsilon_p copy: loss, Dkl, mse, eps, two score values, 0, 0
 
 
 def trajectory_slot(t, every, cap):
@@ -176,6 +186,10 @@ SIGNATURES = {
                                             _vp]),
     "vaek_subspace_record_len": (C.c_int, [_i32]),
     "vaek_subspace_angles": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "vaek_supports_exact_log_likelihood": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_exact_log_likelihood_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "vaek_exact_log_likelihood_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekExactLogLikelihood), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
+                                                     _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

@@ -529,6 +529,59 @@ class Engine:
         self.spectrum_event_replicas(params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
                                      _vec=True, **kw)
 
+    def supports_exact_log_likelihood(self, kind):
+        """True where exact_log_likelihood_replicas covers this engine and dataset kind: where supports_log_likelihood does AND the
+        model has one decoder (the sigmoid second decoder has no closed form), whatever the engine's batch and world are
+        (vaek_supports_exact_log_likelihood)."""
+        f = C.c_int32()
+        _lib.check(self.lib.vaek_supports_exact_log_likelihood(self.h, int(kind), C.byref(f)))
+        return bool(f.value)
+
+    @property
+    def exact_log_likelihood_record_len(self):
+        """Doubles in one exact log-likelihood record (vaek_exact_log_likelihood_record_len): 10 + D = mean log p(x), mean ELBO, mean
+        gap, eps, logdet, sweeps, off_F, |K^T K|_F, the conditioning figure, rows, then the D eigenvalues of K^T K ascending."""
+        n = C.c_int64()
+        _lib.check(self.lib.vaek_exact_log_likelihood_record_len(self.h, C.byref(n)))
+        return int(n.value)
+
+    def exact_log_likelihood_replicas(self, params, rows, out, kind=2, A=None, dd=0, did=0, pad=0, var_added=0.0, x_seeds=None, x_steps=None,
+                                      x=None, x_stride=None, a_stride=0, x_tag=3, row_out=None, row_stride=None, n=None, state_stride=None,
+                                      out_stride=None, struct_size=None):
+        """The exact log-likelihood, exact ELBO and their gap KL(q(z|x) || p(z|x)) of EACH of n one-decoder linear VAEs of this engine's
+        shape in one launch, workgroup r evaluating model r (vaek_exact_log_likelihood_replicas): float64 throughout, p(x) = N(b_d, K^T K
+        + e^eps I) through the eigenvectors of K^T K.  The rows are the caller's (x: float32 [rows, D] shared by all replicas, or
+        [n, rows, D]) or, with x None, drawn under (x_seeds[r], x_steps[r], x_tag) exactly as make_batch draws them.  params:
+        [n, state_stride] (read only), out: float64 [n, out_stride >= exact_log_likelihood_record_len], row_out: None or float64
+        [n, rows, 2] (log p(x_i), ELBO(x_i)) -- device tensors or raw device addresses; n and the strides default to the tensors'
+        shapes.  Asynchronous; capturable."""
+        def addr(v):
+            assert v is None or isinstance(v, int) or v.dtype == torch.float64
+            return None if v is None else (v if isinstance(v, int) else v.data_ptr())
+
+        ll = _lib.VaekExactLogLikelihood()
+        ll.struct_size = C.sizeof(_lib.VaekExactLogLikelihood) if struct_size is None else int(struct_size)
+        ll.n = int(params.shape[0] if n is None else n)
+        ll.rows = int(rows)
+        ll.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        assert x_seeds is None or x_seeds.dtype == torch.int64
+        assert x_steps is None or x_steps.dtype == torch.int32
+        assert x is None or x.dtype == torch.float32
+        ll.x_seeds, ll.x_steps = _ptr(x_seeds), _ptr(x_steps)
+        ll.a_stride = int(a_stride)
+        ll.out = addr(out)
+        ll.out_stride = int((0 if out is None or isinstance(out, int) else out.shape[-1]) if out_stride is None else out_stride)
+        ll.x = _ptr(x)
+        if x_stride is None:
+            x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
+        ll.x_stride = int(x_stride)
+        ll.row_out = addr(row_out)
+        if row_stride is None:
+            row_stride = 0 if row_out is None or isinstance(row_out, int) else 2 * int(rows)
+        ll.row_stride = int(row_stride)
+        _lib.check(self.lib.vaek_exact_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did),
+                                                               int(pad), float(var_added), int(x_tag), _stream()))
+
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
         f = C.c_int32()

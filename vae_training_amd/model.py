@@ -127,7 +127,9 @@ class GenerativeModel(Model):
     def _stats_event(self):
         """The stats of an n_print event: compute_stats(), and with `log_likelihood_samples` = K set (run.py --log_likelihood_samples)
         the importance-weighted log-likelihood of this model on K samples per row (trainer.ReplicaLogLik, one library call), which
-        neither splits the model's key nor advances a draw counter of the run; `mlp_log_likelihood_samples` does the same for a
+        neither splits the model's key nor advances a draw counter of the run; `exact_log_likelihood` (run.py --exact_log_likelihood)
+        adds the closed-form log-likelihood, ELBO and posterior gap of a one-decoder linear model (trainer.ReplicaExactLogLik), on
+        the rows the IWAE event just scored where there is one (then also "IWAE Gap"); `mlp_log_likelihood_samples` does the same for a
         three-hidden-layer MLP model (trainer.ReplicaLogLikMlp3); `eigenvalues` (run.py --eigenvalues) adds the covariance spectra of
         a generated and a real batch (trainer.ReplicaSpectrum), which leaves the run alone in the same way; `subspace` (run.py
         --subspace) adds the principal angles between their leading eigenspaces (trainer.ReplicaSubspace) under the same counter."""
@@ -137,8 +139,14 @@ class GenerativeModel(Model):
             from .trainer import ReplicaLogLik
             if getattr(self, "_loglik", None) is None:
                 self._loglik = ReplicaLogLik([self], K)
-            stats.update(self._loglik.event()[0])
-        K = getattr(self, "mlp_log_likelihood_samples", None)      # run.py --mlp_log_likelihood_samples: the same event for an mlp3 model
+            iwae = self._loglik.event()
+            stats.update(iwae[0])
+        if getattr(self, "exact_log_likelihood", False):           # run.py --exact_log_likelihood: the closed form of a one-decoder linear
+            from .trainer import ReplicaExactLogLik                # model (log p(x), ELBO, their gap), on the IWAE event's rows where there is one
+            if getattr(self, "_exact_loglik", None) is None:
+                self._exact_loglik = ReplicaExactLogLik([self])
+            stats.update(self._exact_loglik.event_after(iwae if K else None)[0])
+        K = getattr(self, "mlp_log_likelihood_samples", None)     # run.py --mlp_log_likelihood_samples: the same event for an mlp3 model
         if K:
             from .trainer import ReplicaLogLikMlp3
             if getattr(self, "_loglik_mlp3", None) is None:

@@ -85,6 +85,15 @@ def build_parser():
                         "own RNG counter and tags, so the training run is bitwise the one without the flag.  Alone or with "
                         "--sweep_dataset_seeds (one call for all models); float32 linear VAEs with D, L <= 32 only; other models are refused "
                         "before any step; single GPU only")
+    p.add_argument("--exact_log_likelihood", dest="exact_log_likelihood", action="store_true",
+                   help="at every n_print step also evaluate, in closed form and float64, the exact log-likelihood of a print batch under "
+                        "the model, the exact ELBO and their difference KL(q(z|x) || p(z|x)) (trainer.ReplicaExactLogLik, "
+                        "vaek_exact_log_likelihood_replicas): losses.npz gains 'Exact Log Likelihood', 'Exact ELBO', 'Posterior KL' and "
+                        "'Exact Likelihood Conditioning'.  With --log_likelihood_samples K both events score the same rows and 'IWAE "
+                        "Gap' = Exact Log Likelihood - Average Log Likelihood is added.  The evaluation has its own RNG counter, so the "
+                        "training run and every other stat are bitwise the ones without the flag.  Alone or with --sweep_dataset_seeds "
+                        "(one launch for all models); float32 linear VAEs with ONE decoder and D, L <= 32 only (the sigmoid second "
+                        "decoder has no closed form); other models are refused before any step; single GPU only")
     p.add_argument("--mlp_log_likelihood_samples", dest="mlp_log_likelihood_samples", type=_positive_int, default=None, metavar="K",
                    help="--log_likelihood_samples for three-hidden-layer MLP VAEs (trainer.ReplicaLogLikMlp3, "
                         "vaek_mlp3_log_likelihood_replicas): the same three stats from the same draws, the training run bitwise the one "
@@ -318,6 +327,21 @@ def check_log_likelihood_model(m, samples):
                            "(vaek_log_likelihood_max_samples)")
 
 
+EXACT_LOGLIK_NEEDS = ("a model vaek_exact_log_likelihood_replicas covers (vaek_supports_exact_log_likelihood): a float32 linear VAE -- no "
+                      "hidden layers -- with ONE decoder (the sigmoid second decoder has no closed form), D, L <= 32, -dd / -did <= 16, on "
+                      "one GPU")
+
+
+def check_exact_log_likelihood_model(m):
+    """--exact_log_likelihood: refuse, before any step, a model the exact call does not cover."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    kind, _, dd, did, _, _ = m.dataset.device_spec()
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_exact_log_likelihood(kind):
+        raise RuntimeError(f"--exact_log_likelihood needs {EXACT_LOGLIK_NEEDS} (this model's step path: {getattr(eng, 'step_path', '?')}, "
+                           f"world {eng.world})")
+
+
 MLP_LOGLIK_NEEDS = ("a model vaek_mlp3_log_likelihood_replicas covers (vaek_supports_mlp3_log_likelihood): float32, one decoder, exactly "
                     "three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32, -dd / -did <= 16, on one GPU")
 
@@ -427,6 +451,11 @@ def main_sweep(args):
         from .trainer import ReplicaLogLikMlp3
         check_mlp_log_likelihood_model(models[0], mlp_samples, len(models))
         loglik = ReplicaLogLikMlp3(models, mlp_samples)
+    exact = None
+    if getattr(args, "exact_log_likelihood", False):     # before any step
+        from .trainer import ReplicaExactLogLik
+        check_exact_log_likelihood_model(models[0])
+        exact = ReplicaExactLogLik(models)
     spectrum = None
     if getattr(args, "eigenvalues", False):  # before any step
         from .trainer import ReplicaSpectrum
@@ -449,6 +478,9 @@ def main_sweep(args):
     if loglik is not None:
         entry = "vaek_log_likelihood_replicas" if mlp_samples is None else "vaek_mlp3_log_likelihood_replicas"
         print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows ({entry})")
+    if exact is not None:
+        print(f"Exact log-likelihood events: {exact.rows} rows per model, one launch for {len(models)} models "
+              "(vaek_exact_log_likelihood_replicas)")
     if spectrum is not None and getattr(args, "eigenvalues", False):
         entry = ("vaek_eigen_event_replicas" if spectrum.fused else "vaek_cov_eigen_rows") if spectrum.VEC else \
                 ("vaek_spectrum_event_replicas" if spectrum.fused else "vaek_cov_spectrum_rows")
@@ -472,12 +504,16 @@ def main_sweep(args):
         fused = loop.stats_event() if (fused_stats or mlp_fused_stats) and ev % n_print == 0 else None      # every model's event in one call
         extra = loglik.event() if loglik is not None and ev % n_print == 0 else None     # every model's log-likelihood in one call
         spectra = spectrum.event() if spectrum is not None and ev % n_print == 0 else None     # every model's two spectra in one call
+        # every model's closed form in one launch, on the rows the IWAE event just scored where there is one
+        closed = exact.event_after(extra if ll_samples is not None else None) if exact is not None and ev % n_print == 0 else None
         for r, m in enumerate(models):
             m.batchnum = ev
             if ev % n_print == 0:
                 stats = m.compute_stats() if fused is None else fused[r]
                 if extra is not None:
                     stats.update(extra[r])
+                if closed is not None:
+                    stats.update(closed[r])
                 if spectra is not None:
                     stats.update(spectra[r] if getattr(args, "eigenvalues", False) else
                                  {k: v for k, v in spectra[r].items() if k not in spectrum.KEYS})
@@ -510,6 +546,9 @@ def main(args):
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1 and getattr(args, "mlp_log_likelihood_samples", None) is not None:
         raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS}: it does not combine with data parallelism "
+                           f"(step path of a world of {world}: one shard per rank)")
+    if world > 1 and getattr(args, "exact_log_likelihood", False):
+        raise RuntimeError(f"--exact_log_likelihood needs {EXACT_LOGLIK_NEEDS}: it does not combine with data parallelism "
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1 and getattr(args, "eigenvalues", False):
         raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS}: it does not combine with data parallelism "
@@ -551,6 +590,10 @@ def main(args):
         check_mlp_log_likelihood_model(model, mlp_samples)      # before any step
         model.mlp_log_likelihood_samples = mlp_samples          # the n_print events add trainer.ReplicaLogLikMlp3([model], K).event()
         print(f"Log-likelihood events: {mlp_samples} samples × {model.print_batch_size} rows (vaek_mlp3_log_likelihood_replicas)")
+    if getattr(args, "exact_log_likelihood", False):
+        check_exact_log_likelihood_model(model)            # before any step
+        model.exact_log_likelihood = True                  # the n_print events add trainer.ReplicaExactLogLik([model]).event_after(...)
+        print(f"Exact log-likelihood events: {model.print_batch_size} rows (vaek_exact_log_likelihood_replicas)")
     if getattr(args, "eigenvalues", False):
         check_eigenvalues_model(model)                     # before any step
         model.eigenvalues = True                           # the n_print events add trainer.ReplicaSpectrum([model]).event()

@@ -645,6 +645,96 @@ class ReplicaLogLikMlp3(ReplicaLogLik):
         self.eng.mlp3_log_likelihood_replicas(*args, **kw)
 
 
+class ReplicaExactLogLik:
+    """The EXACT log-likelihood, the exact ELBO and their difference KL(q(z|x) || p(z|x)) of R one-decoder linear VAEModels of one
+    shape in ONE launch (vaek_exact_log_likelihood_replicas, csrc/cov_spectrum.hip): such a model is a linear-Gaussian
+    latent-variable model, p(x) = N(b_d, K^T K + e^eps I), so what ReplicaLogLik estimates has a closed form -- float64 on the device,
+    through the eigenvectors of K^T K.
+
+    The models are validated as in ReplicaLogLik (one shape, any batch size).  event() copies each model's `model.flat` into its row
+    of an [R, P] stack owned by this object, makes ONE library call and ONE device -> host copy of the [R, 10 + D] float64 records.
+    It does NOT perturb the run: `m.key`, the dataset's `_draws`, `m._latent_draws` and `m._loglik_draws` are left alone.  Its draws
+    have a counter of their own, `m._exact_loglik_draws` (incremented before use), the seed dataset.key[0] ^ dataset.key[1] and row
+    tag 3 -- ReplicaLogLik's row tag, so event(step=s) with the step a ReplicaLogLik event just used scores the rows that event
+    scored, bit for bit (with `step` given the counter is neither read nor advanced).  Returns per model {"Exact Log Likelihood",
+    "Exact ELBO", "Posterior KL", "Exact Likelihood Conditioning"} (Python floats; the last is the record's bound on the relative
+    error of the smallest eigenvalue of the model covariance, (off_F + 64 D 2^-53 |K^T K|_F) e^-eps: large means ill-conditioned,
+    reported, not hidden).  Raises RuntimeError naming the model where the solve ended with off_F > 2^-40 |K^T K|_F."""
+
+    KEYS = ("Exact Log Likelihood", "Exact ELBO", "Posterior KL", "Exact Likelihood Conditioning")
+    SLOTS = (0, 1, 2, 8)
+    X_TAG = ReplicaLogLik.X_TAG
+    NAME = "ReplicaExactLogLik"
+    OFF_BOUND = 2.0 ** -40
+
+    def __init__(self, vae_models, rows=None):
+        _replica_setup(self, vae_models, self.NAME, "launch", "rows", "evaluates", "train_loop_max_replicas", ReplicaLogLik._shape,
+                       self._check_covered)
+        R, m0 = self.R, self.ms[0]
+        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
+        if not 1 <= self.rows <= self.eng.log_likelihood_max_rows:
+            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 1 .. {self.eng.log_likelihood_max_rows} "
+                               "(vaek_log_likelihood_max_rows)")
+        dev = self.eng.device
+        self.record_len = self.eng.exact_log_likelihood_record_len
+        self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
+        self.out = torch.zeros(R, self.record_len, dtype=torch.float64, device=dev)
+
+    def _check_covered(self):
+        if not self.eng.supports_exact_log_likelihood(self.kind):
+            raise RuntimeError("ReplicaExactLogLik: vaek_exact_log_likelihood_replicas does not cover this model / dataset (it needs a "
+                               "float32 linear VAE -- no hidden layers -- with ONE decoder and D, L <= 32: the sigmoid second decoder has "
+                               f"no closed form; this model's step path: {getattr(self.eng, 'step_path', '?')})")
+
+    def event(self, step=None):
+        """One evaluation of every model: [{"Exact Log Likelihood", "Exact ELBO", "Posterior KL", "Exact Likelihood Conditioning"} of
+        model 0, ...].  step: draw the rows under this RNG step (one int, or one per model) instead of the models' own counters."""
+        dev = self.eng.device
+        if step is not None:
+            given = [int(s) for s in step] if isinstance(step, (list, tuple)) else [int(step)] * self.R
+            if len(given) != self.R:
+                raise RuntimeError(f"{self.NAME}.event(step=...): {len(given)} steps for {self.R} models")
+        seeds, steps = [], []
+        for r, m in enumerate(self.ms):
+            self.params[r].copy_(m.model.flat)
+            if step is None:
+                m._exact_loglik_draws = getattr(m, "_exact_loglik_draws", 0) + 1
+                s = m._exact_loglik_draws
+            else:
+                s = given[r]
+            ds = m.dataset
+            seeds.append(_wrap_signed(ds.key[0] ^ ds.key[1], 64))
+            steps.append(_wrap_signed(s, 32))
+        seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
+        steps = torch.tensor(steps, dtype=torch.int32).to(dev)
+        self.eng.exact_log_likelihood_replicas(self.params, self.rows, self.out, kind=self.kind, A=self.A, dd=self.dd, did=self.did,
+                                               pad=self.pad, var_added=self.var, x_seeds=seeds, x_steps=steps, a_stride=self.a_stride,
+                                               x_tag=self.X_TAG)
+        rec = self.out.cpu().numpy()                                              # the event's ONE device -> host copy
+        stats = []
+        for r, m in enumerate(self.ms):
+            row = rec[r]
+            off, norm = row[6], row[7]
+            if not off <= self.OFF_BOUND * norm:
+                raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the solve of K^T K stopped at the cap of "
+                                   f"{int(row[5])} sweeps with off_F = {off:.3e} > 2^-40 |K^T K|_F = {self.OFF_BOUND * norm:.3e}")
+            stats.append({name: float(row[k]) for name, k in zip(self.KEYS, self.SLOTS)})
+        return stats
+
+    IWAE_GAP = "IWAE Gap"
+
+    def event_after(self, iwae_stats=None):
+        """event() of an n_print event.  iwae_stats: what a ReplicaLogLik over the SAME models just returned, or None.  With it the rows
+        are drawn under the step that event used (`m._loglik_draws`), so both score the same rows bitwise, and every dict gains
+        "IWAE Gap" = Exact Log Likelihood - Average Log Likelihood: how far the IWAE-K bound is from the truth."""
+        if iwae_stats is None:
+            return self.event()
+        stats = self.event(step=[m._loglik_draws for m in self.ms])
+        for st, iw in zip(stats, iwae_stats):
+            st[self.IWAE_GAP] = st[self.KEYS[0]] - float(iw[ReplicaLogLik.KEYS[0]])
+        return stats
+
+
 class ReplicaSpectrum:
     """The covariance spectra of a generated and of a real batch of R VAEModels of one shape: per model the eigenvalues of
     cov(fake batch) -- the reference's "learnt eigenvalue" -- and of cov(real batch) -- its "ground truth eigenvalue"
