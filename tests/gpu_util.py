@@ -28,6 +28,14 @@ def host(t):
     return t.detach().cpu().numpy().astype(np.float64)
 
 
+def _i64(seeds):
+    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
+
+
+def _i32(steps):
+    return torch.tensor([s - 2 ** 32 if s >= 2 ** 31 else s for s in steps], dtype=torch.int32, device="cuda")
+
+
 def check_layout(eng, cfg):
     """The library's flat leaf order must equal the oracle's (include/vaek.h conventions)."""
     want = cfg.leaves()

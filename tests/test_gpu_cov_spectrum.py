@@ -22,6 +22,7 @@ import torch
 
 from oracle import elbo_oracle as O
 from tests import cov_spectrum_cases as K
+from tests.gpu_util import _i32, _i64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,14 +42,6 @@ SHAPES = {
     "sphere": dict(sig=False, tdv=False, eps=-1.0, kind=2, D=6, L=6, dd=3, did=3, pad=3, var=0.0),
 }
 EVENT_ROWS = 1000
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
-
-
-def _i32(steps):
-    return torch.tensor([s - 2 ** 32 if s >= 2 ** 31 else s for s in steps], dtype=torch.int32, device="cuda")
 
 
 @functools.lru_cache(maxsize=None)

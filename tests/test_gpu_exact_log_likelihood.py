@@ -22,6 +22,7 @@ import torch
 
 from oracle import elbo_oracle as O
 from tests import exact_loglik_cases as K
+from tests.gpu_util import _i32, _i64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,14 +39,6 @@ def _ref():
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
-
-
-def _i32(steps):
-    return torch.tensor([s - 2 ** 32 if s >= 2 ** 31 else s for s in steps], dtype=torch.int32, device="cuda")
 
 
 def _last(t):

@@ -35,6 +35,7 @@ import torch
 
 from oracle import elbo_oracle as O
 from oracle import philox as PH
+from tests.gpu_util import _i32, _i64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,14 +55,6 @@ SHAPES = {
 }
 ROWS = (1, 37, 256, 257, 1000)
 KS = (1, 2, 5, 64)
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
-
-
-def _i32(steps):
-    return torch.tensor([s - 2 ** 32 if s >= 2 ** 31 else s for s in steps], dtype=torch.int32, device="cuda")
 
 
 def _cfg(s):

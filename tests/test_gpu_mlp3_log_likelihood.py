@@ -38,6 +38,7 @@ import torch
 
 from oracle import elbo_oracle as O
 from oracle import philox as PH
+from tests.gpu_util import _i32, _i64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,14 +141,6 @@ DROPPED = {
     ('notdv', 37, 67): (1.0e-06, 9.4e-07, 4.6e-06),
 }
 # REFERENCE_MOVES_END
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
-
-
-def _i32(steps):
-    return torch.tensor([s - 2 ** 32 if s >= 2 ** 31 else s for s in steps], dtype=torch.int32, device="cuda")
 
 
 def _cfg(s):

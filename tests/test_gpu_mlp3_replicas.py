@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import _i64
 from tests.mlp3_cases import H3, MAX_BATCH
 
 pytestmark = pytest.mark.gpu
@@ -32,10 +33,6 @@ def _up4(n):
 def _engine(D, L, hidden=H3, B=37, **kw):
     from vae_training_amd.engine import Engine
     return Engine(B, D, L, tuple(hidden), tuple(hidden), -3.0, True, False, **kw)
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
 
 
 class _State:

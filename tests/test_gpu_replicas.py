@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import _i64
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LR = 1e-3
@@ -26,10 +28,6 @@ LABEL = "linear_resident_replicas"
 def _engine(sig, D, L, B, **kw):
     from vae_training_amd.engine import Engine
     return Engine(B, D, L, (), (), -3.0 if sig else -1.0, True, sig, **kw)
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
 
 
 class _Sweep:

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from oracle import elbo_oracle as O
+from tests.gpu_util import _i32, _i64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,14 +38,6 @@ SHAPES = {
     "sigmoid28x24": dict(sig=True, tdv=True, eps=-3.0, kind=1, D=28, L=24, dd=7, did=1, pad=20, var=0.0),
 }
 ROWS = (37, 256, 257, 1000)
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
-
-
-def _i32(steps):
-    return torch.tensor([s - 2 ** 32 if s >= 2 ** 31 else s for s in steps], dtype=torch.int32, device="cuda")
 
 
 class _Event:

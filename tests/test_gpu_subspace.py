@@ -19,6 +19,7 @@ import torch
 from oracle import elbo_oracle as O
 from tests import cov_spectrum_cases as K
 from tests import subspace_cases as Z
+from tests.gpu_util import _i32, _i64
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,14 +27,6 @@ SENT = -12345.0
 X_TAG, Z_TAG = 5, 6
 ROWS = 257
 SAMPLE_EPS = -30.0
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
-
-
-def _i32(steps):
-    return torch.tensor([s - 2 ** 32 if s >= 2 ** 31 else s for s in steps], dtype=torch.int32, device="cuda")
 
 
 @functools.lru_cache(maxsize=None)

@@ -17,16 +17,14 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import _i64
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LR = 1e-3
 SENT = -12345.0
 NAMES = ("params", "grads", "m", "v", "step", "ring")
 SOLO_LABEL, REPLICA_LABEL = "linear_resident_traj", "linear_resident_replicas_traj"
-
-
-def _i64(seeds):
-    return torch.tensor([s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds], dtype=torch.int64, device="cuda")
 
 
 class _Case:

@@ -1,4 +1,4 @@
-"""NumPy float64 restatement of vaek_exact_log_likelihood_replicas (csrc/cov_spectrum.hip), from the CPU ALONE (no GPU, no kernel): a
+"""NumPy float64 restatement of vaek_exact_log_likelihood_replicas (csrc/exact_loglik.inc), from the CPU ALONE (no GPU, no kernel): a
 one-decoder linear VAE is a linear-Gaussian latent-variable model, p(x) = N(b_d, K^T K + e^{eps} I), so log p(x), the ELBO of the
 diagonal-Gaussian encoder and their difference KL(q(z|x) || p(z|x)) are closed forms.  G = K^T K is solved by the Jacobi routine of
 tools/cov_eigen_reference.py (imported, not copied: the device's ordering, rotation, off-norm, 2^-43 stop and 32-sweep cap), the

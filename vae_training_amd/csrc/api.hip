@@ -892,10 +892,7 @@ int vaek_trajectory_record_len(const vaek_ctx* ctx, int64_t* floats) {
 // A vaek_trajectory checked against the context (`replicas`: the replica form, where replica_stride counts) and turned into the
 // kernel's TrajArgs: after it every store of the launch lands inside the caller's ring.  Needs a non-null context.
 static int check_trajectory(const char* who, const vaek_ctx* ctx, const vaek_trajectory* traj, bool replicas, TrajArgs* out) {
-    if (traj->struct_size != (int32_t)sizeof(vaek_trajectory)) {
-        set_error("%s: vaek_trajectory.struct_size %d != %d (header / library mismatch)", who, traj->struct_size, (int)sizeof(vaek_trajectory));
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_struct_size(who, "vaek_trajectory", traj->struct_size, sizeof(vaek_trajectory))) return rc;
     const int64_t len = 2 * (int64_t)ctx->P + kExtra;
     if (traj->every < 1) { set_error("%s: trajectory every = %d, need >= 1", who, traj->every); return VAEK_ERR_INVALID; }
     if (traj->cap < 1) { set_error("%s: trajectory cap = %lld, need >= 1", who, (long long)traj->cap); return VAEK_ERR_INVALID; }
@@ -929,18 +926,12 @@ static int train_loop_gen_replicas_impl(const char* who, vaek_ctx* ctx, float* p
         set_error("%s: invalid argument", who);
         return VAEK_ERR_INVALID;
     }
-    if (rep->struct_size != (int32_t)sizeof(vaek_replicas)) {
-        set_error("%s: vaek_replicas.struct_size %d != %d (header / library mismatch)", who, rep->struct_size, (int)sizeof(vaek_replicas));
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_struct_size(who, "vaek_replicas", rep->struct_size, sizeof(vaek_replicas))) return rc;
     if (!ctx->resident) {
         set_error("%s: needs a context vaek_train_loop_gen covers (see vaek_supports_train_loop_gen)", who);
         return VAEK_ERR_INVALID;
     }
-    if (rep->n < 1 || rep->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, rep->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_replica_count(who, rep->n)) return rc;
     if (rep->state_stride < ctx->P || rep->grads_stride < ctx->P + kExtra) {
         set_error("%s: state_stride %lld < P = %lld or grads_stride %lld < grad_len = %lld", who, (long long)rep->state_stride,
                   (long long)ctx->P, (long long)rep->grads_stride, (long long)(ctx->P + kExtra));
@@ -1040,10 +1031,7 @@ int vaek_train_step_gen_replicas(vaek_ctx* ctx, float* params, float* grads, flo
         set_error("%s: null argument", fn);
         return VAEK_ERR_INVALID;
     }
-    if (rep->struct_size != (int32_t)sizeof(vaek_replicas)) {
-        set_error("%s: vaek_replicas.struct_size %d != %d (header / library mismatch)", fn, rep->struct_size, (int)sizeof(vaek_replicas));
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_struct_size(fn, "vaek_replicas", rep->struct_size, sizeof(vaek_replicas))) return rc;
     if (!ctx->mlp3 || ctx->cfg.world != 1) {
         set_error("%s: needs a single-GPU context whose train step path is \"mlp3\" (see vaek_supports_train_step_replicas)", fn);
         return VAEK_ERR_INVALID;

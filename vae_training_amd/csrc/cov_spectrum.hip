@@ -12,44 +12,18 @@
 //     sum row) of both column blocks.  Every matrix element is therefore ONE accumulation chain over the rows in row order, and a
 //     zero row adds +0.  One workgroup sums all <= 4096 rows: no tile partials, no workspace, no second launch, no atomic.
 //   COVARIANCE.  m = S1 / rows, C = (S2 - rows m m^T) / (rows - 1) (jnp.cov's ddof = 1), float64, computed for i <= j and mirrored.
-//   EIGENVALUES.  Cyclic Jacobi in float64 on C in LDS, D padded to even, round-robin ordering: D / 2 disjoint rotations per round,
-//     D - 1 rounds per sweep.  A round is "angles from the current matrix, barrier, A <- J^T A J into the other buffer, barrier";
-//     each new element comes from its four sources, for i <= j, mirrored.  A rotation is skipped where a_pq == 0 and takes
-//     t = 1 / (2 theta) where theta = (a_qq - a_pp) / (2 a_pq) is too large to square (both happen on the exactly-zero padding
-//     columns of real rows).  The off-diagonal norm is the sum of the off-diagonal squares themselves (never |A|^2 - sum a_ii^2,
-//     which stalls at 1e-8 |C|_F); the solve stops when off_F <= 2^-43 |C|_F or after kSpectrumMaxSweeps sweeps, a decision every
-//     thread reads from LDS.  Ranks come from counting, ties break by index; nothing is clamped.
-//   EIGENVECTORS (vaek_cov_eigen_rows, vaek_eigen_event_replicas: the VEC instantiations).  The solve is one routine, jacobi_solve;
-//     with VEC a round also forms V <- V J between its two barriers into two more buffers of the dead tile, and the record gains V
-//     behind the spectrum record, columns in the eigenvalues' order, the largest component of each positive.  V never feeds back, so
-//     the spectrum part is bitwise the VEC = false record.
+//   EIGENVALUES, EIGENVECTORS (vaek_cov_eigen_rows, vaek_eigen_event_replicas: the VEC instantiations).  eigen_dev.h's jacobi_solve
+//     on C in the dead tile; that header says how the solve goes and what the three row sources are.
+//   EXACT LOG-LIKELIHOOD (vaek_exact_log_likelihood_replicas): a third kernel on the same solve; its text is exact_loglik.inc,
+//     included at the end of this file (one translation unit: DESIGN 3.19).
 //   PRINCIPAL ANGLES (vaek_subspace_angles): a second kernel reads two eigen records an earlier launch stored, forms M = U^T W,
 //     R = W - U M and G = R^T R in LDS and solves G with the same jacobi_solve: sin^2 of the principal angles between the two spans.
-//   EXACT LOG-LIKELIHOOD (vaek_exact_log_likelihood_replicas): a third kernel, one workgroup per one-decoder linear VAE, solves
-//     G = K^T K of the decoder kernel with jacobi_solve<true> and evaluates log N(x; b_d, G + e^{eps} I), the closed-form ELBO and
-//     their gap on rows from produce_row (explicit or drawn), float64 throughout; its own header comment is above the kernel.
-//
-// Three row sources feed that one text through the same row -> tile-slot assignment, so a record depends on the rows' bits only:
-// SRC_EXPLICIT reads [rows][D] from HBM, SRC_REAL draws row i as vaek_make_batch writes x, SRC_FAKE draws latent row i as
-// vaek_make_batch writes z1 / z2 and decodes fake = Decoder(z1) [+ sigmoid(SigDecoder(z1))] + z2 exp(sample_eps / 2) in float32 from
-// the zero-padded ParamImage (eval_dev.h), linear_stats.hip's fake row with a one-input decode.
 //
 // The kernels read rows / parameters and store only the records, with per-lane vector stores; they read nothing back.
-#include "eval_dev.h"
+#include "eigen_dev.h"
 #include "mfma_geom.h"
 
 namespace vaek {
-
-constexpr int kSpectrumMaxSweeps = 32;       // bounds one launch -- a cap, not a tuned value
-constexpr int kSpectrumMaxDim = 32;
-constexpr int kSpectrumMaxRows = 4096;       // = vaek_stats_event_max_rows()
-constexpr int kTileStride = 36;              // floats between two rows of the LDS tile: 16-byte aligned, 16 distinct banks per 4 rows
-constexpr int kMatStride = 32;               // doubles between two rows of the Jacobi buffers
-constexpr double kSpectrumTol = 0x1p-43;
-
-enum { SRC_EXPLICIT = 0, SRC_REAL = 1, SRC_FAKE = 2 };
-
-using f64x4 = __attribute__((ext_vector_type(4))) double;
 
 struct SpectrumArgs {
     const float* x; long long x_stride;                              // SRC_EXPLICIT: set s reads x + s * x_stride
@@ -65,199 +39,6 @@ struct SpectrumArgs {
     unsigned z_tag;
     BatchArgs gen;                 // kind, A, dd, did, pad, noise_std, tag = x_tag, D, L; seed / step / pointers are not used
 };
-
-// what a row source needs besides the row index
-struct RowCtx {
-    const float* xr;               // SRC_EXPLICIT: the set's rows
-    const float* W;                // SRC_FAKE: the parameter image
-    BatchArgs g;                   // SRC_REAL: the dataset draw; SRC_FAKE: its tag is z_tag
-    uint2 key; unsigned step;
-    int D, L;
-    float ssigma;                  // SRC_FAKE: exp(sample_eps / 2)
-};
-
-// row `row` of the set as 32 floats, columns >= D zero
-template <int SRC, int DP, int LP, bool SIG>
-__device__ __forceinline__ void produce_row(const RowCtx& c, int row, float (&x)[kSpectrumMaxDim]) {
-    const int D = c.D;
-#pragma unroll
-    for (int d = DP; d < kSpectrumMaxDim; ++d) x[d] = 0.f;
-    if constexpr (SRC == SRC_EXPLICIT) {
-        const float* const xr = c.xr + (long long)row * D;
-#pragma unroll
-        for (int d = 0; d < DP; ++d) x[d] = d < D ? xr[d] : 0.f;
-    } else if constexpr (SRC == SRC_REAL) {
-        // vaek_make_batch's work item for (row, c0), all c0: linear_stats.hip's text
-        float nrm[16];
-        dataset_normals(c.g, c.step, row, c.key, nrm);
-#pragma unroll
-        for (int c0 = 0; c0 < DP; c0 += 4) {
-            float o[4] = {0.f, 0.f, 0.f, 0.f};
-            if (c0 < D) dataset_cols4(c.g, c.step, row, c.key, nrm, c0, o);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) x[c0 + k] = c0 + k < D ? o[k] : 0.f;
-        }
-    } else {
-        using G = ParamImage<DP, LP, SIG>;
-        const int L = c.L;
-        const float* const W = c.W;
-        const int zq0 = L >> 2, zsh = L & 3, nzb = (L + D + 3) / 4;       // z2 starts at element zsh of latent block zq0
-        // the latent row: normal n is element n & 3 of block n >> 2; [0, L) is z1, [L, L + D) z2 (linear_stats.hip's text)
-        float z1[LP], z2[DP];
-#pragma unroll
-        for (int q = 0; q < LP / 4; ++q) {
-            float n4[4] = {0.f, 0.f, 0.f, 0.f};
-            if (4 * q < L) latent_block(c.g, c.step, row, c.key, q, n4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) z1[4 * q + k] = n4[k];            // elements >= L of the last block belong to z2: rows l >= L of the image are 0
-        }
-        {
-            float cat[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            {
-                float n4[4];
-                latent_block(c.g, c.step, row, c.key, zq0, n4);
-                cat[4] = n4[0]; cat[5] = n4[1]; cat[6] = n4[2]; cat[7] = n4[3];
-            }
-#pragma unroll
-            for (int j = 0; j < DP / 4; ++j) {
-                if (4 * j < D) {
-                    float n4[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (zq0 + j + 1 < nzb) latent_block(c.g, c.step, row, c.key, zq0 + j + 1, n4);
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) { cat[k] = cat[4 + k]; cat[4 + k] = n4[k]; }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        z2[4 * j + k] = zsh == 0 ? cat[k] : (zsh == 1 ? cat[k + 1] : (zsh == 2 ? cat[k + 2] : cat[k + 3]));
-                } else {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) z2[4 * j + k] = 0.f;
-                }
-            }
-        }
-        // fake = Decoder(z1) [+ sigmoid(SigDecoder(z1))] + z2 exp(sample_eps / 2): the one-input form of linear_stats.hip's decode2
-        float y[DP], ys[SIG ? DP : 1];
-#pragma unroll
-        for (int d = 0; d < DP; ++d) {
-            y[d] = W[G::BD + d];
-            if (SIG) ys[d] = W[G::BS + d];
-        }
-#pragma unroll
-        for (int l = 0; l < LP; ++l) {
-            if (l < L) {
-#pragma unroll
-                for (int d = 0; d < DP; ++d) {
-                    y[d] = fmaf(z1[l], W[G::WD + l * DP + d], y[d]);
-                    if (SIG) ys[d] = fmaf(z1[l], W[G::WS + l * DP + d], ys[d]);
-                }
-            }
-        }
-#pragma unroll
-        for (int d = 0; d < DP; ++d) {
-            float f = fmaf(c.ssigma, z2[d], y[d]);
-            if (SIG) f += 1.f / (1.f + expf(-ys[d]));
-            x[d] = d < D ? f : 0.f;
-        }
-    }
-}
-
-// the sum of v over the 256 threads, the same value in every thread: a fixed binary tree in LDS
-__device__ __forceinline__ double block_sum256(double v, double* red, int t) {
-    red[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-// the largest v over the 256 threads, the same value in every thread (v >= 0)
-__device__ __forceinline__ double block_max256(double v, double* red, int t) {
-    red[t] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (t < s) red[t] = fmax(red[t], red[t + s]);
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-constexpr int kMatDoubles = kSpectrumMaxDim * kMatStride;     // one Jacobi buffer
-
-// Cyclic Jacobi, round-robin, on the symmetric De x De matrix in buffer 0 of `mat` (two buffers of kMatDoubles; De even, index
-// De - 1 stays, the others turn), published by a barrier before the call.  Leaves the diagonalised matrix in buffer `cur` and returns
-// (cur, sweeps, off_F), the same in every thread.  VEC: buffer 0 of `vec` (two more buffers) starts as I, also published, and every
-// round forms V <- V J between the round's own two barriers: new column i = c_i V[:, i] + s_i V[:, mate(i)]; V ends in buffer `cur`
-// of `vec` with C V = V diag(A).
-template <bool VEC>
-__device__ __forceinline__ void jacobi_solve(double* const mat, double* const vec, const int De, const double norm_c, double* const red,
-                                             double* const rot_c, double* const rot_s, int* const rot_mate, const int t, int& cur_out,
-                                             int& sweeps_out, double& off_out) {
-    int cur = 0, sweeps = 0;
-    double off_f;
-    for (;;) {
-        const double* const A = mat + cur * kMatDoubles;
-        double osq = 0.0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
-            if (i < j && j < De) { const double v = A[i * kMatStride + j]; osq += 2.0 * v * v; }
-        }
-        off_f = sqrt(block_sum256(osq, red, t));                     // the same value in every thread: the decision is uniform
-        if (off_f <= kSpectrumTol * norm_c || sweeps == kSpectrumMaxSweeps) break;
-        const int n1 = De - 1;
-        for (int round = 0; round < n1; ++round) {
-            const double* const Ac = mat + cur * kMatDoubles;
-            double* const An = mat + (cur ^ 1) * kMatDoubles;
-            if (t < De / 2) {
-                const int p = t == 0 ? round : (round + t) % n1;
-                const int q = t == 0 ? n1 : (round - t + n1) % n1;
-                const double apq = Ac[p * kMatStride + q];
-                double cs = 1.0, sn = 0.0;
-                if (apq != 0.0) {
-                    const double theta = (Ac[q * kMatStride + q] - Ac[p * kMatStride + p]) / (2.0 * apq);
-                    const double ath = fabs(theta);
-                    const double tt = ath > 1e150 ? 0.5 / theta : copysign(1.0, theta) / (ath + sqrt(theta * theta + 1.0));
-                    cs = 1.0 / sqrt(tt * tt + 1.0);
-                    sn = tt * cs;
-                }
-                rot_c[p] = cs; rot_c[q] = cs;
-                rot_s[p] = -sn; rot_s[q] = sn;                       // new column i = c col_i + s_i col_mate(i)
-                rot_mate[p] = q; rot_mate[q] = p;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
-                if (i <= j && j < De) {
-                    const int mi = rot_mate[i], mj = rot_mate[j];
-                    const double ci = rot_c[i], si = rot_s[i], cj = rot_c[j], sj = rot_s[j];
-                    const double v = ci * (cj * Ac[i * kMatStride + j] + sj * Ac[i * kMatStride + mj]) +
-                                     si * (cj * Ac[mi * kMatStride + j] + sj * Ac[mi * kMatStride + mj]);
-                    An[i * kMatStride + j] = v;
-                    An[j * kMatStride + i] = v;
-                }
-            }
-            if constexpr (VEC) {
-                const double* const Vc = vec + cur * kMatDoubles;
-                double* const Vn = vec + (cur ^ 1) * kMatDoubles;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
-                    if (i < De && j < De) Vn[i * kMatStride + j] = rot_c[j] * Vc[i * kMatStride + j] + rot_s[j] * Vc[i * kMatStride + rot_mate[j]];
-                }
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
-        ++sweeps;
-    }
-    cur_out = cur; sweeps_out = sweeps; off_out = off_f;
-}
 
 // The whole record of one set.  `smem`: the tile while the rows are summed, then the two Jacobi buffers and, with VEC, the two
 // eigenvector buffers behind them.  src is uniform over the workgroup; an EVENT kernel carries the two drawing sources, the rows
@@ -466,11 +247,20 @@ static const SpectrumVariant* pick_spectrum(const vaek_ctx* c) {
 static int64_t spectrum_record_len(const vaek_ctx* c) { return (int64_t)c->D * c->D + 2 * (int64_t)c->D + 4; }
 static int64_t eigen_record_len(const vaek_ctx* c) { return spectrum_record_len(c) + (int64_t)c->D * c->D; }
 static int spectrum_max_sets() { return 2 * resident_max_replicas(); }
+// the rows and the pairs calls take any context whose data_dim the Jacobi buffers hold
+static int check_spectrum_dim(const char* who, const vaek_ctx* ctx) {
+    if (ctx->D > kSpectrumMaxDim) {
+        set_error("%s: data_dim %d, need <= %d (see vaek_supports_cov_spectrum)", who, ctx->D, kSpectrumMaxDim);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
 
 // ---- principal angles between two eigenbases (vaek_subspace_angles) ----------------------------------------------------------------
 // Pair p: U = the ka eigenvectors of record a's largest eigenvalues, W = the kb of record b's (the last columns of the V blocks an
 // EARLIER launch stored).  M = U^T W, R = W - U M formed explicitly (never I - M^T M, which loses small angles), G = R^T R for i <= j,
 // mirrored, and G's eigenvalues -- sin^2 of the principal angles -- by jacobi_solve, the covariance solve's own text.  All float64 in LDS.
+// The kernel stays in this unit: compiled in one of its own it comes out with other registers.
 struct SubspaceArgs {
     const double* a; long long a_stride;
     const double* b; long long b_stride;
@@ -578,234 +368,6 @@ __global__ __launch_bounds__(256) void subspace_angles_kernel(const SubspaceArgs
     }
 }
 
-// ---- exact log-likelihood, exact ELBO and posterior gap of one-decoder linear VAEs (vaek_exact_log_likelihood_replicas) ------------
-// Model r is a linear-Gaussian latent-variable model: p(x) = N(b_d, K^T K + e^{eps} I).  ONE workgroup per model: the parameter image,
-// G = K^T K (element (i, j) one chain over l of exact float64 products of two float32 values, i <= j, mirrored) into Jacobi buffer 0,
-// V = I, jacobi_solve<true> (the covariance solve's own text), then 1 / s_i, logdet, T and the encoder's constant published in LDS
-// and the rows walked in tiles of 256, thread t taking row 256 j + t through produce_row (the bits vaek_make_batch writes, or the
-// caller's).  Per row, float64 VALU fmas over broadcast LDS reads (V^T c, x E, mu K: at most 3 * 32^2 per row -- the matrix cores
-// would need the rows staged as operands and the three products are chained per row, so a row per thread keeps every chain in
-// registers).  A thread keeps three private running sums over its rows in tile order; one fixed binary tree per sum adds them.
-constexpr int kExactHead = 10;               // doubles of the record in front of the eigenvalues
-constexpr double kLog2PiD = 1.8378770664093454835606594728112;
-
-struct ExactLogLikArgs {
-    const float* params; long long state_stride;
-    const unsigned long long* x_seeds; const unsigned* x_steps;      // [n]: the rows' Philox key and step (drawing mode)
-    long long a_stride;
-    const float* x; long long x_stride;                              // explicit rows [rows][D] per replica, or NULL: drawing mode
-    double* out; long long out_stride;
-    double* row_out; long long row_stride;                           // [rows][2] per replica, or NULL
-    int rows, D, L, off_epsp, off_eps;
-    float eps_cli;
-    BatchArgs gen;                 // kind, A, dd, did, pad, noise_std, tag = x_tag, D, L; seed / step / pointers are not used
-};
-
-template <int DP, int LP>
-__global__ __launch_bounds__(256) void exact_loglik_kernel(const ExactLogLikArgs a) {
-    using G = ParamImage<DP, LP, false>;
-    static_assert(DP <= kSpectrumMaxDim && LP <= kSpectrumMaxDim, "the Jacobi buffers and the tables hold 32");
-    __shared__ __attribute__((aligned(16))) float W[G::N];
-    __shared__ __attribute__((aligned(16))) double mat[2 * kMatDoubles], vec[2 * kMatDoubles];
-    __shared__ double red[3][256];
-    __shared__ __attribute__((aligned(16))) double sinv[kSpectrumMaxDim];
-    __shared__ double rot_c[kSpectrumMaxDim], rot_s[kSpectrumMaxDim], eig[kSpectrumMaxDim], lgs[kSpectrumMaxDim];
-    __shared__ double tl[kSpectrumMaxDim], kl[kSpectrumMaxDim], pub[4];
-    __shared__ int rot_mate[kSpectrumMaxDim];
-
-    const int t = threadIdx.x;
-    const long long r = blockIdx.x;
-    const int D = a.D, L = a.L, rows = a.rows;
-    const float* const p = a.params + r * a.state_stride;
-    double* const out = a.out + r * a.out_stride;
-
-    G::fill(W, p, D, L, a.off_epsp, t);                                 // the parameter image: zero outside [D] x [L]
-    __syncthreads();
-
-    const float eps32 = a.off_eps >= 0 ? p[a.off_eps] * a.eps_cli : a.eps_cli;     // linear_loglik.hip's eps, then widened
-    const double eps = (double)eps32;
-    const double evar = exp(eps), einv = exp(-eps);
-
-    // ---- G = K^T K (i <= j, mirrored) into buffer 0, V = I into both vector buffers, the per-latent terms of T and of the KL constant ----
-    double sq = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
-        if (i <= j) {
-            double v = 0.0;
-            if (j < D)
-                for (int l = 0; l < L; ++l) v = fma((double)W[G::WD + l * DP + i], (double)W[G::WD + l * DP + j], v);
-            mat[i * kMatStride + j] = v;
-            mat[j * kMatStride + i] = v;
-            sq += i == j ? v * v : 2.0 * v * v;
-        }
-        const double id = i == j ? 1.0 : 0.0;
-        vec[i * kMatStride + j] = id;                                   // the solve may end in either buffer: both are I outside De x De
-        vec[kMatDoubles + i * kMatStride + j] = id;
-    }
-    if (t < kSpectrumMaxDim) {
-        double tv = 0.0, kv = 0.0;
-        if (t < L) {
-            double k2 = 0.0;
-            for (int d = 0; d < D; ++d) { const double w = (double)W[G::WD + t * DP + d]; k2 = fma(w, w, k2); }
-            const double lv = (double)W[G::LV + t], ev = exp(lv);
-            tv = ev * k2;
-            kv = ev - 1.0 - lv;
-        }
-        tl[t] = tv;
-        kl[t] = kv;
-    }
-    const double norm_g = sqrt(block_sum256(sq, red[0], t));           // its barriers also publish G, V and the tables
-
-    const int De = D + (D & 1);
-    int cur, sweeps;
-    double off_f;
-    jacobi_solve<true>(mat, vec, De, norm_g, red[0], rot_c, rot_s, rot_mate, t, cur, sweeps, off_f);
-
-    // ---- 1 / s_i, log s_i; then logdet, T and the KL constant, each one serial chain in index order ------------------------------------
-    const double* const A = mat + cur * kMatDoubles;
-    if (t < kSpectrumMaxDim) {
-        const double e = t < D ? A[t * kMatStride + t] : 0.0;
-        const double s = fmax(e, 0.0) + evar;
-        eig[t] = e;
-        sinv[t] = t < D ? 1.0 / s : 0.0;
-        lgs[t] = t < D ? log(s) : 0.0;
-    }
-    __syncthreads();
-    if (t < 3) {
-        const double* const src = t == 0 ? lgs : (t == 1 ? tl : kl);
-        double s = 0.0;
-        for (int i = 0; i < kSpectrumMaxDim; ++i) s += src[i];
-        pub[t] = s;
-    }
-    __syncthreads();
-    const double logdet = pub[0], T = pub[1], klc = pub[2];
-    if (t < D) {
-        const double e = eig[t];
-        int rank = 0;
-        for (int j = 0; j < D; ++j) {
-            const double o = eig[j];
-            rank += (o < e || (o == e && j < t)) ? 1 : 0;
-        }
-        out[kExactHead + rank] = e;
-    }
-
-    // ---- the rows: thread t takes row 256 j + t, j in order ------------------------------------------------------------------------------
-    RowCtx rc{};
-    rc.D = D; rc.L = L; rc.W = W;
-    rc.g = a.gen;
-    const bool explicit_rows = a.x != nullptr;
-    if (explicit_rows) {
-        rc.xr = a.x + r * a.x_stride;
-    } else {
-        if (rc.g.A) rc.g.A += r * a.a_stride;
-        rc.key = philox_key(a.x_seeds[r]);
-        rc.step = a.x_steps[r];
-    }
-    const double* const V = vec + cur * kMatDoubles;
-    const double cst_lp = logdet + (double)D * kLog2PiD;
-    const double cst_el = (double)D * (eps + kLog2PiD);
-    double* const rout = a.row_out ? a.row_out + r * a.row_stride : nullptr;
-    double sum_lp = 0.0, sum_el = 0.0, sum_gap = 0.0;
-    for (int base = 0; base < rows; base += 256) {
-        const int row = base + t;
-        if (row < rows) {
-            // V and the image are loop-invariant: a compiler that knows it lifts them out of the tile loop and spills them
-            asm volatile("" ::: "memory");
-            float x[kSpectrumMaxDim];
-            if (explicit_rows) produce_row<SRC_EXPLICIT, DP, LP, false>(rc, row, x);
-            else produce_row<SRC_REAL, DP, LP, false>(rc, row, x);
-            // ---- log p(x): y = V^T (x - b_d), quad = sum y_i^2 / s_i ------------------------------------------------------------------
-            double y[DP];
-#pragma unroll
-            for (int j = 0; j < DP; ++j) y[j] = 0.0;
-#pragma unroll
-            for (int i = 0; i < DP; ++i) {                                            // rows >= D of V are rows of I and meet c = 0
-                const double c = (double)x[i] - (double)W[G::BD + i];
-#pragma unroll
-                for (int j = 0; j < DP; ++j) y[j] = fma(V[i * kMatStride + j], c, y[j]);
-            }
-            double quad = 0.0;
-#pragma unroll
-            for (int j = 0; j < DP; ++j) quad = fma(y[j] * y[j], sinv[j], quad);       // 1 / s is 0 at j >= D
-            const double lp = -0.5 * (quad + cst_lp);
-            // ---- ELBO(x): mu = x E + b_e, r = mu K + b_d - x ----------------------------------------------------------------------------
-            double mu[LP];
-#pragma unroll
-            for (int l = 0; l < LP; ++l) mu[l] = (double)W[G::BE + l];
-#pragma unroll
-            for (int d = 0; d < DP; ++d) {                                            // a padded row of the image adds 0
-                const double xd = (double)x[d];
-#pragma unroll
-                for (int l = 0; l < LP; ++l) mu[l] = fma(xd, (double)W[G::WE + d * LP + l], mu[l]);
-            }
-            double musq = 0.0;
-#pragma unroll
-            for (int l = 0; l < LP; ++l) musq = fma(mu[l], mu[l], musq);                // mu is 0 at l >= L
-            double rr[DP];
-#pragma unroll
-            for (int d = 0; d < DP; ++d) rr[d] = (double)W[G::BD + d] - (double)x[d];
-#pragma unroll
-            for (int l = 0; l < LP; ++l) {
-#pragma unroll
-                for (int d = 0; d < DP; ++d) rr[d] = fma(mu[l], (double)W[G::WD + l * DP + d], rr[d]);
-            }
-            double rsq = 0.0;
-#pragma unroll
-            for (int d = 0; d < DP; ++d) rsq = fma(rr[d], rr[d], rsq);                  // columns >= D are 0 - 0
-            const double el = -0.5 * (einv * (rsq + T) + cst_el) - 0.5 * (klc + musq);
-            sum_lp += lp;
-            sum_el += el;
-            sum_gap += lp - el;
-            if (rout) {
-                rout[2 * (long long)row] = lp;
-                rout[2 * (long long)row + 1] = el;
-            }
-        }
-    }
-
-    // ---- the three sums: one fixed binary tree each over the 256 threads; the record, lane t storing double t ----------------------------
-    red[0][t] = sum_lp;
-    red[1][t] = sum_el;
-    red[2][t] = sum_gap;
-    tree_sum256(red, t);
-    if (t < kExactHead) {
-        const double n = (double)rows;
-        double v;
-        switch (t) {
-            case 0: v = red[0][0] / n; break;
-            case 1: v = red[1][0] / n; break;
-            case 2: v = red[2][0] / n; break;
-            case 3: v = eps; break;
-            case 4: v = logdet; break;
-            case 5: v = (double)sweeps; break;
-            case 6: v = off_f; break;
-            case 7: v = norm_g; break;
-            case 8: v = (off_f + 64.0 * (double)D * 0x1p-53 * norm_g) * einv; break;
-            default: v = n; break;
-        }
-        out[t] = v;
-    }
-}
-
-// ---- variant table: the one-decoder padded shapes of mfma_geom.h, each side rounded up to 4; a two-decoder row holds no kernel -------
-typedef void (*ExactLogLikKernel)(const ExactLogLikArgs);
-struct ExactLogLikVariant { int dp, lp, sig; ExactLogLikKernel fn; };
-template <int DP, int LP, int SIG> struct ExactLogLikPick { static constexpr ExactLogLikKernel fn = exact_loglik_kernel<DP, LP>; };
-template <int DP, int LP> struct ExactLogLikPick<DP, LP, 1> { static constexpr ExactLogLikKernel fn = nullptr; };
-#define VAEK_EXACT_ROW(DP, LP, SIG, EXACT) {up4(DP), up4(LP), SIG, ExactLogLikPick<up4(DP), up4(LP), SIG>::fn},
-static const ExactLogLikVariant kExactLogLikVariants[] = {VAEK_MFMA_SHAPES(VAEK_EXACT_ROW)};
-#undef VAEK_EXACT_ROW
-
-// vaek_supports_log_likelihood's predicate AND one decoder: the sigmoid second decoder has no closed form
-static const ExactLogLikVariant* pick_exact_loglik(const vaek_ctx* c) {
-    const vaek_config& cfg = c->cfg;
-    if (cfg.dtype != VAEK_F32 || cfg.n_enc_hidden != 0 || cfg.n_dec_hidden != 0 || cfg.sigmoid_decoder) return nullptr;
-    return pick_smallest_shape(kExactLogLikVariants, c->D, c->L, false);
-}
-
-static int64_t exact_loglik_record_len(const vaek_ctx* c) { return kExactHead + (int64_t)c->D; }
-
 }  // namespace vaek
 
 using namespace vaek;
@@ -832,10 +394,7 @@ static int spectrum_rows_call(const char* who, bool vec, vaek_ctx* ctx, const fl
                               int64_t out_stride, void* stream) {
     ProfBind pb(ctx);
     if (!ctx || !x || !out) { set_error("%s: null context, x or out", who); return VAEK_ERR_INVALID; }
-    if (ctx->D > kSpectrumMaxDim) {
-        set_error("%s: data_dim %d, need <= %d (see vaek_supports_cov_spectrum)", who, ctx->D, kSpectrumMaxDim);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_spectrum_dim(who, ctx)) return rc;
     if (n < 1 || n > spectrum_max_sets()) {
         set_error("%s: %d sets, need 1 .. %d (vaek_cov_spectrum_max_sets)", who, n, spectrum_max_sets());
         return VAEK_ERR_INVALID;
@@ -844,17 +403,14 @@ static int spectrum_rows_call(const char* who, bool vec, vaek_ctx* ctx, const fl
         set_error("%s: %d rows, need 2 .. %d (vaek_stats_event_max_rows; one row has no ddof = 1 covariance)", who, rows, kSpectrumMaxRows);
         return VAEK_ERR_INVALID;
     }
-    if (x_stride < 0 || (x_stride > 0 && x_stride < (int64_t)rows * ctx->D)) {
-        set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)x_stride, (long long)rows * ctx->D);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_x_stride(who, ctx, x_stride, rows)) return rc;
     const int64_t len = vec ? eigen_record_len(ctx) : spectrum_record_len(ctx);
     if (out_stride < len) {
         set_error("%s: out_stride %lld < record length %lld (%s)", who, (long long)out_stride, (long long)len,
                   vec ? "vaek_cov_eigen_record_len" : "vaek_cov_spectrum_record_len");
         return VAEK_ERR_INVALID;
     }
-    if (((uintptr_t)out & 7u) != 0) { set_error("%s: out is not 8-byte aligned", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_aligned8(who, "out", (uintptr_t)out)) return rc;
     SpectrumArgs a{};
     a.x = x; a.x_stride = x_stride; a.out = out; a.out_stride = out_stride; a.rows = rows; a.D = ctx->D;
     hipStream_t st = (hipStream_t)stream;
@@ -894,20 +450,14 @@ static int spectrum_event_call(const char* who, bool vec, vaek_ctx* ctx, const f
                                void* stream) {
     ProfBind pb(ctx);
     if (!ctx || !params || !ev) { set_error("%s: null context, params or event", who); return VAEK_ERR_INVALID; }
-    if (ev->struct_size != (int32_t)sizeof(vaek_spectrum_event)) {
-        set_error("%s: vaek_spectrum_event.struct_size %d != %d (header / library mismatch)", who, ev->struct_size, (int)sizeof(vaek_spectrum_event));
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_struct_size(who, "vaek_spectrum_event", ev->struct_size, sizeof(vaek_spectrum_event))) return rc;
     const SpectrumVariant* var = pick_spectrum(ctx);
     if (!var) {
         set_error("%s: needs a float32 linear VAE (no hidden layers) with D, L <= 32, D <= 28 with two decoders (see "
                   "vaek_supports_spectrum_event)", who);
         return VAEK_ERR_INVALID;
     }
-    if (ev->n < 1 || ev->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ev->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_replica_count(who, ev->n)) return rc;
     if (ev->rows < 2 || ev->rows > kSpectrumMaxRows) {
         set_error("%s: %d rows, need 2 .. %d (vaek_stats_event_max_rows; one row has no ddof = 1 covariance)", who, ev->rows, kSpectrumMaxRows);
         return VAEK_ERR_INVALID;
@@ -922,9 +472,9 @@ static int spectrum_event_call(const char* who, bool vec, vaek_ctx* ctx, const f
                   (long long)ctx->P, (long long)ev->out_stride, (long long)len, vec ? "vaek_cov_eigen_record_len" : "vaek_cov_spectrum_record_len");
         return VAEK_ERR_INVALID;
     }
-    if (((uintptr_t)ev->out & 7u) != 0) { set_error("%s: out is not 8-byte aligned", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_aligned8(who, "out", (uintptr_t)ev->out)) return rc;
     if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ev->a_stride, x_tag)) return rc;
-    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_tag(who, z_tag)) return rc;
     SpectrumArgs a{};
     a.out = ev->out; a.out_stride = ev->out_stride; a.rows = ev->rows; a.D = ctx->D;
     a.params = params; a.state_stride = ev->state_stride;
@@ -959,10 +509,7 @@ int vaek_subspace_angles(vaek_ctx* ctx, const double* a, int64_t a_stride, const
     const char* who = "vaek_subspace_angles";
     ProfBind pb(ctx);
     if (!ctx || !a || !b || !out) { set_error("%s: null context, a, b or out", who); return VAEK_ERR_INVALID; }
-    if (ctx->D > kSpectrumMaxDim) {
-        set_error("%s: data_dim %d, need <= %d (see vaek_supports_cov_spectrum)", who, ctx->D, kSpectrumMaxDim);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_spectrum_dim(who, ctx)) return rc;
     if (n < 1 || n > spectrum_max_sets()) {
         set_error("%s: %d pairs, need 1 .. %d (vaek_cov_spectrum_max_sets)", who, n, spectrum_max_sets());
         return VAEK_ERR_INVALID;
@@ -981,7 +528,7 @@ int vaek_subspace_angles(vaek_ctx* ctx, const double* a, int64_t a_stride, const
         set_error("%s: out_stride %lld < record length %d (vaek_subspace_record_len)", who, (long long)out_stride, kb + 4);
         return VAEK_ERR_INVALID;
     }
-    if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) & 7u) != 0) { set_error("%s: a, b or out is not 8-byte aligned", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_aligned8(who, "a, b or out", (uintptr_t)a | (uintptr_t)b | (uintptr_t)out)) return rc;
     SubspaceArgs s{};
     s.a = a; s.a_stride = a_stride; s.b = b; s.b_stride = b_stride; s.out = out; s.out_stride = out_stride;
     s.D = ctx->D; s.ka = ka; s.kb = kb;
@@ -994,86 +541,6 @@ int vaek_subspace_angles(vaek_ctx* ctx, const double* a, int64_t a_stride, const
     return VAEK_OK;
 }
 
-int vaek_supports_exact_log_likelihood(const vaek_ctx* ctx, int32_t kind, int32_t* yes) {
-    if (!ctx || !yes) { set_error("vaek_supports_exact_log_likelihood: null argument"); return VAEK_ERR_INVALID; }
-    *yes = kind >= 0 && kind <= 2 && pick_exact_loglik(ctx) ? 1 : 0;
-    return VAEK_OK;
-}
-
-int vaek_exact_log_likelihood_record_len(const vaek_ctx* ctx, int64_t* doubles) {
-    if (!ctx || !doubles) { set_error("vaek_exact_log_likelihood_record_len: null argument"); return VAEK_ERR_INVALID; }
-    *doubles = exact_loglik_record_len(ctx);
-    return VAEK_OK;
-}
-
-int vaek_exact_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_exact_log_likelihood* ll, int32_t kind,
-                                       const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
-                                       void* stream) {
-    const char* who = "vaek_exact_log_likelihood_replicas";
-    ProfBind pb(ctx);
-    if (!ctx || !params || !ll) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
-    if (ll->struct_size != (int32_t)sizeof(vaek_exact_log_likelihood)) {
-        set_error("%s: vaek_exact_log_likelihood.struct_size %d != %d (header / library mismatch)", who, ll->struct_size,
-                  (int)sizeof(vaek_exact_log_likelihood));
-        return VAEK_ERR_INVALID;
-    }
-    const ExactLogLikVariant* var = pick_exact_loglik(ctx);
-    if (!var) {
-        set_error("%s: needs a float32 linear VAE (no hidden layers) with ONE decoder and D, L <= 32: the sigmoid second decoder has no "
-                  "closed form (see vaek_supports_exact_log_likelihood)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->n < 1 || ll->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ll->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->rows < 1 || ll->rows > kLogLikMaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kLogLikMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    const bool explicit_rows = ll->x != nullptr;
-    if (!ll->out || (!explicit_rows && (!ll->x_seeds || !ll->x_steps))) {
-        set_error("%s: x_seeds, x_steps (drawing mode) or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t len = exact_loglik_record_len(ctx);
-    if (ll->state_stride < ctx->P || ll->out_stride < len) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %lld (vaek_exact_log_likelihood_record_len)", who,
-                  (long long)ll->state_stride, (long long)ctx->P, (long long)ll->out_stride, (long long)len);
-        return VAEK_ERR_INVALID;
-    }
-    if ((((uintptr_t)ll->out | (uintptr_t)ll->row_out) & 7u) != 0) { set_error("%s: out or row_out is not 8-byte aligned", who); return VAEK_ERR_INVALID; }
-    if (ll->row_out && (ll->row_stride < 0 || (ll->row_stride < 2 * (int64_t)ll->rows && (ll->row_stride > 0 || ll->n > 1)))) {
-        set_error("%s: row_stride %lld: need >= 2 * rows = %lld (0 with one replica)", who, (long long)ll->row_stride, 2 * (long long)ll->rows);
-        return VAEK_ERR_INVALID;
-    }
-    if (explicit_rows) {
-        if (ll->x_stride < 0 || (ll->x_stride > 0 && ll->x_stride < (int64_t)ll->rows * ctx->D)) {
-            set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)ll->x_stride, (long long)ll->rows * ctx->D);
-            return VAEK_ERR_INVALID;
-        }
-    } else if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ll->a_stride, x_tag)) {
-        return rc;
-    }
-    ExactLogLikArgs a{};
-    a.params = params; a.state_stride = ll->state_stride;
-    a.x_seeds = reinterpret_cast<const unsigned long long*>(ll->x_seeds); a.x_steps = ll->x_steps;
-    a.x = ll->x; a.x_stride = ll->x_stride;
-    a.out = ll->out; a.out_stride = ll->out_stride; a.row_out = ll->row_out; a.row_stride = ll->row_stride;
-    a.rows = ll->rows; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
-    a.eps_cli = ctx->cfg.eps_cli;
-    if (explicit_rows) {
-        fill_draw_args(&a.gen, ctx, ll->rows, 2, nullptr, 0, 0, 0, 0.f, 0);      // nothing is drawn: the sphere's kind, which has no matrix
-    } else {
-        a.a_stride = ll->a_stride;
-        fill_draw_args(&a.gen, ctx, ll->rows, kind, A, dd, did, pad, var_added, x_tag);
-    }
-    hipStream_t st = (hipStream_t)stream;
-    {
-        ProfScope ps("exact_loglik_replicas", st);
-        launch_k(ps, var->fn, dim3((unsigned)ll->n), dim3(256), 0, st, a);
-    }
-    VAEK_HIP_CHECK(hipGetLastError());
-    return VAEK_OK;
-}
 }  // extern "C"
+
+#include "exact_loglik.inc"      // vaek_exact_log_likelihood_replicas: its kernel, variant table and entry points

@@ -212,10 +212,7 @@ int check_log_likelihood(const char* who, const vaek_ctx* ctx, const float* para
         return VAEK_ERR_INVALID;
     }
     if (!covered) { set_error("%s: %s", who, needs); return VAEK_ERR_INVALID; }
-    if (ll->n < 1 || ll->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ll->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_replica_count(who, ll->n)) return rc;
     if (ll->rows < 1 || ll->rows > kLogLikMaxRows) {
         set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kLogLikMaxRows);
         return VAEK_ERR_INVALID;
@@ -238,13 +235,9 @@ int check_log_likelihood(const char* who, const vaek_ctx* ctx, const float* para
         set_error("%s: workspace is NULL or not %d-byte aligned (%s)", who, ws_align, ws_bytes_fn);
         return VAEK_ERR_INVALID;
     }
-    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_tag(who, z_tag)) return rc;
     if (!explicit_rows) return check_dataset_draw(who, ctx, kind, A, dd, did, pad, ll->a_stride, x_tag);
-    if (ll->x_stride < 0 || (ll->x_stride > 0 && ll->x_stride < (int64_t)ll->rows * ctx->D)) {
-        set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)ll->x_stride, (long long)ll->rows * ctx->D);
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
+    return check_x_stride(who, ctx, ll->x_stride, ll->rows);
 }
 
 int loglik_finalize(const char* label, const vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, const double* part, hipStream_t st) {

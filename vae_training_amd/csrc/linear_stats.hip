@@ -283,10 +283,7 @@ int vaek_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_sta
     }
     const StatsVariant* var = ctx->resident ? pick_stats(ctx) : nullptr;
     if (!var) { set_error("%s: needs a context vaek_train_loop_gen covers (see vaek_supports_stats_event)", who); return VAEK_ERR_INVALID; }
-    if (ev->n < 1 || ev->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ev->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_replica_count(who, ev->n)) return rc;
     if (ev->rows < 1 || ev->rows > kStatsMaxRows) {
         set_error("%s: %d rows, need 1 .. %d (vaek_stats_event_max_rows)", who, ev->rows, kStatsMaxRows);
         return VAEK_ERR_INVALID;
@@ -302,7 +299,7 @@ int vaek_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_sta
         return VAEK_ERR_INVALID;
     }
     if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ev->a_stride, x_tag)) return rc;
-    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_tag(who, z_tag)) return rc;
     StatsArgs a{};
     a.params = params; a.state_stride = ev->state_stride;
     a.x_seeds = reinterpret_cast<const unsigned long long*>(ev->x_seeds); a.x_steps = ev->x_steps;

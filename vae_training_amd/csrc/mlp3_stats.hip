@@ -251,10 +251,7 @@ int vaek_mlp3_stats_event_replicas(vaek_ctx* ctx, const float* params, const vae
                   "vaek_supports_mlp3_stats_event)", who, ML_W, ML_F);
         return VAEK_ERR_INVALID;
     }
-    if (ev->n < 1 || ev->n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, ev->n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_replica_count(who, ev->n)) return rc;
     if (ev->rows < 1 || ev->rows > vaek_stats_event_max_rows()) {
         set_error("%s: %d rows, need 1 .. %d (vaek_stats_event_max_rows)", who, ev->rows, vaek_stats_event_max_rows());
         return VAEK_ERR_INVALID;
@@ -270,7 +267,7 @@ int vaek_mlp3_stats_event_replicas(vaek_ctx* ctx, const float* params, const vae
         return VAEK_ERR_INVALID;
     }
     if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ev->a_stride, x_tag)) return rc;
-    if (z_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_tag(who, z_tag)) return rc;
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
         set_error("%s: workspace is NULL or not 16-byte aligned (vaek_mlp3_stats_event_workspace_bytes)", who);
         return VAEK_ERR_INVALID;

@@ -71,7 +71,41 @@ int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const
         set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
         return VAEK_ERR_INVALID;
     }
-    if (x_tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    return check_tag(who, x_tag);
+}
+
+// ---- the refusals the replica entry points repeat --------------------------------------------------------------------------------
+int check_struct_size(const char* who, const char* name, int32_t got, size_t want) {
+    if (got != (int32_t)want) {
+        set_error("%s: %s.struct_size %d != %d (header / library mismatch)", who, name, got, (int)want);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_replica_count(const char* who, int32_t n) {
+    if (n < 1 || n > resident_max_replicas()) {
+        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, n, resident_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows) {
+    if (x_stride < 0 || (x_stride > 0 && x_stride < (int64_t)rows * ctx->D)) {
+        set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)x_stride, (long long)rows * ctx->D);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_tag(const char* who, uint32_t tag) {
+    if (tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    return VAEK_OK;
+}
+
+int check_aligned8(const char* who, const char* what, uintptr_t addrs) {
+    if ((addrs & 7u) != 0) { set_error("%s: %s is not 8-byte aligned", who, what); return VAEK_ERR_INVALID; }
     return VAEK_OK;
 }
 

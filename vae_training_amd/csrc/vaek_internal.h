@@ -445,6 +445,16 @@ constexpr int kLogLikMaxSamples = 1024;      // ... samples per row: they bound 
 // the dataset arguments of an in-kernel draw under tag x_tag, as `who` refuses them: a_stride, kind, A, dd / did / pad, dimension, tag
 int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
                        int64_t a_stride, uint32_t x_tag);
+// the refusals the replica entry points repeat, each as `who` words it: VAEK_OK, or the error is set and the code to return comes back
+// (hidden: the library's dynamic symbol list stays what it was.  check_dataset_draw and its neighbours were exported before, as every
+// vaek:: function is -- the library is built without -fvisibility=hidden -- and stay so: hiding them would shorten that list)
+#pragma GCC visibility push(hidden)
+int check_struct_size(const char* who, const char* name, int32_t got, size_t want);      // a descriptor `name` of another header's size
+int check_replica_count(const char* who, int32_t n);                                      // outside 1 .. resident_max_replicas()
+int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows); // explicit rows: 0 (shared) or >= rows * D
+int check_tag(const char* who, uint32_t tag);                                             // >= 2^30
+int check_aligned8(const char* who, const char* what, uintptr_t addrs);                   // `addrs`: the outputs `what` names, ORed
+#pragma GCC visibility pop
 // ... and the BatchArgs of that draw: kind, A, dd, did, pad, noise_std, tag, rows, D, L; seed / step / pointers are the kernel's
 void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
                     float var_added, uint32_t x_tag);

@@ -30,6 +30,17 @@ def _f32(t, device):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def _addr(v, dtype=None):
+    """The address of device tensor v (of `dtype`, where one is given) or v itself where it is a raw device address; None stays."""
+    assert v is None or isinstance(v, int) or dtype is None or v.dtype == dtype
+    return None if v is None else C.c_void_p(v if isinstance(v, int) else v.data_ptr())
+
+
+def _last_dim(v, given=None):
+    """`given`, else the last dimension of tensor v: the stride of its records (0 for None or a raw address)."""
+    return int((0 if v is None or isinstance(v, int) else v.shape[-1]) if given is None else given)
+
+
 class Engine:
     """One libvaek context = one (batch, architecture) shape on one GPU."""
 
@@ -103,6 +114,18 @@ class Engine:
             except Exception:
                 pass
 
+    def _flag(self, fn, *args):
+        """A yes / no query of the context: fn(ctx, *args, &int32)."""
+        f = C.c_int32()
+        _lib.check(fn(self.h, *args, C.byref(f)))
+        return bool(f.value)
+
+    def _count(self, fn, *args, ctype=C.c_int64):
+        """A length (int64) or byte count (ctype=C.c_size_t) query of the context: fn(ctx, *args, &count)."""
+        n = ctype()
+        _lib.check(fn(self.h, *args, C.byref(n)))
+        return int(n.value)
+
     # ---- flat buffers ----------------------------------------------------------------------
     def new_flat(self, n=None):
         return torch.zeros(self.P if n is None else n, dtype=torch.float32, device=self.device)
@@ -127,9 +150,7 @@ class Engine:
                                                 _ptr(counter), int(which), int(tag), _stream()))
 
     def supports_train_steps(self):
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_train_steps(self.h, C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_train_steps)
 
     def train_steps(self, params, grads, m, v, step_dev, batches, lr):
         """len(batches) consecutive train steps, batch i = (x, z1, z2) device tensors, software-pipelined over launches
@@ -143,9 +164,7 @@ class Engine:
                                              float(lr), _ptr(self.workspace), _stream()))
 
     def supports_train_steps_gen(self, kind):
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_train_steps_gen(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_train_steps_gen, int(kind))
 
     def train_steps_gen(self, params, grads, m, v, step_dev, n_steps, lr, kind, A, dd, did, pad, var_added, seed, tag=0, row0=0):
         """n_steps consecutive train steps whose batches are drawn INSIDE the launch (vaek_train_steps_gen): the batch of the step
@@ -156,9 +175,7 @@ class Engine:
                                                  int(n_steps), float(lr), _ptr(self.workspace), _stream()))
 
     def supports_train_loop_gen(self, kind):
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_train_loop_gen(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_train_loop_gen, int(kind))
 
     @property
     def train_loop_steps_per_launch(self):
@@ -167,9 +184,7 @@ class Engine:
     @property
     def trajectory_record_len(self):
         """Floats in one trajectory record (vaek_trajectory_record_len): 2 P + 4 = the parameters, then the gradient buffer."""
-        n = C.c_int64()
-        _lib.check(self.lib.vaek_trajectory_record_len(self.h, C.byref(n)))
-        return int(n.value)
+        return self._count(self.lib.vaek_trajectory_record_len)
 
     @staticmethod
     def _trajectory(trajectory):
@@ -214,9 +229,7 @@ class Engine:
     def train_loop_replicas_workspace(self, n):
         """Bytes of the workspace Engine.train_loop_gen_replicas needs for n replicas (its own buffer, not self.workspace): n staged
         batches where the kernel's LDS has no room for one, else 0."""
-        b = C.c_size_t()
-        _lib.check(self.lib.vaek_train_loop_replicas_workspace_bytes(self.h, int(n), C.byref(b)))
-        return int(b.value)
+        return self._count(self.lib.vaek_train_loop_replicas_workspace_bytes, int(n), ctype=C.c_size_t)
 
     def train_loop_gen_replicas(self, params, grads, m, v, step_dev, n_steps, lr, kind, A, dd, did, pad, var_added, seeds, lrs=None,
                                 a_stride=0, loss_hist=None, workspace=None, tag=0, row0=0, n=None, state_stride=None, grads_stride=None,
@@ -237,7 +250,7 @@ class Engine:
         rep.seeds, rep.lrs = _ptr(seeds), _ptr(lrs)
         rep.a_stride = int(a_stride)
         rep.loss_hist = _ptr(loss_hist)
-        rep.loss_hist_cap = int((0 if loss_hist is None else loss_hist.shape[-1]) if loss_hist_cap is None else loss_hist_cap)
+        rep.loss_hist_cap = _last_dim(loss_hist, loss_hist_cap)
         args = (self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep), int(kind), _ptr(A), int(dd), int(did),
                 int(pad), float(var_added), int(row0), int(tag), int(n_steps), float(lr), _ptr(workspace), _stream())
         if trajectory is not None:
@@ -248,16 +261,12 @@ class Engine:
 
     def supports_stats_event(self, kind):
         """True where stats_event_replicas covers this engine and dataset kind: exactly where supports_train_loop_gen does."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_stats_event(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_stats_event, int(kind))
 
     @property
     def stats_record_len(self):
         """Floats in one stats record (vaek_stats_record_len): 8 + L = loss, mean Dkl, mean mse, eps, two score values, 0, 0, epsilon_p."""
-        n = C.c_int64()
-        _lib.check(self.lib.vaek_stats_record_len(self.h, C.byref(n)))
-        return int(n.value)
+        return self._count(self.lib.vaek_stats_record_len)
 
     @property
     def stats_event_max_rows(self):
@@ -294,22 +303,18 @@ class Engine:
         ev.sample_eps = _ptr(sample_eps)
         ev.a_stride = int(a_stride)
         ev.out = _ptr(out)
-        ev.out_stride = int((0 if out is None else out.shape[-1]) if out_stride is None else out_stride)
+        ev.out_stride = _last_dim(out, out_stride)
         return ev
 
     def supports_mlp3_stats_event(self, kind):
         """True where mlp3_stats_event_replicas covers this engine and dataset kind: exactly where supports_mlp3_log_likelihood does --
         float32, one decoder, exactly three hidden layers of 64 .. 256 units both ways, D, L <= 32, whatever the engine's batch, world
         and force_generic are (vaek_supports_mlp3_stats_event)."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_mlp3_stats_event(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_mlp3_stats_event, int(kind))
 
     def mlp3_stats_event_workspace(self, n, rows):
         """Bytes of the workspace mlp3_stats_event_replicas needs (its own buffer, 16-byte aligned, not self.workspace)."""
-        b = C.c_size_t()
-        _lib.check(self.lib.vaek_mlp3_stats_event_workspace_bytes(self.h, int(n), int(rows), C.byref(b)))
-        return int(b.value)
+        return self._count(self.lib.vaek_mlp3_stats_event_workspace_bytes, int(n), int(rows), ctype=C.c_size_t)
 
     def mlp3_stats_event_replicas(self, params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
                                   workspace, a_stride=0, x_tag=1, z_tag=2, n=None, state_stride=None, out_stride=None, struct_size=None):
@@ -318,16 +323,13 @@ class Engine:
         whatever n is.  Asynchronous; capturable."""
         ev = self._stats_event_desc(params, rows, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out, a_stride, n, state_stride, out_stride,
                                     struct_size)
-        wp = None if workspace is None else C.c_void_p(workspace if isinstance(workspace, int) else workspace.data_ptr())
         _lib.check(self.lib.vaek_mlp3_stats_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
-                                                           float(var_added), int(x_tag), int(z_tag), wp, _stream()))
+                                                           float(var_added), int(x_tag), int(z_tag), _addr(workspace), _stream()))
 
     def supports_log_likelihood(self, kind):
         """True where log_likelihood_replicas covers this engine and dataset kind: a float32 linear VAE with one or two decoders, D, L <= 32
         (D <= 28 with two decoders), whatever the engine's batch and world are (vaek_supports_log_likelihood)."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_log_likelihood(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_log_likelihood, int(kind))
 
     @property
     def log_likelihood_record_len(self):
@@ -344,9 +346,7 @@ class Engine:
 
     def log_likelihood_workspace(self, n, rows):
         """Bytes of the workspace log_likelihood_replicas needs for n replicas of `rows` rows (its own buffer, not self.workspace)."""
-        b = C.c_size_t()
-        _lib.check(self.lib.vaek_log_likelihood_workspace_bytes(self.h, int(n), int(rows), C.byref(b)))
-        return int(b.value)
+        return self._count(self.lib.vaek_log_likelihood_workspace_bytes, int(n), int(rows), ctype=C.c_size_t)
 
     @staticmethod
     def _log_likelihood_desc(params, rows, samples, z_seeds, z_steps, out, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride, out_stride,
@@ -364,7 +364,7 @@ class Engine:
         ll.x_seeds, ll.x_steps, ll.z_seeds, ll.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
         ll.a_stride = int(a_stride)
         ll.out = _ptr(out)
-        ll.out_stride = int((0 if out is None else out.shape[-1]) if out_stride is None else out_stride)
+        ll.out_stride = _last_dim(out, out_stride)
         ll.x = _ptr(x)
         if x_stride is None:
             x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
@@ -384,17 +384,14 @@ class Engine:
         tensors' shapes.  Asynchronous; capturable."""
         ll = self._log_likelihood_desc(params, rows, samples, z_seeds, z_steps, out, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride,
                                        out_stride, struct_size)
-        wp = None if workspace is None else C.c_void_p(workspace if isinstance(workspace, int) else workspace.data_ptr())
         _lib.check(self.lib.vaek_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did), int(pad),
-                                                         float(var_added), int(x_tag), int(z_tag), wp, _stream()))
+                                                         float(var_added), int(x_tag), int(z_tag), _addr(workspace), _stream()))
 
     def supports_mlp3_log_likelihood(self, kind):
         """True where mlp3_log_likelihood_replicas covers this engine and dataset kind: float32, one decoder, exactly three hidden layers
         of 64 .. 256 units in the encoder and in the decoder, D, L <= 32 -- whatever the engine's batch, world and force_generic are
         (vaek_supports_mlp3_log_likelihood)."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_mlp3_log_likelihood(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_mlp3_log_likelihood, int(kind))
 
     @property
     def mlp3_log_likelihood_max_columns(self):
@@ -403,9 +400,7 @@ class Engine:
 
     def mlp3_log_likelihood_workspace(self, n, rows, samples):
         """Bytes of the workspace mlp3_log_likelihood_replicas needs (its own buffer, 16-byte aligned, not self.workspace)."""
-        b = C.c_size_t()
-        _lib.check(self.lib.vaek_mlp3_log_likelihood_workspace_bytes(self.h, int(n), int(rows), int(samples), C.byref(b)))
-        return int(b.value)
+        return self._count(self.lib.vaek_mlp3_log_likelihood_workspace_bytes, int(n), int(rows), int(samples), ctype=C.c_size_t)
 
     def mlp3_log_likelihood_replicas(self, params, rows, samples, z_seeds, z_steps, out, workspace, kind=2, A=None, dd=0, did=0, pad=0,
                                      var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, z_tag=4, n=None,
@@ -415,24 +410,19 @@ class Engine:
         mlp3_log_likelihood_workspace(n, rows, samples) bytes.  Four launches whatever n is.  Asynchronous; capturable."""
         ll = self._log_likelihood_desc(params, rows, samples, z_seeds, z_steps, out, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride,
                                        out_stride, struct_size)
-        wp = None if workspace is None else C.c_void_p(workspace if isinstance(workspace, int) else workspace.data_ptr())
         _lib.check(self.lib.vaek_mlp3_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did), int(pad),
-                                                              float(var_added), int(x_tag), int(z_tag), wp, _stream()))
+                                                              float(var_added), int(x_tag), int(z_tag), _addr(workspace), _stream()))
 
     def supports_cov_spectrum(self):
         """True where cov_spectrum_rows covers this engine: data_dim <= 32, whatever its architecture, dtype, batch and world are
         (vaek_supports_cov_spectrum)."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_cov_spectrum(self.h, C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_cov_spectrum)
 
     @property
     def cov_spectrum_record_len(self):
         """Doubles in one spectrum record (vaek_cov_spectrum_record_len): D^2 + 2 D + 4 = D eigenvalues ascending, D column means, the
         covariance matrix row-major, then sweeps run, final off_F, |C|_F and rows."""
-        n = C.c_int64()
-        _lib.check(self.lib.vaek_cov_spectrum_record_len(self.h, C.byref(n)))
-        return int(n.value)
+        return self._count(self.lib.vaek_cov_spectrum_record_len)
 
     @property
     def cov_spectrum_max_sets(self):
@@ -447,24 +437,19 @@ class Engine:
         record s (vaek_cov_spectrum_rows).  x: float32 [n, rows, D] (or [rows, D]: one set), out: float64 [n, out_stride >=
         cov_spectrum_record_len] (or a raw device address) -- device tensors; n and the strides default to the tensors' shapes.  Asynchronous; capturable."""
         assert x is None or x.dtype == torch.float32
-        assert out is None or isinstance(out, int) or out.dtype == torch.float64
+        op = _addr(out, torch.float64)
         if n is None:
             n = 1 if x is None or x.dim() < 3 else x.shape[0]
         if x_stride is None:
             x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
-        if out_stride is None:
-            out_stride = 0 if out is None or isinstance(out, int) else out.shape[-1]
-        op = None if out is None else C.c_void_p(out if isinstance(out, int) else out.data_ptr())
         fn = self.lib.vaek_cov_eigen_rows if _vec else self.lib.vaek_cov_spectrum_rows
-        _lib.check(fn(self.h, _ptr(x), int(n), int(rows), int(x_stride), op, int(out_stride), _stream()))
+        _lib.check(fn(self.h, _ptr(x), int(n), int(rows), int(x_stride), op, _last_dim(out, out_stride), _stream()))
 
     @property
     def cov_eigen_record_len(self):
         """Doubles in one eigen record (vaek_cov_eigen_record_len): 2 D^2 + 2 D + 4 = the spectrum record, then V row-major (column k
         the eigenvector of eigenvalue k, its component of largest magnitude positive)."""
-        n = C.c_int64()
-        _lib.check(self.lib.vaek_cov_eigen_record_len(self.h, C.byref(n)))
-        return int(n.value)
+        return self._count(self.lib.vaek_cov_eigen_record_len)
 
     def cov_eigen_rows(self, x, rows, out, n=None, x_stride=None, out_stride=None):
         """cov_spectrum_rows with eigenvectors (vaek_cov_eigen_rows): out is float64 [n, out_stride >= cov_eigen_record_len]; the first
@@ -480,23 +465,15 @@ class Engine:
         1 <= kb <= ka <= D, for each of n pairs in one launch (vaek_subspace_angles).  a, b: float64 [n, stride >=
         cov_eigen_record_len] written by an EARLIER call (or raw device addresses); out: float64 [n, out_stride >= kb + 4]: sin^2
         ascending, |sin Theta|_F^2, sweeps, off_F, the bases' distance from orthonormal.  Asynchronous; capturable."""
-        def addr(v):
-            assert v is None or isinstance(v, int) or v.dtype == torch.float64
-            return None if v is None else C.c_void_p(v if isinstance(v, int) else v.data_ptr())
-
-        def stride(v, given):
-            return int((0 if v is None or isinstance(v, int) else v.shape[-1]) if given is None else given)
-
         if n is None:
             n = 1 if a is None or isinstance(a, int) or a.dim() < 2 else a.shape[0]
-        _lib.check(self.lib.vaek_subspace_angles(self.h, addr(a), stride(a, a_stride), addr(b), stride(b, b_stride), int(n), int(ka), int(kb),
-                                                 addr(out), stride(out, out_stride), _stream()))
+        f64 = torch.float64
+        _lib.check(self.lib.vaek_subspace_angles(self.h, _addr(a, f64), _last_dim(a, a_stride), _addr(b, f64), _last_dim(b, b_stride), int(n),
+                                                 int(ka), int(kb), _addr(out, f64), _last_dim(out, out_stride), _stream()))
 
     def supports_spectrum_event(self, kind):
         """True where spectrum_event_replicas covers this engine and dataset kind: exactly where supports_log_likelihood does."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_spectrum_event(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_spectrum_event, int(kind))
 
     def spectrum_event_replicas(self, params, rows, kind, A, dd, did, pad, var_added, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out,
                                 a_stride=0, x_tag=5, z_tag=6, n=None, state_stride=None, out_stride=None, struct_size=None, _vec=False):
@@ -513,12 +490,11 @@ class Engine:
         assert all(s is None or s.dtype == torch.int64 for s in (x_seeds, z_seeds))
         assert all(s is None or s.dtype == torch.int32 for s in (x_steps, z_steps))
         assert sample_eps is None or sample_eps.dtype == torch.float32
-        assert out is None or isinstance(out, int) or out.dtype == torch.float64
         ev.x_seeds, ev.x_steps, ev.z_seeds, ev.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
         ev.sample_eps = _ptr(sample_eps)
         ev.a_stride = int(a_stride)
-        ev.out = None if out is None else (out if isinstance(out, int) else out.data_ptr())
-        ev.out_stride = int((0 if out is None or isinstance(out, int) else out.shape[-1]) if out_stride is None else out_stride)
+        ev.out = _addr(out, torch.float64)
+        ev.out_stride = _last_dim(out, out_stride)
         fn = self.lib.vaek_eigen_event_replicas if _vec else self.lib.vaek_spectrum_event_replicas
         _lib.check(fn(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(x_tag),
                       int(z_tag), _stream()))
@@ -533,17 +509,13 @@ class Engine:
         """True where exact_log_likelihood_replicas covers this engine and dataset kind: where supports_log_likelihood does AND the
         model has one decoder (the sigmoid second decoder has no closed form), whatever the engine's batch and world are
         (vaek_supports_exact_log_likelihood)."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_exact_log_likelihood(self.h, int(kind), C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_exact_log_likelihood, int(kind))
 
     @property
     def exact_log_likelihood_record_len(self):
         """Doubles in one exact log-likelihood record (vaek_exact_log_likelihood_record_len): 10 + D = mean log p(x), mean ELBO, mean
         gap, eps, logdet, sweeps, off_F, |K^T K|_F, the conditioning figure, rows, then the D eigenvalues of K^T K ascending."""
-        n = C.c_int64()
-        _lib.check(self.lib.vaek_exact_log_likelihood_record_len(self.h, C.byref(n)))
-        return int(n.value)
+        return self._count(self.lib.vaek_exact_log_likelihood_record_len)
 
     def exact_log_likelihood_replicas(self, params, rows, out, kind=2, A=None, dd=0, did=0, pad=0, var_added=0.0, x_seeds=None, x_steps=None,
                                       x=None, x_stride=None, a_stride=0, x_tag=3, row_out=None, row_stride=None, n=None, state_stride=None,
@@ -555,10 +527,6 @@ class Engine:
         [n, state_stride] (read only), out: float64 [n, out_stride >= exact_log_likelihood_record_len], row_out: None or float64
         [n, rows, 2] (log p(x_i), ELBO(x_i)) -- device tensors or raw device addresses; n and the strides default to the tensors'
         shapes.  Asynchronous; capturable."""
-        def addr(v):
-            assert v is None or isinstance(v, int) or v.dtype == torch.float64
-            return None if v is None else (v if isinstance(v, int) else v.data_ptr())
-
         ll = _lib.VaekExactLogLikelihood()
         ll.struct_size = C.sizeof(_lib.VaekExactLogLikelihood) if struct_size is None else int(struct_size)
         ll.n = int(params.shape[0] if n is None else n)
@@ -569,13 +537,13 @@ class Engine:
         assert x is None or x.dtype == torch.float32
         ll.x_seeds, ll.x_steps = _ptr(x_seeds), _ptr(x_steps)
         ll.a_stride = int(a_stride)
-        ll.out = addr(out)
-        ll.out_stride = int((0 if out is None or isinstance(out, int) else out.shape[-1]) if out_stride is None else out_stride)
+        ll.out = _addr(out, torch.float64)
+        ll.out_stride = _last_dim(out, out_stride)
         ll.x = _ptr(x)
         if x_stride is None:
             x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
         ll.x_stride = int(x_stride)
-        ll.row_out = addr(row_out)
+        ll.row_out = _addr(row_out, torch.float64)
         if row_stride is None:
             row_stride = 0 if row_out is None or isinstance(row_out, int) else 2 * int(rows)
         ll.row_stride = int(row_stride)
@@ -584,9 +552,7 @@ class Engine:
 
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
-        f = C.c_int32()
-        _lib.check(self.lib.vaek_supports_train_step_replicas(self.h, C.byref(f)))
-        return bool(f.value)
+        return self._flag(self.lib.vaek_supports_train_step_replicas)
 
     @property
     def train_step_max_replicas(self):
@@ -595,9 +561,7 @@ class Engine:
     def train_step_replicas_workspace(self, n):
         """Bytes of the workspace Engine.train_step_gen_replicas needs for n replicas (its own buffer, not self.workspace): n times
         the mlp3 step's region of stored activations."""
-        b = C.c_size_t()
-        _lib.check(self.lib.vaek_train_step_replicas_workspace_bytes(self.h, int(n), C.byref(b)))
-        return int(b.value)
+        return self._count(self.lib.vaek_train_step_replicas_workspace_bytes, int(n), ctype=C.c_size_t)
 
     def train_step_gen_replicas(self, params, grads, m, v, step_dev, cur, lr, kind, A, dd, did, pad, var_added, nxt, seeds, counter,
                                 which, lrs=None, a_stride=0, loss_hist=None, workspace=None, tag=0, row0=0, n=None, state_stride=None,
@@ -621,7 +585,7 @@ class Engine:
         rep.seeds, rep.lrs = _ptr(seeds), _ptr(lrs)
         rep.a_stride = int(a_stride)
         rep.loss_hist = _ptr(loss_hist)
-        rep.loss_hist_cap = int((0 if loss_hist is None else loss_hist.shape[-1]) if loss_hist_cap is None else loss_hist_cap)
+        rep.loss_hist_cap = _last_dim(loss_hist, loss_hist_cap)
         nxt = (None, None, None) if nxt is None else nxt
         _lib.check(self.lib.vaek_train_step_gen_replicas(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep),
                                                          _ptr(cur[0]), _ptr(cur[1]), _ptr(cur[2]), float(lr), _ptr(workspace), int(kind),

@@ -115,6 +115,29 @@ def _replica_setup(self, vae_models, name, noun, draws, verb, cap, signature, co
         self.a_stride = self.A.shape[1]
 
 
+def _event_rows(name, m0, rows, lo, hi, cap_fn, note=""):
+    """The rows per event of a replica evaluation: `rows`, else model 0's print_batch_size, refused outside lo .. hi (hi: the engine's
+    cap, `cap_fn` the C function that reports it)."""
+    rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
+    if not lo <= rows <= hi:
+        raise RuntimeError(f"{name}: {rows} rows per event, need {lo} .. {hi} ({cap_fn}{note})")
+    return rows
+
+
+def _seed_step_tensors(seeds, steps, dev):
+    """The uint64 seeds and uint32 RNG steps of a call as the int64 / int32 device tensors the library takes (their bits)."""
+    return (torch.tensor([_wrap_signed(s, 64) for s in seeds], dtype=torch.int64).to(dev),
+            torch.tensor([_wrap_signed(s, 32) for s in steps], dtype=torch.int32).to(dev))
+
+
+def _check_solve(name, r, m, what, mat, sweeps, off, bound):
+    """Refuse the record of model r whose Jacobi solve (`what`, of the matrix `mat`) hit the sweep cap with off_F above `bound` =
+    2^-40 of the matrix's norm; `name` is the class in the message."""
+    if not off <= bound:
+        raise RuntimeError(f"{name}: model {r} ({getattr(m, 'dirname', '?')}): the {what} stopped at the cap of "
+                           f"{int(sweeps)} sweeps with off_F = {off:.3e} > 2^-40 |{mat}|_F = {bound:.3e}")
+
+
 # What GraphLoop(resident=None) resolves to where the engine supports the resident loop and the model has no moments path.  The gate
 # is tools/time_resident.py: True only once the resident loop's slowest repeat has beaten the hipGraph loop's fastest on all seven
 # shapes.  That table has NOT been measured yet (DESIGN 3.8), so the default is off: resident=True asks for the loop explicitly.
@@ -445,9 +468,7 @@ class ReplicaStats:
         _replica_setup(self, vae_models, self.NAME, "launch", "batches", "evaluates", "train_loop_max_replicas", ReplicaLoop._signature,
                        self._check_covered)
         R, m0 = self.R, self.ms[0]
-        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
-        if not 1 <= self.rows <= self.eng.stats_event_max_rows:
-            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 1 .. {self.eng.stats_event_max_rows} (vaek_stats_event_max_rows)")
+        self.rows = _event_rows(self.NAME, m0, rows, 1, self.eng.stats_event_max_rows, "vaek_stats_event_max_rows")
         self.score_keys = SCORE_KEYS[self.kind]
         dev = self.eng.device
         self.L = self.eng.L
@@ -477,14 +498,12 @@ class ReplicaStats:
             key, m.key = vrandom.split(m.key)                                    # compute_stats
             ds = m.dataset
             ds._draws = getattr(ds, "_draws", 0) + 1                              # _device_batch: seed, step, tag 1
-            x_seeds.append(_wrap_signed(ds.key[0] ^ ds.key[1], 64))
-            x_steps.append(_wrap_signed(ds._draws, 32))
+            x_seeds.append(ds.key[0] ^ ds.key[1])
+            x_steps.append(ds._draws)
             m._latent_draws = getattr(m, "_latent_draws", 0) + 1                   # _latent_pair: seed, step, tag 2
-            z_seeds.append(_wrap_signed(key[0] ^ key[1], 64))
-            z_steps.append(_wrap_signed(m._latent_draws, 32))
+            z_seeds.append(key[0] ^ key[1])
+            z_steps.append(m._latent_draws)
             eps_in.append(m.current_epsilon)                                      # sample_batch: the PREVIOUS event's eps
-        t64 = lambda v: torch.tensor(v, dtype=torch.int64).to(dev)
-        t32 = lambda v: torch.tensor(v, dtype=torch.int32).to(dev)
         # an eps a host event left is a device tensor: it stays on the device (no read-back); every other one goes up in one copy
         on_dev = [torch.is_tensor(e) and e.device.type != "cpu" for e in eps_in]
         sample_eps = torch.tensor([0.0 if d else float(torch.as_tensor(e).reshape(-1)[0]) for e, d in zip(eps_in, on_dev)],
@@ -492,8 +511,8 @@ class ReplicaStats:
         for r, (e, d) in enumerate(zip(eps_in, on_dev)):
             if d:
                 sample_eps[r:r + 1].copy_(e.reshape(-1)[:1])
-        self._call(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, t64(x_seeds), t32(x_steps),
-                   t64(z_seeds), t32(z_steps), sample_eps, self.out, a_stride=self.a_stride, x_tag=1, z_tag=2)
+        self._call(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, *_seed_step_tensors(x_seeds, x_steps, dev),
+                   *_seed_step_tensors(z_seeds, z_steps, dev), sample_eps, self.out, a_stride=self.a_stride, x_tag=1, z_tag=2)
         rec = self.out.cpu()                                                      # the event's ONE device -> host copy
         stats = []
         for r, m in enumerate(self.ms):
@@ -561,10 +580,7 @@ class ReplicaLogLik:
         if not 1 <= self.samples <= self.eng.log_likelihood_max_samples:
             raise RuntimeError(f"{self.NAME}: {self.samples} samples per row, need 1 .. {self.eng.log_likelihood_max_samples} "
                                "(vaek_log_likelihood_max_samples)")
-        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
-        if not 1 <= self.rows <= self.eng.log_likelihood_max_rows:
-            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 1 .. {self.eng.log_likelihood_max_rows} "
-                               "(vaek_log_likelihood_max_rows)")
+        self.rows = _event_rows(self.NAME, m0, rows, 1, self.eng.log_likelihood_max_rows, "vaek_log_likelihood_max_rows")
         self._check_size()
         dev = self.eng.device
         self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
@@ -601,10 +617,9 @@ class ReplicaLogLik:
             self.params[r].copy_(m.model.flat)
             m._loglik_draws = getattr(m, "_loglik_draws", 0) + 1
             ds = m.dataset
-            seeds.append(_wrap_signed(ds.key[0] ^ ds.key[1], 64))
-            steps.append(_wrap_signed(m._loglik_draws, 32))
-        seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
-        steps = torch.tensor(steps, dtype=torch.int32).to(dev)
+            seeds.append(ds.key[0] ^ ds.key[1])
+            steps.append(m._loglik_draws)
+        seeds, steps = _seed_step_tensors(seeds, steps, dev)
         self._call(self.params, self.rows, self.samples, seeds, steps, self.out, self.workspace, kind=self.kind,
                    A=self.A, dd=self.dd, did=self.did, pad=self.pad, var_added=self.var, x_seeds=seeds, x_steps=steps,
                    a_stride=self.a_stride, x_tag=self.X_TAG, z_tag=self.Z_TAG)
@@ -647,7 +662,7 @@ class ReplicaLogLikMlp3(ReplicaLogLik):
 
 class ReplicaExactLogLik:
     """The EXACT log-likelihood, the exact ELBO and their difference KL(q(z|x) || p(z|x)) of R one-decoder linear VAEModels of one
-    shape in ONE launch (vaek_exact_log_likelihood_replicas, csrc/cov_spectrum.hip): such a model is a linear-Gaussian
+    shape in ONE launch (vaek_exact_log_likelihood_replicas, csrc/exact_loglik.inc): such a model is a linear-Gaussian
     latent-variable model, p(x) = N(b_d, K^T K + e^eps I), so what ReplicaLogLik estimates has a closed form -- float64 on the device,
     through the eigenvectors of K^T K.
 
@@ -671,10 +686,7 @@ class ReplicaExactLogLik:
         _replica_setup(self, vae_models, self.NAME, "launch", "rows", "evaluates", "train_loop_max_replicas", ReplicaLogLik._shape,
                        self._check_covered)
         R, m0 = self.R, self.ms[0]
-        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
-        if not 1 <= self.rows <= self.eng.log_likelihood_max_rows:
-            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 1 .. {self.eng.log_likelihood_max_rows} "
-                               "(vaek_log_likelihood_max_rows)")
+        self.rows = _event_rows(self.NAME, m0, rows, 1, self.eng.log_likelihood_max_rows, "vaek_log_likelihood_max_rows")
         dev = self.eng.device
         self.record_len = self.eng.exact_log_likelihood_record_len
         self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
@@ -703,10 +715,9 @@ class ReplicaExactLogLik:
             else:
                 s = given[r]
             ds = m.dataset
-            seeds.append(_wrap_signed(ds.key[0] ^ ds.key[1], 64))
-            steps.append(_wrap_signed(s, 32))
-        seeds = torch.tensor(seeds, dtype=torch.int64).to(dev)
-        steps = torch.tensor(steps, dtype=torch.int32).to(dev)
+            seeds.append(ds.key[0] ^ ds.key[1])
+            steps.append(s)
+        seeds, steps = _seed_step_tensors(seeds, steps, dev)
         self.eng.exact_log_likelihood_replicas(self.params, self.rows, self.out, kind=self.kind, A=self.A, dd=self.dd, did=self.did,
                                                pad=self.pad, var_added=self.var, x_seeds=seeds, x_steps=steps, a_stride=self.a_stride,
                                                x_tag=self.X_TAG)
@@ -714,10 +725,7 @@ class ReplicaExactLogLik:
         stats = []
         for r, m in enumerate(self.ms):
             row = rec[r]
-            off, norm = row[6], row[7]
-            if not off <= self.OFF_BOUND * norm:
-                raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the solve of K^T K stopped at the cap of "
-                                   f"{int(row[5])} sweeps with off_F = {off:.3e} > 2^-40 |K^T K|_F = {self.OFF_BOUND * norm:.3e}")
+            _check_solve(self.NAME, r, m, "solve of K^T K", "K^T K", row[5], row[6], self.OFF_BOUND * row[7])
             stats.append({name: float(row[k]) for name, k in zip(self.KEYS, self.SLOTS)})
         return stats
 
@@ -763,10 +771,7 @@ class ReplicaSpectrum:
         _replica_setup(self, vae_models, self.NAME, "call", "rows", "evaluates", "train_loop_max_replicas", ReplicaLogLik._shape,
                        self._check_covered)
         R, m0 = self.R, self.ms[0]
-        self.rows = int(getattr(m0, "print_batch_size", 1000) if rows is None else rows)
-        if not 2 <= self.rows <= self.eng.stats_event_max_rows:
-            raise RuntimeError(f"{self.NAME}: {self.rows} rows per event, need 2 .. {self.eng.stats_event_max_rows} (vaek_stats_event_max_rows; "
-                               "one row has no covariance)")
+        self.rows = _event_rows(self.NAME, m0, rows, 2, self.eng.stats_event_max_rows, "vaek_stats_event_max_rows", "; one row has no covariance")
         dev = self.eng.device
         self.D = self.eng.D
         self.record_len = self.eng.cov_eigen_record_len if self.VEC else self.eng.cov_spectrum_record_len
@@ -803,8 +808,7 @@ class ReplicaSpectrum:
         if self.fused:
             for r, m in enumerate(self.ms):
                 self.params[r].copy_(m.model.flat)
-            sd = torch.tensor([_wrap_signed(s, 64) for s in seeds], dtype=torch.int64).to(dev)
-            st = torch.tensor([_wrap_signed(s, 32) for s in steps], dtype=torch.int32).to(dev)
+            sd, st = _seed_step_tensors(seeds, steps, dev)
             call = self.eng.eigen_event_replicas if self.VEC else self.eng.spectrum_event_replicas
             call(self.params, self.rows, self.kind, self.A, self.dd, self.did, self.pad, self.var, sd, st, sd, st,
                  torch.tensor(eps_in, dtype=torch.float32).to(dev), self.out.view(R, 2 * self.record_len), a_stride=self.a_stride,
@@ -836,10 +840,8 @@ class ReplicaSpectrum:
         st = {}
         for side, name in enumerate(self.KEYS):                                   # record 2 r: the fake side, 2 r + 1: the real side
             row = rec[2 * r + side]
-            off, norm = row[2 * D + D * D + 1], row[2 * D + D * D + 2]
-            if not off <= self.OFF_BOUND * norm:
-                raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the {name} solve stopped at the cap of "
-                                   f"{int(row[2 * D + D * D])} sweeps with off_F = {off:.3e} > 2^-40 |C|_F = {self.OFF_BOUND * norm:.3e}")
+            tail = row[2 * D + D * D:]                                             # sweeps, off_F, |C|_F, rows
+            _check_solve(self.NAME, r, m, f"{name} solve", "C", tail[0], tail[1], self.OFF_BOUND * tail[2])
             st[name] = row[:D].copy()
         return st
 
@@ -891,9 +893,7 @@ class ReplicaSubspace(ReplicaSpectrum):
         row = host[2 * self.R * self.record_len:].reshape(self.R, self.angle_len)[r]
         sin2, off = row[:k], row[k + 2]
         norm = float(np.sqrt(np.sum(sin2 * sin2) + off * off))
-        if not off <= self.OFF_BOUND * norm:
-            raise RuntimeError(f"{self.NAME}: model {r} ({getattr(m, 'dirname', '?')}): the principal-angle solve stopped at the cap of "
-                               f"{int(row[k + 1])} sweeps with off_F = {off:.3e} > 2^-40 |G|_F = {self.OFF_BOUND * norm:.3e}")
+        _check_solve(self.NAME, r, m, "principal-angle solve", "G", row[k + 1], off, self.OFF_BOUND * norm)
         st[self.ANGLES] = np.arcsin(np.sqrt(np.clip(sin2, 0.0, 1.0)))
         st[self.DISTANCE] = float(np.sqrt(row[k]))
         for name, key in (("principal_angles", self.ANGLES), ("subspace_distances", self.DISTANCE)):
