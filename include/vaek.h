@@ -727,6 +727,80 @@ int vaek_exact_log_likelihood_record_len(const vaek_ctx* ctx, int64_t* doubles);
 int vaek_exact_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_exact_log_likelihood* ll, int32_t kind,
                                        const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
                                        void* stream);
+/* DECODER JACOBIAN SPECTRA of N THREE-HIDDEN-LAYER MLP VAEs of the context's shape in one call (csrc/mlp3_jacobian.hip): how many
+ * directions of the latent space the decoder moves its output along, row by row.  For a latent row z of replica r
+ *   J(z) = d Decoder(z) / dz  (D x L)  = K3^T M3 K2^T M2 K1^T M1 K0^T,   M_i = diag(pre_i(z) > 0),
+ * the four decoder kernels with the three relu masks of the primal pass between them (a unit is live iff its float32 pre-activation is
+ * > 0; the derivative at exactly 0 is 0, where jax.grad of `maximum` gives 0.5: a difference on a set of measure zero), and
+ *   G(z) = J^T J  (L x L, float64 from the float32 J),  lambda_1 >= .. >= lambda_L its eigenvalues = the squared singular values of J.
+ * ROW RECORD of vaek_decoder_jacobian_row_record_len = 2 L + 4 doubles (row i of replica r at row_out + r * row_out_stride + i * (2 L
+ * + 4), where row_out is given):
+ *   [0, L)     lambda, descending (ranked by counting, ties by index; nothing is clamped)
+ *   [L, 2 L)   diag G: |d Decoder / d z_l|^2, the sensitivity of the output to latent l
+ *   [2 L]      the numerical rank #{k : lambda_k > rank_tol * lambda_1}, 0 where lambda_1 = 0
+ *   [2 L + 1]  sweeps of the Jacobi solve,  [2 L + 2] off_F where it stopped,  [2 L + 3] |G|_F.
+ * MODEL RECORD of vaek_decoder_jacobian_record_len = 2 L + 8 doubles at out + r * out_stride, written with per-lane vector stores:
+ *   [0] rows   [1] mean rank   [2] min rank   [3] max rank   [4] mean |J|_F^2   [5] max sweeps
+ *   [6] max off_F / |G|_F (0 where |G|_F = 0)   [7] rank_tol as used
+ *   [8, 8 + L)       mean over rows of the k-th largest eigenvalue of J^T J
+ *   [8 + L, 8 + 2 L) mean over rows of diag J^T J.
+ * Doubles between two records where a stride exceeds the length are not touched; nothing but the records and the workspace is written.
+ * Replica r reads params + r * state_stride (vaek_param_count floats; never written; the decoder's leaves only) and its latents:
+ *   - EXPLICIT ROWS (z != NULL): from z + r * z_stride as [rows][L] floats (z_stride == 0: one set shared by all replicas); z_seeds,
+ *     z_steps and z_tag are not read;
+ *   - DRAWING MODE (z == NULL): row i is the z1 that vaek_make_batch writes for row i under (z_seeds[r], step_host = z_steps[r], z_tag),
+ *     row0 = 0: Philox blocks q < ceil(L / 4) of the row's latent stream, bit for bit -- sample 0 of the block rule of
+ *     vaek_log_likelihood_replicas, the latents sample_batch decodes at a stats event.
+ * THREE launches per call whatever n is (profile labels mlp3_jacobian_tangent, mlp3_jacobian_solve, mlp3_jacobian_finalize): a
+ * workgroup per tile of 64 / (L + 1) rows carries each row's primal column and its L tangent columns through the four decoder products
+ * together (v_mfma_f32_16x16x4_f32, exact f32; the bias on the primal column only, relu and its mask applied to the stored image) and
+ * stores J (float32) in the workspace; a workgroup per row forms G in float64 (each entry a sum over d in d order of exact products)
+ * and solves it with the cyclic Jacobi of the covariance spectra (stop at off_F <= 2^-43 |G|_F or vaek_cov_spectrum_max_sweeps); n
+ * workgroups add the rows in a binary tree per 256 rows, then the tiles in order.  Nothing stored in a launch is read back in it; no
+ * atomic, counter, wait or status word.
+ * DEFINING PROPERTIES: a column's arithmetic does not depend on its place in a tile, so a row's record depends on its latent's and the
+ * parameters' bits only: replica r's records are BITWISE what a call with n = 1 on its slices leaves, two runs are bitwise equal,
+ * drawing mode equals explicit mode on the z1 vaek_make_batch writes, and the records do not depend on ctx.batch, state_stride or
+ * whether row_out is given.  sum lambda = trace G to 1e-12 relative; G = 0 (a dead decoder, an exact kink) ends at 0 sweeps, rank 0.
+ * Away from the kinks (every |pre| above the float32 forward's error) lambda and diag G agree with the float64 evaluation within the
+ * float32 error of G plus 64 L 2^-53 |G|_F.  Float32 J does not resolve singular values below about 2^-12 sigma_max in J^T J: choose
+ * rank_tol above 2^-24.
+ * rows is 1 .. vaek_stats_event_max_rows() = 4096, n 1 .. vaek_train_loop_max_replicas(), and n * rows * L <=
+ * vaek_mlp3_decoder_jacobian_max_columns() = 2^20 (a cap that bounds the workspace at 128 MB of J and the length of a call on a shared
+ * machine, not a tuned value).  `workspace`: device memory of vaek_mlp3_decoder_jacobian_workspace_bytes(ctx, n, rows) bytes, 16-byte
+ * aligned, the call's own, no need to clear; it holds J and the row records.  The weights are read one dword at a time: state_stride
+ * has no alignment rule.  Asynchronous on `stream`, allocates nothing, does not synchronise, capturable into a hipGraph.
+ * vaek_supports_mlp3_decoder_jacobian: vaek_supports_mlp3_log_likelihood's predicate without the kind (the call draws no data rows):
+ * float32, one decoder, exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32 -- whatever
+ * ctx.batch, world and force_generic are.  NOT covered: other depths, bf16, D or L > 32, two-decoder models, right singular vectors.
+ * VAEK_ERR_INVALID (message names vaek_mlp3_decoder_jacobian_replicas, nothing touched): a NULL or unsupported context, NULL params or
+ * description, a wrong struct_size, n, rows or n * rows * L out of range, a NULL out, NULL z_seeds or z_steps in drawing mode,
+ * state_stride < P, out_stride < 2 L + 8, row_out_stride < rows * (2 L + 4) where row_out is given, z_stride < 0 or 0 < z_stride <
+ * rows * L, rank_tol outside [0, 1) or NaN, z_tag >= 2^30, out or row_out not 8-byte aligned, a NULL or misaligned workspace.
+ * vaek_mlp3_decoder_jacobian_workspace_bytes refuses an unsupported context and sizes outside those ranges and leaves *bytes alone. */
+typedef struct vaek_decoder_jacobian {
+    int32_t struct_size;                  /* = sizeof(vaek_decoder_jacobian), ABI guard                 */
+    int32_t n;                            /* replicas                                                   */
+    int32_t rows;                         /* latent rows, 1 .. vaek_stats_event_max_rows()              */
+    int32_t reserved;                     /* 0                                                          */
+    int64_t state_stride;                 /* floats between two replicas' params, >= P                  */
+    const uint64_t* z_seeds;              /* device [n]: seed of the latents (drawing mode)             */
+    const uint32_t* z_steps;              /* device [n]: their RNG step (drawing mode)                  */
+    const float* z;                       /* device [rows][L] per replica: explicit rows; NULL = draw   */
+    int64_t z_stride;                     /* floats between two replicas' latents; 0 = shared           */
+    double rank_tol;                      /* 0 <= rank_tol < 1                                          */
+    double* out;                          /* device: model record r at out + r * out_stride             */
+    int64_t out_stride;                   /* >= vaek_decoder_jacobian_record_len()                      */
+    double* row_out;                      /* device [rows][2 L + 4] per replica, or NULL                */
+    int64_t row_out_stride;               /* doubles between two replicas' row blocks                   */
+} vaek_decoder_jacobian;
+int vaek_supports_mlp3_decoder_jacobian(const vaek_ctx* ctx, int32_t* yes);
+int vaek_decoder_jacobian_record_len(const vaek_ctx* ctx, int64_t* doubles);
+int vaek_decoder_jacobian_row_record_len(const vaek_ctx* ctx, int64_t* doubles);
+int vaek_mlp3_decoder_jacobian_max_columns(void);
+int vaek_mlp3_decoder_jacobian_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes);
+int vaek_mlp3_decoder_jacobian_replicas(vaek_ctx* ctx, const float* params, const vaek_decoder_jacobian* dj, uint32_t z_tag,
+                                        void* workspace, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

@@ -78,6 +78,16 @@ class VaekExactLogLikelihood(C.Structure):
     ]
 
 
+class VaekDecoderJacobian(C.Structure):
+    """vaek_decoder_jacobian of include/vaek.h: the per-replica description of vaek_mlp3_decoder_jacobian_replicas (device pointers)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n", C.c_int32), ("rows", C.c_int32), ("reserved", C.c_int32), ("state_stride", C.c_int64),
+        ("z_seeds", C.c_void_p), ("z_steps", C.c_void_p), ("z", C.c_void_p), ("z_stride", C.c_int64), ("rank_tol", C.c_double),
+        ("out", C.c_void_p), ("out_stride", C.c_int64), ("row_out", C.c_void_p), ("row_out_stride", C.c_int64),
+    ]
+
+
+DECODER_JACOBIAN_RECORD_HEAD = 8   # doubles of a decoder-Jacobian model record in front of the L mean eigenvalues and the L mean diagonals
 EXACT_LOGLIK_RECORD_HEAD = 10      # doubles of an exact log-likelihood record in front of the D eigenvalues of K^T K
 STATS_RECORD_HEAD = 8     # floats of a stats record in front of the epsilon_p copy: loss, Dkl, mse, eps, two score values, 0, 0
 
@@ -190,6 +200,12 @@ SIGNATURES = {
     "vaek_exact_log_likelihood_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
     "vaek_exact_log_likelihood_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekExactLogLikelihood), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
                                                      _vp]),
+    "vaek_supports_mlp3_decoder_jacobian": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "vaek_decoder_jacobian_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "vaek_decoder_jacobian_row_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
+    "vaek_mlp3_decoder_jacobian_max_columns": (C.c_int, []),
+    "vaek_mlp3_decoder_jacobian_workspace_bytes": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "vaek_mlp3_decoder_jacobian_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekDecoderJacobian), C.c_uint32, _vp, _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

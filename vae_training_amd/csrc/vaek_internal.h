@@ -470,5 +470,7 @@ int loglik_finalize(const char* label, const vaek_ctx* ctx, const float* params,
 
 // ---- mlp3_loglik.hip: importance-weighted log-likelihood of three-hidden-layer MLP VAEs; whatever the batch, world or force_generic
 bool mlp3_loglik_supported(const vaek_ctx* c);
+// ---- mlp3_jacobian.hip: decoder Jacobian spectra of the same contexts (vaek_ctx::mlp3_loglik is its predicate too: the call draws no
+// data rows, so there is no kind); it shares check_struct_size, check_replica_count, check_tag and check_aligned8 above and nothing else
 
 }  // namespace vaek

@@ -413,6 +413,65 @@ class Engine:
         _lib.check(self.lib.vaek_mlp3_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did), int(pad),
                                                               float(var_added), int(x_tag), int(z_tag), _addr(workspace), _stream()))
 
+    def supports_mlp3_decoder_jacobian(self):
+        """True where mlp3_decoder_jacobian_replicas covers this engine: supports_mlp3_log_likelihood's predicate without the dataset
+        kind (the call draws no data rows) -- whatever the engine's batch, world and force_generic are
+        (vaek_supports_mlp3_decoder_jacobian)."""
+        return self._flag(self.lib.vaek_supports_mlp3_decoder_jacobian)
+
+    @property
+    def decoder_jacobian_record_len(self):
+        """Doubles of a decoder-Jacobian model record: 2 L + 8 (vaek_decoder_jacobian_record_len)."""
+        return self._count(self.lib.vaek_decoder_jacobian_record_len)
+
+    @property
+    def decoder_jacobian_row_record_len(self):
+        """Doubles of a decoder-Jacobian row record: 2 L + 4 (vaek_decoder_jacobian_row_record_len)."""
+        return self._count(self.lib.vaek_decoder_jacobian_row_record_len)
+
+    @property
+    def mlp3_decoder_jacobian_max_columns(self):
+        """The cap on n * rows * L of one mlp3_decoder_jacobian_replicas call (vaek_mlp3_decoder_jacobian_max_columns)."""
+        return int(self.lib.vaek_mlp3_decoder_jacobian_max_columns())
+
+    def mlp3_decoder_jacobian_workspace(self, n, rows):
+        """Bytes of the workspace mlp3_decoder_jacobian_replicas needs (its own buffer, 16-byte aligned, not self.workspace)."""
+        return self._count(self.lib.vaek_mlp3_decoder_jacobian_workspace_bytes, int(n), int(rows), ctype=C.c_size_t)
+
+    def mlp3_decoder_jacobian_replicas(self, params, rows, out, workspace, z_seeds=None, z_steps=None, z=None, z_stride=None, rank_tol=1e-4,
+                                       row_out=None, row_out_stride=None, z_tag=5, n=None, state_stride=None, out_stride=None,
+                                       struct_size=None):
+        """The spectra of the decoder Jacobian J(z) = d Decoder(z) / dz of EACH of n independent three-hidden-layer MLP VAEs of this
+        engine's shape in one call (vaek_mlp3_decoder_jacobian_replicas): per latent row the eigenvalues of J^T J (descending), its
+        diagonal and the numerical rank #{lambda_k > rank_tol lambda_1}; model record r = [rows, mean / min / max rank, mean |J|_F^2,
+        max sweeps, max off_F / |G|_F, rank_tol, L mean eigenvalues, L mean diagonals] in out[r, :2 L + 8], the row records in
+        row_out[r, i, :2 L + 4] where row_out is given.  The latents are the caller's (z: float32 [rows, L] shared by all replicas, or
+        [n, rows, L]) or, with z None, the z1 make_batch draws under (z_seeds[r], z_steps[r], z_tag).  params: [n, state_stride] (read
+        only), seeds int64 [n], steps int32 [n], out / row_out: float64, workspace: uint8 of mlp3_decoder_jacobian_workspace(n, rows)
+        bytes -- all device tensors; n and the strides default to the tensors' shapes.  Three launches whatever n is.  Asynchronous;
+        capturable."""
+        dj = _lib.VaekDecoderJacobian()
+        dj.struct_size = C.sizeof(_lib.VaekDecoderJacobian) if struct_size is None else int(struct_size)
+        dj.n = int(params.shape[0] if n is None else n)
+        dj.rows = int(rows)
+        dj.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        assert z_seeds is None or z_seeds.dtype == torch.int64
+        assert z_steps is None or z_steps.dtype == torch.int32
+        assert z is None or z.dtype == torch.float32
+        assert all(o is None or o.dtype == torch.float64 for o in (out, row_out))
+        dj.z_seeds, dj.z_steps, dj.z = _ptr(z_seeds), _ptr(z_steps), _ptr(z)
+        if z_stride is None:
+            z_stride = 0 if z is None or z.dim() < 3 else z.shape[-2] * z.shape[-1]
+        dj.z_stride = int(z_stride)
+        dj.rank_tol = float(rank_tol)
+        dj.out = _ptr(out)
+        dj.out_stride = _last_dim(out, out_stride)
+        dj.row_out = _ptr(row_out)
+        if row_out_stride is None:
+            row_out_stride = 0 if row_out is None else row_out.shape[-2] * row_out.shape[-1]
+        dj.row_out_stride = int(row_out_stride)
+        _lib.check(self.lib.vaek_mlp3_decoder_jacobian_replicas(self.h, _ptr(params), C.byref(dj), int(z_tag), _addr(workspace), _stream()))
+
     def supports_cov_spectrum(self):
         """True where cov_spectrum_rows covers this engine: data_dim <= 32, whatever its architecture, dtype, batch and world are
         (vaek_supports_cov_spectrum)."""

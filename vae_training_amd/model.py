@@ -70,6 +70,9 @@ class Model:
         self.load_model()
 
 
+JACOBIAN_KEYS = ("Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity")      # trainer.ReplicaJacobianMlp3.KEYS
+
+
 class GenerativeModel(Model):
     def __init__(self, dirname, num_batches, num_epochs, batch_size, learning_rate, latent_distribution,
                  state_dict, dataset, data_fn, tqdm=False, latent_dimension=None):
@@ -132,7 +135,9 @@ class GenerativeModel(Model):
         the rows the IWAE event just scored where there is one (then also "IWAE Gap"); `mlp_log_likelihood_samples` does the same for a
         three-hidden-layer MLP model (trainer.ReplicaLogLikMlp3); `eigenvalues` (run.py --eigenvalues) adds the covariance spectra of
         a generated and a real batch (trainer.ReplicaSpectrum), which leaves the run alone in the same way; `subspace` (run.py
-        --subspace) adds the principal angles between their leading eigenspaces (trainer.ReplicaSubspace) under the same counter."""
+        --subspace) adds the principal angles between their leading eigenspaces (trainer.ReplicaSubspace) under the same counter;
+        `decoder_jacobian` = "prior" | "posterior" (run.py --decoder_jacobian) adds the spectra of the decoder Jacobian of a
+        three-hidden-layer MLP model (trainer.ReplicaJacobianMlp3), under a counter and tags of its own."""
         stats = self.compute_stats()
         K = getattr(self, "log_likelihood_samples", None)
         if K:
@@ -163,11 +168,22 @@ class GenerativeModel(Model):
             if getattr(self, "_spectrum", None) is None:
                 self._spectrum = ReplicaSpectrum([self])
             stats.update(self._spectrum.event()[0])
+        at = getattr(self, "decoder_jacobian", None)               # run.py --decoder_jacobian: the decoder Jacobian spectra of an mlp3 model
+        if at:
+            from .trainer import ReplicaJacobianMlp3
+            if getattr(self, "_jacobian", None) is None:
+                self._jacobian = ReplicaJacobianMlp3([self], at=at, rank_tol=getattr(self, "decoder_jacobian_tol", 1e-4))
+            stats.update(self._jacobian.event()[0])
         return stats
 
     def write_stats(self, stats):
         message = f"Batch | {self.batchnum}"
         for stat, val in stats.items():
+            if stat in JACOBIAN_KEYS:                      # arrays whatever L is; the stats line shows the mean rank
+                self.stats[stat].append(_to_numpy(val))
+                if stat == JACOBIAN_KEYS[1]:
+                    message += f" | {stat} (mean) | {float(val[0]):.3f}"
+                continue
             try:
                 fval = float(val)
             except Exception:

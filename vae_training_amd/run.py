@@ -3,7 +3,7 @@
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
---fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples, --eigenvalues, --subspace."""
+--fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples, --eigenvalues, --subspace, --decoder_jacobian."""
 from __future__ import annotations
 
 import argparse
@@ -115,7 +115,31 @@ def build_parser():
                         "vaek_cov_spectrum_rows call.  The evaluation has its own RNG counter and tags, so the training run is bitwise "
                         "the one without the flag.  Alone or with --sweep_dataset_seeds; combines with the stats and log-likelihood "
                         "flags; data_dim <= 32; single GPU only")
+    p.add_argument("--decoder_jacobian", dest="decoder_jacobian", default=None, choices=["prior", "posterior"],
+                   help="at every n_print step also evaluate the spectrum of the decoder Jacobian J(z) = d Decoder(z) / dz of a "
+                        "three-hidden-layer MLP VAE on a print batch of latent rows (trainer.ReplicaJacobianMlp3, "
+                        "vaek_mlp3_decoder_jacobian_replicas): losses.npz gains 'Decoder Jacobian Spectrum' (mean eigenvalues of J^T J, "
+                        "descending), 'Decoder Jacobian Rank' (mean, min, max numerical rank) and 'Latent Sensitivity' (mean "
+                        "|d Decoder / d z_l|^2 per latent, next to 'Encoder Variance'); the stats line shows the mean rank.  prior: the "
+                        "latents sample_batch decodes; posterior: the encoder means of a real print batch.  The evaluation has its own RNG "
+                        "counter and tags, so the training run is bitwise the one without the flag.  Alone or with --sweep_dataset_seeds "
+                        "(one call for all models); combines with --mlp_fused_stats and --mlp_log_likelihood_samples; float32, one decoder, "
+                        "three hidden layers of 64 .. 256 units both ways, D, L <= 32; linear models (J is the decoder kernel: use "
+                        "--exact_log_likelihood), other models and data parallelism are refused before any step")
+    p.add_argument("--decoder_jacobian_tol", dest="decoder_jacobian_tol", type=_rank_tol, default=None, metavar="T",
+                   help="with --decoder_jacobian: an eigenvalue of J^T J counts towards the rank where it exceeds T times the largest "
+                        "(0 <= T < 1, default 1e-4); refused without --decoder_jacobian")
     return p
+
+
+def _rank_tol(text):
+    try:
+        t = float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not a number")
+    if not 0.0 <= t < 1.0:
+        raise argparse.ArgumentTypeError(f"{text} is not in [0, 1)")
+    return t
 
 
 def _positive_int(text):
@@ -376,6 +400,42 @@ def check_mlp_log_likelihood_model(m, samples, n_models=1):
                            f"model's step path: {path})")
 
 
+JACOBIAN_NEEDS = ("a model vaek_mlp3_decoder_jacobian_replicas covers (vaek_supports_mlp3_decoder_jacobian): float32, one decoder, "
+                  "exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32, -dd / -did <= 16, on one GPU")
+JACOBIAN_DEFAULT_TOL = 1e-4
+
+
+def check_decoder_jacobian_flags(args):
+    """--decoder_jacobian_tol without --decoder_jacobian: refused before anything is created."""
+    if getattr(args, "decoder_jacobian_tol", None) is not None and getattr(args, "decoder_jacobian", None) is None:
+        raise RuntimeError("--decoder_jacobian_tol sets the rank threshold of --decoder_jacobian prior|posterior: give that flag too")
+
+
+def decoder_jacobian_tol(args):
+    """The rank threshold of --decoder_jacobian: --decoder_jacobian_tol, else 1e-4."""
+    tol = getattr(args, "decoder_jacobian_tol", None)
+    return JACOBIAN_DEFAULT_TOL if tol is None else float(tol)
+
+
+def check_decoder_jacobian_model(m, n_models=1):
+    """--decoder_jacobian: refuse, before any step, a model the call does not cover or more columns (models x print rows x L) than one
+    call takes."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    kind, _, dd, did, _, _ = m.dataset.device_spec()
+    path = getattr(eng, "step_path", "?")
+    if eng.world == 1 and eng.supports_log_likelihood(kind):
+        raise RuntimeError(f"--decoder_jacobian needs {JACOBIAN_NEEDS}; this is a linear VAE, whose J is the decoder kernel itself at every "
+                           f"z: use --exact_log_likelihood, whose record holds the eigenvalues of K^T K (this model's step path: {path})")
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_mlp3_decoder_jacobian():
+        raise RuntimeError(f"--decoder_jacobian needs {JACOBIAN_NEEDS} (this model's step path: {path}, world {eng.world})")
+    cols = n_models * m.print_batch_size * eng.L
+    if cols > eng.mlp3_decoder_jacobian_max_columns:
+        raise RuntimeError(f"--decoder_jacobian: {n_models} models x {m.print_batch_size} rows x {eng.L} latents = {cols} columns, at most "
+                           f"{eng.mlp3_decoder_jacobian_max_columns} fit one call (vaek_mlp3_decoder_jacobian_max_columns; this model's "
+                           f"step path: {path})")
+
+
 EIGEN_NEEDS = "data_dim <= 32 (vaek_supports_cov_spectrum), -dd / -did <= 16, on one GPU"
 
 
@@ -469,6 +529,11 @@ def main_sweep(args):
         spectrum = ReplicaSubspace(models, k=check_subspace_model(models[0], args.subspace))
         for m in models:
             m.subspace = True                # model_save_data writes "Subspace Distance" and "Principal Angles"
+    jacobian = None
+    if getattr(args, "decoder_jacobian", None) is not None:      # before any step
+        from .trainer import ReplicaJacobianMlp3
+        check_decoder_jacobian_model(models[0], len(models))
+        jacobian = ReplicaJacobianMlp3(models, at=args.decoder_jacobian, rank_tol=decoder_jacobian_tol(args))
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
     if fused_stats:
@@ -489,6 +554,9 @@ def main_sweep(args):
         entry = "vaek_eigen_event_replicas" if spectrum.fused else "vaek_cov_eigen_rows"
         print(f"Subspace events: the {spectrum.k} leading eigenvectors of {spectrum.rows} generated and {spectrum.rows} real rows per model "
               f"({entry}, vaek_subspace_angles)")
+    if jacobian is not None:
+        print(f"Decoder Jacobian events: {jacobian.rows} {jacobian.at} latent rows per model, rank threshold {jacobian.rank_tol:g}, one call "
+              f"for {len(models)} models (vaek_mlp3_decoder_jacobian_replicas)")
     for r, m in enumerate(models):
         m._graph_loop = loop.view(r)
         score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
@@ -506,6 +574,7 @@ def main_sweep(args):
         spectra = spectrum.event() if spectrum is not None and ev % n_print == 0 else None     # every model's two spectra in one call
         # every model's closed form in one launch, on the rows the IWAE event just scored where there is one
         closed = exact.event_after(extra if ll_samples is not None else None) if exact is not None and ev % n_print == 0 else None
+        jac = jacobian.event() if jacobian is not None and ev % n_print == 0 else None     # every model's decoder Jacobian spectra in one call
         for r, m in enumerate(models):
             m.batchnum = ev
             if ev % n_print == 0:
@@ -517,6 +586,8 @@ def main_sweep(args):
                 if spectra is not None:
                     stats.update(spectra[r] if getattr(args, "eigenvalues", False) else
                                  {k: v for k, v in spectra[r].items() if k not in spectrum.KEYS})
+                if jac is not None:
+                    stats.update(jac[r])
                 m.write_stats(stats)
             if ev % n_plot == 0 or ev == n - 1:
                 m.plot_epoch()
@@ -536,6 +607,7 @@ def main(args):
 
     check_fused_stats_args(args)
     check_log_likelihood_flags(args)
+    check_decoder_jacobian_flags(args)
     if getattr(args, "sweep_dataset_seeds", None):
         return main_sweep(args)
     from .utils import get_output_dir, make_output_dir
@@ -555,6 +627,9 @@ def main(args):
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1 and getattr(args, "subspace", None) is not None:
         raise RuntimeError(f"--subspace needs {SUBSPACE_NEEDS}: it does not combine with data parallelism "
+                           f"(step path of a world of {world}: one shard per rank)")
+    if world > 1 and getattr(args, "decoder_jacobian", None) is not None:
+        raise RuntimeError(f"--decoder_jacobian needs {JACOBIAN_NEEDS}: it does not combine with data parallelism "
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1:
         import torch
@@ -602,6 +677,12 @@ def main(args):
         model.subspace_k = check_subspace_model(model, args.subspace)      # before any step
         model.subspace = True                              # the n_print events add trainer.ReplicaSubspace([model], k).event()
         print(f"Subspace events: {model.print_batch_size} generated and {model.print_batch_size} real rows (csrc/cov_spectrum.hip)")
+    if getattr(args, "decoder_jacobian", None) is not None:
+        check_decoder_jacobian_model(model)                # before any step
+        model.decoder_jacobian = args.decoder_jacobian     # the n_print events add trainer.ReplicaJacobianMlp3([model], at=...).event()
+        model.decoder_jacobian_tol = decoder_jacobian_tol(args)
+        print(f"Decoder Jacobian events: {model.print_batch_size} {args.decoder_jacobian} latent rows, rank threshold "
+              f"{model.decoder_jacobian_tol:g} (vaek_mlp3_decoder_jacobian_replicas)")
     if rank == 0:
         eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
         loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")

@@ -743,6 +743,103 @@ class ReplicaExactLogLik:
         return stats
 
 
+class ReplicaJacobianMlp3:
+    """The decoder Jacobian spectra of R three-hidden-layer MLP VAEModels of one shape in ONE library call
+    (vaek_mlp3_decoder_jacobian_replicas, csrc/mlp3_jacobian.hip): per model, over `rows` latent rows z, the eigenvalues of J^T J with
+    J = d Decoder(z) / dz -- the squared singular values of the decoder's local linear map --, their numerical rank and the
+    sensitivity |d Decoder / d z_l|^2 of every latent: how many directions of the latent space the decoder uses, and which are off.
+
+    The models are validated as in ReplicaLogLik (one shape, any batch size).  `at` chooses the latents:
+      "prior"      the call draws them: the z1 vaek_make_batch writes under the event's seed, step and latent tag -- the latents
+                   sample_batch decodes at a stats event;
+      "posterior"  per model the event's real rows are drawn with make_batch (row tag), mu comes from vaek_forward(sampling=0) and goes
+                   to the call as explicit rows: the Jacobian on the encoded data manifold.
+    event() copies each model's `model.flat` into its row of an [R, P] stack owned by this object, makes ONE
+    vaek_mlp3_decoder_jacobian_replicas call for all models and ONE device -> host copy of the [R, 2 L + 8] float64 records.  It does NOT
+    perturb the run: `m.key`, the dataset's `_draws`, `m._latent_draws` and the other events' counters are left alone.  Its draws have a
+    counter of their own, `m._jacobian_draws` (incremented before use), the seed dataset.key[0] ^ dataset.key[1] and the tags 7 (rows)
+    and 8 (latents); tags 0 .. 6 belong to the train loop, the dataset's batches, the latents, the log-likelihood and the spectra.
+    Returns per model {"Decoder Jacobian Spectrum" (float64 [L], descending), "Decoder Jacobian Rank" (float64 [3]: mean, min, max),
+    "Latent Sensitivity" (float64 [L])} and appends them to `m.jacobian_spectra`, `m.jacobian_ranks` and `m.latent_sensitivities`.
+    Raises RuntimeError naming the model where a row's solve ended with off_F > 2^-40 |J^T J|_F."""
+
+    KEYS = ("Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity")
+    X_TAG, Z_TAG = 7, 8
+    NAME = "ReplicaJacobianMlp3"
+    OFF_BOUND = 2.0 ** -40
+    MODES = ("prior", "posterior")
+
+    def __init__(self, vae_models, rows=None, at="prior", rank_tol=1e-4):
+        if at not in self.MODES:
+            raise RuntimeError(f"{self.NAME}(at={at!r}): need one of {self.MODES}")
+        self.at = at
+        self.rank_tol = float(rank_tol)
+        if not 0.0 <= self.rank_tol < 1.0:
+            raise RuntimeError(f"{self.NAME}(rank_tol={rank_tol}): need 0 <= rank_tol < 1")
+        _replica_setup(self, vae_models, self.NAME, "call", "rows", "evaluates", "train_loop_max_replicas", ReplicaLogLik._shape,
+                       self._check_covered)
+        R, m0 = self.R, self.ms[0]
+        self.rows = _event_rows(self.NAME, m0, rows, 1, self.eng.stats_event_max_rows, "vaek_stats_event_max_rows")
+        self.L = self.eng.L
+        cols, cap = R * self.rows * self.L, self.eng.mlp3_decoder_jacobian_max_columns
+        if cols > cap:
+            raise RuntimeError(f"{self.NAME}: {R} models x {self.rows} rows x {self.L} latents = {cols} columns, at most {cap} fit one call "
+                               "(vaek_mlp3_decoder_jacobian_max_columns)")
+        dev = self.eng.device
+        self.record_len = self.eng.decoder_jacobian_record_len
+        self.params = torch.zeros(R, m0.model.flat.numel(), dtype=torch.float32, device=dev)
+        self.out = torch.zeros(R, self.record_len, dtype=torch.float64, device=dev)
+        self.workspace = torch.empty(max(self.eng.mlp3_decoder_jacobian_workspace(R, self.rows), 16), dtype=torch.uint8, device=dev)
+        if at == "posterior":
+            self.z = torch.zeros(R, self.rows, self.L, dtype=torch.float32, device=dev)
+
+    def _check_covered(self):
+        if not self.eng.supports_mlp3_decoder_jacobian():
+            raise RuntimeError("ReplicaJacobianMlp3: vaek_mlp3_decoder_jacobian_replicas does not cover this model (it needs a float32 "
+                               "VAE with one decoder and exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, "
+                               "D, L <= 32; the Jacobian of a linear decoder is its kernel: ReplicaExactLogLik's record holds the "
+                               f"eigenvalues of K^T K; this model's step path: {getattr(self.eng, 'step_path', '?')})")
+
+    def event(self):
+        """One evaluation of every model: [{"Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity"} of model 0, ...]."""
+        dev = self.eng.device
+        L = self.L
+        seeds, steps = [], []
+        for r, m in enumerate(self.ms):
+            self.params[r].copy_(m.model.flat)
+            m._jacobian_draws = getattr(m, "_jacobian_draws", 0) + 1
+            ds = m.dataset
+            seeds.append(ds.key[0] ^ ds.key[1])
+            steps.append(m._jacobian_draws)
+        if self.at == "posterior":
+            for r, m in enumerate(self.ms):
+                eng = m.model.module.engine(self.rows)                                 # forward takes at most its context's batch
+                Ar = None if self.A is None else self.A[r]
+                x, z1, z2 = eng.make_batch(self.kind, Ar, self.dd, self.did, self.pad, self.var, self.rows, seeds[r], step=steps[r],
+                                           tag=self.X_TAG)
+                _, mu = eng.forward(m.model.flat, x, z1, z2, sampling=False, want_mu=True)
+                self.z[r].copy_(mu)
+            self.eng.mlp3_decoder_jacobian_replicas(self.params, self.rows, self.out, self.workspace, z=self.z, rank_tol=self.rank_tol,
+                                                    z_tag=self.Z_TAG)
+        else:
+            sd, st = _seed_step_tensors(seeds, steps, dev)
+            self.eng.mlp3_decoder_jacobian_replicas(self.params, self.rows, self.out, self.workspace, z_seeds=sd, z_steps=st,
+                                                    rank_tol=self.rank_tol, z_tag=self.Z_TAG)
+        rec = self.out.cpu().numpy()                                                  # the event's ONE device -> host copy
+        stats = []
+        for r, m in enumerate(self.ms):
+            row = rec[r]
+            # slot [6] is the largest off_F / |G|_F over the rows: the bound is relative
+            _check_solve(self.NAME, r, m, "solve of J^T J", "J^T J", row[5], row[6], self.OFF_BOUND)
+            st = {self.KEYS[0]: row[8:8 + L].copy(), self.KEYS[1]: row[1:4].copy(), self.KEYS[2]: row[8 + L:8 + 2 * L].copy()}
+            for name, attr in zip(self.KEYS, ("jacobian_spectra", "jacobian_ranks", "latent_sensitivities")):
+                if not hasattr(m, attr):
+                    setattr(m, attr, [])
+                getattr(m, attr).append(st[name])
+            stats.append(st)
+        return stats
+
+
 class ReplicaSpectrum:
     """The covariance spectra of a generated and of a real batch of R VAEModels of one shape: per model the eigenvalues of
     cov(fake batch) -- the reference's "learnt eigenvalue" -- and of cov(real batch) -- its "ground truth eigenvalue"
