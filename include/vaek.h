@@ -727,6 +727,119 @@ int vaek_exact_log_likelihood_record_len(const vaek_ctx* ctx, int64_t* doubles);
 int vaek_exact_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_exact_log_likelihood* ll, int32_t kind,
                                        const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
                                        void* stream);
+/* HESSIAN OF THE EXACT ELBO of N one-decoder linear VAEs of the context's shape in one launch (csrc/elbo_hessian.hip): Hessian-vector
+ * products, the exact gradient and a Lanczos spectrum of
+ *   f(theta) = - mean_x ELBO(x),      ELBO(x) exactly as vaek_exact_log_likelihood_replicas defines it above,
+ * the population training objective on the rows (it differs from the expectation of the training loss by the constant D / 2 of the z2
+ * term).  theta is the parameter vector in the library's leaf order: E [D][L], b_e [L], K [L][D], b_d [D], epsilon_p = p [L] and, under
+ * tunable_eps, epsilon = c [1]; P = vaek_param_count.  The float32 leaves are widened to float64 once and everything below is float64;
+ * eps = c * eps_cli formed in FLOAT64 (eps_cli without tunable_eps), so f is a smooth function of c.  vaek_exact_log_likelihood_replicas
+ * forms that product in float32: record [0] below is minus its record [1] to rounding wherever c * eps_cli is exact in float32 (c = 1,
+ * the initial value), and to 2^-24 |eps| D / 2 otherwise.  Over `rows` float32 rows x, widened:
+ *   S = (1 / rows) sum [x; 1][x; 1]^T  ((D + 1) x (D + 1))     U = [E; b_e]     C = [-I_D; b_d]     R = U K + C
+ *   a = e^{-eps}     w = e^{p}     k2_l = |K_l|^2     Q = tr(R^T S R) + sum_l w_l k2_l
+ *   f = 1/2 tr(U^T S U) + 1/2 sum_l (w_l - 1 - p_l) + 1/2 a Q + 1/2 D (eps + log 2 pi)                          G = a S R
+ *   df/dU = S U + G K^T     df/dK = U^T G + a diag(w) K     df/db_d = last row of G
+ *   df/dp_l = 1/2 (w_l - 1) + 1/2 a w_l k2_l                df/dc = eps_cli (D / 2 - a Q / 2)
+ * and for a direction v = (dU, dK, db_d, dp, dc), with deps = eps_cli dc (0 without tunable_eps), dw = w dp, dC = [0; db_d]:
+ *   dR = dU K + U dK + dC                                   dG = a S dR - deps G
+ *   (Hv)_U = S dU + dG K^T + G dK^T
+ *   (Hv)_K = dU^T G + U^T dG + a diag(w) dK + a diag(dw) K - deps a diag(w) K
+ *   (Hv)_b_d = last row of dG
+ *   (Hv)_p_l = 1/2 dw_l + 1/2 a dw_l k2_l + a w_l (K_l . dK_l) - 1/2 deps a w_l k2_l
+ *   dQ = 2 tr(R^T S dR) + sum_l (dw_l k2_l + 2 w_l K_l . dK_l)            (Hv)_c = eps_cli (deps a Q / 2 - a dQ / 2).
+ * H never exists as a matrix: f sees the rows through S alone, so a product is a handful of products of matrices of at most 33 x 32,
+ * whatever `rows` is.  ONE workgroup of 256 threads per model, no workspace, no second launch, no atomic, counter or wait:
+ *   S: the rows through the row sources and the row -> slot assignment of vaek_cov_spectrum_rows (thread t produces rows 256 j + t;
+ *   sum x x^T and sum x on the float64 matrix cores, every element ONE chain over the rows in row order), so the results depend on the
+ *   rows' bits only; the products: plain float64 fmas, thread t owning elements t, t + 256, .. of an output, every sum in index order,
+ *   every sum over threads one fixed binary tree.
+ * vaek_elbo_hvp_replicas: for replica r and i < nvec, hv + r * hv_stride + i * P <- H (v + r * v_stride + i * P) ([nvec][P] doubles per
+ * replica, v_stride == 0: one set of directions shared by all replicas); grad (optional; NULL: none): the gradient, [P] doubles at grad
+ * + r * grad_stride; RECORD of vaek_elbo_hvp_record_len() = 4 doubles at out + r * out_stride: [0] f  [1] |grad f|_2  [2] eps as used
+ * [3] rows.  nvec is 0 .. vaek_elbo_hvp_max_vectors() = 64 (a cap on the length of a launch, not a tuned value); nvec = 0 gives the
+ * gradient and the record only (v and hv are not read and may be NULL).  v and hv must NOT overlap: a direction is read again after
+ * parts of its product are stored.  Unit vectors give columns of H, 64 a call.
+ * vaek_elbo_hessian_lanczos_replicas: m = `steps` <= vaek_elbo_hessian_max_steps() = 32 Lanczos steps on H from the start vector v0 + r
+ * * v0_stride ([P] doubles, v0_stride == 0: shared; normalised in the kernel), with FULL reorthogonalisation: step j forms w = H v_j,
+ * applies classical Gram-Schmidt twice against v_1 .. v_j (alpha_j = the sum of what the two passes take out along v_j), beta_j = |w|,
+ * v_{j+1} = w / beta_j.  BREAKDOWN -- beta_j <= 2^-40 max(|alpha_1 .. alpha_j|, beta_1 .. beta_{j-1}) -- ends the run; it is not an
+ * error (it happens at small P and on symmetric models).  k = min(steps, P, the step of breakdown) steps are reported; v0 = 0 (or not
+ * finite) gives k = 0.  The BASIS is an output: row j < k of basis + r * basis_stride ([steps][P] doubles, vaek_elbo_hessian_basis_doubles
+ * = steps * P) holds v_{j+1}; rows >= k are not written.  The k x k tridiagonal T (alpha on, beta_1 .. beta_{k-1} beside the diagonal)
+ * is solved by the SOLVE RULE of vaek_cov_spectrum_rows with eigenvectors (the same device routine, its 2^-43 stop and 32-sweep cap; an
+ * odd k padded with a zero row and column, excluded by index; T may be indefinite).  Ritz value theta_i comes with rho_i = |beta_k
+ * s_{k,i}|, s_{k,i} the last component of T's i-th eigenvector: in exact arithmetic an eigenvalue of H lies within rho_i of theta_i.
+ * RECORD of vaek_elbo_hessian_record_len() = 12 + 4 * 32 = 140 doubles at out + r * out_stride:
+ *   [0] f   [1] |grad f|_2   [2] k   [3] beta_k   [4] Jacobi sweeps   [5] off_F   [6] |T|_F   [7] rows   [8] eps as used
+ *   [9] theta_max   [10] theta_min   [11] omega = max_{i < j < k} |v_i . v_j| of the stored basis, measured after the run
+ *   [12, 44) theta ascending (counting ranks, ties by index)   [44, 76) rho in the same order   [76, 108) alpha_1 .. alpha_k
+ *   [108, 140) beta_1 .. beta_k                                                                       (slots >= k are 0)
+ * Both calls: replica r reads params + r * state_stride (never written) and its rows in the two modes of
+ * vaek_exact_log_likelihood_replicas (EXPLICIT ROWS x != NULL, x_stride == 0 shared; DRAWING MODE x == NULL: row i as vaek_make_batch
+ * writes x under (x_seeds[r], x_steps[r], x_tag)).  rows is 1 .. vaek_log_likelihood_max_rows() = 4096, n 1 ..
+ * vaek_train_loop_max_replicas().  Doubles between two replicas' blocks where a stride exceeds the length are not touched; nothing but
+ * the named outputs is written.  Replica r's outputs are BITWISE what a call with n = 1 on its slices leaves, two runs are bitwise
+ * equal, drawing mode equals explicit mode on the rows vaek_make_batch writes, nothing depends on ctx.batch.  Asynchronous on `stream`,
+ * allocates nothing, does not synchronise, capturable into a hipGraph; profile labels elbo_hvp_replicas / elbo_hessian_replicas.
+ * vaek_supports_elbo_hessian: vaek_supports_exact_log_likelihood's predicate (float32, no hidden layers, ONE decoder, D, L <= 32) --
+ * whatever ctx.batch, world and force_generic are.  NOT covered: two-decoder and MLP models (no closed form), bf16, D or L > 32, more
+ * than 32 steps, Ritz vectors, the Hessian of the sampled loss.
+ * VAEK_ERR_INVALID (message names the call, nothing touched): a NULL or unsupported context, NULL params or description, a wrong
+ * struct_size, n or rows out of range, state_stride < P; explicit rows: x_stride < 0 or 0 < x_stride < rows * D; drawing mode: NULL
+ * x_seeds or x_steps, a_stride < 0, NULL A for kind 0 or 1, dd or did > 16, dd + pad (+ 1 for kind 1) != data_dim, kind outside 0 .. 2,
+ * x_tag >= 2^30; nvec outside 0 .. 64 or steps outside 1 .. 32; a NULL out, v0 or basis, a NULL v or hv with nvec > 0; a double buffer
+ * (grad included, where given) that is not 8-byte aligned; out_stride below the record length, hv_stride < nvec * P, grad_stride < P,
+ * basis_stride < steps * P, a v_stride or v0_stride that is neither 0 nor at least its length (nvec * P, P).
+ * vaek_elbo_hessian_basis_doubles refuses an unsupported context and steps outside 1 .. 32 and leaves *doubles alone. */
+typedef struct vaek_elbo_hvp {
+    int32_t struct_size;                  /* = sizeof(vaek_elbo_hvp), ABI guard                         */
+    int32_t n;                            /* replicas: the launch has n workgroups                      */
+    int32_t rows;                         /* data rows, 1 .. vaek_log_likelihood_max_rows()             */
+    int32_t nvec;                         /* directions per replica, 0 .. vaek_elbo_hvp_max_vectors()   */
+    int64_t state_stride;                 /* floats between two replicas' params, >= P                  */
+    const uint64_t* x_seeds;              /* device [n]: seed of the rows (drawing mode)                */
+    const uint32_t* x_steps;              /* device [n]: their RNG step (drawing mode)                  */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared (drawing mode)  */
+    const float* x;                       /* device [rows][D] per replica: explicit rows; NULL = draw   */
+    int64_t x_stride;                     /* floats between two replicas' rows; 0 = shared              */
+    const double* v;                      /* device [nvec][P] per replica: the directions               */
+    int64_t v_stride;                     /* doubles between two replicas' directions; 0 = shared       */
+    double* hv;                           /* device [nvec][P] per replica: H v                          */
+    int64_t hv_stride;                    /* doubles, >= nvec * P                                       */
+    double* grad;                         /* device [P] per replica, or NULL                            */
+    int64_t grad_stride;                  /* doubles, >= P                                              */
+    double* out;                          /* device: record r at out + r * out_stride                   */
+    int64_t out_stride;                   /* doubles, >= vaek_elbo_hvp_record_len()                     */
+} vaek_elbo_hvp;
+typedef struct vaek_elbo_hessian {
+    int32_t struct_size;                  /* = sizeof(vaek_elbo_hessian), ABI guard                     */
+    int32_t n;                            /* replicas: the launch has n workgroups                      */
+    int32_t rows;                         /* data rows, 1 .. vaek_log_likelihood_max_rows()             */
+    int32_t steps;                        /* Lanczos steps, 1 .. vaek_elbo_hessian_max_steps()          */
+    int64_t state_stride;                 /* floats between two replicas' params, >= P                  */
+    const uint64_t* x_seeds;              /* device [n]: seed of the rows (drawing mode)                */
+    const uint32_t* x_steps;              /* device [n]: their RNG step (drawing mode)                  */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared (drawing mode)  */
+    const float* x;                       /* device [rows][D] per replica: explicit rows; NULL = draw   */
+    int64_t x_stride;                     /* floats between two replicas' rows; 0 = shared              */
+    const double* v0;                     /* device [P] per replica: the start vector                   */
+    int64_t v0_stride;                    /* doubles between two replicas' start vectors; 0 = shared    */
+    double* basis;                        /* device [steps][P] per replica: the Lanczos vectors (output)*/
+    int64_t basis_stride;                 /* doubles, >= steps * P (vaek_elbo_hessian_basis_doubles)    */
+    double* out;                          /* device: record r at out + r * out_stride                   */
+    int64_t out_stride;                   /* doubles, >= vaek_elbo_hessian_record_len()                 */
+} vaek_elbo_hessian;
+int vaek_supports_elbo_hessian(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_elbo_hvp_max_vectors(void);
+int vaek_elbo_hvp_record_len(void);
+int vaek_elbo_hessian_max_steps(void);
+int vaek_elbo_hessian_record_len(void);
+int vaek_elbo_hessian_basis_doubles(const vaek_ctx* ctx, int32_t steps, int64_t* doubles);
+int vaek_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vaek_elbo_hvp* hp, int32_t kind, const float* A, int32_t dd,
+                           int32_t did, int32_t pad, float var_added, uint32_t x_tag, void* stream);
+int vaek_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* params, const vaek_elbo_hessian* hs, int32_t kind, const float* A,
+                                       int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, void* stream);
 /* DECODER JACOBIAN SPECTRA of N THREE-HIDDEN-LAYER MLP VAEs of the context's shape in one call (csrc/mlp3_jacobian.hip): how many
  * directions of the latent space the decoder moves its output along, row by row.  For a latent row z of replica r
  *   J(z) = d Decoder(z) / dz  (D x L)  = K3^T M3 K2^T M2 K1^T M1 K0^T,   M_i = diag(pre_i(z) > 0),

@@ -87,6 +87,28 @@ class VaekDecoderJacobian(C.Structure):
     ]
 
 
+class VaekElboHvp(C.Structure):
+    """vaek_elbo_hvp of include/vaek.h: the per-replica description of vaek_elbo_hvp_replicas (device pointers)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n", C.c_int32), ("rows", C.c_int32), ("nvec", C.c_int32), ("state_stride", C.c_int64),
+        ("x_seeds", C.c_void_p), ("x_steps", C.c_void_p), ("a_stride", C.c_int64), ("x", C.c_void_p), ("x_stride", C.c_int64),
+        ("v", C.c_void_p), ("v_stride", C.c_int64), ("hv", C.c_void_p), ("hv_stride", C.c_int64), ("grad", C.c_void_p),
+        ("grad_stride", C.c_int64), ("out", C.c_void_p), ("out_stride", C.c_int64),
+    ]
+
+
+class VaekElboHessian(C.Structure):
+    """vaek_elbo_hessian of include/vaek.h: the per-replica description of vaek_elbo_hessian_lanczos_replicas (device pointers)."""
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n", C.c_int32), ("rows", C.c_int32), ("steps", C.c_int32), ("state_stride", C.c_int64),
+        ("x_seeds", C.c_void_p), ("x_steps", C.c_void_p), ("a_stride", C.c_int64), ("x", C.c_void_p), ("x_stride", C.c_int64),
+        ("v0", C.c_void_p), ("v0_stride", C.c_int64), ("basis", C.c_void_p), ("basis_stride", C.c_int64), ("out", C.c_void_p),
+        ("out_stride", C.c_int64),
+    ]
+
+
+ELBO_HESSIAN_RECORD_HEAD = 12      # doubles of a Lanczos record in front of the four blocks of 32: theta, rho, alpha, beta
+ELBO_HESSIAN_MAX_STEPS = 32
 DECODER_JACOBIAN_RECORD_HEAD = 8   # doubles of a decoder-Jacobian model record in front of the L mean eigenvalues and the L mean diagonals
 EXACT_LOGLIK_RECORD_HEAD = 10      # doubles of an exact log-likelihood record in front of the D eigenvalues of K^T K
 STATS_RECORD_HEAD = 8     # floats of a stats record in front of the epsilon_p copy: loss, Dkl, mse, eps, two score values, 0, 0
@@ -199,6 +221,15 @@ SIGNATURES = {
     "vaek_supports_exact_log_likelihood": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
     "vaek_exact_log_likelihood_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
     "vaek_exact_log_likelihood_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekExactLogLikelihood), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
+                                                     _vp]),
+    "vaek_supports_elbo_hessian": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_elbo_hvp_max_vectors": (C.c_int, []),
+    "vaek_elbo_hvp_record_len": (C.c_int, []),
+    "vaek_elbo_hessian_max_steps": (C.c_int, []),
+    "vaek_elbo_hessian_record_len": (C.c_int, []),
+    "vaek_elbo_hessian_basis_doubles": (C.c_int, [_vp, _i32, C.POINTER(_i64)]),
+    "vaek_elbo_hvp_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekElboHvp), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, _vp]),
+    "vaek_elbo_hessian_lanczos_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekElboHessian), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
                                                      _vp]),
     "vaek_supports_mlp3_decoder_jacobian": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_decoder_jacobian_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),

@@ -609,6 +609,101 @@ class Engine:
         _lib.check(self.lib.vaek_exact_log_likelihood_replicas(self.h, _ptr(params), C.byref(ll), int(kind), _ptr(A), int(dd), int(did),
                                                                int(pad), float(var_added), int(x_tag), _stream()))
 
+    def supports_elbo_hessian(self, kind):
+        """True where elbo_hvp_replicas and elbo_hessian_lanczos_replicas cover this engine and dataset kind: exactly where
+        supports_exact_log_likelihood does (vaek_supports_elbo_hessian)."""
+        return self._flag(self.lib.vaek_supports_elbo_hessian, int(kind))
+
+    @property
+    def elbo_hvp_max_vectors(self):
+        return int(self.lib.vaek_elbo_hvp_max_vectors())
+
+    @property
+    def elbo_hvp_record_len(self):
+        """Doubles in one record of elbo_hvp_replicas (vaek_elbo_hvp_record_len): 4 = f, |grad f|_2, eps as used, rows."""
+        return int(self.lib.vaek_elbo_hvp_record_len())
+
+    @property
+    def elbo_hessian_max_steps(self):
+        return int(self.lib.vaek_elbo_hessian_max_steps())
+
+    @property
+    def elbo_hessian_record_len(self):
+        """Doubles in one Lanczos record (vaek_elbo_hessian_record_len): 12 + 4 * 32 = f, |grad f|_2, k, beta_k, sweeps, off_F, |T|_F,
+        rows, eps, theta_max, theta_min, omega, then theta ascending, rho, alpha and beta in blocks of 32."""
+        return int(self.lib.vaek_elbo_hessian_record_len())
+
+    def elbo_hessian_basis_doubles(self, steps):
+        """Doubles of one replica's Lanczos basis (vaek_elbo_hessian_basis_doubles): steps * P."""
+        return self._count(self.lib.vaek_elbo_hessian_basis_doubles, int(steps))
+
+    def _hessian_rows(self, d, params, rows, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride):
+        """The fields vaek_elbo_hvp and vaek_elbo_hessian share: replicas, rows and the two row modes."""
+        d.n = int(params.shape[0] if n is None else n)
+        d.rows = int(rows)
+        d.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        assert x_seeds is None or x_seeds.dtype == torch.int64
+        assert x_steps is None or x_steps.dtype == torch.int32
+        assert x is None or x.dtype == torch.float32
+        d.x_seeds, d.x_steps = _ptr(x_seeds), _ptr(x_steps)
+        d.a_stride = int(a_stride)
+        d.x = _ptr(x)
+        if x_stride is None:
+            x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
+        d.x_stride = int(x_stride)
+
+    def elbo_hvp_replicas(self, params, rows, out, v=None, hv=None, grad=None, nvec=None, kind=2, A=None, dd=0, did=0, pad=0, var_added=0.0,
+                          x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, n=None, state_stride=None,
+                          v_stride=None, hv_stride=None, grad_stride=None, out_stride=None, struct_size=None):
+        """Hessian-vector products of f = -mean exact ELBO of EACH of n one-decoder linear VAEs of this engine's shape in one launch
+        (vaek_elbo_hvp_replicas): hv[r, i] = H_r v[r, i], float64, flat in the leaf order.  v: float64 [nvec, P] shared by all replicas,
+        or [n, nvec, P]; hv: float64 [n, nvec, P]; grad: None or float64 [n, P] (the exact gradient); out: float64 [n, out_stride >= 4] =
+        f, |grad f|_2, eps as used, rows.  v = None (nvec = 0): the gradient and the record only.  The rows are the caller's (x) or
+        drawn, as in exact_log_likelihood_replicas.  Device tensors or raw device addresses; n, nvec and the strides default to the
+        tensors' shapes.  Asynchronous; capturable."""
+        hp = _lib.VaekElboHvp()
+        hp.struct_size = C.sizeof(_lib.VaekElboHvp) if struct_size is None else int(struct_size)
+        self._hessian_rows(hp, params, rows, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride)
+        f64 = torch.float64
+        if nvec is None:
+            nvec = 0 if v is None else v.shape[-2]
+        hp.nvec = int(nvec)
+        hp.v, hp.hv, hp.grad, hp.out = _addr(v, f64), _addr(hv, f64), _addr(grad, f64), _addr(out, f64)
+        if v_stride is None:
+            v_stride = 0 if v is None or isinstance(v, int) or v.dim() < 3 else v.shape[-2] * v.shape[-1]
+        if hv_stride is None:
+            hv_stride = 0 if hv is None or isinstance(hv, int) else hv.shape[-2] * hv.shape[-1]
+        hp.v_stride, hp.hv_stride = int(v_stride), int(hv_stride)
+        hp.grad_stride = _last_dim(grad, grad_stride)
+        hp.out_stride = _last_dim(out, out_stride)
+        _lib.check(self.lib.vaek_elbo_hvp_replicas(self.h, _ptr(params), C.byref(hp), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                   float(var_added), int(x_tag), _stream()))
+
+    def elbo_hessian_lanczos_replicas(self, params, rows, steps, v0, basis, out, kind=2, A=None, dd=0, did=0, pad=0, var_added=0.0,
+                                      x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, n=None, state_stride=None,
+                                      v0_stride=None, basis_stride=None, out_stride=None, struct_size=None):
+        """`steps` <= 32 Lanczos steps with full reorthogonalisation on the Hessian of f = -mean exact ELBO of EACH of n one-decoder
+        linear VAEs of this engine's shape in one launch (vaek_elbo_hessian_lanczos_replicas).  v0: float64 [P] shared by all replicas,
+        or [n, P]: the start vector; basis: float64 [n, steps, P]: the Lanczos vectors, an output (rows >= k are not written); out:
+        float64 [n, out_stride >= elbo_hessian_record_len]: f, |grad f|_2, k, beta_k, sweeps, off_F, |T|_F, rows, eps, theta_max,
+        theta_min, omega, then the Ritz values ascending, their residual bounds, alpha and beta.  The rows are the caller's (x) or drawn,
+        as in exact_log_likelihood_replicas.  Device tensors or raw device addresses; n and the strides default to the tensors' shapes.
+        Asynchronous; capturable."""
+        hs = _lib.VaekElboHessian()
+        hs.struct_size = C.sizeof(_lib.VaekElboHessian) if struct_size is None else int(struct_size)
+        self._hessian_rows(hs, params, rows, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride)
+        f64 = torch.float64
+        hs.steps = int(steps)
+        hs.v0, hs.basis, hs.out = _addr(v0, f64), _addr(basis, f64), _addr(out, f64)
+        if v0_stride is None:
+            v0_stride = 0 if v0 is None or isinstance(v0, int) or v0.dim() < 2 else v0.shape[-1]
+        if basis_stride is None:
+            basis_stride = 0 if basis is None or isinstance(basis, int) else basis.shape[-2] * basis.shape[-1]
+        hs.v0_stride, hs.basis_stride = int(v0_stride), int(basis_stride)
+        hs.out_stride = _last_dim(out, out_stride)
+        _lib.check(self.lib.vaek_elbo_hessian_lanczos_replicas(self.h, _ptr(params), C.byref(hs), int(kind), _ptr(A), int(dd), int(did),
+                                                               int(pad), float(var_added), int(x_tag), _stream()))
+
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
         return self._flag(self.lib.vaek_supports_train_step_replicas)

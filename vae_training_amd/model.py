@@ -70,6 +70,7 @@ class Model:
         self.load_model()
 
 
+HESSIAN_ARRAY_KEYS = ("ELBO Hessian Ritz Values", "ELBO Hessian Ritz Residuals")      # trainer.ReplicaElboHessian.KEYS[:2]
 JACOBIAN_KEYS = ("Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity")      # trainer.ReplicaJacobianMlp3.KEYS
 
 
@@ -137,7 +138,9 @@ class GenerativeModel(Model):
         a generated and a real batch (trainer.ReplicaSpectrum), which leaves the run alone in the same way; `subspace` (run.py
         --subspace) adds the principal angles between their leading eigenspaces (trainer.ReplicaSubspace) under the same counter;
         `decoder_jacobian` = "prior" | "posterior" (run.py --decoder_jacobian) adds the spectra of the decoder Jacobian of a
-        three-hidden-layer MLP model (trainer.ReplicaJacobianMlp3), under a counter and tags of its own."""
+        three-hidden-layer MLP model (trainer.ReplicaJacobianMlp3), under a counter and tags of its own; `elbo_hessian` = STEPS (run.py
+        --elbo_hessian) adds the Ritz values of the Hessian of the exact ELBO of a one-decoder linear model
+        (trainer.ReplicaElboHessian), under a counter and tags of its own, on the exact event's rows where there is one."""
         stats = self.compute_stats()
         K = getattr(self, "log_likelihood_samples", None)
         if K:
@@ -151,6 +154,12 @@ class GenerativeModel(Model):
             if getattr(self, "_exact_loglik", None) is None:
                 self._exact_loglik = ReplicaExactLogLik([self])
             stats.update(self._exact_loglik.event_after(iwae if K else None)[0])
+        steps = getattr(self, "elbo_hessian", None)                # run.py --elbo_hessian: Ritz values of the Hessian of the exact ELBO,
+        if steps:                                                  # on the exact event's rows where there is one
+            from .trainer import ReplicaElboHessian
+            if getattr(self, "_elbo_hessian", None) is None:
+                self._elbo_hessian = ReplicaElboHessian([self], steps)
+            stats.update(self._elbo_hessian.event_after(exact=bool(getattr(self, "exact_log_likelihood", False)), iwae=bool(K))[0])
         K = getattr(self, "mlp_log_likelihood_samples", None)     # run.py --mlp_log_likelihood_samples: the same event for an mlp3 model
         if K:
             from .trainer import ReplicaLogLikMlp3
@@ -183,6 +192,9 @@ class GenerativeModel(Model):
                 self.stats[stat].append(_to_numpy(val))
                 if stat == JACOBIAN_KEYS[1]:
                     message += f" | {stat} (mean) | {float(val[0]):.3f}"
+                continue
+            if stat in HESSIAN_ARRAY_KEYS:                 # arrays whatever k is; Sharpness and the smallest Ritz value are on the line
+                self.stats[stat].append(_to_numpy(val))
                 continue
             try:
                 fval = float(val)

@@ -94,6 +94,16 @@ def build_parser():
                         "training run and every other stat are bitwise the ones without the flag.  Alone or with --sweep_dataset_seeds "
                         "(one launch for all models); float32 linear VAEs with ONE decoder and D, L <= 32 only (the sigmoid second "
                         "decoder has no closed form); other models are refused before any step; single GPU only")
+    p.add_argument("--elbo_hessian", dest="elbo_hessian", nargs="?", type=_hessian_steps, const=ELBO_HESSIAN_MAX_STEPS, default=None,
+                   metavar="STEPS",
+                   help="at every n_print step also run STEPS (1 .. 32, default 32) Lanczos steps with full reorthogonalisation on the "
+                        "Hessian of the exact ELBO of the model(s) on a print batch, in closed form and float64 "
+                        "(trainer.ReplicaElboHessian, vaek_elbo_hessian_lanczos_replicas): losses.npz gains 'ELBO Hessian Ritz Values' and "
+                        "'ELBO Hessian Ritz Residuals' (k each), 'Sharpness' (the largest Ritz value), 'ELBO Hessian Min Ritz' and 'ELBO "
+                        "Gradient Norm'; the stats line shows the last three.  With --exact_log_likelihood both events score the same "
+                        "rows.  The evaluation has its own RNG counter and tags, so the training run and every other stat are bitwise "
+                        "the ones without the flag.  Alone or with --sweep_dataset_seeds (one launch for all models); refused where "
+                        "--exact_log_likelihood is: MLP and two-decoder models and data parallelism, before any step")
     p.add_argument("--mlp_log_likelihood_samples", dest="mlp_log_likelihood_samples", type=_positive_int, default=None, metavar="K",
                    help="--log_likelihood_samples for three-hidden-layer MLP VAEs (trainer.ReplicaLogLikMlp3, "
                         "vaek_mlp3_log_likelihood_replicas): the same three stats from the same draws, the training run bitwise the one "
@@ -130,6 +140,19 @@ def build_parser():
                    help="with --decoder_jacobian: an eigenvalue of J^T J counts towards the rank where it exceeds T times the largest "
                         "(0 <= T < 1, default 1e-4); refused without --decoder_jacobian")
     return p
+
+
+ELBO_HESSIAN_MAX_STEPS = 32      # vaek_elbo_hessian_max_steps(): the size of the device's Jacobi routine
+
+
+def _hessian_steps(text):
+    try:
+        k = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"{text!r} is not an integer")
+    if not 1 <= k <= ELBO_HESSIAN_MAX_STEPS:
+        raise argparse.ArgumentTypeError(f"{k} Lanczos steps: need 1 .. {ELBO_HESSIAN_MAX_STEPS}")
+    return k
 
 
 def _rank_tol(text):
@@ -366,6 +389,20 @@ def check_exact_log_likelihood_model(m):
                            f"world {eng.world})")
 
 
+ELBO_HESSIAN_NEEDS = ("a model vaek_elbo_hessian_lanczos_replicas covers (vaek_supports_elbo_hessian): a float32 linear VAE -- no hidden "
+                      "layers -- with ONE decoder (the ELBO of other models has no closed form), D, L <= 32, -dd / -did <= 16, on one GPU")
+
+
+def check_elbo_hessian_model(m):
+    """--elbo_hessian: refuse, before any step, a model the Lanczos call does not cover."""
+    from .datasets import DEVICE_DRAW_MAX_DIM
+    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
+    kind, _, dd, did, _, _ = m.dataset.device_spec()
+    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_elbo_hessian(kind):
+        raise RuntimeError(f"--elbo_hessian needs {ELBO_HESSIAN_NEEDS} (this model's step path: {getattr(eng, 'step_path', '?')}, "
+                           f"world {eng.world})")
+
+
 MLP_LOGLIK_NEEDS = ("a model vaek_mlp3_log_likelihood_replicas covers (vaek_supports_mlp3_log_likelihood): float32, one decoder, exactly "
                     "three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32, -dd / -did <= 16, on one GPU")
 
@@ -516,6 +553,11 @@ def main_sweep(args):
         from .trainer import ReplicaExactLogLik
         check_exact_log_likelihood_model(models[0])
         exact = ReplicaExactLogLik(models)
+    hessian = None
+    if getattr(args, "elbo_hessian", None) is not None:  # before any step
+        from .trainer import ReplicaElboHessian
+        check_elbo_hessian_model(models[0])
+        hessian = ReplicaElboHessian(models, args.elbo_hessian)
     spectrum = None
     if getattr(args, "eigenvalues", False):  # before any step
         from .trainer import ReplicaSpectrum
@@ -546,6 +588,9 @@ def main_sweep(args):
     if exact is not None:
         print(f"Exact log-likelihood events: {exact.rows} rows per model, one launch for {len(models)} models "
               "(vaek_exact_log_likelihood_replicas)")
+    if hessian is not None:
+        print(f"ELBO Hessian events: {hessian.steps} Lanczos steps on {hessian.rows} rows per model, one launch for {len(models)} models "
+              "(vaek_elbo_hessian_lanczos_replicas)")
     if spectrum is not None and getattr(args, "eigenvalues", False):
         entry = ("vaek_eigen_event_replicas" if spectrum.fused else "vaek_cov_eigen_rows") if spectrum.VEC else \
                 ("vaek_spectrum_event_replicas" if spectrum.fused else "vaek_cov_spectrum_rows")
@@ -574,6 +619,8 @@ def main_sweep(args):
         spectra = spectrum.event() if spectrum is not None and ev % n_print == 0 else None     # every model's two spectra in one call
         # every model's closed form in one launch, on the rows the IWAE event just scored where there is one
         closed = exact.event_after(extra if ll_samples is not None else None) if exact is not None and ev % n_print == 0 else None
+        # every model's Lanczos run in one launch, on the rows the exact event just scored where there is one
+        curv = hessian.event_after(exact=exact is not None, iwae=ll_samples is not None) if hessian is not None and ev % n_print == 0 else None
         jac = jacobian.event() if jacobian is not None and ev % n_print == 0 else None     # every model's decoder Jacobian spectra in one call
         for r, m in enumerate(models):
             m.batchnum = ev
@@ -583,6 +630,8 @@ def main_sweep(args):
                     stats.update(extra[r])
                 if closed is not None:
                     stats.update(closed[r])
+                if curv is not None:
+                    stats.update(curv[r])
                 if spectra is not None:
                     stats.update(spectra[r] if getattr(args, "eigenvalues", False) else
                                  {k: v for k, v in spectra[r].items() if k not in spectrum.KEYS})
@@ -621,6 +670,9 @@ def main(args):
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1 and getattr(args, "exact_log_likelihood", False):
         raise RuntimeError(f"--exact_log_likelihood needs {EXACT_LOGLIK_NEEDS}: it does not combine with data parallelism "
+                           f"(step path of a world of {world}: one shard per rank)")
+    if world > 1 and getattr(args, "elbo_hessian", None) is not None:
+        raise RuntimeError(f"--elbo_hessian needs {ELBO_HESSIAN_NEEDS}: it does not combine with data parallelism "
                            f"(step path of a world of {world}: one shard per rank)")
     if world > 1 and getattr(args, "eigenvalues", False):
         raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS}: it does not combine with data parallelism "
@@ -669,6 +721,10 @@ def main(args):
         check_exact_log_likelihood_model(model)            # before any step
         model.exact_log_likelihood = True                  # the n_print events add trainer.ReplicaExactLogLik([model]).event_after(...)
         print(f"Exact log-likelihood events: {model.print_batch_size} rows (vaek_exact_log_likelihood_replicas)")
+    if getattr(args, "elbo_hessian", None) is not None:
+        check_elbo_hessian_model(model)                    # before any step
+        model.elbo_hessian = args.elbo_hessian             # the n_print events add trainer.ReplicaElboHessian([model], STEPS).event_after(...)
+        print(f"ELBO Hessian events: {args.elbo_hessian} Lanczos steps on {model.print_batch_size} rows (vaek_elbo_hessian_lanczos_replicas)")
     if getattr(args, "eigenvalues", False):
         check_eigenvalues_model(model)                     # before any step
         model.eigenvalues = True                           # the n_print events add trainer.ReplicaSpectrum([model]).event()

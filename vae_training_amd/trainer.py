@@ -743,6 +743,94 @@ class ReplicaExactLogLik:
         return stats
 
 
+class ReplicaElboHessian:
+    """The curvature of the loss surface R one-decoder linear VAEModels of one shape sit on, in ONE launch
+    (vaek_elbo_hessian_lanczos_replicas, csrc/elbo_hessian.hip): `steps` <= 32 Lanczos steps with full reorthogonalisation on the
+    Hessian of f = -mean exact ELBO over `rows` data rows -- the population training objective on those rows, float64, closed form
+    -- give its extreme Ritz values (sharpness and the smallest curvature: minimum or saddle), a rigorous residual bound per value,
+    and the exact gradient norm: how stationary the point Adam sits at really is.
+
+    The models are validated as in ReplicaExactLogLik (one shape, any batch size).  event() copies each model's `model.flat` into its
+    row of an [R, P] stack owned by this object, draws each model's start vector with vaek_rng_fill (float32 normals, widened), makes
+    ONE Lanczos call and ONE device -> host copy of the [R, 140] float64 records.  It does NOT perturb the run: `m.key`, the
+    dataset's `_draws`, `m._latent_draws` and the other events' counters are left alone.  Its draws have a counter of their own,
+    `m._elbo_hessian_draws` (incremented before use), the seed dataset.key[0] ^ dataset.key[1] and the tags 9 (rows) and 10 (start
+    vector); tags 0 .. 8 belong to the train loop, the dataset's batches, the latents, the log-likelihood, the spectra and the
+    Jacobian.  event(step=s) draws the ROWS under step s and ReplicaExactLogLik's row tag instead, so the Hessian is that of the
+    objective on the rows a ReplicaExactLogLik event just scored, bit for bit (the start vector stays under the own counter).
+    Returns per model {"ELBO Hessian Ritz Values" (float64 [k], ascending), "ELBO Hessian Ritz Residuals" (float64 [k]: an eigenvalue
+    of H lies within each of its Ritz value), "Sharpness" (the largest Ritz value), "ELBO Hessian Min Ritz", "ELBO Gradient Norm"}.
+    Raises RuntimeError naming the model where the solve of T ended with off_F > 2^-40 |T|_F."""
+
+    KEYS = ("ELBO Hessian Ritz Values", "ELBO Hessian Ritz Residuals", "Sharpness", "ELBO Hessian Min Ritz", "ELBO Gradient Norm")
+    X_TAG, V_TAG = 9, 10
+    NAME = "ReplicaElboHessian"
+    OFF_BOUND = 2.0 ** -40
+    HEAD, BLOCK = 12, 32
+
+    def __init__(self, vae_models, steps=32, rows=None):
+        _replica_setup(self, vae_models, self.NAME, "launch", "rows", "evaluates", "train_loop_max_replicas", ReplicaLogLik._shape,
+                       self._check_covered)
+        R, m0 = self.R, self.ms[0]
+        self.steps = int(steps)
+        if not 1 <= self.steps <= self.eng.elbo_hessian_max_steps:
+            raise RuntimeError(f"{self.NAME}: {self.steps} Lanczos steps, need 1 .. {self.eng.elbo_hessian_max_steps} "
+                               "(vaek_elbo_hessian_max_steps)")
+        self.rows = _event_rows(self.NAME, m0, rows, 1, self.eng.log_likelihood_max_rows, "vaek_log_likelihood_max_rows")
+        dev = self.eng.device
+        self.P = P = m0.model.flat.numel()
+        self.record_len = self.eng.elbo_hessian_record_len
+        self.params = torch.zeros(R, P, dtype=torch.float32, device=dev)
+        self.v0 = torch.zeros(R, P, dtype=torch.float64, device=dev)
+        self.basis = torch.zeros(R, self.steps, P, dtype=torch.float64, device=dev)
+        self.out = torch.zeros(R, self.record_len, dtype=torch.float64, device=dev)
+
+    def _check_covered(self):
+        if not self.eng.supports_elbo_hessian(self.kind):
+            raise RuntimeError("ReplicaElboHessian: vaek_elbo_hessian_lanczos_replicas does not cover this model / dataset (it needs a "
+                               "float32 linear VAE -- no hidden layers -- with ONE decoder and D, L <= 32: the ELBO of other models has "
+                               f"no closed form; this model's step path: {getattr(self.eng, 'step_path', '?')})")
+
+    def event(self, step=None):
+        """One evaluation of every model.  step: draw the ROWS under this RNG step (one int, or one per model) and ReplicaExactLogLik's
+        row tag instead of the own counter and tag 9."""
+        dev = self.eng.device
+        if step is not None:
+            given = [int(s) for s in step] if isinstance(step, (list, tuple)) else [int(step)] * self.R
+            if len(given) != self.R:
+                raise RuntimeError(f"{self.NAME}.event(step=...): {len(given)} steps for {self.R} models")
+        seeds, steps = [], []
+        for r, m in enumerate(self.ms):
+            self.params[r].copy_(m.model.flat)
+            m._elbo_hessian_draws = getattr(m, "_elbo_hessian_draws", 0) + 1
+            ds = m.dataset
+            seed = ds.key[0] ^ ds.key[1]
+            self.v0[r].copy_(self.eng.rng_fill(self.P, seed, step=m._elbo_hessian_draws, tag=self.V_TAG))      # widened on the copy
+            seeds.append(seed)
+            steps.append(m._elbo_hessian_draws if step is None else given[r])
+        seeds, steps = _seed_step_tensors(seeds, steps, dev)
+        self.eng.elbo_hessian_lanczos_replicas(self.params, self.rows, self.steps, self.v0, self.basis, self.out, kind=self.kind, A=self.A,
+                                               dd=self.dd, did=self.did, pad=self.pad, var_added=self.var, x_seeds=seeds, x_steps=steps,
+                                               a_stride=self.a_stride, x_tag=self.X_TAG if step is None else ReplicaExactLogLik.X_TAG)
+        rec = self.out.cpu().numpy()                                              # the event's ONE device -> host copy
+        stats = []
+        for r, m in enumerate(self.ms):
+            row = rec[r]
+            _check_solve(self.NAME, r, m, "solve of the Lanczos matrix T", "T", row[4], row[5], self.OFF_BOUND * row[6])
+            k, h, b = int(row[2]), self.HEAD, self.BLOCK
+            stats.append({self.KEYS[0]: row[h:h + k].copy(), self.KEYS[1]: row[h + b:h + b + k].copy(), self.KEYS[2]: float(row[9]),
+                          self.KEYS[3]: float(row[10]), self.KEYS[4]: float(row[1])})
+        return stats
+
+    def event_after(self, exact=False, iwae=False):
+        """event() of an n_print event.  exact: a ReplicaExactLogLik over the SAME models has just had its event (iwae: after a
+        ReplicaLogLik's, whose step it then used); the rows are drawn under the step that event used, so the Hessian is the one of the
+        objective on the rows it scored."""
+        if not exact:
+            return self.event()
+        return self.event(step=[m._loglik_draws if iwae else m._exact_loglik_draws for m in self.ms])
+
+
 class ReplicaJacobianMlp3:
     """The decoder Jacobian spectra of R three-hidden-layer MLP VAEModels of one shape in ONE library call
     (vaek_mlp3_decoder_jacobian_replicas, csrc/mlp3_jacobian.hip): per model, over `rows` latent rows z, the eigenvalues of J^T J with
