@@ -381,12 +381,16 @@ def test_arguments_predicate_and_profile_labels():
         a = dict(params=e.params, rows=rows, out=outs["hout"], v=v, hv=outs["hv"], grad=outs["grad"], nvec=2)
         a.update(e.rows_kw(rows, slice(None), True))
         a.update(kw)
+        if torch.is_tensor(a["hv"]):                                      # [R, nvec * P]: replica r's block starts at row r, which the
+            a.setdefault("hv_stride", a["hv"].shape[1])                    # engine's default (that of [n, nvec, P]) would not say
         return a
 
     def lan_args(e=cs, **kw):
         a = dict(params=e.params, rows=rows, steps=steps, v0=e.v0, basis=outs["basis"], out=outs["lout"])
         a.update(e.rows_kw(rows, slice(None), True))
         a.update(kw)
+        if torch.is_tensor(a["basis"]):                                   # [R, steps * P]: as for hv
+            a.setdefault("basis_stride", a["basis"].shape[1])
         return a
 
     def refused(why, which="both", e=cs, **kw):

@@ -41,6 +41,36 @@ def _last_dim(v, given=None):
     return int((0 if v is None or isinstance(v, int) else v.shape[-1]) if given is None else given)
 
 
+def _describe(d, params, rows, out, out_dtype, n, state_stride, out_stride, struct_size, draws, a_stride=None, given=None, raw_out=False):
+    """Fill, in the fresh descriptor `d` of an evaluation call (vaek_stats_event, vaek_log_likelihood, ...), the fields they share:
+    struct_size, n, rows and state_stride; per stream p of `draws` = {p: (seeds int64 [n], steps int32 [n])} the fields p_seeds and
+    p_steps; a_stride where the call draws data rows; the caller's rows `given` = (p, float32 tensor [rows, .] or [n, rows, .] or
+    None, stride or None) as p and p_stride (0: shared by all replicas); out (of `out_dtype`; with raw_out also a raw device
+    address) and out_stride.  n and the strides default to the tensors' shapes."""
+    d.struct_size = C.sizeof(type(d)) if struct_size is None else int(struct_size)
+    d.n = int(params.shape[0] if n is None else n)
+    d.rows = int(rows)
+    d.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+    for p, (seeds, steps) in draws.items():
+        assert seeds is None or seeds.dtype == torch.int64
+        assert steps is None or steps.dtype == torch.int32
+        setattr(d, p + "_seeds", _ptr(seeds))
+        setattr(d, p + "_steps", _ptr(steps))
+    if a_stride is not None:
+        d.a_stride = int(a_stride)
+    if given is not None:
+        p, t, stride = given
+        assert t is None or t.dtype == torch.float32
+        setattr(d, p, _ptr(t))
+        if stride is None:
+            stride = 0 if t is None or t.dim() < 3 else t.shape[-2] * t.shape[-1]
+        setattr(d, p + "_stride", int(stride))
+    assert out is None or isinstance(out, int) or out.dtype == out_dtype
+    d.out = _addr(out) if raw_out else _ptr(out)
+    d.out_stride = _last_dim(out, out_stride)
+    return d
+
+
 class Engine:
     """One libvaek context = one (batch, architecture) shape on one GPU."""
 
@@ -290,20 +320,10 @@ class Engine:
     @staticmethod
     def _stats_event_desc(params, rows, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out, a_stride, n, state_stride, out_stride, struct_size):
         """The vaek_stats_event description both stats-event calls take, from tensors; strides default to the tensors' shapes."""
-        ev = _lib.VaekStatsEvent()
-        ev.struct_size = C.sizeof(_lib.VaekStatsEvent) if struct_size is None else int(struct_size)
-        ev.n = int(params.shape[0] if n is None else n)
-        ev.rows = int(rows)
-        ev.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        assert all(s is None or s.dtype == torch.int64 for s in (x_seeds, z_seeds))
-        assert all(s is None or s.dtype == torch.int32 for s in (x_steps, z_steps))
+        ev = _describe(_lib.VaekStatsEvent(), params, rows, out, torch.float32, n, state_stride, out_stride, struct_size, a_stride=a_stride,
+                       draws=dict(x=(x_seeds, x_steps), z=(z_seeds, z_steps)))
         assert sample_eps is None or sample_eps.dtype == torch.float32
-        assert out is None or out.dtype == torch.float32
-        ev.x_seeds, ev.x_steps, ev.z_seeds, ev.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
         ev.sample_eps = _ptr(sample_eps)
-        ev.a_stride = int(a_stride)
-        ev.out = _ptr(out)
-        ev.out_stride = _last_dim(out, out_stride)
         return ev
 
     def supports_mlp3_stats_event(self, kind):
@@ -352,23 +372,9 @@ class Engine:
     def _log_likelihood_desc(params, rows, samples, z_seeds, z_steps, out, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride, out_stride,
                              struct_size):
         """The vaek_log_likelihood description both log-likelihood calls take, from tensors; strides default to the tensors' shapes."""
-        ll = _lib.VaekLogLikelihood()
-        ll.struct_size = C.sizeof(_lib.VaekLogLikelihood) if struct_size is None else int(struct_size)
-        ll.n = int(params.shape[0] if n is None else n)
-        ll.rows, ll.samples = int(rows), int(samples)
-        ll.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        assert all(s is None or s.dtype == torch.int64 for s in (x_seeds, z_seeds))
-        assert all(s is None or s.dtype == torch.int32 for s in (x_steps, z_steps))
-        assert out is None or out.dtype == torch.float32
-        assert x is None or x.dtype == torch.float32
-        ll.x_seeds, ll.x_steps, ll.z_seeds, ll.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
-        ll.a_stride = int(a_stride)
-        ll.out = _ptr(out)
-        ll.out_stride = _last_dim(out, out_stride)
-        ll.x = _ptr(x)
-        if x_stride is None:
-            x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
-        ll.x_stride = int(x_stride)
+        ll = _describe(_lib.VaekLogLikelihood(), params, rows, out, torch.float32, n, state_stride, out_stride, struct_size, a_stride=a_stride,
+                       draws=dict(x=(x_seeds, x_steps), z=(z_seeds, z_steps)), given=("x", x, x_stride))
+        ll.samples = int(samples)
         return ll
 
     def log_likelihood_replicas(self, params, rows, samples, z_seeds, z_steps, out, workspace, kind=2, A=None, dd=0, did=0, pad=0,
@@ -450,22 +456,10 @@ class Engine:
         only), seeds int64 [n], steps int32 [n], out / row_out: float64, workspace: uint8 of mlp3_decoder_jacobian_workspace(n, rows)
         bytes -- all device tensors; n and the strides default to the tensors' shapes.  Three launches whatever n is.  Asynchronous;
         capturable."""
-        dj = _lib.VaekDecoderJacobian()
-        dj.struct_size = C.sizeof(_lib.VaekDecoderJacobian) if struct_size is None else int(struct_size)
-        dj.n = int(params.shape[0] if n is None else n)
-        dj.rows = int(rows)
-        dj.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        assert z_seeds is None or z_seeds.dtype == torch.int64
-        assert z_steps is None or z_steps.dtype == torch.int32
-        assert z is None or z.dtype == torch.float32
-        assert all(o is None or o.dtype == torch.float64 for o in (out, row_out))
-        dj.z_seeds, dj.z_steps, dj.z = _ptr(z_seeds), _ptr(z_steps), _ptr(z)
-        if z_stride is None:
-            z_stride = 0 if z is None or z.dim() < 3 else z.shape[-2] * z.shape[-1]
-        dj.z_stride = int(z_stride)
+        dj = _describe(_lib.VaekDecoderJacobian(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size,
+                       draws=dict(z=(z_seeds, z_steps)), given=("z", z, z_stride))
+        assert row_out is None or row_out.dtype == torch.float64
         dj.rank_tol = float(rank_tol)
-        dj.out = _ptr(out)
-        dj.out_stride = _last_dim(out, out_stride)
         dj.row_out = _ptr(row_out)
         if row_out_stride is None:
             row_out_stride = 0 if row_out is None else row_out.shape[-2] * row_out.shape[-1]
@@ -541,19 +535,10 @@ class Engine:
         latent rows under (z_seeds[r], z_steps[r], z_tag) exactly as make_batch draws them, the fake batch sampled from the latents
         with eps = sample_eps[r].  out: float64 [n, out_stride >= 2 * cov_spectrum_record_len]: the fake record, then the real one.
         The other arguments are stats_event_replicas'.  Asynchronous; capturable."""
-        ev = _lib.VaekSpectrumEvent()
-        ev.struct_size = C.sizeof(_lib.VaekSpectrumEvent) if struct_size is None else int(struct_size)
-        ev.n = int(params.shape[0] if n is None else n)
-        ev.rows = int(rows)
-        ev.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        assert all(s is None or s.dtype == torch.int64 for s in (x_seeds, z_seeds))
-        assert all(s is None or s.dtype == torch.int32 for s in (x_steps, z_steps))
+        ev = _describe(_lib.VaekSpectrumEvent(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size, a_stride=a_stride,
+                       draws=dict(x=(x_seeds, x_steps), z=(z_seeds, z_steps)), raw_out=True)
         assert sample_eps is None or sample_eps.dtype == torch.float32
-        ev.x_seeds, ev.x_steps, ev.z_seeds, ev.z_steps = _ptr(x_seeds), _ptr(x_steps), _ptr(z_seeds), _ptr(z_steps)
         ev.sample_eps = _ptr(sample_eps)
-        ev.a_stride = int(a_stride)
-        ev.out = _addr(out, torch.float64)
-        ev.out_stride = _last_dim(out, out_stride)
         fn = self.lib.vaek_eigen_event_replicas if _vec else self.lib.vaek_spectrum_event_replicas
         _lib.check(fn(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(x_tag),
                       int(z_tag), _stream()))
@@ -586,22 +571,8 @@ class Engine:
         [n, state_stride] (read only), out: float64 [n, out_stride >= exact_log_likelihood_record_len], row_out: None or float64
         [n, rows, 2] (log p(x_i), ELBO(x_i)) -- device tensors or raw device addresses; n and the strides default to the tensors'
         shapes.  Asynchronous; capturable."""
-        ll = _lib.VaekExactLogLikelihood()
-        ll.struct_size = C.sizeof(_lib.VaekExactLogLikelihood) if struct_size is None else int(struct_size)
-        ll.n = int(params.shape[0] if n is None else n)
-        ll.rows = int(rows)
-        ll.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        assert x_seeds is None or x_seeds.dtype == torch.int64
-        assert x_steps is None or x_steps.dtype == torch.int32
-        assert x is None or x.dtype == torch.float32
-        ll.x_seeds, ll.x_steps = _ptr(x_seeds), _ptr(x_steps)
-        ll.a_stride = int(a_stride)
-        ll.out = _addr(out, torch.float64)
-        ll.out_stride = _last_dim(out, out_stride)
-        ll.x = _ptr(x)
-        if x_stride is None:
-            x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
-        ll.x_stride = int(x_stride)
+        ll = _describe(_lib.VaekExactLogLikelihood(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size,
+                       a_stride=a_stride, draws=dict(x=(x_seeds, x_steps)), given=("x", x, x_stride), raw_out=True)
         ll.row_out = _addr(row_out, torch.float64)
         if row_stride is None:
             row_stride = 0 if row_out is None or isinstance(row_out, int) else 2 * int(rows)
@@ -637,21 +608,6 @@ class Engine:
         """Doubles of one replica's Lanczos basis (vaek_elbo_hessian_basis_doubles): steps * P."""
         return self._count(self.lib.vaek_elbo_hessian_basis_doubles, int(steps))
 
-    def _hessian_rows(self, d, params, rows, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride):
-        """The fields vaek_elbo_hvp and vaek_elbo_hessian share: replicas, rows and the two row modes."""
-        d.n = int(params.shape[0] if n is None else n)
-        d.rows = int(rows)
-        d.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        assert x_seeds is None or x_seeds.dtype == torch.int64
-        assert x_steps is None or x_steps.dtype == torch.int32
-        assert x is None or x.dtype == torch.float32
-        d.x_seeds, d.x_steps = _ptr(x_seeds), _ptr(x_steps)
-        d.a_stride = int(a_stride)
-        d.x = _ptr(x)
-        if x_stride is None:
-            x_stride = 0 if x is None or x.dim() < 3 else x.shape[-2] * x.shape[-1]
-        d.x_stride = int(x_stride)
-
     def elbo_hvp_replicas(self, params, rows, out, v=None, hv=None, grad=None, nvec=None, kind=2, A=None, dd=0, did=0, pad=0, var_added=0.0,
                           x_seeds=None, x_steps=None, x=None, x_stride=None, a_stride=0, x_tag=3, n=None, state_stride=None,
                           v_stride=None, hv_stride=None, grad_stride=None, out_stride=None, struct_size=None):
@@ -661,21 +617,19 @@ class Engine:
         f, |grad f|_2, eps as used, rows.  v = None (nvec = 0): the gradient and the record only.  The rows are the caller's (x) or
         drawn, as in exact_log_likelihood_replicas.  Device tensors or raw device addresses; n, nvec and the strides default to the
         tensors' shapes.  Asynchronous; capturable."""
-        hp = _lib.VaekElboHvp()
-        hp.struct_size = C.sizeof(_lib.VaekElboHvp) if struct_size is None else int(struct_size)
-        self._hessian_rows(hp, params, rows, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride)
+        hp = _describe(_lib.VaekElboHvp(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size, a_stride=a_stride,
+                       draws=dict(x=(x_seeds, x_steps)), given=("x", x, x_stride), raw_out=True)
         f64 = torch.float64
         if nvec is None:
             nvec = 0 if v is None else v.shape[-2]
         hp.nvec = int(nvec)
-        hp.v, hp.hv, hp.grad, hp.out = _addr(v, f64), _addr(hv, f64), _addr(grad, f64), _addr(out, f64)
+        hp.v, hp.hv, hp.grad = _addr(v, f64), _addr(hv, f64), _addr(grad, f64)
         if v_stride is None:
             v_stride = 0 if v is None or isinstance(v, int) or v.dim() < 3 else v.shape[-2] * v.shape[-1]
         if hv_stride is None:
             hv_stride = 0 if hv is None or isinstance(hv, int) else hv.shape[-2] * hv.shape[-1]
         hp.v_stride, hp.hv_stride = int(v_stride), int(hv_stride)
         hp.grad_stride = _last_dim(grad, grad_stride)
-        hp.out_stride = _last_dim(out, out_stride)
         _lib.check(self.lib.vaek_elbo_hvp_replicas(self.h, _ptr(params), C.byref(hp), int(kind), _ptr(A), int(dd), int(did), int(pad),
                                                    float(var_added), int(x_tag), _stream()))
 
@@ -689,18 +643,16 @@ class Engine:
         theta_min, omega, then the Ritz values ascending, their residual bounds, alpha and beta.  The rows are the caller's (x) or drawn,
         as in exact_log_likelihood_replicas.  Device tensors or raw device addresses; n and the strides default to the tensors' shapes.
         Asynchronous; capturable."""
-        hs = _lib.VaekElboHessian()
-        hs.struct_size = C.sizeof(_lib.VaekElboHessian) if struct_size is None else int(struct_size)
-        self._hessian_rows(hs, params, rows, x_seeds, x_steps, x, x_stride, a_stride, n, state_stride)
+        hs = _describe(_lib.VaekElboHessian(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size, a_stride=a_stride,
+                       draws=dict(x=(x_seeds, x_steps)), given=("x", x, x_stride), raw_out=True)
         f64 = torch.float64
         hs.steps = int(steps)
-        hs.v0, hs.basis, hs.out = _addr(v0, f64), _addr(basis, f64), _addr(out, f64)
+        hs.v0, hs.basis = _addr(v0, f64), _addr(basis, f64)
         if v0_stride is None:
             v0_stride = 0 if v0 is None or isinstance(v0, int) or v0.dim() < 2 else v0.shape[-1]
         if basis_stride is None:
             basis_stride = 0 if basis is None or isinstance(basis, int) else basis.shape[-2] * basis.shape[-1]
         hs.v0_stride, hs.basis_stride = int(v0_stride), int(basis_stride)
-        hs.out_stride = _last_dim(out, out_stride)
         _lib.check(self.lib.vaek_elbo_hessian_lanczos_replicas(self.h, _ptr(params), C.byref(hs), int(kind), _ptr(A), int(dd), int(did),
                                                                int(pad), float(var_added), int(x_tag), _stream()))
 

@@ -12,6 +12,7 @@ from copy import deepcopy
 import numpy as np
 import torch
 
+from . import observables
 from . import random as vrandom
 
 
@@ -70,8 +71,10 @@ class Model:
         self.load_model()
 
 
-HESSIAN_ARRAY_KEYS = ("ELBO Hessian Ritz Values", "ELBO Hessian Ritz Residuals")      # trainer.ReplicaElboHessian.KEYS[:2]
-JACOBIAN_KEYS = ("Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity")      # trainer.ReplicaJacobianMlp3.KEYS
+# the keys whose values are arrays whatever their length, from the table of observables: they stay off the stats line
+HESSIAN_ARRAY_KEYS = observables.array_keys("elbo_hessian")
+JACOBIAN_KEYS = observables.array_keys("decoder_jacobian")
+_ARRAY_KEY_LINES = observables.stats_line_rules()
 
 
 class GenerativeModel(Model):
@@ -129,72 +132,21 @@ class GenerativeModel(Model):
         return stats
 
     def _stats_event(self):
-        """The stats of an n_print event: compute_stats(), and with `log_likelihood_samples` = K set (run.py --log_likelihood_samples)
-        the importance-weighted log-likelihood of this model on K samples per row (trainer.ReplicaLogLik, one library call), which
-        neither splits the model's key nor advances a draw counter of the run; `exact_log_likelihood` (run.py --exact_log_likelihood)
-        adds the closed-form log-likelihood, ELBO and posterior gap of a one-decoder linear model (trainer.ReplicaExactLogLik), on
-        the rows the IWAE event just scored where there is one (then also "IWAE Gap"); `mlp_log_likelihood_samples` does the same for a
-        three-hidden-layer MLP model (trainer.ReplicaLogLikMlp3); `eigenvalues` (run.py --eigenvalues) adds the covariance spectra of
-        a generated and a real batch (trainer.ReplicaSpectrum), which leaves the run alone in the same way; `subspace` (run.py
-        --subspace) adds the principal angles between their leading eigenspaces (trainer.ReplicaSubspace) under the same counter;
-        `decoder_jacobian` = "prior" | "posterior" (run.py --decoder_jacobian) adds the spectra of the decoder Jacobian of a
-        three-hidden-layer MLP model (trainer.ReplicaJacobianMlp3), under a counter and tags of its own; `elbo_hessian` = STEPS (run.py
-        --elbo_hessian) adds the Ritz values of the Hessian of the exact ELBO of a one-decoder linear model
-        (trainer.ReplicaElboHessian), under a counter and tags of its own, on the exact event's rows where there is one."""
+        """The stats of an n_print event: compute_stats(), then every observable whose attribute run.py set on this model
+        (observables.OBSERVABLES: `log_likelihood_samples`, `mlp_log_likelihood_samples`, `exact_log_likelihood`, `elbo_hessian`,
+        `eigenvalues` / `subspace`, `decoder_jacobian`), one device call each, in the table's order.  Each event object is built on
+        its first event and kept on the model; none of them splits the model's key or advances a draw counter of the run."""
         stats = self.compute_stats()
-        K = getattr(self, "log_likelihood_samples", None)
-        if K:
-            from .trainer import ReplicaLogLik
-            if getattr(self, "_loglik", None) is None:
-                self._loglik = ReplicaLogLik([self], K)
-            iwae = self._loglik.event()
-            stats.update(iwae[0])
-        if getattr(self, "exact_log_likelihood", False):           # run.py --exact_log_likelihood: the closed form of a one-decoder linear
-            from .trainer import ReplicaExactLogLik                # model (log p(x), ELBO, their gap), on the IWAE event's rows where there is one
-            if getattr(self, "_exact_loglik", None) is None:
-                self._exact_loglik = ReplicaExactLogLik([self])
-            stats.update(self._exact_loglik.event_after(iwae if K else None)[0])
-        steps = getattr(self, "elbo_hessian", None)                # run.py --elbo_hessian: Ritz values of the Hessian of the exact ELBO,
-        if steps:                                                  # on the exact event's rows where there is one
-            from .trainer import ReplicaElboHessian
-            if getattr(self, "_elbo_hessian", None) is None:
-                self._elbo_hessian = ReplicaElboHessian([self], steps)
-            stats.update(self._elbo_hessian.event_after(exact=bool(getattr(self, "exact_log_likelihood", False)), iwae=bool(K))[0])
-        K = getattr(self, "mlp_log_likelihood_samples", None)     # run.py --mlp_log_likelihood_samples: the same event for an mlp3 model
-        if K:
-            from .trainer import ReplicaLogLikMlp3
-            if getattr(self, "_loglik_mlp3", None) is None:
-                self._loglik_mlp3 = ReplicaLogLikMlp3([self], K)
-            stats.update(self._loglik_mlp3.event()[0])
-        if getattr(self, "subspace", False):                       # run.py --subspace: eigenvectors too, and the principal angles between
-            from .trainer import ReplicaSubspace                   # the two leading eigenspaces; one device call serves --eigenvalues as well
-            if getattr(self, "_subspace", None) is None:
-                self._subspace = ReplicaSubspace([self], k=getattr(self, "subspace_k", None))
-            st = self._subspace.event()[0]
-            stats.update(st if getattr(self, "eigenvalues", False) else {k: v for k, v in st.items() if k not in ReplicaSubspace.KEYS})
-        elif getattr(self, "eigenvalues", False):                  # run.py --eigenvalues: the covariance spectra of a fake and a real batch
-            from .trainer import ReplicaSpectrum
-            if getattr(self, "_spectrum", None) is None:
-                self._spectrum = ReplicaSpectrum([self])
-            stats.update(self._spectrum.event()[0])
-        at = getattr(self, "decoder_jacobian", None)               # run.py --decoder_jacobian: the decoder Jacobian spectra of an mlp3 model
-        if at:
-            from .trainer import ReplicaJacobianMlp3
-            if getattr(self, "_jacobian", None) is None:
-                self._jacobian = ReplicaJacobianMlp3([self], at=at, rank_tol=getattr(self, "decoder_jacobian_tol", 1e-4))
-            stats.update(self._jacobian.event()[0])
+        stats.update(observables.run_events([self], self)[0])
         return stats
 
     def write_stats(self, stats):
         message = f"Batch | {self.batchnum}"
         for stat, val in stats.items():
-            if stat in JACOBIAN_KEYS:                      # arrays whatever L is; the stats line shows the mean rank
+            if stat in _ARRAY_KEY_LINES:                   # an observable's array: off the line, or its element 0 under a label
                 self.stats[stat].append(_to_numpy(val))
-                if stat == JACOBIAN_KEYS[1]:
-                    message += f" | {stat} (mean) | {float(val[0]):.3f}"
-                continue
-            if stat in HESSIAN_ARRAY_KEYS:                 # arrays whatever k is; Sharpness and the smallest Ritz value are on the line
-                self.stats[stat].append(_to_numpy(val))
+                if _ARRAY_KEY_LINES[stat] is not None:
+                    message += f" | {_ARRAY_KEY_LINES[stat]} | {float(val[0]):.3f}"
                 continue
             try:
                 fval = float(val)

@@ -3,10 +3,16 @@
 losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never reads on the VAE path
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
---fused_stats, --log_likelihood_samples, --mlp_log_likelihood_samples, --eigenvalues, --subspace, --decoder_jacobian."""
+--fused_stats, --mlp_fused_stats, and the observables of the n_print events, which observables.py tables: --log_likelihood_samples,
+--mlp_log_likelihood_samples, --exact_log_likelihood, --elbo_hessian, --eigenvalues, --subspace, --decoder_jacobian (with
+--decoder_jacobian_tol)."""
 from __future__ import annotations
 
 import argparse
+import types
+
+from . import observables
+from .observables import FLAGS, JACOBIAN_DEFAULT_TOL, check_model, decoder_jacobian_tol      # noqa: F401 (names callers import here)
 
 
 def build_parser():
@@ -357,54 +363,52 @@ def check_mlp_fused_stats_loop(loop, fused_stats=False):
                            "vaek_supports_mlp3_stats_event does not cover")
 
 
-LOGLIK_NEEDS = ("a model vaek_log_likelihood_replicas covers (vaek_supports_log_likelihood): a float32 linear VAE -- no hidden layers -- "
-                "with one or two decoders, D, L <= 32 (D <= 28 with two decoders), -dd / -did <= 16, on one GPU")
+# ---- the observables of the n_print events: observables.OBSERVABLES holds their NEEDS texts, refusals and banners; the names below
+# are what callers and tests import
+LOGLIK_NEEDS = FLAGS["log_likelihood_samples"][1].needs
+MLP_LOGLIK_NEEDS = FLAGS["mlp_log_likelihood_samples"][1].needs
+EXACT_LOGLIK_NEEDS = FLAGS["exact_log_likelihood"][1].needs
+ELBO_HESSIAN_NEEDS = FLAGS["elbo_hessian"][1].needs
+EIGEN_NEEDS = FLAGS["eigenvalues"][1].needs
+SUBSPACE_NEEDS = FLAGS["subspace"][1].needs
+JACOBIAN_NEEDS = FLAGS["decoder_jacobian"][1].needs
 
 
 def check_log_likelihood_model(m, samples):
     """--log_likelihood_samples: refuse, before any step, a model the log-likelihood call does not cover or a K above its cap."""
-    from .datasets import DEVICE_DRAW_MAX_DIM
-    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
-    kind, _, dd, did, _, _ = m.dataset.device_spec()
-    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_log_likelihood(kind):
-        raise RuntimeError(f"--log_likelihood_samples needs {LOGLIK_NEEDS} (this model's step path: {getattr(eng, 'step_path', '?')}, "
-                           f"world {eng.world})")
-    if samples > eng.log_likelihood_max_samples:
-        raise RuntimeError(f"--log_likelihood_samples {samples}: at most {eng.log_likelihood_max_samples} samples per row fit one call "
-                           "(vaek_log_likelihood_max_samples)")
+    check_model("log_likelihood_samples", m, samples)
 
 
-EXACT_LOGLIK_NEEDS = ("a model vaek_exact_log_likelihood_replicas covers (vaek_supports_exact_log_likelihood): a float32 linear VAE -- no "
-                      "hidden layers -- with ONE decoder (the sigmoid second decoder has no closed form), D, L <= 32, -dd / -did <= 16, on "
-                      "one GPU")
+def check_mlp_log_likelihood_model(m, samples, n_models=1):
+    """--mlp_log_likelihood_samples: refuse, before any step, a model the call does not cover, a K above its cap or more columns
+    (models x print rows x K) than one call takes."""
+    check_model("mlp_log_likelihood_samples", m, samples, n_models)
 
 
 def check_exact_log_likelihood_model(m):
     """--exact_log_likelihood: refuse, before any step, a model the exact call does not cover."""
-    from .datasets import DEVICE_DRAW_MAX_DIM
-    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
-    kind, _, dd, did, _, _ = m.dataset.device_spec()
-    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_exact_log_likelihood(kind):
-        raise RuntimeError(f"--exact_log_likelihood needs {EXACT_LOGLIK_NEEDS} (this model's step path: {getattr(eng, 'step_path', '?')}, "
-                           f"world {eng.world})")
-
-
-ELBO_HESSIAN_NEEDS = ("a model vaek_elbo_hessian_lanczos_replicas covers (vaek_supports_elbo_hessian): a float32 linear VAE -- no hidden "
-                      "layers -- with ONE decoder (the ELBO of other models has no closed form), D, L <= 32, -dd / -did <= 16, on one GPU")
+    check_model("exact_log_likelihood", m)
 
 
 def check_elbo_hessian_model(m):
     """--elbo_hessian: refuse, before any step, a model the Lanczos call does not cover."""
-    from .datasets import DEVICE_DRAW_MAX_DIM
-    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
-    kind, _, dd, did, _, _ = m.dataset.device_spec()
-    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_elbo_hessian(kind):
-        raise RuntimeError(f"--elbo_hessian needs {ELBO_HESSIAN_NEEDS} (this model's step path: {getattr(eng, 'step_path', '?')}, "
-                           f"world {eng.world})")
+    check_model("elbo_hessian", m)
 
 
-MLP_LOGLIK_NEEDS = ("a model vaek_mlp3_log_likelihood_replicas covers (vaek_supports_mlp3_log_likelihood): float32, one decoder, exactly "
-                    "three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32, -dd / -did <= 16, on one GPU")
+def check_eigenvalues_model(m):
+    """--eigenvalues: refuse, before any step, a model the spectrum calls do not cover."""
+    check_model("eigenvalues", m)
+
+
+def check_subspace_model(m, k):
+    """--subspace: refuse, before any step, a model the eigen calls do not cover or a K outside 1 .. data_dim.  Returns K (None: auto)."""
+    return check_model("subspace", m, k)
+
+
+def check_decoder_jacobian_model(m, n_models=1):
+    """--decoder_jacobian: refuse, before any step, a model the call does not cover or more columns (models x print rows x L) than one
+    call takes."""
+    check_model("decoder_jacobian", m, None, n_models)
 
 
 def check_log_likelihood_flags(args):
@@ -415,91 +419,10 @@ def check_log_likelihood_flags(args):
                            "disjoint models: give the one that matches the model's step path")
 
 
-def check_mlp_log_likelihood_model(m, samples, n_models=1):
-    """--mlp_log_likelihood_samples: refuse, before any step, a model the call does not cover, a K above its cap or more columns
-    (models x print rows x K) than one call takes."""
-    from .datasets import DEVICE_DRAW_MAX_DIM
-    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
-    kind, _, dd, did, _, _ = m.dataset.device_spec()
-    path = getattr(eng, "step_path", "?")
-    if eng.world == 1 and eng.supports_log_likelihood(kind):
-        raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS}; this is a linear VAE: use --log_likelihood_samples "
-                           f"(this model's step path: {path})")
-    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_mlp3_log_likelihood(kind):
-        raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS} (this model's step path: {path}, world {eng.world})")
-    if samples > eng.log_likelihood_max_samples:
-        raise RuntimeError(f"--mlp_log_likelihood_samples {samples}: at most {eng.log_likelihood_max_samples} samples per row fit one call "
-                           f"(vaek_log_likelihood_max_samples; this model's step path: {path})")
-    cols = n_models * m.print_batch_size * samples
-    if cols > eng.mlp3_log_likelihood_max_columns:
-        raise RuntimeError(f"--mlp_log_likelihood_samples {samples}: {n_models} models x {m.print_batch_size} rows x {samples} samples = {cols} "
-                           f"columns, at most {eng.mlp3_log_likelihood_max_columns} fit one call (vaek_mlp3_log_likelihood_max_columns; this "
-                           f"model's step path: {path})")
-
-
-JACOBIAN_NEEDS = ("a model vaek_mlp3_decoder_jacobian_replicas covers (vaek_supports_mlp3_decoder_jacobian): float32, one decoder, "
-                  "exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32, -dd / -did <= 16, on one GPU")
-JACOBIAN_DEFAULT_TOL = 1e-4
-
-
 def check_decoder_jacobian_flags(args):
     """--decoder_jacobian_tol without --decoder_jacobian: refused before anything is created."""
     if getattr(args, "decoder_jacobian_tol", None) is not None and getattr(args, "decoder_jacobian", None) is None:
         raise RuntimeError("--decoder_jacobian_tol sets the rank threshold of --decoder_jacobian prior|posterior: give that flag too")
-
-
-def decoder_jacobian_tol(args):
-    """The rank threshold of --decoder_jacobian: --decoder_jacobian_tol, else 1e-4."""
-    tol = getattr(args, "decoder_jacobian_tol", None)
-    return JACOBIAN_DEFAULT_TOL if tol is None else float(tol)
-
-
-def check_decoder_jacobian_model(m, n_models=1):
-    """--decoder_jacobian: refuse, before any step, a model the call does not cover or more columns (models x print rows x L) than one
-    call takes."""
-    from .datasets import DEVICE_DRAW_MAX_DIM
-    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
-    kind, _, dd, did, _, _ = m.dataset.device_spec()
-    path = getattr(eng, "step_path", "?")
-    if eng.world == 1 and eng.supports_log_likelihood(kind):
-        raise RuntimeError(f"--decoder_jacobian needs {JACOBIAN_NEEDS}; this is a linear VAE, whose J is the decoder kernel itself at every "
-                           f"z: use --exact_log_likelihood, whose record holds the eigenvalues of K^T K (this model's step path: {path})")
-    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_mlp3_decoder_jacobian():
-        raise RuntimeError(f"--decoder_jacobian needs {JACOBIAN_NEEDS} (this model's step path: {path}, world {eng.world})")
-    cols = n_models * m.print_batch_size * eng.L
-    if cols > eng.mlp3_decoder_jacobian_max_columns:
-        raise RuntimeError(f"--decoder_jacobian: {n_models} models x {m.print_batch_size} rows x {eng.L} latents = {cols} columns, at most "
-                           f"{eng.mlp3_decoder_jacobian_max_columns} fit one call (vaek_mlp3_decoder_jacobian_max_columns; this model's "
-                           f"step path: {path})")
-
-
-EIGEN_NEEDS = "data_dim <= 32 (vaek_supports_cov_spectrum), -dd / -did <= 16, on one GPU"
-
-
-def check_eigenvalues_model(m):
-    """--eigenvalues: refuse, before any step, a model the spectrum calls do not cover."""
-    from .datasets import DEVICE_DRAW_MAX_DIM
-    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
-    _, _, dd, did, _, _ = m.dataset.device_spec()
-    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_cov_spectrum():
-        raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS} (this model's data_dim: {getattr(eng, 'D', '?')}, world {eng.world})")
-
-
-SUBSPACE_NEEDS = "data_dim <= 32 (vaek_supports_cov_spectrum), K in 1 .. data_dim, -dd / -did <= 16, on one GPU"
-
-
-def check_subspace_model(m, k):
-    """--subspace: refuse, before any step, a model the eigen calls do not cover or a K outside 1 .. data_dim.  Returns K (None: auto)."""
-    from .datasets import DEVICE_DRAW_MAX_DIM
-    eng = m.model.module.engine(m.batch_size, m.optimizer.global_batch)
-    _, _, dd, did, _, _ = m.dataset.device_spec()
-    D = getattr(eng, "D", None)
-    if eng.world > 1 or dd > DEVICE_DRAW_MAX_DIM or did > DEVICE_DRAW_MAX_DIM or not eng.supports_cov_spectrum():
-        raise RuntimeError(f"--subspace needs {SUBSPACE_NEEDS} (this model's data_dim: {D if D is not None else '?'}, world {eng.world})")
-    k = None if k == "auto" else int(k)
-    if k is not None and not 1 <= k <= D:
-        raise RuntimeError(f"--subspace {k} needs {SUBSPACE_NEEDS} (this model's data_dim: {D})")
-    return k
 
 
 def main_sweep(args):
@@ -537,71 +460,21 @@ def main_sweep(args):
         if not isinstance(loop, ReplicaLoop):
             raise RuntimeError(f"--fused_stats needs {FUSED_STATS_NEEDS}; this sweep's step path is {eng.step_path!r} "
                                "(trainer.ReplicaGraphLoop), whose fused stats event is --mlp_fused_stats")
-    ll_samples = getattr(args, "log_likelihood_samples", None)
-    loglik = None
-    if ll_samples is not None:               # before any step
-        from .trainer import ReplicaLogLik
-        check_log_likelihood_model(models[0], ll_samples)
-        loglik = ReplicaLogLik(models, ll_samples)
-    mlp_samples = getattr(args, "mlp_log_likelihood_samples", None)
-    if mlp_samples is not None:              # before any step
-        from .trainer import ReplicaLogLikMlp3
-        check_mlp_log_likelihood_model(models[0], mlp_samples, len(models))
-        loglik = ReplicaLogLikMlp3(models, mlp_samples)
-    exact = None
-    if getattr(args, "exact_log_likelihood", False):     # before any step
-        from .trainer import ReplicaExactLogLik
-        check_exact_log_likelihood_model(models[0])
-        exact = ReplicaExactLogLik(models)
-    hessian = None
-    if getattr(args, "elbo_hessian", None) is not None:  # before any step
-        from .trainer import ReplicaElboHessian
-        check_elbo_hessian_model(models[0])
-        hessian = ReplicaElboHessian(models, args.elbo_hessian)
-    spectrum = None
-    if getattr(args, "eigenvalues", False):  # before any step
-        from .trainer import ReplicaSpectrum
-        check_eigenvalues_model(models[0])
-        if getattr(args, "subspace", None) is None:
-            spectrum = ReplicaSpectrum(models)
-        for m in models:
-            m.eigenvalues = True             # model_save_data writes "EigenValues"
-    if getattr(args, "subspace", None) is not None:      # before any step; with --eigenvalues its one device call serves both
-        from .trainer import ReplicaSubspace
-        spectrum = ReplicaSubspace(models, k=check_subspace_model(models[0], args.subspace))
-        for m in models:
-            m.subspace = True                # model_save_data writes "Subspace Distance" and "Principal Angles"
-    jacobian = None
-    if getattr(args, "decoder_jacobian", None) is not None:      # before any step
-        from .trainer import ReplicaJacobianMlp3
-        check_decoder_jacobian_model(models[0], len(models))
-        jacobian = ReplicaJacobianMlp3(models, at=args.decoder_jacobian, rank_tol=decoder_jacobian_tol(args))
+    sweep = types.SimpleNamespace()          # what the observable flags set; the event objects are kept on it too
+    for fl in observables.attach(args, models, sweep, build=True):      # refused, and the events built, before any step
+        if fl.save_flag:
+            for m in models:
+                setattr(m, fl.dest, True)    # model_save_data
     print(f"Train step: {eng.step_path} kernels (vaek_train_step_path), replica sweep over dataset seeds {seeds}")
     print(f"Train loop: {loop.describe()}")
     if fused_stats:
         print(f"Stats events: one launch for {len(models)} models (vaek_stats_event_replicas)")
     if mlp_fused_stats:
         print(f"Stats events: one call for {len(models)} models (vaek_mlp3_stats_event_replicas)")
-    if loglik is not None:
-        entry = "vaek_log_likelihood_replicas" if mlp_samples is None else "vaek_mlp3_log_likelihood_replicas"
-        print(f"Log-likelihood events: {loglik.samples} samples × {loglik.rows} rows ({entry})")
-    if exact is not None:
-        print(f"Exact log-likelihood events: {exact.rows} rows per model, one launch for {len(models)} models "
-              "(vaek_exact_log_likelihood_replicas)")
-    if hessian is not None:
-        print(f"ELBO Hessian events: {hessian.steps} Lanczos steps on {hessian.rows} rows per model, one launch for {len(models)} models "
-              "(vaek_elbo_hessian_lanczos_replicas)")
-    if spectrum is not None and getattr(args, "eigenvalues", False):
-        entry = ("vaek_eigen_event_replicas" if spectrum.fused else "vaek_cov_eigen_rows") if spectrum.VEC else \
-                ("vaek_spectrum_event_replicas" if spectrum.fused else "vaek_cov_spectrum_rows")
-        print(f"Eigenvalue events: {spectrum.rows} generated and {spectrum.rows} real rows per model ({entry})")
-    if spectrum is not None and spectrum.VEC:
-        entry = "vaek_eigen_event_replicas" if spectrum.fused else "vaek_cov_eigen_rows"
-        print(f"Subspace events: the {spectrum.k} leading eigenvectors of {spectrum.rows} generated and {spectrum.rows} real rows per model "
-              f"({entry}, vaek_subspace_angles)")
-    if jacobian is not None:
-        print(f"Decoder Jacobian events: {jacobian.rows} {jacobian.at} latent rows per model, rank threshold {jacobian.rank_tol:g}, one call "
-              f"for {len(models)} models (vaek_mlp3_decoder_jacobian_replicas)")
+    for ob, event in observables.active(models, sweep):
+        for fl in ob.flags:
+            if fl.value(args) is not None:
+                print(fl.banner_sweep(event, len(models), sweep))
     for r, m in enumerate(models):
         m._graph_loop = loop.view(r)
         score = m.dataset.score_batch(m.dataset.get_batch(m.print_batch_size))
@@ -615,28 +488,12 @@ def main_sweep(args):
         pos = ev
         loop.check()
         fused = loop.stats_event() if (fused_stats or mlp_fused_stats) and ev % n_print == 0 else None      # every model's event in one call
-        extra = loglik.event() if loglik is not None and ev % n_print == 0 else None     # every model's log-likelihood in one call
-        spectra = spectrum.event() if spectrum is not None and ev % n_print == 0 else None     # every model's two spectra in one call
-        # every model's closed form in one launch, on the rows the IWAE event just scored where there is one
-        closed = exact.event_after(extra if ll_samples is not None else None) if exact is not None and ev % n_print == 0 else None
-        # every model's Lanczos run in one launch, on the rows the exact event just scored where there is one
-        curv = hessian.event_after(exact=exact is not None, iwae=ll_samples is not None) if hessian is not None and ev % n_print == 0 else None
-        jac = jacobian.event() if jacobian is not None and ev % n_print == 0 else None     # every model's decoder Jacobian spectra in one call
+        extra = observables.run_events(models, sweep) if ev % n_print == 0 else None      # every model's observables: one call each
         for r, m in enumerate(models):
             m.batchnum = ev
             if ev % n_print == 0:
                 stats = m.compute_stats() if fused is None else fused[r]
-                if extra is not None:
-                    stats.update(extra[r])
-                if closed is not None:
-                    stats.update(closed[r])
-                if curv is not None:
-                    stats.update(curv[r])
-                if spectra is not None:
-                    stats.update(spectra[r] if getattr(args, "eigenvalues", False) else
-                                 {k: v for k, v in spectra[r].items() if k not in spectrum.KEYS})
-                if jac is not None:
-                    stats.update(jac[r])
+                stats.update(extra[r])
                 m.write_stats(stats)
             if ev % n_plot == 0 or ev == n - 1:
                 m.plot_epoch()
@@ -662,27 +519,8 @@ def main(args):
     from .utils import get_output_dir, make_output_dir
     dist = None
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
-    if world > 1 and getattr(args, "log_likelihood_samples", None) is not None:      # before a process group exists
-        raise RuntimeError(f"--log_likelihood_samples needs {LOGLIK_NEEDS}: it does not combine with data parallelism "
-                           f"(step path of a world of {world}: one shard per rank)")
-    if world > 1 and getattr(args, "mlp_log_likelihood_samples", None) is not None:
-        raise RuntimeError(f"--mlp_log_likelihood_samples needs {MLP_LOGLIK_NEEDS}: it does not combine with data parallelism "
-                           f"(step path of a world of {world}: one shard per rank)")
-    if world > 1 and getattr(args, "exact_log_likelihood", False):
-        raise RuntimeError(f"--exact_log_likelihood needs {EXACT_LOGLIK_NEEDS}: it does not combine with data parallelism "
-                           f"(step path of a world of {world}: one shard per rank)")
-    if world > 1 and getattr(args, "elbo_hessian", None) is not None:
-        raise RuntimeError(f"--elbo_hessian needs {ELBO_HESSIAN_NEEDS}: it does not combine with data parallelism "
-                           f"(step path of a world of {world}: one shard per rank)")
-    if world > 1 and getattr(args, "eigenvalues", False):
-        raise RuntimeError(f"--eigenvalues needs {EIGEN_NEEDS}: it does not combine with data parallelism "
-                           f"(step path of a world of {world}: one shard per rank)")
-    if world > 1 and getattr(args, "subspace", None) is not None:
-        raise RuntimeError(f"--subspace needs {SUBSPACE_NEEDS}: it does not combine with data parallelism "
-                           f"(step path of a world of {world}: one shard per rank)")
-    if world > 1 and getattr(args, "decoder_jacobian", None) is not None:
-        raise RuntimeError(f"--decoder_jacobian needs {JACOBIAN_NEEDS}: it does not combine with data parallelism "
-                           f"(step path of a world of {world}: one shard per rank)")
+    if world > 1:                            # before a process group exists
+        observables.refuse_data_parallel(args, world)
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -707,38 +545,8 @@ def main(args):
             raise RuntimeError(f"--trajectory_every needs {TRAJECTORY_NEEDS}: it does not combine with data parallelism")
         check_trajectory_model(model)            # before any step
         model.trajectory_every = tevery          # train() takes GraphLoop(resident=True, trajectory_every=K) and prints the Train loop: line
-    ll_samples = getattr(args, "log_likelihood_samples", None)
-    if ll_samples is not None:
-        check_log_likelihood_model(model, ll_samples)      # before any step
-        model.log_likelihood_samples = ll_samples          # the n_print events add trainer.ReplicaLogLik([model], K).event()
-        print(f"Log-likelihood events: {ll_samples} samples × {model.print_batch_size} rows (vaek_log_likelihood_replicas)")
-    mlp_samples = getattr(args, "mlp_log_likelihood_samples", None)
-    if mlp_samples is not None:
-        check_mlp_log_likelihood_model(model, mlp_samples)      # before any step
-        model.mlp_log_likelihood_samples = mlp_samples          # the n_print events add trainer.ReplicaLogLikMlp3([model], K).event()
-        print(f"Log-likelihood events: {mlp_samples} samples × {model.print_batch_size} rows (vaek_mlp3_log_likelihood_replicas)")
-    if getattr(args, "exact_log_likelihood", False):
-        check_exact_log_likelihood_model(model)            # before any step
-        model.exact_log_likelihood = True                  # the n_print events add trainer.ReplicaExactLogLik([model]).event_after(...)
-        print(f"Exact log-likelihood events: {model.print_batch_size} rows (vaek_exact_log_likelihood_replicas)")
-    if getattr(args, "elbo_hessian", None) is not None:
-        check_elbo_hessian_model(model)                    # before any step
-        model.elbo_hessian = args.elbo_hessian             # the n_print events add trainer.ReplicaElboHessian([model], STEPS).event_after(...)
-        print(f"ELBO Hessian events: {args.elbo_hessian} Lanczos steps on {model.print_batch_size} rows (vaek_elbo_hessian_lanczos_replicas)")
-    if getattr(args, "eigenvalues", False):
-        check_eigenvalues_model(model)                     # before any step
-        model.eigenvalues = True                           # the n_print events add trainer.ReplicaSpectrum([model]).event()
-        print(f"Eigenvalue events: {model.print_batch_size} generated and {model.print_batch_size} real rows (csrc/cov_spectrum.hip)")
-    if getattr(args, "subspace", None) is not None:
-        model.subspace_k = check_subspace_model(model, args.subspace)      # before any step
-        model.subspace = True                              # the n_print events add trainer.ReplicaSubspace([model], k).event()
-        print(f"Subspace events: {model.print_batch_size} generated and {model.print_batch_size} real rows (csrc/cov_spectrum.hip)")
-    if getattr(args, "decoder_jacobian", None) is not None:
-        check_decoder_jacobian_model(model)                # before any step
-        model.decoder_jacobian = args.decoder_jacobian     # the n_print events add trainer.ReplicaJacobianMlp3([model], at=...).event()
-        model.decoder_jacobian_tol = decoder_jacobian_tol(args)
-        print(f"Decoder Jacobian events: {model.print_batch_size} {args.decoder_jacobian} latent rows, rank threshold "
-              f"{model.decoder_jacobian_tol:g} (vaek_mlp3_decoder_jacobian_replicas)")
+    for fl in observables.attach(args, [model], model, build=False):      # refused before any step; the n_print events read the
+        print(fl.banner_one(model))                                       # attributes (GenerativeModel._stats_event)
     if rank == 0:
         eng = model.model.module.engine(model.batch_size, model.optimizer.global_batch)
         loop = {True: "graph loop (--fast_loop)", None: "loop chosen by model"}.get(getattr(args, "fast_loop", False), "one library call per step")
