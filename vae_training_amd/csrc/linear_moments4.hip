@@ -1,7 +1,6 @@
 // The four-block (49 .. 64 features) instantiations of the persistent form of vaek_train_steps, in a translation unit of their own:
-// see lin_persist_four in linear_moments.hip.
-#define VAEK_LIN_FOUR_BLOCK_TU
-#include "linear_moments.hip"
+// see linear_moments_dev.h.
+#include "linear_moments_dev.h"
 
 namespace vaek {
 
