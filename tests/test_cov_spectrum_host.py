@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from tests import cov_spectrum_cases as K
+from tests.abi_util import _c_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_supports_cov_spectrum", "vaek_cov_spectrum_record_len", "vaek_cov_spectrum_max_sets", "vaek_cov_spectrum_max_sweeps",
@@ -67,13 +68,6 @@ def test_the_restatement_on_the_degenerate_matrices():
             assert sorted(i for p in pairs for i in p) == list(range(de))           # de / 2 DISJOINT rotations
             seen |= {tuple(sorted(p)) for p in pairs}
         assert len(seen) == de * (de - 1) // 2                                        # every pair once per sweep
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_spectrum_calls():

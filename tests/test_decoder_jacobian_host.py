@@ -11,17 +11,12 @@ import numpy as np
 import pytest
 import torch
 
+from tests.abi_util import _c_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"vaek_supports_mlp3_decoder_jacobian": 2, "vaek_decoder_jacobian_record_len": 2, "vaek_decoder_jacobian_row_record_len": 2,
        "vaek_mlp3_decoder_jacobian_max_columns": 0, "vaek_mlp3_decoder_jacobian_workspace_bytes": 4, "vaek_mlp3_decoder_jacobian_replicas": 6}
 KEYS = ["Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity"]
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_decoder_jacobian():

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import elbo_hessian_cases as K
+from tests.abi_util import _c_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_supports_elbo_hessian", "vaek_elbo_hvp_max_vectors", "vaek_elbo_hvp_record_len", "vaek_elbo_hessian_max_steps",
@@ -107,13 +108,6 @@ def test_lanczos_edges_of_the_restatement():
 
 
 # ---- the C ABI surface ------------------------------------------------------------------------------------------------------------------
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    inner = m.group(1).strip()
-    return 0 if inner == "void" else len(inner.split(","))
-
-
 def test_abi_surface_of_the_elbo_hessian():
     from vae_training_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "vaek.h")).read()

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from tests import exact_loglik_cases as K
+from tests.abi_util import _c_args
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST_ROWS = 32
@@ -102,12 +103,6 @@ def test_record_layout_of_the_restatement():
 
 
 # ---- the C ABI surface ------------------------------------------------------------------------------------------------------------------
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    return len(m.group(1).strip().split(","))
-
-
 def test_abi_surface_of_the_exact_log_likelihood():
     from vae_training_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "vaek.h")).read()

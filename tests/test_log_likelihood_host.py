@@ -11,19 +11,14 @@ import types
 import pytest
 import torch
 
+from tests.abi_util import _c_args, check_description_guard
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_supports_log_likelihood", "vaek_log_likelihood_record_len", "vaek_log_likelihood_max_rows", "vaek_log_likelihood_max_samples",
        "vaek_log_likelihood_workspace_bytes", "vaek_log_likelihood_replicas")
 FIELDS = ["struct_size", "n", "rows", "samples", "state_stride", "x_seeds", "x_steps", "z_seeds", "z_steps", "a_stride", "out", "out_stride",
           "x", "x_stride"]
 KEYS = ["Average Log Likelihood", "ELBO estimate", "Effective Sample Size"]
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_log_likelihood():
@@ -42,8 +37,7 @@ def test_abi_surface_of_the_log_likelihood():
     body = re.search(r"typedef struct vaek_log_likelihood \{(.*?)\} vaek_log_likelihood;", hdr, flags=re.S).group(1)
     fields = re.findall(r"(\w+);", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
     assert fields == [f[0] for f in _lib.VaekLogLikelihood._fields_] == FIELDS, fields
-    src = open(os.path.join(ROOT, "vae_training_amd", "csrc", "linear_loglik.hip")).read()
-    assert "ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)" in src
+    check_description_guard(lib, "vaek_log_likelihood_replicas")        # the guard as behaviour: refused by its size, before the context
     assert "linear_loglik.hip" in open(os.path.join(ROOT, "vae_training_amd", "csrc", "Makefile")).read()
     # a NULL context is refused before anything is touched, and the message names the entry point
     yes = C.c_int32(7)

@@ -4,23 +4,17 @@ and tags, the run's RNG state untouched, what it refuses, ReplicaLogLik's behavi
 of model.py and run.py's --mlp_log_likelihood_samples flag."""
 import ctypes as C
 import os
-import re
 import types
 
 import pytest
 import torch
 
+from tests.abi_util import _c_args, check_description_guard
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_supports_mlp3_log_likelihood", "vaek_mlp3_log_likelihood_max_columns", "vaek_mlp3_log_likelihood_workspace_bytes",
        "vaek_mlp3_log_likelihood_replicas")
 KEYS = ["Average Log Likelihood", "ELBO estimate", "Effective Sample Size"]
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_mlp3_log_likelihood():
@@ -36,10 +30,8 @@ def test_abi_surface_of_the_mlp3_log_likelihood():
     assert _lib.SIGNATURES["vaek_mlp3_log_likelihood_replicas"] == _lib.SIGNATURES["vaek_log_likelihood_replicas"]      # one description
     assert _c_args(hdr, "vaek_mlp3_log_likelihood_workspace_bytes") == 5
     assert lib.vaek_mlp3_log_likelihood_max_columns() == 4194304 == 2 ** 22
-    # the description's checks are one text for both calls: linear_loglik.hip's check_log_likelihood, which this entry point goes through
-    csrc = os.path.join(ROOT, "vae_training_amd", "csrc")
-    assert "ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)" in open(os.path.join(csrc, "linear_loglik.hip")).read()
-    assert "check_log_likelihood(who, ctx, params, ll," in open(os.path.join(csrc, "mlp3_loglik.hip")).read()
+    # the description's checks are the linear call's, as behaviour: refused by its size, before the context, with this entry's name
+    check_description_guard(lib, "vaek_mlp3_log_likelihood_replicas")
     assert "mlp3_loglik.hip" in open(os.path.join(ROOT, "vae_training_amd", "csrc", "Makefile")).read()
     # a NULL context is refused before anything is touched, and the message names the entry point
     yes = C.c_int32(7)

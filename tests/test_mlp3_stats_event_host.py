@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests import test_stats_event_host as SE
+from tests.abi_util import _c_args, check_description_guard
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_supports_mlp3_stats_event", "vaek_mlp3_stats_event_workspace_bytes", "vaek_mlp3_stats_event_replicas")
@@ -23,14 +24,13 @@ def test_abi_surface_of_the_mlp3_stats_event():
     lib = _lib.load()
     for name in NEW:
         assert name in _lib.SIGNATURES, name
-        assert SE._c_args(hdr, name) == len(_lib.SIGNATURES[name][1]), name
+        assert _c_args(hdr, name) == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(lib, name), name
-    assert SE._c_args(hdr, "vaek_mlp3_stats_event_replicas") == SE._c_args(hdr, "vaek_stats_event_replicas") + 1 == 13      # + workspace
-    assert SE._c_args(hdr, "vaek_mlp3_stats_event_workspace_bytes") == 4 and SE._c_args(hdr, "vaek_supports_mlp3_stats_event") == 3
+    assert _c_args(hdr, "vaek_mlp3_stats_event_replicas") == _c_args(hdr, "vaek_stats_event_replicas") + 1 == 13      # + workspace
+    assert _c_args(hdr, "vaek_mlp3_stats_event_workspace_bytes") == 4 and _c_args(hdr, "vaek_supports_mlp3_stats_event") == 3
     assert _lib.SIGNATURES["vaek_mlp3_stats_event_replicas"][1][2]._type_ is _lib.VaekStatsEvent
     assert C.sizeof(_lib.VaekStatsEvent) == 88
-    src = open(os.path.join(ROOT, "vae_training_amd", "csrc", "mlp3_stats.hip")).read()
-    assert "ev->struct_size != (int32_t)sizeof(vaek_stats_event)" in src
+    check_description_guard(lib, "vaek_mlp3_stats_event_replicas")      # the guard as behaviour: refused by its size, before the context
     assert "mlp3_stats.hip" in open(os.path.join(ROOT, "vae_training_amd", "csrc", "Makefile")).read()
     yes = C.c_int32(7)
     assert lib.vaek_supports_mlp3_stats_event(None, 2, C.byref(yes)) == -1 and yes.value == 7

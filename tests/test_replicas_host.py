@@ -7,15 +7,10 @@ import types
 import pytest
 import torch
 
+from tests.abi_util import _c_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_train_loop_gen_replicas", "vaek_train_loop_max_replicas", "vaek_train_loop_replicas_workspace_bytes")
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_replica_loop():

@@ -1,19 +1,13 @@
 """Host side of vaek_train_loop_gen, no GPU: the C ABI surface of the two entry points, and which loop trainer.GraphLoop picks."""
 import os
-import re
 import types
 
 import pytest
 import torch
 
+from tests.abi_util import _c_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_resident_loop():

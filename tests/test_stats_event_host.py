@@ -8,16 +8,11 @@ import types
 import pytest
 import torch
 
+from tests.abi_util import _c_args, check_description_guard
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_supports_stats_event", "vaek_stats_record_len", "vaek_stats_event_max_rows", "vaek_stats_event_replicas")
 STATS_KEYS = ["VAE Loss", "KL divergence", "mse", "Squared Norm of Padding Dimensions", "Squared Norm of Manifold Dimension"]
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_stats_event():
@@ -40,7 +35,7 @@ def test_abi_surface_of_the_stats_event():
     assert fields == ["struct_size", "n", "rows", "reserved", "state_stride", "x_seeds", "x_steps", "z_seeds", "z_steps", "sample_eps",
                       "a_stride", "out", "out_stride"]
     assert C.sizeof(_lib.VaekStatsEvent) == 88
-    assert "ev->struct_size != (int32_t)sizeof(vaek_stats_event)" in open(os.path.join(ROOT, "vae_training_amd", "csrc", "linear_stats.hip")).read()
+    check_description_guard(lib, "vaek_stats_event_replicas")          # the guard as behaviour: refused by its size, before the context
     # argument checks that need no device: a NULL context is refused before anything is touched, and the message names the entry point
     n = C.c_int64(7)
     assert lib.vaek_stats_record_len(None, C.byref(n)) == -1 and n.value == 7

@@ -6,7 +6,6 @@ stub engine (both routes, one solve call, one angles call, the run untouched, wh
 import ctypes as C
 import importlib.util
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,6 +13,7 @@ import torch
 
 from tests import cov_spectrum_cases as K
 from tests import subspace_cases as Z
+from tests.abi_util import _c_args
 from tests.test_cov_spectrum_host import _StubEngine, _model
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -78,13 +78,6 @@ def test_the_restatement_angles_agree_with_scipy():
     assert apart["sin2"].tolist() == [1.0, 1.0] and apart["frob2"] == 2.0
     v = ref.fix_signs(np.array([[0.5, -0.5], [-0.5, -0.5]]))
     assert v.tolist() == [[0.5, 0.5], [-0.5, 0.5]]            # a tie goes to the lowest row
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_eigen_and_angle_calls():

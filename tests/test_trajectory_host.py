@@ -9,15 +9,10 @@ import numpy as np
 import pytest
 import torch
 
+from tests.abi_util import _c_args
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("vaek_trajectory_record_len", "vaek_train_loop_gen_traj", "vaek_train_loop_gen_replicas_traj")
-
-
-def _c_args(hdr, name):
-    m = re.search(r"^int\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/vaek.h"
-    args = m.group(1).strip()
-    return 0 if args == "void" else len(args.split(","))
 
 
 def test_abi_surface_of_the_trajectory_ring():

@@ -8,7 +8,7 @@
 #include <new>
 #include <utility>
 
-#include "vaek_internal.h"
+#include "eval_check.h"      // check_struct_size, check_replica_count of the train-loop entry points; vaek_internal.h through it
 
 namespace vaek {
 

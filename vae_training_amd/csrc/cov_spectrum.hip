@@ -22,6 +22,7 @@
 // The kernels read rows / parameters and store only the records, with per-lane vector stores; they read nothing back.
 #include "eigen_dev.h"
 #include "mfma_geom.h"
+#include "eval_check.h"
 
 namespace vaek {
 
@@ -247,6 +248,7 @@ static const SpectrumVariant* pick_spectrum(const vaek_ctx* c) {
 static int64_t spectrum_record_len(const vaek_ctx* c) { return (int64_t)c->D * c->D + 2 * (int64_t)c->D + 4; }
 static int64_t eigen_record_len(const vaek_ctx* c) { return spectrum_record_len(c) + (int64_t)c->D * c->D; }
 static int spectrum_max_sets() { return 2 * resident_max_replicas(); }
+static const char* const kSpectrumRowsQuery = "vaek_stats_event_max_rows; one row has no ddof = 1 covariance";
 // the rows and the pairs calls take any context whose data_dim the Jacobi buffers hold
 static int check_spectrum_dim(const char* who, const vaek_ctx* ctx) {
     if (ctx->D > kSpectrumMaxDim) {
@@ -399,10 +401,7 @@ static int spectrum_rows_call(const char* who, bool vec, vaek_ctx* ctx, const fl
         set_error("%s: %d sets, need 1 .. %d (vaek_cov_spectrum_max_sets)", who, n, spectrum_max_sets());
         return VAEK_ERR_INVALID;
     }
-    if (rows < 2 || rows > kSpectrumMaxRows) {
-        set_error("%s: %d rows, need 2 .. %d (vaek_stats_event_max_rows; one row has no ddof = 1 covariance)", who, rows, kSpectrumMaxRows);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_row_count(who, rows, 2, kSpectrumMaxRows, kSpectrumRowsQuery)) return rc;
     if (int rc = check_x_stride(who, ctx, x_stride, rows)) return rc;
     const int64_t len = vec ? eigen_record_len(ctx) : spectrum_record_len(ctx);
     if (out_stride < len) {
@@ -449,32 +448,17 @@ static int spectrum_event_call(const char* who, bool vec, vaek_ctx* ctx, const f
                                const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
                                void* stream) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !ev) { set_error("%s: null context, params or event", who); return VAEK_ERR_INVALID; }
-    if (int rc = check_struct_size(who, "vaek_spectrum_event", ev->struct_size, sizeof(vaek_spectrum_event))) return rc;
-    const SpectrumVariant* var = pick_spectrum(ctx);
-    if (!var) {
-        set_error("%s: needs a float32 linear VAE (no hidden layers) with D, L <= 32, D <= 28 with two decoders (see "
-                  "vaek_supports_spectrum_event)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_replica_count(who, ev->n)) return rc;
-    if (ev->rows < 2 || ev->rows > kSpectrumMaxRows) {
-        set_error("%s: %d rows, need 2 .. %d (vaek_stats_event_max_rows; one row has no ddof = 1 covariance)", who, ev->rows, kSpectrumMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    if (!ev->x_seeds || !ev->x_steps || !ev->z_seeds || !ev->z_steps || !ev->sample_eps || !ev->out) {
-        set_error("%s: x_seeds, x_steps, z_seeds, z_steps, sample_eps or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t len = vec ? eigen_record_len(ctx) : spectrum_record_len(ctx);
-    if (ev->state_stride < ctx->P || ev->out_stride < 2 * len) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < two records of %lld (%s)", who, (long long)ev->state_stride,
-                  (long long)ctx->P, (long long)ev->out_stride, (long long)len, vec ? "vaek_cov_eigen_record_len" : "vaek_cov_spectrum_record_len");
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_aligned8(who, "out", (uintptr_t)ev->out)) return rc;
-    if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ev->a_stride, x_tag)) return rc;
-    if (int rc = check_tag(who, z_tag)) return rc;
+    const SpectrumVariant* var = ctx ? pick_spectrum(ctx) : nullptr;
+    const EvalDesc d = describe(ev);
+    EvalRules r{};
+    r.covered = var != nullptr;
+    r.needs = "needs a float32 linear VAE (no hidden layers) with D, L <= 32, D <= 28 with two decoders (see vaek_supports_spectrum_event)";
+    r.rows_min = 2; r.rows_cap = kSpectrumMaxRows; r.rows_query = kSpectrumRowsQuery;
+    r.records = 2; r.record_len = !ctx ? 0 : vec ? eigen_record_len(ctx) : spectrum_record_len(ctx);      // the fake record, the real one behind it
+    r.record_query = vec ? "vaek_cov_eigen_record_len" : "vaek_cov_spectrum_record_len";
+    r.draws = true; r.kind = kind; r.A = A; r.dd = dd; r.did = did; r.pad = pad; r.x_tag = x_tag;
+    r.has_z_tag = true; r.z_tag = z_tag;
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
     SpectrumArgs a{};
     a.out = ev->out; a.out_stride = ev->out_stride; a.rows = ev->rows; a.D = ctx->D;
     a.params = params; a.state_stride = ev->state_stride;

@@ -19,6 +19,7 @@
 //
 // The kernels read rows / parameters / directions and store only the named outputs, with per-lane vector stores.
 #include "eigen_dev.h"
+#include "eval_check.h"
 
 namespace vaek {
 
@@ -496,53 +497,29 @@ static bool elbo_hessian_covered(const vaek_ctx* c) {
            c->D <= kSpectrumMaxDim && c->L <= kSpectrumMaxDim;
 }
 
-// the checks the two calls share, in the order of include/vaek.h, on the fields vaek_elbo_hvp and vaek_elbo_hessian both have; fills
-// what the kernels share
-template <class Desc>
-static int hessian_common(const char* who, const char* sname, vaek_ctx* ctx, const float* params, const Desc* d, int32_t kind, const float* A,
-                          int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, HessArgs* a) {
-    if (!ctx || !params || !d) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
-    if (int rc = check_struct_size(who, sname, d->struct_size, sizeof(Desc))) return rc;
-    const int32_t n = d->n, rows = d->rows;
-    const int64_t state_stride = d->state_stride, a_stride = d->a_stride, x_stride = d->x_stride;
-    const uint64_t* const x_seeds = d->x_seeds;
-    const uint32_t* const x_steps = d->x_steps;
-    const float* const x = d->x;
-    const int D = ctx->D, L = ctx->L;
-    const int64_t off_p = (int64_t)(D + 1) * L + (int64_t)L * D + D;
-    if (!elbo_hessian_covered(ctx) || ctx->off_epsp != off_p || (ctx->off_eps >= 0 && ctx->off_eps != off_p + L) ||
-        ctx->P != off_p + L + (ctx->off_eps >= 0 ? 1 : 0)) {
-        set_error("%s: needs a float32 linear VAE (no hidden layers) with ONE decoder and D, L <= 32: the sigmoid second decoder has no "
-                  "closed form (see vaek_supports_elbo_hessian)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_replica_count(who, n)) return rc;
-    if (rows < 1 || rows > kLogLikMaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, rows, kLogLikMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    const bool explicit_rows = x != nullptr;
-    if (!explicit_rows && (!x_seeds || !x_steps)) { set_error("%s: x_seeds or x_steps is NULL (drawing mode)", who); return VAEK_ERR_INVALID; }
-    if (state_stride < ctx->P) {
-        set_error("%s: state_stride %lld < P = %lld", who, (long long)state_stride, (long long)ctx->P);
-        return VAEK_ERR_INVALID;
-    }
-    if (explicit_rows) {
-        if (int rc = check_x_stride(who, ctx, x_stride, rows)) return rc;
-    } else if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, a_stride, x_tag)) {
-        return rc;
-    }
-    a->params = params; a->state_stride = state_stride;
-    a->x_seeds = reinterpret_cast<const unsigned long long*>(x_seeds); a->x_steps = x_steps;
-    a->x = x; a->x_stride = x_stride;
-    a->rows = rows; a->D = D; a->L = L; a->P = (int)ctx->P; a->off_p = (int)ctx->off_epsp; a->off_c = (int)ctx->off_eps;
+// the leaf layout the kernel indexes by: E, b_e, K, b_d, epsilon_p and, under tunable_eps, epsilon
+static bool elbo_hessian_layout(const vaek_ctx* c) {
+    const int64_t off_p = (int64_t)(c->D + 1) * c->L + (int64_t)c->L * c->D + c->D;
+    return c->off_epsp == off_p && (c->off_eps < 0 || c->off_eps == off_p + c->L) && c->P == off_p + c->L + (c->off_eps >= 0 ? 1 : 0);
+}
+
+// the description's checks (`record`: the call's record length and its query) and what the two kernels share of HessArgs
+static int hessian_common(const char* who, const EvalDesc& d, int record, const char* record_query, vaek_ctx* ctx, const float* params,
+                          int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, HessArgs* a) {
+    EvalRules r{};
+    r.covered = ctx && elbo_hessian_covered(ctx) && elbo_hessian_layout(ctx);
+    r.needs = "needs a float32 linear VAE (no hidden layers) with ONE decoder and D, L <= 32: the sigmoid second decoder has no closed form (see "
+              "vaek_supports_elbo_hessian)";
+    r.rows_min = 1; r.rows_cap = kLogLikMaxRows; r.rows_query = "vaek_log_likelihood_max_rows";
+    r.records = 1; r.record_len = record; r.record_query = record_query;
+    r.draws = true; r.kind = kind; r.A = A; r.dd = dd; r.did = did; r.pad = pad; r.x_tag = x_tag;
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
+    a->params = params; a->state_stride = d.state_stride;
+    a->x_seeds = reinterpret_cast<const unsigned long long*>(d.x_seeds); a->x_steps = d.x_steps;
+    a->x = d.rows_ptr; a->x_stride = d.rows_stride;
+    a->rows = d.rows; a->D = ctx->D; a->L = ctx->L; a->P = (int)ctx->P; a->off_p = (int)ctx->off_epsp; a->off_c = (int)ctx->off_eps;
     a->eps_cli = ctx->cfg.eps_cli;
-    if (explicit_rows) {
-        fill_draw_args(&a->gen, ctx, rows, 2, nullptr, 0, 0, 0, 0.f, 0);       // nothing is drawn: the sphere's kind, which has no matrix
-    } else {
-        a->a_stride = a_stride;
-        fill_draw_args(&a->gen, ctx, rows, kind, A, dd, did, pad, var_added, x_tag);
-    }
+    fill_rows_source(&a->gen, &a->a_stride, ctx, d.rows, d.explicit_rows(), kind, A, dd, did, pad, var_added, x_tag, d.a_stride);
     return VAEK_OK;
 }
 
@@ -606,13 +583,13 @@ int vaek_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vaek_elbo_h
     const char* who = "vaek_elbo_hvp_replicas";
     ProfBind pb(ctx);
     HessArgs a{};
-    if (int rc = hessian_common(who, "vaek_elbo_hvp", ctx, params, hp, kind, A, dd, did, pad, var_added, x_tag, &a)) return rc;
+    if (int rc = hessian_common(who, describe(hp), kHvpRecord, "vaek_elbo_hvp_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag, &a))
+        return rc;
     if (hp->nvec < 0 || hp->nvec > kHvpMaxVectors) {
         set_error("%s: %d vectors, need 0 .. %d (vaek_elbo_hvp_max_vectors)", who, hp->nvec, kHvpMaxVectors);
         return VAEK_ERR_INVALID;
     }
     const int64_t P = ctx->P;
-    if (int rc = check_doubles(who, "out", hp->out, hp->out_stride, kHvpRecord, false)) return rc;
     if (hp->nvec > 0) {
         if (int rc = check_doubles(who, "v", hp->v, hp->v_stride, hp->nvec * P, true)) return rc;
         if (int rc = check_doubles(who, "hv", hp->hv, hp->hv_stride, hp->nvec * P, false)) return rc;
@@ -630,13 +607,13 @@ int vaek_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* params, const
     const char* who = "vaek_elbo_hessian_lanczos_replicas";
     ProfBind pb(ctx);
     HessArgs a{};
-    if (int rc = hessian_common(who, "vaek_elbo_hessian", ctx, params, hs, kind, A, dd, did, pad, var_added, x_tag, &a)) return rc;
+    if (int rc = hessian_common(who, describe(hs), kHessRecord, "vaek_elbo_hessian_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag, &a))
+        return rc;
     if (hs->steps < 1 || hs->steps > kHessMaxSteps) {
         set_error("%s: %d steps, need 1 .. %d (vaek_elbo_hessian_max_steps)", who, hs->steps, kHessMaxSteps);
         return VAEK_ERR_INVALID;
     }
     const int64_t P = ctx->P;
-    if (int rc = check_doubles(who, "out", hs->out, hs->out_stride, kHessRecord, false)) return rc;
     if (int rc = check_doubles(who, "v0", hs->v0, hs->v0_stride, P, true)) return rc;
     if (int rc = check_doubles(who, "basis", hs->basis, hs->basis_stride, hs->steps * P, false)) return rc;
     a.out = hs->out; a.out_stride = hs->out_stride;

@@ -1,0 +1,82 @@
+// The host-side checks of the ten vaek_*_replicas evaluation entry points, once (eval_check.hip; no kernels).  An entry point copies
+// its description into an EvalDesc (describe), states what it adds in an EvalRules and calls check_eval; its own refusals (samples,
+// columns, nvec, steps, further buffers, rank_tol) follow in its unit.  check_eval refuses, in this order and with the first that fails:
+//    1. a NULL description                          7. a NULL seeds / steps / sample_eps array the mode needs, a NULL out
+//    2. a struct_size of another header             8. state_stride < P, out_stride below the record(s)
+//    3. a NULL context or params                    9. an out that is not 8-byte aligned, where the records are doubles
+//    4. a context the entry does not cover         10. the rows source: explicit rows' stride, else the dataset draw with x_tag
+//    5. n outside 1 .. the replica cap             11. z_tag
+//    6. rows outside the entry's range             12. a NULL or misaligned workspace
+// Every message starts with the entry point's name and gives the field, its value, the bound and the query function that returns it.
+#pragma once
+#include "vaek_internal.h"
+
+namespace vaek {
+
+constexpr int kLogLikMaxRows = 4096;         // rows per call and ...
+constexpr int kLogLikMaxSamples = 1024;      // ... samples per row: they bound one launch on a shared machine -- caps, not tuned values
+
+// the dataset arguments of an in-kernel draw under tag x_tag, as `who` refuses them: a_stride, kind, A, dd / did / pad, dimension, tag
+int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                       int64_t a_stride, uint32_t x_tag);
+// ... and the BatchArgs of that draw: kind, A, dd, did, pad, noise_std, tag, rows, D, L; seed / step / pointers are the kernel's
+void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                    float var_added, uint32_t x_tag);
+
+// Hidden: the library's dynamic symbol list gains nothing.  (The two above were exported before this block existed, as every vaek::
+// function is -- the library is built without -fvisibility=hidden -- and stay so.)
+#pragma GCC visibility push(hidden)
+
+enum class Need : uint8_t { ABSENT, DRAWING, ALWAYS };      // a field the description lacks / reads in drawing mode only / always reads
+
+// The normalised head of a description.  `given` false: the caller passed NULL; a struct_size that differs from `want` leaves
+// everything behind it unread (another header's struct may end earlier).
+struct EvalDesc {
+    const char* name; bool given; int32_t struct_size; size_t want;
+    int32_t n, rows; int64_t state_stride;
+    const uint64_t* x_seeds; const uint32_t* x_steps; Need x_need;
+    const uint64_t* z_seeds; const uint32_t* z_steps; Need z_need;
+    const float* sample_eps; Need eps_need;
+    int64_t a_stride;
+    const char* rows_name; const float* rows_ptr; int64_t rows_stride; char rows_dim;      // explicit rows: "x" of width 'D', "z" of 'L'; none: NULL
+    const void* out; int64_t out_stride; bool out_doubles;
+    bool explicit_rows() const { return rows_ptr != nullptr; }
+};
+EvalDesc describe(const vaek_stats_event* d);
+EvalDesc describe(const vaek_log_likelihood* d);
+EvalDesc describe(const vaek_spectrum_event* d);
+EvalDesc describe(const vaek_exact_log_likelihood* d);
+EvalDesc describe(const vaek_elbo_hvp* d);
+EvalDesc describe(const vaek_elbo_hessian* d);
+EvalDesc describe(const vaek_decoder_jacobian* d);
+
+// What an entry point adds to the list.  A `_query` is the name of the function a message points to.
+struct EvalRules {
+    bool covered; const char* needs;                                 // the entry's predicate and the sentence for when it fails
+    int rows_min; int rows_cap; const char* rows_query;
+    int records; int64_t record_len; const char* record_query;      // out_stride >= records * record_len
+    bool draws; int32_t kind; const float* A; int32_t dd, did, pad; uint32_t x_tag;      // a dataset draw takes part (drawing mode)
+    bool has_z_tag; uint32_t z_tag;
+    const void* workspace; int ws_align; const char* ws_query;      // ws_align 0: the call has no workspace
+};
+int check_eval(const char* who, const vaek_ctx* ctx, const float* params, const EvalDesc& d, const EvalRules& r);
+
+// the BatchArgs of the rows and the kernel's a_stride: explicit rows draw nothing (the sphere's kind, which has no matrix, and
+// *a_stride_out left alone), else a_stride and the real draw
+void fill_rows_source(BatchArgs* gen, long long* a_stride_out, const vaek_ctx* ctx, int rows, bool explicit_rows, int32_t kind, const float* A,
+                      int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, int64_t a_stride);
+
+// One range check per counted quantity, for a call and for its workspace query alike
+int check_replica_count(const char* who, int32_t n);                                                           // 1 .. resident_max_replicas()
+int check_row_count(const char* who, int32_t rows, int rows_min, int rows_cap, const char* rows_query);
+int check_sample_count(const char* who, int32_t samples);                                                      // 1 .. kLogLikMaxSamples
+// n * rows * per_row columns (`unit`: what per_row counts) against `cap`
+int check_column_count(const char* who, int32_t n, int32_t rows, int32_t per_row, const char* unit, int cap, const char* cap_query);
+
+int check_struct_size(const char* who, const char* name, int32_t got, size_t want);      // a descriptor `name` of another header's size
+int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows); // explicit rows: 0 (shared) or >= rows * D
+int check_tag(const char* who, uint32_t tag);                                             // >= 2^30
+int check_aligned8(const char* who, const char* what, uintptr_t addrs);                   // `addrs`: the outputs `what` names, ORed
+#pragma GCC visibility pop
+
+}  // namespace vaek

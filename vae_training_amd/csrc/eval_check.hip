@@ -1,0 +1,212 @@
+// Host only: the one refusal list of the evaluation entry points (eval_check.h), the adapters of the seven description structs and
+// the small checks they and the train-loop entry points of api.hip share.  No kernels.
+#include "eval_check.h"
+
+namespace vaek {
+
+// ---- one adapter per description: the head every struct has, then what this one has and lacks ---------------------------------------
+// false: NULL, or another header's size -- the fields behind struct_size stay unread
+template <class T>
+static bool desc_head(EvalDesc* e, const char* name, const T* d) {
+    e->name = name; e->given = d != nullptr; e->want = sizeof(T);
+    if (!d) return false;
+    e->struct_size = d->struct_size;
+    if (d->struct_size != (int32_t)sizeof(T)) return false;
+    e->n = d->n; e->rows = d->rows; e->state_stride = d->state_stride;
+    e->out = d->out; e->out_stride = d->out_stride;
+    return true;
+}
+
+// the two event descriptions: both streams and sample_eps always read, no explicit rows (an event always draws)
+template <class T>
+static EvalDesc describe_event(const char* name, const T* d, bool out_doubles) {
+    EvalDesc e{};
+    if (!desc_head(&e, name, d)) return e;
+    e.x_seeds = d->x_seeds; e.x_steps = d->x_steps; e.x_need = Need::ALWAYS;
+    e.z_seeds = d->z_seeds; e.z_steps = d->z_steps; e.z_need = Need::ALWAYS;
+    e.sample_eps = d->sample_eps; e.eps_need = Need::ALWAYS;
+    e.a_stride = d->a_stride; e.out_doubles = out_doubles;
+    return e;
+}
+EvalDesc describe(const vaek_stats_event* d) { return describe_event("vaek_stats_event", d, false); }
+EvalDesc describe(const vaek_spectrum_event* d) { return describe_event("vaek_spectrum_event", d, true); }
+
+EvalDesc describe(const vaek_log_likelihood* d) {
+    EvalDesc e{};
+    if (!desc_head(&e, "vaek_log_likelihood", d)) return e;
+    e.x_seeds = d->x_seeds; e.x_steps = d->x_steps; e.x_need = Need::DRAWING;
+    e.z_seeds = d->z_seeds; e.z_steps = d->z_steps; e.z_need = Need::ALWAYS;      // no sample_eps
+    e.a_stride = d->a_stride;
+    e.rows_name = "x"; e.rows_ptr = d->x; e.rows_stride = d->x_stride; e.rows_dim = 'D';
+    return e;
+}
+
+// the three descriptions of the exact calls: x rows, no z_seeds / z_steps, no sample_eps, records of doubles
+template <class T>
+static EvalDesc describe_exact(const char* name, const T* d) {
+    EvalDesc e{};
+    if (!desc_head(&e, name, d)) return e;
+    e.x_seeds = d->x_seeds; e.x_steps = d->x_steps; e.x_need = Need::DRAWING;
+    e.a_stride = d->a_stride; e.out_doubles = true;
+    e.rows_name = "x"; e.rows_ptr = d->x; e.rows_stride = d->x_stride; e.rows_dim = 'D';
+    return e;
+}
+EvalDesc describe(const vaek_exact_log_likelihood* d) { return describe_exact("vaek_exact_log_likelihood", d); }
+EvalDesc describe(const vaek_elbo_hvp* d) { return describe_exact("vaek_elbo_hvp", d); }
+EvalDesc describe(const vaek_elbo_hessian* d) { return describe_exact("vaek_elbo_hessian", d); }
+
+EvalDesc describe(const vaek_decoder_jacobian* d) {
+    EvalDesc e{};
+    if (!desc_head(&e, "vaek_decoder_jacobian", d)) return e;
+    e.z_seeds = d->z_seeds; e.z_steps = d->z_steps; e.z_need = Need::DRAWING;      // no x_seeds / x_steps, sample_eps or a_stride: latent rows
+    e.out_doubles = true;
+    e.rows_name = "z"; e.rows_ptr = d->z; e.rows_stride = d->z_stride; e.rows_dim = 'L';
+    return e;
+}
+
+// ---- the list ------------------------------------------------------------------------------------------------------------------------
+static int check_present(const char* who, const void* p, const char* field, Need need, bool explicit_rows) {
+    if (p || need == Need::ABSENT || (need == Need::DRAWING && explicit_rows)) return VAEK_OK;
+    set_error("%s: %s is NULL%s", who, field, need == Need::DRAWING ? " (drawing mode reads it)" : "");
+    return VAEK_ERR_INVALID;
+}
+
+// explicit rows of `width` floats each: stride 0 (one set shared) or at least a replica's rows
+static int check_rows_stride(const char* who, const char* name, char dim, int64_t stride, int32_t rows, int width) {
+    if (stride < 0 || (stride > 0 && stride < (int64_t)rows * width)) {
+        set_error("%s: %s_stride %lld: need 0 (shared rows) or >= rows * %c = %lld", who, name, (long long)stride, dim, (long long)rows * width);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_eval(const char* who, const vaek_ctx* ctx, const float* params, const EvalDesc& d, const EvalRules& r) {
+    if (!d.given) { set_error("%s: null description", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_struct_size(who, d.name, d.struct_size, d.want)) return rc;
+    if (!ctx || !params) { set_error("%s: null context or params", who); return VAEK_ERR_INVALID; }
+    if (!r.covered) { set_error("%s: %s", who, r.needs); return VAEK_ERR_INVALID; }
+    if (int rc = check_replica_count(who, d.n)) return rc;
+    if (int rc = check_row_count(who, d.rows, r.rows_min, r.rows_cap, r.rows_query)) return rc;
+    const bool ex = d.explicit_rows();
+    if (int rc = check_present(who, d.x_seeds, "x_seeds", d.x_need, ex)) return rc;
+    if (int rc = check_present(who, d.x_steps, "x_steps", d.x_need, ex)) return rc;
+    if (int rc = check_present(who, d.z_seeds, "z_seeds", d.z_need, ex)) return rc;
+    if (int rc = check_present(who, d.z_steps, "z_steps", d.z_need, ex)) return rc;
+    if (int rc = check_present(who, d.sample_eps, "sample_eps", d.eps_need, ex)) return rc;
+    if (int rc = check_present(who, d.out, "out", Need::ALWAYS, ex)) return rc;
+    if (d.state_stride < ctx->P) {
+        set_error("%s: state_stride %lld < P = %lld (vaek_param_count)", who, (long long)d.state_stride, (long long)ctx->P);
+        return VAEK_ERR_INVALID;
+    }
+    if (d.out_stride < r.records * r.record_len) {
+        set_error("%s: out_stride %lld < %d x record length %lld (%s)", who, (long long)d.out_stride, r.records, (long long)r.record_len, r.record_query);
+        return VAEK_ERR_INVALID;
+    }
+    if (d.out_doubles)
+        if (int rc = check_aligned8(who, "out", (uintptr_t)d.out)) return rc;
+    if (ex) {
+        if (int rc = check_rows_stride(who, d.rows_name, d.rows_dim, d.rows_stride, d.rows, d.rows_dim == 'D' ? ctx->D : ctx->L)) return rc;
+    } else if (r.draws) {
+        if (int rc = check_dataset_draw(who, ctx, r.kind, r.A, r.dd, r.did, r.pad, d.a_stride, r.x_tag)) return rc;
+    }
+    if (r.has_z_tag)
+        if (int rc = check_tag(who, r.z_tag)) return rc;
+    if (r.ws_align && (!r.workspace || ((uintptr_t)r.workspace & (uintptr_t)(r.ws_align - 1)) != 0)) {
+        set_error("%s: workspace is NULL or not %d-byte aligned (%s)", who, r.ws_align, r.ws_query);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+void fill_rows_source(BatchArgs* gen, long long* a_stride_out, const vaek_ctx* ctx, int rows, bool explicit_rows, int32_t kind, const float* A,
+                      int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, int64_t a_stride) {
+    if (explicit_rows) {
+        fill_draw_args(gen, ctx, rows, 2, nullptr, 0, 0, 0, 0.f, 0);
+    } else {
+        *a_stride_out = a_stride;
+        fill_draw_args(gen, ctx, rows, kind, A, dd, did, pad, var_added, x_tag);
+    }
+}
+
+// ---- the counted quantities ------------------------------------------------------------------------------------------------------------
+int check_replica_count(const char* who, int32_t n) {
+    if (n < 1 || n > resident_max_replicas()) {
+        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, n, resident_max_replicas());
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_row_count(const char* who, int32_t rows, int rows_min, int rows_cap, const char* rows_query) {
+    if (rows < rows_min || rows > rows_cap) {
+        set_error("%s: %d rows, need %d .. %d (%s)", who, rows, rows_min, rows_cap, rows_query);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_sample_count(const char* who, int32_t samples) {
+    if (samples < 1 || samples > kLogLikMaxSamples) {
+        set_error("%s: %d samples, need 1 .. %d (vaek_log_likelihood_max_samples)", who, samples, kLogLikMaxSamples);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_column_count(const char* who, int32_t n, int32_t rows, int32_t per_row, const char* unit, int cap, const char* cap_query) {
+    const long long columns = (long long)n * rows * per_row;
+    if (columns > cap) {
+        set_error("%s: %d replicas x %d rows x %d %s = %lld columns, at most %d (%s)", who, n, rows, per_row, unit, columns, cap, cap_query);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+// ---- the in-kernel dataset draw --------------------------------------------------------------------------------------------------------
+int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                       int64_t a_stride, uint32_t x_tag) {
+    if (a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)a_stride); return VAEK_ERR_INVALID; }
+    if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
+    if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
+    if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
+        set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
+        return VAEK_ERR_INVALID;
+    }
+    if (dd + pad + (kind == 1 ? 1 : 0) != ctx->D) {
+        set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
+        return VAEK_ERR_INVALID;
+    }
+    return check_tag(who, x_tag);
+}
+
+void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                    float var_added, uint32_t x_tag) {
+    g->kind = kind; g->A = kind == 2 ? nullptr : A; g->dd = dd; g->did = did; g->pad = pad;
+    g->noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
+    g->rows = rows; g->row0 = 0; g->D = ctx->D; g->L = ctx->L; g->tag = x_tag;
+}
+
+// ---- the small checks, also the train-loop entry points' -------------------------------------------------------------------------------
+int check_struct_size(const char* who, const char* name, int32_t got, size_t want) {
+    if (got != (int32_t)want) {
+        set_error("%s: %s.struct_size %d != %d (header / library mismatch)", who, name, got, (int)want);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows) {
+    return check_rows_stride(who, "x", 'D', x_stride, rows, ctx->D);
+}
+
+int check_tag(const char* who, uint32_t tag) {
+    if (tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
+    return VAEK_OK;
+}
+
+int check_aligned8(const char* who, const char* what, uintptr_t addrs) {
+    if ((addrs & 7u) != 0) { set_error("%s: %s is not 8-byte aligned", who, what); return VAEK_ERR_INVALID; }
+    return VAEK_OK;
+}
+
+}  // namespace vaek

@@ -258,39 +258,20 @@ int vaek_exact_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const
                                        void* stream) {
     const char* who = "vaek_exact_log_likelihood_replicas";
     ProfBind pb(ctx);
-    if (!ctx || !params || !ll) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
-    if (int rc = check_struct_size(who, "vaek_exact_log_likelihood", ll->struct_size, sizeof(vaek_exact_log_likelihood))) return rc;
-    const ExactLogLikVariant* var = pick_exact_loglik(ctx);
-    if (!var) {
-        set_error("%s: needs a float32 linear VAE (no hidden layers) with ONE decoder and D, L <= 32: the sigmoid second decoder has no "
-                  "closed form (see vaek_supports_exact_log_likelihood)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_replica_count(who, ll->n)) return rc;
-    if (ll->rows < 1 || ll->rows > kLogLikMaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kLogLikMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    const bool explicit_rows = ll->x != nullptr;
-    if (!ll->out || (!explicit_rows && (!ll->x_seeds || !ll->x_steps))) {
-        set_error("%s: x_seeds, x_steps (drawing mode) or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t len = exact_loglik_record_len(ctx);
-    if (ll->state_stride < ctx->P || ll->out_stride < len) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %lld (vaek_exact_log_likelihood_record_len)", who,
-                  (long long)ll->state_stride, (long long)ctx->P, (long long)ll->out_stride, (long long)len);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_aligned8(who, "out or row_out", (uintptr_t)ll->out | (uintptr_t)ll->row_out)) return rc;
+    const ExactLogLikVariant* var = ctx ? pick_exact_loglik(ctx) : nullptr;
+    const EvalDesc d = describe(ll);
+    EvalRules r{};
+    r.covered = var != nullptr;
+    r.needs = "needs a float32 linear VAE (no hidden layers) with ONE decoder and D, L <= 32: the sigmoid second decoder has no closed form (see "
+              "vaek_supports_exact_log_likelihood)";
+    r.rows_min = 1; r.rows_cap = kLogLikMaxRows; r.rows_query = "vaek_log_likelihood_max_rows";
+    r.records = 1; r.record_len = ctx ? exact_loglik_record_len(ctx) : 0; r.record_query = "vaek_exact_log_likelihood_record_len";
+    r.draws = true; r.kind = kind; r.A = A; r.dd = dd; r.did = did; r.pad = pad; r.x_tag = x_tag;
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
+    if (int rc = check_aligned8(who, "row_out", (uintptr_t)ll->row_out)) return rc;
     if (ll->row_out && (ll->row_stride < 0 || (ll->row_stride < 2 * (int64_t)ll->rows && (ll->row_stride > 0 || ll->n > 1)))) {
         set_error("%s: row_stride %lld: need >= 2 * rows = %lld (0 with one replica)", who, (long long)ll->row_stride, 2 * (long long)ll->rows);
         return VAEK_ERR_INVALID;
-    }
-    if (explicit_rows) {
-        if (int rc = check_x_stride(who, ctx, ll->x_stride, ll->rows)) return rc;
-    } else if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ll->a_stride, x_tag)) {
-        return rc;
     }
     ExactLogLikArgs a{};
     a.params = params; a.state_stride = ll->state_stride;
@@ -299,12 +280,7 @@ int vaek_exact_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const
     a.out = ll->out; a.out_stride = ll->out_stride; a.row_out = ll->row_out; a.row_stride = ll->row_stride;
     a.rows = ll->rows; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
     a.eps_cli = ctx->cfg.eps_cli;
-    if (explicit_rows) {
-        fill_draw_args(&a.gen, ctx, ll->rows, 2, nullptr, 0, 0, 0, 0.f, 0);      // nothing is drawn: the sphere's kind, which has no matrix
-    } else {
-        a.a_stride = ll->a_stride;
-        fill_draw_args(&a.gen, ctx, ll->rows, kind, A, dd, did, pad, var_added, x_tag);
-    }
+    fill_rows_source(&a.gen, &a.a_stride, ctx, ll->rows, d.explicit_rows(), kind, A, dd, did, pad, var_added, x_tag, ll->a_stride);
     hipStream_t st = (hipStream_t)stream;
     {
         ProfScope ps("exact_loglik_replicas", st);

@@ -23,6 +23,7 @@
 //     counter or wait.  A record therefore depends on neither n, nor the replica index, nor the run.
 #include "eval_dev.h"
 #include "mfma_geom.h"
+#include "eval_check.h"
 
 namespace vaek {
 
@@ -203,43 +204,6 @@ static const LogLikVariant* pick_loglik(const vaek_ctx* c) {
 
 static size_t loglik_workspace_bytes(int n, int rows) { return sizeof(double) * 4 * (size_t)n * (size_t)((rows + 255) / 256); }
 
-int check_log_likelihood(const char* who, const vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, bool covered,
-                         const char* needs, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, uint32_t x_tag, uint32_t z_tag,
-                         const void* workspace, int ws_align, const char* ws_bytes_fn) {
-    if (!ctx || !params || !ll) { set_error("%s: null context, params or description", who); return VAEK_ERR_INVALID; }
-    if (ll->struct_size != (int32_t)sizeof(vaek_log_likelihood)) {
-        set_error("%s: vaek_log_likelihood.struct_size %d != %d (header / library mismatch)", who, ll->struct_size, (int)sizeof(vaek_log_likelihood));
-        return VAEK_ERR_INVALID;
-    }
-    if (!covered) { set_error("%s: %s", who, needs); return VAEK_ERR_INVALID; }
-    if (int rc = check_replica_count(who, ll->n)) return rc;
-    if (ll->rows < 1 || ll->rows > kLogLikMaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_log_likelihood_max_rows)", who, ll->rows, kLogLikMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->samples < 1 || ll->samples > kLogLikMaxSamples) {
-        set_error("%s: %d samples, need 1 .. %d (vaek_log_likelihood_max_samples)", who, ll->samples, kLogLikMaxSamples);
-        return VAEK_ERR_INVALID;
-    }
-    const bool explicit_rows = ll->x != nullptr;
-    if (!ll->z_seeds || !ll->z_steps || !ll->out || (!explicit_rows && (!ll->x_seeds || !ll->x_steps))) {
-        set_error("%s: x_seeds, x_steps (drawing mode), z_seeds, z_steps or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (ll->state_stride < ctx->P || ll->out_stride < kLogLikRecord) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %d (vaek_log_likelihood_record_len)", who,
-                  (long long)ll->state_stride, (long long)ctx->P, (long long)ll->out_stride, kLogLikRecord);
-        return VAEK_ERR_INVALID;
-    }
-    if (!workspace || ((uintptr_t)workspace & (uintptr_t)(ws_align - 1)) != 0) {
-        set_error("%s: workspace is NULL or not %d-byte aligned (%s)", who, ws_align, ws_bytes_fn);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_tag(who, z_tag)) return rc;
-    if (!explicit_rows) return check_dataset_draw(who, ctx, kind, A, dd, did, pad, ll->a_stride, x_tag);
-    return check_x_stride(who, ctx, ll->x_stride, ll->rows);
-}
-
 int loglik_finalize(const char* label, const vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, const double* part, hipStream_t st) {
     LogLikFinalArgs f{};
     f.params = params; f.state_stride = ll->state_stride; f.part = part; f.out = ll->out; f.out_stride = ll->out_stride;
@@ -271,10 +235,8 @@ int vaek_log_likelihood_max_samples(void) { return kLogLikMaxSamples; }
 int vaek_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes) {
     const char* who = "vaek_log_likelihood_workspace_bytes";
     if (!ctx || !bytes) { set_error("%s: null argument", who); return VAEK_ERR_INVALID; }
-    if (n < 1 || n > resident_max_replicas() || rows < 1 || rows > kLogLikMaxRows) {
-        set_error("%s: %d replicas of %d rows, need 1 .. %d replicas and 1 .. %d rows", who, n, rows, resident_max_replicas(), kLogLikMaxRows);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_replica_count(who, n)) return rc;
+    if (int rc = check_row_count(who, rows, 1, kLogLikMaxRows, "vaek_log_likelihood_max_rows")) return rc;
     *bytes = loglik_workspace_bytes(n, rows);
     return VAEK_OK;
 }
@@ -284,12 +246,17 @@ int vaek_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_
     const char* who = "vaek_log_likelihood_replicas";
     ProfBind pb(ctx);
     const LogLikVariant* var = ctx ? pick_loglik(ctx) : nullptr;
-    if (int rc = check_log_likelihood(who, ctx, params, ll, var != nullptr,
-                                      "needs a float32 linear VAE (no hidden layers) with D, L <= 32, D <= 28 with two decoders (see "
-                                      "vaek_supports_log_likelihood)",
-                                      kind, A, dd, did, pad, x_tag, z_tag, workspace, 8, "vaek_log_likelihood_workspace_bytes"))
-        return rc;
-    const bool explicit_rows = ll->x != nullptr;
+    const EvalDesc d = describe(ll);
+    EvalRules r{};
+    r.covered = var != nullptr;
+    r.needs = "needs a float32 linear VAE (no hidden layers) with D, L <= 32, D <= 28 with two decoders (see vaek_supports_log_likelihood)";
+    r.rows_min = 1; r.rows_cap = kLogLikMaxRows; r.rows_query = "vaek_log_likelihood_max_rows";
+    r.records = 1; r.record_len = kLogLikRecord; r.record_query = "vaek_log_likelihood_record_len";
+    r.draws = true; r.kind = kind; r.A = A; r.dd = dd; r.did = did; r.pad = pad; r.x_tag = x_tag;
+    r.has_z_tag = true; r.z_tag = z_tag;
+    r.workspace = workspace; r.ws_align = 8; r.ws_query = "vaek_log_likelihood_workspace_bytes";
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
+    if (int rc = check_sample_count(who, ll->samples)) return rc;
     const int tiles = (ll->rows + 255) / 256;
     LogLikArgs a{};
     a.params = params; a.state_stride = ll->state_stride;
@@ -299,12 +266,7 @@ int vaek_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const vaek_
     a.part = static_cast<double*>(workspace);
     a.rows = ll->rows; a.samples = ll->samples; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
     a.eps_cli = ctx->cfg.eps_cli; a.z_tag = z_tag;
-    if (explicit_rows) {
-        fill_draw_args(&a.gen, ctx, ll->rows, 2, nullptr, 0, 0, 0, 0.f, 0);      // nothing is drawn: the sphere's kind, which has no matrix
-    } else {
-        a.a_stride = ll->a_stride;
-        fill_draw_args(&a.gen, ctx, ll->rows, kind, A, dd, did, pad, var_added, x_tag);
-    }
+    fill_rows_source(&a.gen, &a.a_stride, ctx, ll->rows, d.explicit_rows(), kind, A, dd, did, pad, var_added, x_tag, ll->a_stride);
     hipStream_t st = (hipStream_t)stream;
     {
         ProfScope ps("linear_loglik_replicas", st);

@@ -24,6 +24,7 @@
 // back.
 #include "eval_dev.h"
 #include "mfma_geom.h"
+#include "eval_check.h"
 
 namespace vaek {
 
@@ -276,30 +277,15 @@ int vaek_stats_event_replicas(vaek_ctx* ctx, const float* params, const vaek_sta
                               int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* stream) {
     const char* who = "vaek_stats_event_replicas";
     ProfBind pb(ctx);
-    if (!ctx || !params || !ev) { set_error("%s: null context, params or event", who); return VAEK_ERR_INVALID; }
-    if (ev->struct_size != (int32_t)sizeof(vaek_stats_event)) {
-        set_error("%s: vaek_stats_event.struct_size %d != %d (header / library mismatch)", who, ev->struct_size, (int)sizeof(vaek_stats_event));
-        return VAEK_ERR_INVALID;
-    }
-    const StatsVariant* var = ctx->resident ? pick_stats(ctx) : nullptr;
-    if (!var) { set_error("%s: needs a context vaek_train_loop_gen covers (see vaek_supports_stats_event)", who); return VAEK_ERR_INVALID; }
-    if (int rc = check_replica_count(who, ev->n)) return rc;
-    if (ev->rows < 1 || ev->rows > kStatsMaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_stats_event_max_rows)", who, ev->rows, kStatsMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    if (!ev->x_seeds || !ev->x_steps || !ev->z_seeds || !ev->z_steps || !ev->sample_eps || !ev->out) {
-        set_error("%s: x_seeds, x_steps, z_seeds, z_steps, sample_eps or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t len = kStatsHead + (int64_t)ctx->L;
-    if (ev->state_stride < ctx->P || ev->out_stride < len) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %lld (vaek_stats_record_len)", who,
-                  (long long)ev->state_stride, (long long)ctx->P, (long long)ev->out_stride, (long long)len);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ev->a_stride, x_tag)) return rc;
-    if (int rc = check_tag(who, z_tag)) return rc;
+    const StatsVariant* var = ctx && ctx->resident ? pick_stats(ctx) : nullptr;
+    const EvalDesc d = describe(ev);
+    EvalRules r{};
+    r.covered = var != nullptr; r.needs = "needs a context vaek_train_loop_gen covers (see vaek_supports_stats_event)";
+    r.rows_min = 1; r.rows_cap = kStatsMaxRows; r.rows_query = "vaek_stats_event_max_rows";
+    r.records = 1; r.record_len = ctx ? kStatsHead + (int64_t)ctx->L : 0; r.record_query = "vaek_stats_record_len";
+    r.draws = true; r.kind = kind; r.A = A; r.dd = dd; r.did = did; r.pad = pad; r.x_tag = x_tag;
+    r.has_z_tag = true; r.z_tag = z_tag;
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
     StatsArgs a{};
     a.params = params; a.state_stride = ev->state_stride;
     a.x_seeds = reinterpret_cast<const unsigned long long*>(ev->x_seeds); a.x_steps = ev->x_steps;

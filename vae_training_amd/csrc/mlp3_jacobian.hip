@@ -29,6 +29,7 @@
 //      stores double t of the model record (2 L + 8 doubles).
 #include "mlp3_dev.h"
 #include "eigen_dev.h"
+#include "eval_check.h"
 
 namespace vaek {
 
@@ -307,28 +308,13 @@ static MjWs mj_workspace(const vaek_ctx* c, int n, int rows) {
     w.total = w.rec + mj_up16(sizeof(double) * (size_t)n * rows * (size_t)mj_row_record_len(c));
     return w;
 }
-// n, rows and the column product as `who` refuses them
-static int mj_check_size(const char* who, const vaek_ctx* c, int32_t n, int32_t rows) {
-    if (int rc = check_replica_count(who, n)) return rc;
-    if (rows < 1 || rows > kSpectrumMaxRows) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_stats_event_max_rows)", who, rows, kSpectrumMaxRows);
-        return VAEK_ERR_INVALID;
-    }
-    if ((long long)n * rows * c->L > kMjMaxColumns) {
-        set_error("%s: %d replicas x %d rows x %d latents = %lld columns, at most %d (vaek_mlp3_decoder_jacobian_max_columns)", who, n, rows,
-                  c->L, (long long)n * rows * c->L, kMjMaxColumns);
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
+// the column product as `who` refuses it: the call's and its workspace query's
+static int mj_check_columns(const char* who, const vaek_ctx* c, int32_t n, int32_t rows) {
+    return check_column_count(who, n, rows, c->L, "latents", kMjMaxColumns, "vaek_mlp3_decoder_jacobian_max_columns");
 }
-static int mj_check_ctx(const char* who, const vaek_ctx* c) {
-    if (!c->mlp3_loglik) {
-        set_error("%s: needs a float32 VAE with one decoder and three hidden layers of 64 .. %d units both ways, D, L <= %d (see "
-                  "vaek_supports_mlp3_decoder_jacobian)", who, ML_W, ML_F);
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
-}
+static_assert(ML_W == 256 && ML_F == 32, "kMjNeeds states the bounds of mlp3_dev.h");
+static const char kMjNeeds[] = "needs a float32 VAE with one decoder and three hidden layers of 64 .. 256 units both ways, D, L <= 32 (see "
+                               "vaek_supports_mlp3_decoder_jacobian)";
 
 }  // namespace vaek
 
@@ -359,8 +345,10 @@ int vaek_mlp3_decoder_jacobian_max_columns(void) { return kMjMaxColumns; }
 int vaek_mlp3_decoder_jacobian_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes) {
     const char* who = "vaek_mlp3_decoder_jacobian_workspace_bytes";
     if (!ctx || !bytes) { set_error("%s: null argument", who); return VAEK_ERR_INVALID; }
-    if (int rc = mj_check_ctx(who, ctx)) return rc;
-    if (int rc = mj_check_size(who, ctx, n, rows)) return rc;
+    if (!ctx->mlp3_loglik) { set_error("%s: %s", who, kMjNeeds); return VAEK_ERR_INVALID; }
+    if (int rc = check_replica_count(who, n)) return rc;
+    if (int rc = check_row_count(who, rows, 1, kSpectrumMaxRows, "vaek_stats_event_max_rows")) return rc;
+    if (int rc = mj_check_columns(who, ctx, n, rows)) return rc;
     *bytes = mj_workspace(ctx, n, rows).total;
     return VAEK_OK;
 }
@@ -369,39 +357,24 @@ int vaek_mlp3_decoder_jacobian_replicas(vaek_ctx* ctx, const float* params, cons
                                         void* stream) {
     const char* who = "vaek_mlp3_decoder_jacobian_replicas";
     ProfBind pb(ctx);
-    if (!dj) { set_error("%s: null description", who); return VAEK_ERR_INVALID; }
-    if (int rc = check_struct_size(who, "vaek_decoder_jacobian", dj->struct_size, sizeof(vaek_decoder_jacobian))) return rc;
-    if (!ctx || !params) { set_error("%s: null context or params", who); return VAEK_ERR_INVALID; }
-    if (int rc = mj_check_ctx(who, ctx)) return rc;
-    if (int rc = mj_check_size(who, ctx, dj->n, dj->rows)) return rc;
-    const bool explicit_rows = dj->z != nullptr;
-    if (!dj->out || (!explicit_rows && (!dj->z_seeds || !dj->z_steps))) {
-        set_error("%s: z_seeds, z_steps (drawing mode) or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t len = mj_record_len(ctx), rlen = mj_row_record_len(ctx);
-    if (dj->state_stride < ctx->P || dj->out_stride < len) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %lld (vaek_decoder_jacobian_record_len)", who,
-                  (long long)dj->state_stride, (long long)ctx->P, (long long)dj->out_stride, (long long)len);
-        return VAEK_ERR_INVALID;
-    }
+    const EvalDesc d = describe(dj);
+    EvalRules r{};
+    r.covered = ctx && ctx->mlp3_loglik; r.needs = kMjNeeds;
+    r.rows_min = 1; r.rows_cap = kSpectrumMaxRows; r.rows_query = "vaek_stats_event_max_rows";
+    r.records = 1; r.record_len = ctx ? mj_record_len(ctx) : 0; r.record_query = "vaek_decoder_jacobian_record_len";
+    r.has_z_tag = true; r.z_tag = z_tag;                             // no dataset draw: the rows are latents
+    r.workspace = workspace; r.ws_align = 16; r.ws_query = "vaek_mlp3_decoder_jacobian_workspace_bytes";
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
+    if (int rc = mj_check_columns(who, ctx, dj->n, dj->rows)) return rc;
+    const int64_t rlen = mj_row_record_len(ctx);
     if (dj->row_out && dj->row_out_stride < (int64_t)dj->rows * rlen) {
         set_error("%s: row_out_stride %lld < rows x row record length = %lld (vaek_decoder_jacobian_row_record_len)", who,
                   (long long)dj->row_out_stride, (long long)dj->rows * rlen);
         return VAEK_ERR_INVALID;
     }
-    if (explicit_rows && (dj->z_stride < 0 || (dj->z_stride > 0 && dj->z_stride < (int64_t)dj->rows * ctx->L))) {
-        set_error("%s: z_stride %lld: need 0 (shared latents) or >= rows * L = %lld", who, (long long)dj->z_stride, (long long)dj->rows * ctx->L);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_aligned8(who, "row_out", (uintptr_t)dj->row_out)) return rc;
     if (!(dj->rank_tol >= 0.0 && dj->rank_tol < 1.0)) {
         set_error("%s: rank_tol %g, need 0 <= rank_tol < 1", who, dj->rank_tol);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_tag(who, z_tag)) return rc;
-    if (int rc = check_aligned8(who, "out or row_out", (uintptr_t)dj->out | (uintptr_t)dj->row_out)) return rc;
-    if (!workspace || ((uintptr_t)workspace & 15u) != 0) {
-        set_error("%s: workspace is NULL or not 16-byte aligned (vaek_mlp3_decoder_jacobian_workspace_bytes)", who);
         return VAEK_ERR_INVALID;
     }
     const int n = dj->n, rows = dj->rows, L = ctx->L, D = ctx->D;

@@ -27,6 +27,7 @@
 //      loglik_finalize: one kernel for both calls).
 // mlp3_dev.h describes the LDS images and the weight reads (no stride rule).
 #include "mlp3_dev.h"
+#include "eval_check.h"
 
 namespace vaek {
 
@@ -239,12 +240,10 @@ int vaek_mlp3_log_likelihood_max_columns(void) { return kMl3MaxColumns; }
 int vaek_mlp3_log_likelihood_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, int32_t samples, size_t* bytes) {
     const char* who = "vaek_mlp3_log_likelihood_workspace_bytes";
     if (!ctx || !bytes) { set_error("%s: null argument", who); return VAEK_ERR_INVALID; }
-    if (n < 1 || n > resident_max_replicas() || rows < 1 || rows > kLogLikMaxRows || samples < 1 || samples > kLogLikMaxSamples ||
-        (long long)n * rows * samples > kMl3MaxColumns) {
-        set_error("%s: %d replicas of %d rows x %d samples, need 1 .. %d replicas, 1 .. %d rows, 1 .. %d samples and at most %d columns in all", who,
-                  n, rows, samples, resident_max_replicas(), kLogLikMaxRows, kLogLikMaxSamples, kMl3MaxColumns);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_replica_count(who, n)) return rc;
+    if (int rc = check_row_count(who, rows, 1, kLogLikMaxRows, "vaek_log_likelihood_max_rows")) return rc;
+    if (int rc = check_sample_count(who, samples)) return rc;
+    if (int rc = check_column_count(who, n, rows, samples, "samples", kMl3MaxColumns, "vaek_mlp3_log_likelihood_max_columns")) return rc;
     *bytes = ml3_workspace(ctx, n, rows, samples).total;
     return VAEK_OK;
 }
@@ -256,15 +255,18 @@ int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const 
     char needs[256];
     snprintf(needs, sizeof(needs), "needs a float32 VAE with one decoder and three hidden layers of 64 .. %d units both ways, D, L <= %d (see "
              "vaek_supports_mlp3_log_likelihood)", ML_W, ML_F);
-    if (int rc = check_log_likelihood(who, ctx, params, ll, ctx && ctx->mlp3_loglik, needs, kind, A, dd, did, pad, x_tag, z_tag, workspace, 16,
-                                      "vaek_mlp3_log_likelihood_workspace_bytes"))
-        return rc;
-    if ((long long)ll->n * ll->rows * ll->samples > kMl3MaxColumns) {
-        set_error("%s: %d replicas x %d rows x %d samples = %lld columns, at most %d (vaek_mlp3_log_likelihood_max_columns)", who, ll->n, ll->rows,
-                  ll->samples, (long long)ll->n * ll->rows * ll->samples, kMl3MaxColumns);
-        return VAEK_ERR_INVALID;
-    }
-    const bool explicit_rows = ll->x != nullptr;
+    const EvalDesc d = describe(ll);
+    EvalRules r{};
+    r.covered = ctx && ctx->mlp3_loglik; r.needs = needs;
+    r.rows_min = 1; r.rows_cap = kLogLikMaxRows; r.rows_query = "vaek_log_likelihood_max_rows";
+    r.records = 1; r.record_len = kLogLikRecord; r.record_query = "vaek_log_likelihood_record_len";
+    r.draws = true; r.kind = kind; r.A = A; r.dd = dd; r.did = did; r.pad = pad; r.x_tag = x_tag;
+    r.has_z_tag = true; r.z_tag = z_tag;
+    r.workspace = workspace; r.ws_align = 16; r.ws_query = "vaek_mlp3_log_likelihood_workspace_bytes";
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
+    if (int rc = check_sample_count(who, ll->samples)) return rc;
+    if (int rc = check_column_count(who, ll->n, ll->rows, ll->samples, "samples", kMl3MaxColumns, "vaek_mlp3_log_likelihood_max_columns")) return rc;
+    const bool explicit_rows = d.explicit_rows();
     const int n = ll->n, rows = ll->rows, K = ll->samples, tiles = ml3_tiles(rows);
     const Ml3Ws w = ml3_workspace(ctx, n, rows, K);
     char* const ws = static_cast<char*>(workspace);
@@ -278,12 +280,7 @@ int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const 
     a.lw = reinterpret_cast<float*>(ws + w.lw);
     a.rows = rows; a.samples = K; a.D = ctx->D; a.L = ctx->L; a.off_epsp = (int)ctx->off_epsp; a.off_eps = (int)ctx->off_eps;
     a.eps_cli = ctx->cfg.eps_cli; a.z_tag = z_tag;
-    if (explicit_rows) {
-        fill_draw_args(&a.gen, ctx, rows, 2, nullptr, 0, 0, 0, 0.f, 0);          // nothing is drawn: the sphere's kind, which has no matrix
-    } else {
-        a.a_stride = ll->a_stride;
-        fill_draw_args(&a.gen, ctx, rows, kind, A, dd, did, pad, var_added, x_tag);
-    }
+    fill_rows_source(&a.gen, &a.a_stride, ctx, rows, explicit_rows, kind, A, dd, did, pad, var_added, x_tag, ll->a_stride);
     ml3_net(ctx->enc, &a.net);
     Ml3Args s = a;                               // the sample launch reads the rows the encode launch read or drew
     if (!explicit_rows) { s.x = a.x_out; s.x_stride = (long long)rows * ctx->D; }

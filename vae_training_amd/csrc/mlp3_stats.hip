@@ -21,6 +21,7 @@
 // latents live in LDS because z1 / z2 start at run-time offsets of the row's normals (a per-thread array indexed at run time would
 // live in scratch memory: see rng_dev.h).
 #include "mlp3_dev.h"
+#include "eval_check.h"
 
 namespace vaek {
 
@@ -241,37 +242,18 @@ int vaek_mlp3_stats_event_replicas(vaek_ctx* ctx, const float* params, const vae
                                    int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* workspace, void* stream) {
     const char* who = "vaek_mlp3_stats_event_replicas";
     ProfBind pb(ctx);
-    if (!ctx || !params || !ev) { set_error("%s: null context, params or event", who); return VAEK_ERR_INVALID; }
-    if (ev->struct_size != (int32_t)sizeof(vaek_stats_event)) {
-        set_error("%s: vaek_stats_event.struct_size %d != %d (header / library mismatch)", who, ev->struct_size, (int)sizeof(vaek_stats_event));
-        return VAEK_ERR_INVALID;
-    }
-    if (!ctx->mlp3_loglik) {
-        set_error("%s: needs a float32 VAE with one decoder and three hidden layers of 64 .. %d units both ways, D, L <= %d (see "
-                  "vaek_supports_mlp3_stats_event)", who, ML_W, ML_F);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_replica_count(who, ev->n)) return rc;
-    if (ev->rows < 1 || ev->rows > vaek_stats_event_max_rows()) {
-        set_error("%s: %d rows, need 1 .. %d (vaek_stats_event_max_rows)", who, ev->rows, vaek_stats_event_max_rows());
-        return VAEK_ERR_INVALID;
-    }
-    if (!ev->x_seeds || !ev->x_steps || !ev->z_seeds || !ev->z_steps || !ev->sample_eps || !ev->out) {
-        set_error("%s: x_seeds, x_steps, z_seeds, z_steps, sample_eps or out is NULL", who);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t len = kMs3Head + (int64_t)ctx->L;
-    if (ev->state_stride < ctx->P || ev->out_stride < len) {
-        set_error("%s: state_stride %lld < P = %lld or out_stride %lld < record length %lld (vaek_stats_record_len)", who,
-                  (long long)ev->state_stride, (long long)ctx->P, (long long)ev->out_stride, (long long)len);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, ev->a_stride, x_tag)) return rc;
-    if (int rc = check_tag(who, z_tag)) return rc;
-    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
-        set_error("%s: workspace is NULL or not 16-byte aligned (vaek_mlp3_stats_event_workspace_bytes)", who);
-        return VAEK_ERR_INVALID;
-    }
+    char needs[256];
+    snprintf(needs, sizeof(needs), "needs a float32 VAE with one decoder and three hidden layers of 64 .. %d units both ways, D, L <= %d (see "
+             "vaek_supports_mlp3_stats_event)", ML_W, ML_F);
+    const EvalDesc d = describe(ev);
+    EvalRules r{};
+    r.covered = ctx && ctx->mlp3_loglik; r.needs = needs;
+    r.rows_min = 1; r.rows_cap = vaek_stats_event_max_rows(); r.rows_query = "vaek_stats_event_max_rows";
+    r.records = 1; r.record_len = ctx ? kMs3Head + (int64_t)ctx->L : 0; r.record_query = "vaek_stats_record_len";
+    r.draws = true; r.kind = kind; r.A = A; r.dd = dd; r.did = did; r.pad = pad; r.x_tag = x_tag;
+    r.has_z_tag = true; r.z_tag = z_tag;
+    r.workspace = workspace; r.ws_align = 16; r.ws_query = "vaek_mlp3_stats_event_workspace_bytes";
+    if (int rc = check_eval(who, ctx, params, d, r)) return rc;
     const int n = ev->n, rows = ev->rows, tiles = ms3_tiles(rows);
     Ms3Args a{};
     a.params = params; a.state_stride = ev->state_stride;

@@ -57,65 +57,6 @@ int make_batch_args(vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int
     return VAEK_OK;
 }
 
-// ---- the in-kernel draw of the evaluation calls (vaek_stats_event_replicas and the two log-likelihood calls) -------------------
-int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                       int64_t a_stride, uint32_t x_tag) {
-    if (a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)a_stride); return VAEK_ERR_INVALID; }
-    if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
-    if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
-    if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
-        set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
-        return VAEK_ERR_INVALID;
-    }
-    if (dd + pad + (kind == 1 ? 1 : 0) != ctx->D) {
-        set_error("%s: dataset dimension %d != context data_dim %d", who, dd + pad + (kind == 1 ? 1 : 0), ctx->D);
-        return VAEK_ERR_INVALID;
-    }
-    return check_tag(who, x_tag);
-}
-
-// ---- the refusals the replica entry points repeat --------------------------------------------------------------------------------
-int check_struct_size(const char* who, const char* name, int32_t got, size_t want) {
-    if (got != (int32_t)want) {
-        set_error("%s: %s.struct_size %d != %d (header / library mismatch)", who, name, got, (int)want);
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
-}
-
-int check_replica_count(const char* who, int32_t n) {
-    if (n < 1 || n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, n, resident_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
-}
-
-int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows) {
-    if (x_stride < 0 || (x_stride > 0 && x_stride < (int64_t)rows * ctx->D)) {
-        set_error("%s: x_stride %lld: need 0 (shared rows) or >= rows * D = %lld", who, (long long)x_stride, (long long)rows * ctx->D);
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
-}
-
-int check_tag(const char* who, uint32_t tag) {
-    if (tag >= 0x40000000u) { set_error("%s: a tag >= 2^30", who); return VAEK_ERR_INVALID; }
-    return VAEK_OK;
-}
-
-int check_aligned8(const char* who, const char* what, uintptr_t addrs) {
-    if ((addrs & 7u) != 0) { set_error("%s: %s is not 8-byte aligned", who, what); return VAEK_ERR_INVALID; }
-    return VAEK_OK;
-}
-
-void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                    float var_added, uint32_t x_tag) {
-    g->kind = kind; g->A = kind == 2 ? nullptr : A; g->dd = dd; g->did = did; g->pad = pad;
-    g->noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
-    g->rows = rows; g->row0 = 0; g->D = ctx->D; g->L = ctx->L; g->tag = x_tag;
-}
-
 int make_batch_launch(vaek_ctx* ctx, const BatchArgs& a, hipStream_t st) {
     Profiler* outer = g_prof;
     g_prof = &ctx->prof;

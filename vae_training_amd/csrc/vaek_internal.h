@@ -439,30 +439,7 @@ int mlp3_train_step_replicas(vaek_ctx* c, float* params, float* grads, float* m,
                              long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
                              long long a_stride, float* loss_hist, long long loss_hist_cap);
 
-// ---- the dataset draw of the evaluation calls (rng.hip) and what the two log-likelihood calls share (linear_loglik.hip) ----------
-constexpr int kLogLikMaxRows = 4096;         // rows per call and ...
-constexpr int kLogLikMaxSamples = 1024;      // ... samples per row: they bound one launch on a shared machine -- caps, not tuned values
-// the dataset arguments of an in-kernel draw under tag x_tag, as `who` refuses them: a_stride, kind, A, dd / did / pad, dimension, tag
-int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                       int64_t a_stride, uint32_t x_tag);
-// the refusals the replica entry points repeat, each as `who` words it: VAEK_OK, or the error is set and the code to return comes back
-// (hidden: the library's dynamic symbol list stays what it was.  check_dataset_draw and its neighbours were exported before, as every
-// vaek:: function is -- the library is built without -fvisibility=hidden -- and stay so: hiding them would shorten that list)
-#pragma GCC visibility push(hidden)
-int check_struct_size(const char* who, const char* name, int32_t got, size_t want);      // a descriptor `name` of another header's size
-int check_replica_count(const char* who, int32_t n);                                      // outside 1 .. resident_max_replicas()
-int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows); // explicit rows: 0 (shared) or >= rows * D
-int check_tag(const char* who, uint32_t tag);                                             // >= 2^30
-int check_aligned8(const char* who, const char* what, uintptr_t addrs);                   // `addrs`: the outputs `what` names, ORed
-#pragma GCC visibility pop
-// ... and the BatchArgs of that draw: kind, A, dd, did, pad, noise_std, tag, rows, D, L; seed / step / pointers are the kernel's
-void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                    float var_added, uint32_t x_tag);
-// every check of a vaek_log_likelihood call, in the order of include/vaek.h; `covered` / `needs`: the entry's own predicate and what
-// it says when that fails; ws_align: 8 or 16, ws_bytes_fn: the function the message points to.  VAEK_OK or the code to return
-int check_log_likelihood(const char* who, const vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, bool covered,
-                         const char* needs, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, uint32_t x_tag, uint32_t z_tag,
-                         const void* workspace, int ws_align, const char* ws_bytes_fn);
+// ---- what the two log-likelihood calls share (linear_loglik.hip); the checks of the evaluation calls are eval_check.h's ----------
 // the last launch of both calls under the profile label `label`: n workgroups add the tile partials part[n][tiles][4] in tile order
 // and store the records
 int loglik_finalize(const char* label, const vaek_ctx* ctx, const float* params, const vaek_log_likelihood* ll, const double* part,
@@ -471,6 +448,6 @@ int loglik_finalize(const char* label, const vaek_ctx* ctx, const float* params,
 // ---- mlp3_loglik.hip: importance-weighted log-likelihood of three-hidden-layer MLP VAEs; whatever the batch, world or force_generic
 bool mlp3_loglik_supported(const vaek_ctx* c);
 // ---- mlp3_jacobian.hip: decoder Jacobian spectra of the same contexts (vaek_ctx::mlp3_loglik is its predicate too: the call draws no
-// data rows, so there is no kind); it shares check_struct_size, check_replica_count, check_tag and check_aligned8 above and nothing else
+// data rows, so there is no kind)
 
 }  // namespace vaek

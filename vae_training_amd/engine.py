@@ -270,17 +270,7 @@ class Engine:
         floats (0: shared), loss_hist: [n, cap] or None -- all device tensors; n, the strides and cap default to the tensors'
         shapes.  Replica r ends bitwise where train_loop_gen alone on its slices would.  Asynchronous; capturable.
         `trajectory` (see _trajectory; vaek_train_loop_gen_replicas_traj): replica r's ring is buf[r]."""
-        rep = _lib.VaekReplicas()
-        rep.struct_size = C.sizeof(_lib.VaekReplicas)
-        rep.n = int(params.shape[0] if n is None else n)
-        rep.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        rep.grads_stride = int(grads.shape[1] if grads_stride is None else grads_stride)
-        assert seeds is None or seeds.dtype == torch.int64
-        assert lrs is None or lrs.dtype == torch.float32
-        rep.seeds, rep.lrs = _ptr(seeds), _ptr(lrs)
-        rep.a_stride = int(a_stride)
-        rep.loss_hist = _ptr(loss_hist)
-        rep.loss_hist_cap = _last_dim(loss_hist, loss_hist_cap)
+        rep = self._replicas_desc(params, grads, seeds, lrs, a_stride, loss_hist, n, state_stride, grads_stride, loss_hist_cap)
         args = (self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep), int(kind), _ptr(A), int(dd), int(did),
                 int(pad), float(var_added), int(row0), int(tag), int(n_steps), float(lr), _ptr(workspace), _stream())
         if trajectory is not None:
@@ -316,6 +306,22 @@ class Engine:
                                     struct_size)
         _lib.check(self.lib.vaek_stats_event_replicas(self.h, _ptr(params), C.byref(ev), int(kind), _ptr(A), int(dd), int(did), int(pad),
                                                       float(var_added), int(x_tag), int(z_tag), _stream()))
+
+    @staticmethod
+    def _replicas_desc(params, grads, seeds, lrs, a_stride, loss_hist, n, state_stride, grads_stride, loss_hist_cap):
+        """The vaek_replicas description both replica train calls take, from tensors; n, the strides and cap default to the tensors' shapes."""
+        rep = _lib.VaekReplicas()
+        rep.struct_size = C.sizeof(_lib.VaekReplicas)
+        rep.n = int(params.shape[0] if n is None else n)
+        rep.state_stride = int(params.shape[1] if state_stride is None else state_stride)
+        rep.grads_stride = int(grads.shape[1] if grads_stride is None else grads_stride)
+        assert seeds is None or seeds.dtype == torch.int64
+        assert lrs is None or lrs.dtype == torch.float32
+        rep.seeds, rep.lrs = _ptr(seeds), _ptr(lrs)
+        rep.a_stride = int(a_stride)
+        rep.loss_hist = _ptr(loss_hist)
+        rep.loss_hist_cap = _last_dim(loss_hist, loss_hist_cap)
+        return rep
 
     @staticmethod
     def _stats_event_desc(params, rows, x_seeds, x_steps, z_seeds, z_steps, sample_eps, out, a_stride, n, state_stride, out_stride, struct_size):
@@ -680,18 +686,8 @@ class Engine:
         (then `lr` for all), A: replica r's at A + r * a_stride floats (0: shared), loss_hist: [n, cap] or None, workspace: uint8 of
         train_step_replicas_workspace(n) bytes -- all device tensors; n, the strides and cap default to the tensors' shapes.
         Replica r ends bitwise where train_step_gen alone on its slices would.  Asynchronous; capturable."""
-        rep = _lib.VaekReplicas()
-        rep.struct_size = C.sizeof(_lib.VaekReplicas)
-        rep.n = int(params.shape[0] if n is None else n)
-        rep.state_stride = int(params.shape[1] if state_stride is None else state_stride)
-        rep.grads_stride = int(grads.shape[1] if grads_stride is None else grads_stride)
-        assert seeds is None or seeds.dtype == torch.int64
-        assert lrs is None or lrs.dtype == torch.float32
         assert counter is None or (counter.dtype == torch.int32 and counter.is_cuda)
-        rep.seeds, rep.lrs = _ptr(seeds), _ptr(lrs)
-        rep.a_stride = int(a_stride)
-        rep.loss_hist = _ptr(loss_hist)
-        rep.loss_hist_cap = _last_dim(loss_hist, loss_hist_cap)
+        rep = self._replicas_desc(params, grads, seeds, lrs, a_stride, loss_hist, n, state_stride, grads_stride, loss_hist_cap)
         nxt = (None, None, None) if nxt is None else nxt
         _lib.check(self.lib.vaek_train_step_gen_replicas(self.h, _ptr(params), _ptr(grads), _ptr(m), _ptr(v), _ptr(step_dev), C.byref(rep),
                                                          _ptr(cur[0]), _ptr(cur[1]), _ptr(cur[2]), float(lr), _ptr(workspace), int(kind),
