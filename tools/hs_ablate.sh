@@ -1,4 +1,5 @@
-# Diagnostic builds of the persistent bf16-storage GEMM: 1 = no MFMAs, 2 = no output stores, 4 = no operand loads (bit mask).
+# Diagnostic builds of the bf16-storage GEMMs: 1 = no MFMAs (every NT-shaped kernel: the shared k-tile product of hs_tile_dev.h),
+# 2 = no bf16 output stores (both NT kernels: the shared epilogue), 4 = no operand loads (the persistent kernel only) (bit mask).
 # Prints the forward / dX kernel times of each build (outputs are wrong by construction; only the clock matters).
 set -e
 cd $GRAFT_REPO_ROOT/vae_training_amd/csrc

@@ -14,13 +14,9 @@
 // (four parity-phase GEMMs with 2 x 2 taps each) and the kernel gradient (batch-split GEMM with the gather transposed): every
 // product of both layer kinds' forward and backward passes (oracle: conv_fwd / conv_bwd / conv_t_fwd / conv_t_bwd).  The
 // convolutional VAE's train step (bottleneck Dense layers + ELBO around them) is not assembled yet.
-#include "vaek_internal.h"
+#include "hs_tile_dev.h"      // the vector types, bf16_lo / bf16_hi
 
 namespace vaek {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
 
 constexpr int CBM = 128, CBN = 128, CNT = 256, CBK = 32, CSTR = CBK + 8, CKU = CBK / 8;     // (64-deep k-tiles measured slower: forward 1.1 -> 2.0 ms, kernel gradient unchanged)
 
@@ -455,10 +451,8 @@ __global__ __launch_bounds__(256) void conv_colsum8_bf16_kernel(const uint4* dy8
 #pragma unroll
         for (int e = 0; e < 8; ++e) a[u][e] = 0.f;
     auto add8 = [&](float (&acc)[8], const uint4 v) {
-        acc[0] += __builtin_bit_cast(float, v.x << 16); acc[1] += __builtin_bit_cast(float, v.x & 0xffff0000u);
-        acc[2] += __builtin_bit_cast(float, v.y << 16); acc[3] += __builtin_bit_cast(float, v.y & 0xffff0000u);
-        acc[4] += __builtin_bit_cast(float, v.z << 16); acc[5] += __builtin_bit_cast(float, v.z & 0xffff0000u);
-        acc[6] += __builtin_bit_cast(float, v.w << 16); acc[7] += __builtin_bit_cast(float, v.w & 0xffff0000u);
+        acc[0] += bf16_lo(v.x); acc[1] += bf16_hi(v.x); acc[2] += bf16_lo(v.y); acc[3] += bf16_hi(v.y);
+        acc[4] += bf16_lo(v.z); acc[5] += bf16_hi(v.z); acc[6] += bf16_lo(v.w); acc[7] += bf16_hi(v.w);
     };
     long long f = f0 + threadIdx.x;
     for (; f + 768 < f1; f += 1024) {
@@ -649,8 +643,7 @@ __global__ __launch_bounds__(256) void thin_conv_t_fwd4s_kernel(const ThinArgs g
                 float4 f;
                 if constexpr (X16) {                        // (four bf16 widened)
                     const uint2 u = *reinterpret_cast<const uint2*>(g.x16 + eo);
-                    f = make_float4(__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
-                                    __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u));
+                    f = make_float4(bf16_lo(u.x), bf16_hi(u.x), bf16_lo(u.y), bf16_hi(u.y));
                 } else f = *reinterpret_cast<const float4*>(g.x + eo);
                 v[r][c] = in ? f : make_float4(0.f, 0.f, 0.f, 0.f);
             }
@@ -766,9 +759,8 @@ __global__ __launch_bounds__(256) void thin_conv_fwd8_kernel(const ThinArgs g, c
         *reinterpret_cast<float4*>(g.y + p * C + o0) = make_float4(acc[0], acc[1], acc[2], acc[3]);
         *reinterpret_cast<float4*>(g.y + p * C + o0 + 4) = make_float4(acc[4], acc[5], acc[6], acc[7]);
         if (g.y16) {
-            typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-            const bf16x8_t o8 = {(__bf16)acc[0], (__bf16)acc[1], (__bf16)acc[2], (__bf16)acc[3], (__bf16)acc[4], (__bf16)acc[5], (__bf16)acc[6], (__bf16)acc[7]};
-            *reinterpret_cast<bf16x8_t*>(g.y16 + p * C + o0) = o8;
+            const bf16x8 o8 = {(__bf16)acc[0], (__bf16)acc[1], (__bf16)acc[2], (__bf16)acc[3], (__bf16)acc[4], (__bf16)acc[5], (__bf16)acc[6], (__bf16)acc[7]};
+            *reinterpret_cast<bf16x8*>(g.y16 + p * C + o0) = o8;
         }
     }
 }
@@ -924,9 +916,8 @@ __global__ __launch_bounds__(256) void thin_conv_fwd_mfma_kernel(const ThinArgs 
             if (q < g.pixels) {
                 if (g.y) g.y[q * g.C + c0 + i] = v;
                 if (g.y16 && !(i & 1)) {
-                    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-                    const bf16x2_t pr = {(__bf16)v, (__bf16)nb};
-                    *reinterpret_cast<bf16x2_t*>(g.y16 + q * g.C + c0 + i) = pr;
+                    const bf16x2 pr = {(__bf16)v, (__bf16)nb};
+                    *reinterpret_cast<bf16x2*>(g.y16 + q * g.C + c0 + i) = pr;
                 }
             }
         }

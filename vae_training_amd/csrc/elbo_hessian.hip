@@ -538,10 +538,7 @@ static int check_doubles(const char* who, const char* what, const void* ptr, int
 template <bool LANCZOS>
 static int hessian_launch(const char* label, const HessArgs& a, int n, hipStream_t st) {
     static thread_local PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)elbo_hessian_kernel<LANCZOS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kHessLds));
-        attr_set.mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set, elbo_hessian_kernel<LANCZOS>, kHessLds));
     {
         ProfScope ps(label, st);
         launch_k(ps, elbo_hessian_kernel<LANCZOS>, dim3((unsigned)n), dim3(256), kHessLds, st, a);

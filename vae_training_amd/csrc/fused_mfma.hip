@@ -650,10 +650,7 @@ int fused_mfma_launch(const vaek_ctx* c, const float* params, const void* args_v
     static thread_local PerDeviceOnce attr_set[2][sizeof(kMfmaVariants) / sizeof(kMfmaVariants[0])];
     PerDeviceOnce& once = attr_set[a.single ? 1 : 0][var - kMfmaVariants];
     const MfmaKernel fn = a.single ? var->fn_single : var->fn;
-    if (var->lds_bytes > 64 * 1024 && once.need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)var->lds_bytes));
-        once.mark();
-    }
+    if (var->lds_bytes > 64 * 1024) VAEK_HIP_CHECK(set_max_dynamic_lds(once, fn, var->lds_bytes));
     {
         ProfScope ps(a.single ? "fused_linear_mfma_single" : "fused_linear_mfma", st);
         launch_k(ps, fn, dim3(grid), dim3(256), var->lds_bytes, st, params, a);

@@ -492,10 +492,7 @@ int mlp1_launch(vaek_ctx* c, const float* params, const float* x, const float* z
                               : (sig ? mlp1_fused_kernel<8, 8, true> : mlp1_fused_kernel<8, 8, false>);
     static thread_local PerDeviceOnce attr_set[4];
     const int vi = (big ? 2 : 0) + (sig ? 1 : 0);
-    if (attr_set[vi].need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Mlp1Lds)));
-        attr_set[vi].mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set[vi], fn, sizeof(Mlp1Lds)));
     ProfScope ps("fused_mlp1_fwd_bwd", st);
     launch_k(ps, fn, dim3((unsigned)mlp1_grid(c)), dim3(M1_NT), sizeof(Mlp1Lds), st, a);
     VAEK_HIP_CHECK(hipGetLastError());

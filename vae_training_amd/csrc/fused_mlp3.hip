@@ -409,12 +409,8 @@ static int mlp3_step_impl(vaek_ctx* c, float* params, float* grads, float* m, fl
 #endif
     a.step_dev = step_dev; a.stamps = rep ? nullptr : c->dbg_stamps;
     static thread_local PerDeviceOnce attr_set[2];
-    PerDeviceOnce& once = attr_set[rep ? 1 : 0];
-    if (once.need()) {
-        const void* fn = rep ? (const void*)mlp3_chain_replicas_kernel : (const void*)mlp3_chain_kernel;
-        VAEK_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Mlp3Lds)));
-        once.mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set[rep ? 1 : 0], rep ? (const void*)mlp3_chain_replicas_kernel : (const void*)mlp3_chain_kernel,
+                                       sizeof(Mlp3Lds)));
     const unsigned ny = rep ? (unsigned)rep->n : 1u;
     {
         ProfScope ps(rep ? "fused_mlp3_chain_replicas" : "fused_mlp3_chain", st);

@@ -573,10 +573,7 @@ int fused_train_step(vaek_ctx* c, float* params, float* grads, float* m, float* 
     const bool mlp1 = !var && mlp1_supported(c);        // one-hidden-layer MLPs: fused_mlp1.hip writes the partial rows
     if (!var && !mlp1) { set_error("fused path not available for this configuration"); return VAEK_ERR_INVALID; }
     static thread_local PerDeviceOnce attr_set[sizeof(kVariants) / sizeof(kVariants[0])];
-    if (var && var->lds_bytes > 64 * 1024 && attr_set[var - kVariants].need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)var->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)var->lds_bytes));
-        attr_set[var - kVariants].mark();
-    }
+    if (var && var->lds_bytes > 64 * 1024) VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set[var - kVariants], var->fn, var->lds_bytes));
     float* partials = reinterpret_cast<float*>(static_cast<char*>(ws) + c->ws_fused);
     const int grid = mlp1 ? mlp1_grid(c) : fused_grid(c, var), pstride = fused_pstride(c);
     FusedArgs a{};

@@ -20,43 +20,22 @@
 //                  operand in the workgroups of the first row of tiles.
 //   cvt_w_kernel   bf16 copies W and W^T of the wide layers' kernels (weights change every step; 1 MB at C3).
 //
-// Main loop (both kernels): 64-deep k-tiles, two LDS buffers, ONE barrier per k-tile -- wait for tile t (vmcnt(0)),
-// barrier, issue the loads of tile t+1 into the other buffer, multiply tile t.  LDS images are lane-linear (what
-// global_load_lds writes) with the bank swizzle applied to the per-lane SOURCE address and the same XOR on the read.
-#include "vaek_internal.h"
+// Main loop (every kernel): a ring of NS LDS stages of 64- / 32-deep k-tiles, ONE barrier per k-tile -- wait for tile t (a
+// counted vmcnt: the younger tiles stay in flight), barrier, issue the loads of tile t + NS - 1 into the slot tile t - 1 was
+// read from, multiply tile t.  The loads are global_load_lds in inline assembly (through the builtin the compiler drained the
+// ring in front of every operand read) and LDS images are lane-linear (what global_load_lds writes) with the bank swizzle
+// applied to the per-lane SOURCE address and the same XOR on the read.  The mechanics -- glds16, the counted waits, and the
+// tile core HsTile that hs_nt_kernel, hs_nt_p_kernel and hs_conv_kernel share (geometry, swizzle, staging positions,
+// fragments, k-tile product, ring step, bf16 epilogue) -- are in hs_tile_dev.h; a kernel here is its tile walk, its source
+// addresses, the loop skeleton and its epilogue.
+#include "hs_tile_dev.h"
 
 namespace vaek {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef const __attribute__((address_space(1))) void glb_void_t;
-
-// 16 bytes per lane global -> LDS; the LDS side is wave-uniform base + 16 * lane.  In inline assembly since round 3: through
-// __builtin_amdgcn_global_load_lds hipcc knows that LDS is being written and puts s_waitcnt vmcnt(0) in front of the next LDS
-// read it cannot tell apart -- in every kernel of this file that was the operand reads of the k-tile being multiplied, RIGHT BEHIND
-// the issue of the next k-tile's loads: the ring never overlapped a load with a product (ISA: "8 x global_load_lds, s_waitcnt
-// vmcnt(0), ds_read_b128 ..."; round 2's ablation found loads and MFMAs additive and every ring depth equally fast).  Every wait
-// on these loads is the kernels' own counted one (wait_tiles) in front of a barrier.
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-    const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(lds_void_t*)lds_wave_base);
-    _Pragma("clang diagnostic push") _Pragma("clang diagnostic ignored \"-Winline-asm\"")      // (M0 on the clobber list: it is what the LDS-DMA takes its LDS address from)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(m0v) : "memory", "m0");
-    _Pragma("clang diagnostic pop")
-}
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi) {
-    const bf16x2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned, v);
-}
-
-enum { HS_FWD = 0, HS_DX = 1 };
 
 // Diagnostic build only (-DVAEK_HS_STAMPS, tools/hs_stamps.sh): per-wave s_memtime sums of the main loop's phases, written
 // to a buffer nothing else reads.  The shipped build contains no stamp.
 #ifdef VAEK_HS_STAMPS
-__device__ unsigned long long* g_hs_stamp_buf = nullptr;
+__device__ unsigned long long* g_hs_stamp_buf = nullptr;      // tools/hs_stamps.py reads it back (vaek_debug_hs_stamps)
 __device__ __forceinline__ unsigned long long hs_now() {
     unsigned long long t;
     __builtin_amdgcn_sched_barrier(0);
@@ -71,38 +50,11 @@ __device__ __forceinline__ unsigned long long hs_now() {
 #define HS_ADD(acc, a, b) do {} while (0)
 #endif
 
-struct HsArgs {
-    const __bf16* A; const __bf16* Bt; __bf16* C;   // A [M, K] (lda), Bt [N, K] (ldb), C [M, N] (ldc); K, N multiples of 64
-    int M, N, K, lda, ldb, ldc;
-    const float* bias; int relu;                    // FWD
-    const __bf16* aux;                              // DX: relu-mask source [M, ldc] (the layer's bf16 input), or nullptr
-};
-
-// Counted waits: s_waitcnt vmcnt(N) returns once at most N of this wave's vector-memory operations are still outstanding
-// (they retire in issue order), i.e. "everything up to tile kt has landed, the `newer` younger tiles may stay in flight".
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int P, int MAXT> __device__ __forceinline__ void wait_tiles(int newer) {       // P loads per tile, newer in [0, MAXT]
-    static_assert(P * MAXT <= 63, "vmcnt is a 6-bit counter");
-    if constexpr (MAXT == 0) wait_vmcnt<0>();
-    else if (newer >= MAXT) wait_vmcnt<P * MAXT>();
-    else wait_tiles<P, MAXT - 1>(newer);
-}
-
-// LDS image of an R-row x BK-k operand tile (BK = 64 / 32): 128- / 64-byte rows, 16-byte chunk c of row r at chunk position
-// c ^ f(r), f = (r >> 1) & 7 / (r >> 2) & 3: the 16 lanes ds_read_b128 services together (rows {0-3,12-15,20-27} /
-// {4-11,16-19,28-31} of a fragment, one chunk column) then cover all 16 chunk slots of the 256-byte bank row.
-//
-// Ring of NS stages: a k-tile's MFMAs take ~0.25 us per wave, an HBM / L2 round trip under load 1-3 us, so ONE tile of
-// prefetch (round 2's first version: 2.8 us per k-tile) is a latency chain; NS - 1 tiles are in flight while one is multiplied.
+// One output tile per workgroup.  The tile core (LDS image, swizzle, fragments, k-tile product, ring step, epilogue): HsTile.
 template <int EPI, int BM, int BN, int WM, int WN, int BK, int NS>
 __global__ __launch_bounds__(64 * WM * WN) void hs_nt_kernel(const HsArgs g) {
-    constexpr int NTH = 64 * WM * WN;
-    constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    constexpr int RB = 2 * BK, CPR = BK / 8;                 // row bytes, 16-byte chunks per row
-    constexpr int A_BYTES = BM * RB, B_BYTES = BN * RB, BUF = A_BYTES + B_BYTES;
-    constexpr int A_PASSES = BM * CPR / NTH, B_PASSES = BN * CPR / NTH, P = A_PASSES + B_PASSES;
-    static_assert(BM * CPR % NTH == 0 && BN * CPR % NTH == 0, "whole staging passes");
-    static_assert(BK == 64 || BK == 32, "k-tile depth");
+    using T = HsTile<BM, BN, WM, WN, BK, NS>;
+    constexpr int TM = T::TM, TN = T::TN, A_PASSES = T::A_PASSES, B_PASSES = T::B_PASSES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     HS_STAMP(k0);
     // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs; give each XCD a contiguous run of the
@@ -114,41 +66,29 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_nt_kernel(const HsArgs g) {
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wv / WN, wn = wv % WN;
-    auto swz = [](int row) { return BK == 64 ? (row >> 1) & 7 : (row >> 2) & 3; };
 
-    // per-lane source of each staging pass (the swizzle lives here)
+    // per-lane source of each staging pass (rows past the end re-read the last one; those outputs are not stored)
     const __bf16* a_src[A_PASSES]; const __bf16* b_src[B_PASSES];
 #pragma unroll
     for (int i = 0; i < A_PASSES; ++i) {
-        const int p = i * NTH + t, row = p / CPR, c = (p % CPR) ^ swz(row);
-        a_src[i] = g.A + (long long)min(m0 + row, g.M - 1) * g.lda + c * 8;
+        int row, col; T::stage_pos(t, i, row, col);
+        a_src[i] = g.A + (long long)min(m0 + row, g.M - 1) * g.lda + col;
     }
 #pragma unroll
     for (int i = 0; i < B_PASSES; ++i) {
-        const int p = i * NTH + t, row = p / CPR, c = (p % CPR) ^ swz(row);
-        b_src[i] = g.Bt + (long long)min(n0 + row, g.N - 1) * g.ldb + c * 8;
+        int row, col; T::stage_pos(t, i, row, col);
+        b_src[i] = g.Bt + (long long)min(n0 + row, g.N - 1) * g.ldb + col;
     }
     auto stage = [&](int kt, int slot) {
-        char* base = smem + slot * BUF;
+        char* base = smem + slot * T::BUF;
 #pragma unroll
-        for (int i = 0; i < A_PASSES; ++i) glds16(a_src[i] + kt * BK, base + (i * NTH + wv * 64) * 16);
+        for (int i = 0; i < A_PASSES; ++i) glds16(a_src[i] + kt * BK, base + T::stage_dst(wv, i));
 #pragma unroll
-        for (int i = 0; i < B_PASSES; ++i) glds16(b_src[i] + kt * BK, base + A_BYTES + (i * NTH + wv * 64) * 16);
+        for (int i = 0; i < B_PASSES; ++i) glds16(b_src[i] + kt * BK, base + T::A_BYTES + T::stage_dst(wv, i));
     };
-    // fragment addresses: lane (r = lane & 31, h = lane >> 5) reads chunk 2 s + h of its row for k-step s
-    const int r = lane & 31, h = lane >> 5;
-    const int arow = wm * (BM / WM) + r, brow = wn * (BN / WN) + r;
-    const int ax = swz(arow), bx = swz(brow);
-    const int a_lo = arow * RB + ((h ^ ax) & 1) * 16, a_x6 = (ax & 6) * 16;
-    const int b_lo = brow * RB + ((h ^ bx) & 1) * 16 + A_BYTES, b_x6 = (bx & 6) * 16;
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+    const typename T::Frag frag(wm, wn, lane);
+    typename T::Acc acc;
+    acc.zero();
 
     const int nt = g.K / BK;
     // dX with a ring of two: the relu-mask source (this wave's output tile of the layer's bf16 input, 16 x 16 bytes per lane) is
@@ -166,9 +106,13 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_nt_kernel(const HsArgs g) {
     int slot = 0, fill = NS - 1;                          // ring positions of the tile being multiplied / being loaded
     for (int kt = 0; kt < nt; ++kt) {
         HS_STAMP(s0);
-        wait_tiles<P, NS - 2>(min(NS - 2, nt - 1 - kt));   // this wave's share of tile kt has landed ...
+#ifdef VAEK_HS_STAMPS                                          // (T::wait_tile spelled out, to stamp between the counted wait and the barrier)
+        wait_tiles<T::P, NS - 2>(min(NS - 2, nt - 1 - kt));
         HS_STAMP(s1);
-        __builtin_amdgcn_s_barrier();                      // ... and everyone's; everyone is done reading tile kt - 1
+        __builtin_amdgcn_s_barrier();
+#else
+        T::wait_tile(nt - 1 - kt);
+#endif
         HS_STAMP(s2);
         if (kt + NS - 1 < nt) stage(kt + NS - 1, fill);    // into the slot tile kt - 1 was read from
         if constexpr (PRE_MASK) {
@@ -191,96 +135,29 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_nt_kernel(const HsArgs g) {
         }
         HS_STAMP(s3);
         HS_ADD(st_wait, s0, s1); HS_ADD(st_bar, s1, s2); HS_ADD(st_issue, s2, s3);
-        const char* base = smem + slot * BUF;
-#pragma unroll
-        for (int s = 0; s < BK / 16; ++s) {
-            bf16x8 fa[TM], fb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(base + a_lo + i * 32 * RB + ((32 * s) ^ a_x6));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(base + b_lo + j * 32 * RB + ((32 * s) ^ b_x6));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)      // swapped: D[n][m] -- lane & 31 = output row m, registers = columns n
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-        }
-        slot = slot + 1 == NS ? 0 : slot + 1;
-        fill = fill + 1 == NS ? 0 : fill + 1;
+        acc.multiply(smem + slot * T::BUF, frag);
+        T::advance(slot, fill);
         HS_STAMP(s4);
         HS_ADD(st_comp, s3, s4);
     }
     HS_STAMP(e0);
 #ifdef VAEK_HS_STAMPS
     if (g_hs_stamp_buf && lane == 0) {
-        unsigned long long* o = g_hs_stamp_buf + ((long long)blockIdx.x * (NTH / 64) + wv) * 8;
+        unsigned long long* o = g_hs_stamp_buf + ((long long)blockIdx.x * (T::NTH / 64) + wv) * 8;
         o[0] = p1 - p0; o[1] = st_wait; o[2] = st_bar; o[3] = st_issue; o[4] = st_comp; o[5] = e0 - p0; o[6] = k0; o[7] = e0;
     }
 #endif
 
-    // ---- epilogue: register q of tile (i, j) = C[m0 + wm.. + 32 i + r][nb + 32 j + (q & 3) + 8 (q >> 2) + 4 h]
+    // ---- epilogue
     const int nbase = n0 + wn * (BN / WN);
     if (nbase >= g.N) return;                      // wave-uniform: N is a multiple of 64 = the wave's column span
-    const float floor_v = g.relu ? 0.f : -__builtin_huge_valf();      // relu as one v_max with a uniform floor: no branch per value
     float4 bias4[TN][4];
-    if (EPI == HS_FWD) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) bias4[j][q] = *reinterpret_cast<const float4*>(g.bias + nbase + j * 32 + 8 * q + 4 * h);
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = m0 + wm * (BM / WM) + i * 32 + r;
-        const bool row_ok = m < g.M;
-        const long long rowoff = (long long)(row_ok ? m : g.M - 1) * g.ldc;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int nj = nbase + j * 32;
-            // after the swaps lanes 0-31 own columns [8 qq, 8 qq + 8), lanes 32-63 [8 qq + 8, 8 qq + 16), qq = 0, 2
-            uint4 mask[2];
-            if (EPI == HS_DX && g.aux) {
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    if constexpr (PRE_MASK) mask[u] = pmask[i][j][u];
-                    else mask[u] = *reinterpret_cast<const uint4*>(g.aux + rowoff + nj + 16 * u + 8 * h);
-                }
-            }
-            unsigned d[4][2];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float v[4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p) v[p] = acc[i][j][4 * q + p];
-                if (EPI == HS_FWD) {
-                    const float4 b = bias4[j][q];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) v[p] = fmaxf(v[p] + (p == 0 ? b.x : p == 1 ? b.y : p == 2 ? b.z : b.w), floor_v);
-                }
-                d[q][0] = pack_bf16(v[0], v[1]); d[q][1] = pack_bf16(v[2], v[3]);
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int qq = 2 * u;
-                const auto sx = __builtin_amdgcn_permlane32_swap(d[qq][0], d[qq + 1][0], false, false);
-                const auto sy = __builtin_amdgcn_permlane32_swap(d[qq][1], d[qq + 1][1], false, false);
-                uint4 o = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-                if (EPI == HS_DX && g.aux) {
-                    auto keep = [](unsigned a) {      // per bf16 half: 0xffff where the activation is > 0 (relu'), else 0
-                        const unsigned lo = (int)(short)(a & 0xffffu) > 0 ? 0xffffu : 0u;
-                        const unsigned hi = (int)a > 0xffff ? 0xffff0000u : 0u;
-                        return lo | hi;
-                    };
-                    o.x &= keep(mask[u].x); o.y &= keep(mask[u].y); o.z &= keep(mask[u].z); o.w &= keep(mask[u].w);
-                }
-                if (row_ok) *reinterpret_cast<uint4*>(g.C + rowoff + nj + 16 * u + 8 * h) = o;
-            }
-        }
-    }
+    if (EPI == HS_FWD) T::load_bias(g.bias, nbase, lane, bias4);
+    hs_nt_epilogue<EPI, T, PRE_MASK, const HsArgs>(g, acc, m0 + wm * (BM / WM), nbase, lane, bias4, &pmask[0][0][0]);
 #ifdef VAEK_HS_STAMPS
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     HS_STAMP(x1);
-    if (g_hs_stamp_buf && lane == 0) g_hs_stamp_buf[((long long)gridDim.x * (NTH / 64) + (long long)blockIdx.x * (NTH / 64) + wv) * 8] = x1;
+    if (g_hs_stamp_buf && lane == 0) g_hs_stamp_buf[((long long)gridDim.x * (T::NTH / 64) + (long long)blockIdx.x * (T::NTH / 64) + wv) * 8] = x1;
 #endif
 }
 
@@ -294,19 +171,14 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_nt_kernel(const HsArgs g) {
 //    so the epilogue's stores run beside loads already in flight and no tile starts on an exposed HBM round trip.
 template <int EPI, int BM, int BN, int WM, int WN, int BK, int NS>
 __global__ __launch_bounds__(64 * WM * WN) void hs_nt_p_kernel(const HsArgs g) {
-    constexpr int NTH = 64 * WM * WN;
-    constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    constexpr int RB = 2 * BK, CPR = BK / 8;
-    constexpr int A_BYTES = BM * RB, B_BYTES = BN * RB, BUF = A_BYTES + B_BYTES;
-    constexpr int A_PASSES = BM * CPR / NTH, B_PASSES = BN * CPR / NTH, P = A_PASSES + B_PASSES;
-    static_assert(BM * CPR % NTH == 0 && BN * CPR % NTH == 0, "whole staging passes");
+    using T = HsTile<BM, BN, WM, WN, BK, NS>;
+    constexpr int TN = T::TN, A_PASSES = T::A_PASSES, B_PASSES = T::B_PASSES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM, ntiles = tiles_m * tiles_n;
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wv / WN, wn = wv % WN;
     const bool late = wv >= WM * WN / 2;                 // wave-uniform: multiply first, issue afterwards
-    auto swz = [](int row) { return BK == 64 ? (row >> 1) & 7 : (row >> 2) & 3; };
     // this workgroup's j-th tile; each XCD (workgroups b with equal b % 8) walks a contiguous run of the n-fastest tile space
     const int G = gridDim.x, b = blockIdx.x;
     const int my_tiles = b < ntiles ? (ntiles - b + G - 1) / G : 0;
@@ -315,12 +187,12 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_nt_p_kernel(const HsArgs g) {
         if (ntiles % 8 == 0 && G % 8 == 0) L = (b % 8) * (ntiles / 8) + (b / 8) + j * (G / 8);
         m0 = (L / tiles_n) * BM; n0 = (L % tiles_n) * BN;
     };
-    // staging positions of this thread (row, logical chunk) per pass: the swizzle lives in the source address
+    // staging positions of this thread per pass, kept across tiles; the sources of the tile the load cursor is in
     int a_row[A_PASSES], a_c[A_PASSES], b_row[B_PASSES], b_c[B_PASSES];
 #pragma unroll
-    for (int i = 0; i < A_PASSES; ++i) { const int p = i * NTH + t; a_row[i] = p / CPR; a_c[i] = ((p % CPR) ^ swz(p / CPR)) * 8; }
+    for (int i = 0; i < A_PASSES; ++i) T::stage_pos(t, i, a_row[i], a_c[i]);
 #pragma unroll
-    for (int i = 0; i < B_PASSES; ++i) { const int p = i * NTH + t; b_row[i] = p / CPR; b_c[i] = ((p % CPR) ^ swz(p / CPR)) * 8; }
+    for (int i = 0; i < B_PASSES; ++i) T::stage_pos(t, i, b_row[i], b_c[i]);
     const __bf16* a_src[A_PASSES]; const __bf16* b_src[B_PASSES];
     auto set_sources = [&](int m0, int n0) {
 #pragma unroll
@@ -329,94 +201,29 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_nt_p_kernel(const HsArgs g) {
         for (int i = 0; i < B_PASSES; ++i) b_src[i] = g.Bt + (long long)min(n0 + b_row[i], g.N - 1) * g.ldb + b_c[i];
     };
     auto stage = [&](int kt, int slot) {
-        char* base = smem + slot * BUF;
+        char* base = smem + slot * T::BUF;
 #if defined(VAEK_HS_ABLATE) && (VAEK_HS_ABLATE & 4)      // diagnostic: no operand loads at all
         (void)base; (void)kt;
 #else
 #pragma unroll
-        for (int i = 0; i < A_PASSES; ++i) glds16(a_src[i] + kt * BK, base + (i * NTH + wv * 64) * 16);
+        for (int i = 0; i < A_PASSES; ++i) glds16(a_src[i] + kt * BK, base + T::stage_dst(wv, i));
 #pragma unroll
-        for (int i = 0; i < B_PASSES; ++i) glds16(b_src[i] + kt * BK, base + A_BYTES + (i * NTH + wv * 64) * 16);
+        for (int i = 0; i < B_PASSES; ++i) glds16(b_src[i] + kt * BK, base + T::A_BYTES + T::stage_dst(wv, i));
 #endif
     };
-    const int r = lane & 31, h = lane >> 5;
-    const int arow = wm * (BM / WM) + r, brow = wn * (BN / WN) + r;
-    const int ax = swz(arow), bx = swz(brow);
-    const int a_lo = arow * RB + ((h ^ ax) & 1) * 16, a_x6 = (ax & 6) * 16;
-    const int b_lo = brow * RB + ((h ^ bx) & 1) * 16 + A_BYTES, b_x6 = (bx & 6) * 16;
-    const float floor_v = g.relu ? 0.f : -__builtin_huge_valf();
+    const typename T::Frag frag(wm, wn, lane);
 
     // the bias of the tile being multiplied, loaded when the tile starts: a load issued in the epilogue would be YOUNGER than the
     // next tile's stages already in flight, and vmcnt retires in order -- using it would drain the ring first
     float4 bias4[TN][4];
     auto load_bias = [&](int n0) {
-        if (EPI != HS_FWD) return;
-        const int nbase = min(n0 + wn * (BN / WN), g.N - BN / WN);
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) bias4[j][q] = *reinterpret_cast<const float4*>(g.bias + nbase + j * 32 + 8 * q + 4 * h);
+        if (EPI == HS_FWD) T::load_bias(g.bias, min(n0 + wn * (BN / WN), g.N - BN / WN), lane, bias4);
     };
-    f32x16 acc[TM][TN];
-    auto zero_acc = [&]() {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-    };
+    typename T::Acc acc;
     auto epilogue = [&](int m0, int n0) {
         const int nbase = n0 + wn * (BN / WN);
         if (nbase >= g.N) return;                      // wave-uniform: N is a multiple of 64 = the wave's column span
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int m = m0 + wm * (BM / WM) + i * 32 + r;
-            const bool row_ok = m < g.M;
-            const long long rowoff = (long long)(row_ok ? m : g.M - 1) * g.ldc;
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                const int nj = nbase + j * 32;
-                uint4 mask[2];
-                if (EPI == HS_DX && g.aux) {
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) mask[u] = *reinterpret_cast<const uint4*>(g.aux + rowoff + nj + 16 * u + 8 * h);
-                }
-                unsigned d[4][2];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float v[4];
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) v[p] = acc[i][j][4 * q + p];
-                    if (EPI == HS_FWD) {
-                        const float4 bq = bias4[j][q];
-#pragma unroll
-                        for (int p = 0; p < 4; ++p) v[p] = fmaxf(v[p] + (p == 0 ? bq.x : p == 1 ? bq.y : p == 2 ? bq.z : bq.w), floor_v);
-                    }
-                    d[q][0] = pack_bf16(v[0], v[1]); d[q][1] = pack_bf16(v[2], v[3]);
-                }
-#pragma unroll
-                for (int u = 0; u < 2; ++u) {
-                    const int qq = 2 * u;
-                    const auto sx = __builtin_amdgcn_permlane32_swap(d[qq][0], d[qq + 1][0], false, false);
-                    const auto sy = __builtin_amdgcn_permlane32_swap(d[qq][1], d[qq + 1][1], false, false);
-                    uint4 o = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-                    if (EPI == HS_DX && g.aux) {
-                        auto keep = [](unsigned a) {
-                            const unsigned lo = (int)(short)(a & 0xffffu) > 0 ? 0xffffu : 0u;
-                            const unsigned hi = (int)a > 0xffff ? 0xffff0000u : 0u;
-                            return lo | hi;
-                        };
-                        o.x &= keep(mask[u].x); o.y &= keep(mask[u].y); o.z &= keep(mask[u].z); o.w &= keep(mask[u].w);
-                    }
-#if defined(VAEK_HS_ABLATE) && (VAEK_HS_ABLATE & 2)      // diagnostic: no output stores (values kept alive)
-                    asm volatile("" ::"v"(o.x), "v"(o.y), "v"(o.z), "v"(o.w));
-#else
-                    if (row_ok) *reinterpret_cast<uint4*>(g.C + rowoff + nj + 16 * u + 8 * h) = o;
-#endif
-                }
-            }
-        }
+        hs_nt_epilogue<EPI, T, false, const HsArgs&>(g, acc, m0 + wm * (BM / WM), nbase, lane, bias4, nullptr);
     };
 
     // ---- one flat stream of k-tiles over all of this workgroup's output tiles: q = tile j * nt + kt --------------------
@@ -433,43 +240,21 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_nt_p_kernel(const HsArgs g) {
 #pragma unroll
     for (int qq = 0; qq < NS - 1; ++qq) if (issued < Q) { issue_next(qq); ++issued; }
     int slot = 0, fill = NS - 1, cj = 0;
-    zero_acc();
+    acc.zero();
     load_bias(cn0);
     for (int q = 0; q < Q; ++q) {
         // loads of the stores of an earlier epilogue count in vmcnt too, but they are OLDER than every tile in flight, so
         // "at most P * newer outstanding" still implies tile q has landed
-        wait_tiles<P, NS - 2>(min(NS - 2, Q - 1 - q));
-        __builtin_amdgcn_s_barrier();
+        T::wait_tile(Q - 1 - q);
         const bool more = issued < Q;
         if (!late && more) issue_next(fill);
-        const char* base = smem + slot * BUF;
-#pragma unroll
-        for (int s = 0; s < BK / 16; ++s) {
-            bf16x8 fa[TM], fb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(base + a_lo + i * 32 * RB + ((32 * s) ^ a_x6));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(base + b_lo + j * 32 * RB + ((32 * s) ^ b_x6));
-#if defined(VAEK_HS_ABLATE) && (VAEK_HS_ABLATE & 1)      // diagnostic (tools/hs_ablate.sh): no MFMAs, operands kept alive
-#pragma unroll
-            for (int i = 0; i < TM; ++i) asm volatile("" ::"v"(fa[i]));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) asm volatile("" ::"v"(fb[j]));
-#else
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-#endif
-        }
+        acc.multiply(smem + slot * T::BUF, frag);
         if (late && more) issue_next(fill);
         if (more) ++issued;
-        slot = slot + 1 == NS ? 0 : slot + 1;
-        fill = fill + 1 == NS ? 0 : fill + 1;
+        T::advance(slot, fill);
         if (++ckt == nt) {                               // this output tile is complete (the next one's loads are already in flight)
             epilogue(cm0, cn0);
-            zero_acc();
+            acc.zero();
             ckt = 0; ++cj;
             if (cj < my_tiles) { tile_of(cj, cm0, cn0); load_bias(cn0); }
         }
@@ -645,7 +430,7 @@ __global__ __launch_bounds__(2 * BM + 64 * LW) void hs_tn_kernel(const HsDwArgs 
                 for (int j = 0; j < 2; ++j) accb[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, fb[j], accb[j], 0, 0, 0);
             }
         }
-        slot = slot + 1 == NS ? 0 : slot + 1;
+        slot = slot + 1 == NS ? 0 : slot + 1;      // (spelled out, not HsTile::advance: profiles/hs_tile_core.txt, section 3)
         fill = fill + 1 == NS ? 0 : fill + 1;
     }
     // ---- slab store: register r of tile (i, j) = G[m0 + 64 wm + 32 i + (r & 3) + 8 (r >> 2) + 4 h][n0 + 64 wn + 32 j + (lane & 31)]
@@ -684,12 +469,8 @@ struct HsConvArgs {
 };
 template <int MODE, int BN, int WM, int WN, int BK, int NS, int BM = 128>
 __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs g) {
-    constexpr int NTH = 64 * WM * WN;
-    constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-    constexpr int RB = 2 * BK, CPR = BK / 8;
-    constexpr int A_BYTES = BM * RB, B_BYTES = BN * RB, BUF = A_BYTES + B_BYTES;
-    constexpr int A_PASSES = BM * CPR / NTH, B_PASSES = BN * CPR / NTH, P = A_PASSES + B_PASSES;
-    static_assert(BM * CPR % NTH == 0 && BN * CPR % NTH == 0 && B_PASSES >= 1, "whole staging passes");
+    using T = HsTile<BM, BN, WM, WN, BK, NS>;
+    constexpr int TM = T::TM, TN = T::TN, A_PASSES = T::A_PASSES, B_PASSES = T::B_PASSES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // T: the four parity classes of a tile are neighbours in the launch order -- they read the same input pixels (one HBM read, three L2 hits)
     // XCD-aware order (workgroups are dealt round-robin over the 8 XCDs, each with its own L2): every XCD gets a contiguous run of
@@ -703,15 +484,13 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs 
     const int t = threadIdx.x, lane = t & 63;
     const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
     const int wm = wv / WN, wn = wv % WN;
-    auto swz = [](int row) { return BK == 64 ? (row >> 1) & 7 : (row >> 2) & 3; };
     const int cmask = g.Cin - 1;
     const bool pow2 = g.sh_hw >= 0 && g.sh_wo >= 0;      // (uniform: config 5's image sizes)
 
     int a_n[A_PASSES], a_y[A_PASSES], a_x[A_PASSES], a_c[A_PASSES];
 #pragma unroll
     for (int i = 0; i < A_PASSES; ++i) {
-        const int p = i * NTH + t, row = p / CPR;
-        a_c[i] = ((p % CPR) ^ swz(row)) * 8;
+        int row; T::stage_pos(t, i, row, a_c[i]);
         const int m = min(m0 + row, g.M - 1);
         int n, ij, ii, jj;
         if (pow2) { n = m >> g.sh_hw; ij = m & (g.hw - 1); ii = ij >> g.sh_wo; jj = ij & (g.wo - 1); }
@@ -723,13 +502,12 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs 
     const __bf16* b_src[B_PASSES]; int b_c[B_PASSES], b_row[B_PASSES];
 #pragma unroll
     for (int i = 0; i < B_PASSES; ++i) {
-        const int p = i * NTH + t, row = p / CPR;
-        b_c[i] = ((p % CPR) ^ swz(row)) * 8;
+        int row; T::stage_pos(t, i, row, b_c[i]);
         b_row[i] = min(n0 + row, g.N - 1);
         b_src[i] = g.Wb + (long long)b_row[i] * g.K + b_c[i];
     }
     auto stage = [&](int kt, int slot) {
-        char* base = smem + slot * BUF;
+        char* base = smem + slot * T::BUF;
 #pragma unroll
         for (int i = 0; i < A_PASSES; ++i) {
             const int k = kt * BK + a_c[i], tap = k >> g.sh_c, ch = k & cmask;
@@ -737,7 +515,7 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs 
             const int xx = MODE == HC_FWD ? a_x[i] + (tap & 3) : a_x[i] - (tap & 1);
             const bool in = (unsigned)yy < (unsigned)g.H && (unsigned)xx < (unsigned)g.W;
             const __bf16* src = in ? g.X + (((long long)(a_n[i] + yy * g.W + xx)) << g.sh_c) + ch : g.zeros;
-            glds16(src, base + (i * NTH + wv * 64) * 16);
+            glds16(src, base + T::stage_dst(wv, i));
         }
 #pragma unroll
         for (int i = 0; i < B_PASSES; ++i) {
@@ -748,22 +526,13 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs 
                 const int kh = 1 - pp + 2 * (tap >> 1), kw = 1 - qq + 2 * (tap & 1);
                 src = g.Wb + ((long long)((kh * 4 + kw) * g.Cout + b_row[i]) << g.sh_c) + ch;
             }
-            glds16(src, base + A_BYTES + (i * NTH + wv * 64) * 16);
+            glds16(src, base + T::A_BYTES + T::stage_dst(wv, i));
         }
     };
     const int r = lane & 31, h = lane >> 5;
-    const int arow = wm * (BM / WM) + r, brow = wn * (BN / WN) + r;
-    const int ax = swz(arow), bx = swz(brow);
-    const int a_lo = arow * RB + ((h ^ ax) & 1) * 16, a_x6 = (ax & 6) * 16;
-    const int b_lo = brow * RB + ((h ^ bx) & 1) * 16 + A_BYTES, b_x6 = (bx & 6) * 16;
-
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
+    const typename T::Frag frag(wm, wn, lane);
+    typename T::Acc acc;
+    acc.zero();
 
     // the epilogue's row offsets; with a small register tile the relu mask is fetched NOW, under the whole main loop (a workgroup of
     // these shapes sees only 4-16 k-tiles: a mask fetched in the epilogue is one more exposed HBM round trip per tile)
@@ -785,8 +554,7 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs 
     auto mask_at = [&](long long e) {                      // four mask values at element e: float32, or the bf16 copy widened
         if (g.mask16) {
             const uint2 u = *reinterpret_cast<const uint2*>(g.mask16 + e);
-            return make_float4(__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
-                               __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u));
+            return make_float4(bf16_lo(u.x), bf16_hi(u.x), bf16_lo(u.y), bf16_hi(u.y));
         }
         return *reinterpret_cast<const float4*>(g.mask + e);
     };
@@ -805,25 +573,10 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs 
     for (int q = 0; q < NS - 1; ++q) if (q < nt) stage(q, q);
     int slot = 0, fill = NS - 1;
     for (int kt = 0; kt < nt; ++kt) {
-        wait_tiles<P, NS - 2>(min(NS - 2, nt - 1 - kt));
-        __builtin_amdgcn_s_barrier();
+        T::wait_tile(nt - 1 - kt);
         if (kt + NS - 1 < nt) stage(kt + NS - 1, fill);
-        const char* base = smem + slot * BUF;
-#pragma unroll
-        for (int s = 0; s < BK / 16; ++s) {
-            bf16x8 fa[TM], fb[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(base + a_lo + i * 32 * RB + ((32 * s) ^ a_x6));
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(base + b_lo + j * 32 * RB + ((32 * s) ^ b_x6));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
-        }
-        slot = slot + 1 == NS ? 0 : slot + 1;
-        fill = fill + 1 == NS ? 0 : fill + 1;
+        acc.multiply(smem + slot * T::BUF, frag);
+        T::advance(slot, fill);
     }
 
     // ---- epilogue: register 4 q + p of tile (i, j) = C[row][nbase + 32 j + 8 q + 4 h + p]
@@ -838,7 +591,7 @@ __global__ __launch_bounds__(64 * WM * WN) void hs_conv_kernel(const HsConvArgs 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int col = nbase + 32 * j + 8 * q + 4 * h;
-                float4 v = make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
+                float4 v = make_float4(acc.v[i][j][4 * q], acc.v[i][j][4 * q + 1], acc.v[i][j][4 * q + 2], acc.v[i][j][4 * q + 3]);
                 if (g.bias) {
                     const float4 b = *reinterpret_cast<const float4*>(g.bias + col);
                     v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
@@ -947,10 +700,7 @@ static int hs_launch_nt(const HsArgs& g, const char* label, hipStream_t st) {
     const HsNtVariant& v = kNt[vi];
     const HsNtKernel fn = EPI == HS_FWD ? v.fwd : v.dx;
     static thread_local PerDeviceOnce attr_set[2][kNtCount];
-    if (attr_set[EPI][vi].need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds));
-        attr_set[EPI][vi].mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set[EPI][vi], fn, v.lds));
     unsigned grid = (unsigned)(((g.M + v.bm - 1) / v.bm) * ((g.N + v.bn - 1) / v.bn));
     if (v.persistent) grid = std::min(grid, 256u);         // one resident workgroup per CU walks the tiles
     ProfScope ps(label, st);
@@ -990,10 +740,7 @@ int launch_hs_dw(const __bf16* x, const __bf16* dy, float* slab0, int64_t slab_s
     const HsTnVariant& v = kTn[vi];
     g.tiles_m = (n_in + v.bm - 1) / v.bm; g.tiles_n = (n_out + 127) / 128;
     static thread_local PerDeviceOnce attr_set[kTnCount];
-    if (attr_set[vi].need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)v.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds));
-        attr_set[vi].mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set[vi], v.fn, v.lds));
     ProfScope ps("gemm_bf16s_dw", st);
     launch_k(ps, v.fn, dim3((unsigned)(g.tiles_m * g.tiles_n * S)), dim3(v.nth ? v.nth : 2 * v.bm), v.lds, st, g);
     VAEK_HIP_CHECK(hipGetLastError());
@@ -1035,7 +782,7 @@ int launch_hs_conv_dw(const __bf16* x, const __bf16* dy, const __bf16* zeros, fl
     const auto fn = narrow ? hs_tn_kernel<64, 2, true, true> : hs_tn_kernel<64, 2, true>;
     const size_t lds = 2 * 2 * 64 * 256;
     static thread_local PerDeviceOnce attr_set[2];
-    if (attr_set[narrow].need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set[narrow].mark(); }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set[narrow], fn, lds));
     ProfScope ps("conv_wgrad_bf16s", st);
     launch_k(ps, fn, dim3((unsigned)(g.tiles_m * g.tiles_n * S)), dim3(256), lds, st, g);
     VAEK_HIP_CHECK(hipGetLastError());
@@ -1048,7 +795,7 @@ static int hs_conv_launch(const HsConvArgs& g, hipStream_t st) {
     const auto fn = hs_conv_kernel<MODE, BN, WM, WN, BK, NS, BM>;
     constexpr size_t lds = (size_t)NS * (BM + BN) * 2 * BK;
     static thread_local PerDeviceOnce attr_set;
-    if (attr_set.need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); attr_set.mark(); }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set, fn, lds));
     ProfScope ps(MODE == HC_FWD ? "conv_fwd_bf16s" : "conv_t_fwd_bf16s", st);
     launch_k(ps, fn, dim3((unsigned)(((g.M + BM - 1) / BM) * (g.N / BN)) * (MODE == HC_T ? 4u : 1u)), dim3(64 * WM * WN), lds, st, g);
     VAEK_HIP_CHECK(hipGetLastError());

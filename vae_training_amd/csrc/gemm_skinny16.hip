@@ -19,27 +19,16 @@
 // Batch reductions (G) are per-workgroup register sums -> one partial image per workgroup -> sk_partials_reduce sums fixed
 // groups of 64 partials in fixed order into the layer's S slabs (flat-gradient layout, as every other dW kernel writes them):
 // no atomics, bitwise repeatable.
-#include "vaek_internal.h"
+#include "hs_tile_dev.h"      // the vector types, glds16, pack_bf16, bf16_lo / bf16_hi
 
 namespace vaek {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x2 = __attribute__((ext_vector_type(2))) __bf16;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) void glb_void_t;
 
-__device__ __forceinline__ unsigned sk_pack(float lo, float hi) {
-    const bf16x2 v = {(__bf16)lo, (__bf16)hi};
-    return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ void sk_unpack8(const uint4 u, float (&f)[8]) {      // bf16 -> f32 is a 16-bit shift
-    f[0] = __builtin_bit_cast(float, u.x << 16); f[1] = __builtin_bit_cast(float, u.x & 0xffff0000u);
-    f[2] = __builtin_bit_cast(float, u.y << 16); f[3] = __builtin_bit_cast(float, u.y & 0xffff0000u);
-    f[4] = __builtin_bit_cast(float, u.z << 16); f[5] = __builtin_bit_cast(float, u.z & 0xffff0000u);
-    f[6] = __builtin_bit_cast(float, u.w << 16); f[7] = __builtin_bit_cast(float, u.w & 0xffff0000u);
+__device__ __forceinline__ void sk_unpack8(const uint4 u, float (&f)[8]) {
+    f[0] = bf16_lo(u.x); f[1] = bf16_hi(u.x); f[2] = bf16_lo(u.y); f[3] = bf16_hi(u.y);
+    f[4] = bf16_lo(u.z); f[5] = bf16_hi(u.z); f[6] = bf16_lo(u.w); f[7] = bf16_hi(u.w);
 }
 
 // ---- first layer forward ------------------------------------------------------------------------------------------------
@@ -88,7 +77,7 @@ __global__ __launch_bounds__(256) void sk_first_fwd_kernel(const SkFwdArgs a) {
             for (int j = 0; j < 8; ++j) o[j] = fmaxf(o[j], floor_v);
             if (rr < a.rows)
                 *reinterpret_cast<uint4*>(a.y + rr * a.H + 8 * chunk) =
-                    make_uint4(sk_pack(o[0], o[1]), sk_pack(o[2], o[3]), sk_pack(o[4], o[5]), sk_pack(o[6], o[7]));
+                    make_uint4(pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7]));
         }
     }
 }
@@ -227,7 +216,7 @@ __global__ __launch_bounds__(256) void sk_last_bwd_kernel(const SkBwdArgs a) {
                 for (int n = 0; n < DP; ++n) gb[n] += dyv[u][n];
                 if (in)
                     *reinterpret_cast<uint4*>(a.dh + rr * a.H + 8 * chunk) =
-                        make_uint4(sk_pack(o[0], o[1]), sk_pack(o[2], o[3]), sk_pack(o[4], o[5]), sk_pack(o[6], o[7]));
+                        make_uint4(pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7]));
             }
         }
     // the rpp row phases of a column chunk: phases 1.. park their sums in LDS, phase 0 adds them in order
@@ -279,15 +268,8 @@ __global__ __launch_bounds__(256) void sk_last_bwd_kernel(const SkBwdArgs a) {
 // rows_per_wg a multiple of 16 (the host checks): every piece starts on a 16-byte boundary.
 // FIRST: the first layer's [x | 1]^T dY instead -- the same G product with big = dY, small = x and a ones column behind x's d
 // (its row of the image is the bias gradient); no dh.
-// One 1 KB LDS-DMA piece in inline assembly: through the builtin hipcc knows that LDS is being written and puts s_waitcnt vmcnt(0)
-// in front of every later LDS read it cannot tell apart -- the ring below was drained four times per block (ISA; 36 us per launch).
-// The waits are this kernel's own (counted) ones.
-__device__ __forceinline__ void sk_glds16(const void* gsrc, void* lds_wave_base) {
-    const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(lds_void_t*)lds_wave_base);
-    _Pragma("clang diagnostic push") _Pragma("clang diagnostic ignored \"-Winline-asm\"")      // (M0 on the clobber list: it is what the LDS-DMA takes its LDS address from)
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(m0v) : "memory", "m0");
-    _Pragma("clang diagnostic pop")
-}
+// The 1 KB LDS-DMA pieces are glds16 (hs_tile_dev.h: inline assembly, so that the compiler puts no s_waitcnt vmcnt(0) of its own
+// in front of the LDS reads and drains the ring).  The waits are this kernel's own (counted) ones.
 template <int NT, bool FIRST = false>
 __global__ __launch_bounds__(256) void sk_last_bwd_mfma_kernel(const SkBwdArgs a) {
     extern __shared__ __attribute__((aligned(1024))) float sk_lds[];
@@ -311,11 +293,11 @@ __global__ __launch_bounds__(256) void sk_last_bwd_mfma_kernel(const SkBwdArgs a
         for (int i = 0; i < RPW; ++i) {
             const int piece = wave * RPW + i, row = piece / (2 * H / 1024), part = piece % (2 * H / 1024);
             const long long rr = min(rb + row, r1 - 1);
-            sk_glds16(reinterpret_cast<const char*>(a.big) + rr * (2 * H) + part * 1024 + lane * 16, slot + row * RS + part * 1024);
+            glds16(reinterpret_cast<const char*>(a.big) + rr * (2 * H) + part * 1024 + lane * 16, slot + row * RS + part * 1024);
         }
         if (wave == 0) {                                       // ... and the 16 d floats of dy behind them (clamped inside the tensor)
             const long long off = min(rb * d * 4 + lane * 16, (long long)a.rows * d * 4 - 16);
-            sk_glds16(reinterpret_cast<const char*>(a.small) + off, slot + 16 * RS);
+            glds16(reinterpret_cast<const char*>(a.small) + off, slot + 16 * RS);
         }
     };
     // A of the dh product: this wave's W rows in the paired order, k = n
@@ -393,7 +375,7 @@ __global__ __launch_bounds__(256) void sk_last_bwd_mfma_kernel(const SkBwdArgs a
             for (int r = 0; r < 4; ++r) { o[r] = hf[r] > 0.f ? o0[r] : 0.f; o[4 + r] = hf[4 + r] > 0.f ? o1[r] : 0.f; }
             if (rb + c < r1) {
                 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 pk = {sk_pack(o[0], o[1]), sk_pack(o[2], o[3]), sk_pack(o[4], o[5]), sk_pack(o[6], o[7])};
+                const u32x4 pk = {pack_bf16(o[0], o[1]), pack_bf16(o[2], o[3]), pack_bf16(o[4], o[5]), pack_bf16(o[6], o[7])};
                 // (a store the compiler does not count: its own waits must not drain the LDS-DMA pieces in flight)
                 asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(a.dh + (rb + c) * H + hc), "v"(pk) : "memory");
             }
@@ -608,18 +590,18 @@ int launch_sk_last_bwd(const __bf16* h, const float* dy, const float* w, __bf16*
         ProfScope ps("sk16_last_bwd", st);
         const size_t lds_m = (size_t)4 * (16 * (2 * H + 32) + 1024);
         static thread_local PerDeviceOnce setm;
-        if (setm.need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)sk_last_bwd_mfma_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); setm.mark(); }
+        VAEK_HIP_CHECK(set_max_dynamic_lds(setm, sk_last_bwd_mfma_kernel<8>, 160 * 1024));
         launch_k(ps, sk_last_bwd_mfma_kernel<8>, dim3(nwg), dim3(256), lds_m, st, a);
         VAEK_HIP_CHECK(hipGetLastError());
     } else {
         ProfScope ps("sk16_last_bwd", st);
         if (d <= 8) {
             static thread_local PerDeviceOnce set8;
-            if (set8.need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)sk_last_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set8.mark(); }
+            VAEK_HIP_CHECK(set_max_dynamic_lds(set8, sk_last_bwd_kernel<8>, 160 * 1024));
             launch_k(ps, sk_last_bwd_kernel<8>, dim3(nwg), dim3(256), lds, st, a);
         } else {
             static thread_local PerDeviceOnce set16;
-            if (set16.need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)sk_last_bwd_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set16.mark(); }
+            VAEK_HIP_CHECK(set_max_dynamic_lds(set16, sk_last_bwd_kernel<16>, 160 * 1024));
             launch_k(ps, sk_last_bwd_kernel<16>, dim3(nwg), dim3(256), lds, st, a);
         }
         VAEK_HIP_CHECK(hipGetLastError());
@@ -638,18 +620,18 @@ int launch_sk_first_bwd(const float* x, const __bf16* dy, float* partial, float*
         ProfScope ps("sk16_first_bwd", st);
         const size_t lds_m = (size_t)4 * (16 * (2 * H + 32) + 1024);
         static thread_local PerDeviceOnce setm;
-        if (setm.need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)sk_last_bwd_mfma_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); setm.mark(); }
+        VAEK_HIP_CHECK(set_max_dynamic_lds(setm, sk_last_bwd_mfma_kernel<8, true>, 160 * 1024));
         launch_k(ps, sk_last_bwd_mfma_kernel<8, true>, dim3(nwg), dim3(256), lds_m, st, a);
         VAEK_HIP_CHECK(hipGetLastError());
     } else {
         ProfScope ps("sk16_first_bwd", st);
         if (d <= 8) {
             static thread_local PerDeviceOnce set8;
-            if (set8.need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)sk_first_bwd_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set8.mark(); }
+            VAEK_HIP_CHECK(set_max_dynamic_lds(set8, sk_first_bwd_kernel<8>, 160 * 1024));
             launch_k(ps, sk_first_bwd_kernel<8>, dim3(nwg), dim3(256), lds, st, a);
         } else {
             static thread_local PerDeviceOnce set16;
-            if (set16.need()) { VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)sk_first_bwd_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); set16.mark(); }
+            VAEK_HIP_CHECK(set_max_dynamic_lds(set16, sk_first_bwd_kernel<16>, 160 * 1024));
             launch_k(ps, sk_first_bwd_kernel<16>, dim3(nwg), dim3(256), lds, st, a);
         }
         VAEK_HIP_CHECK(hipGetLastError());

@@ -155,10 +155,7 @@ static const LinPersistGenKernel kLinPersistGen[] = {lin_persist_kernel<3, 12, 2
 static const LinStepKernel kLinStep[] = {lin_step_kernel<3, 0, 0>, lin_step_kernel<4, 0, 0>, lin_step_kernel<3, 12, 20>};
 template <typename K, size_t N> static int lin_kernel(const K (&table)[N], int which, K* fn) {
     static thread_local PerDeviceOnce attr_set[N];
-    if (attr_set[which].need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)table[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLinMaxLds));
-        attr_set[which].mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set[which], table[which], kLinMaxLds));
     *fn = table[which];
     return VAEK_OK;
 }

@@ -651,12 +651,8 @@ int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, floa
     const size_t lds = var->base_bytes + (in_lds ? stage_bytes(c) : 0);
     static thread_local PerDeviceOnce attr_set[2][sizeof(kResidentVariants) / sizeof(kResidentVariants[0])];      // [traced]: two kernels
     PerDeviceOnce& once = attr_set[traj ? 1 : 0][var - kResidentVariants];
-    if (lds > 64 * 1024 && once.need()) {
-        // the most this variant ever asks for (the batch image grows with the batch, which another context may have larger)
-        VAEK_HIP_CHECK(hipFuncSetAttribute(traj ? (const void*)var->fn_traj : (const void*)var->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)kLdsLimit));
-        once.mark();
-    }
+    if (lds > 64 * 1024)      // the most this variant ever asks for (the batch image grows with the batch, which another context may have larger)
+        VAEK_HIP_CHECK(set_max_dynamic_lds(once, traj ? (const void*)var->fn_traj : (const void*)var->fn, kLdsLimit));
     ResidentArgs a{};
     a.params = params; a.grads = grads; a.m = m; a.v = v; a.step_dev = step_dev;
     a.stage = in_lds ? nullptr : reinterpret_cast<float*>(static_cast<char*>(ws) + c->ws_resident);
@@ -698,11 +694,8 @@ int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float
     const size_t lds = var->base_bytes + (in_lds ? stage_bytes(c) : 0);
     static thread_local PerDeviceOnce attr_set[2][sizeof(kResidentVariants) / sizeof(kResidentVariants[0])];      // [traced]: two kernels
     PerDeviceOnce& once = attr_set[traj ? 1 : 0][var - kResidentVariants];
-    if (lds > 64 * 1024 && once.need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute(traj ? (const void*)var->fn_replicas_traj : (const void*)var->fn_replicas,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLimit));
-        once.mark();
-    }
+    if (lds > 64 * 1024)
+        VAEK_HIP_CHECK(set_max_dynamic_lds(once, traj ? (const void*)var->fn_replicas_traj : (const void*)var->fn_replicas, kLdsLimit));
     ResidentArgs a{};
     a.params = params; a.grads = grads; a.m = m; a.v = v; a.step_dev = step_dev;
     a.stage = in_lds ? nullptr : static_cast<float*>(ws);

@@ -395,10 +395,7 @@ int vaek_mlp3_decoder_jacobian_replicas(vaek_ctx* ctx, const float* params, cons
 
     constexpr size_t lds = sizeof(float) * 2 * ML_W * MJ_NC;
     static thread_local PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)mlp3_jacobian_tangent_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set.mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set, mlp3_jacobian_tangent_kernel, lds));
     hipStream_t st = (hipStream_t)stream;
     {
         ProfScope ps("mlp3_jacobian_tangent", st);

@@ -291,10 +291,7 @@ int vaek_mlp3_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const 
 
     constexpr size_t lds_enc = sizeof(float) * 2 * ML_W * ML_ENC_NC, lds_smp = sizeof(float) * 2 * ML_W * ML_NC;
     static thread_local PerDeviceOnce attr_set;
-    if (attr_set.need()) {
-        VAEK_HIP_CHECK(hipFuncSetAttribute((const void*)mlp3_loglik_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_smp));
-        attr_set.mark();
-    }
+    VAEK_HIP_CHECK(set_max_dynamic_lds(attr_set, mlp3_loglik_sample_kernel, lds_smp));
     hipStream_t st = (hipStream_t)stream;
     {
         ProfScope ps("mlp3_loglik_encode", st);

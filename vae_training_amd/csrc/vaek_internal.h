@@ -311,6 +311,13 @@ struct PerDeviceOnce {
     bool need() const { const int d = slot(); return !(mask[d >> 6] >> (d & 63) & 1ull); }
     void mark() { const int d = slot(); mask[d >> 6] |= 1ull << (d & 63); }
 };
+// Its use: raise a kernel's dynamic-LDS limit on the current device, the first time `once` sees that device.
+template <class Kernel> inline hipError_t set_max_dynamic_lds(PerDeviceOnce& once, Kernel fn, size_t bytes) {
+    if (!once.need()) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) once.mark();
+    return e;
+}
 int launch_hs_conv(int mode, const __bf16* x, const __bf16* wb, const __bf16* zeros, const float* bias, const float* mask, const __bf16* mask16,
                    float* out, __bf16* out16, int batch, int H, int W, int Cin, int Cout, bool relu, hipStream_t st);      // mode 0: forward, 1: transposed
 int launch_hs_conv_dw(const __bf16* x, const __bf16* dy, const __bf16* zeros, float* slab0, int64_t slab_stride, int S, int rows_per_split,
