@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "vaek_internal.h"
+
 namespace vaek {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
@@ -40,6 +42,9 @@ struct MGeom {
     static constexpr int R_PER_WAVE = NBLK * 256 + NCS + 4;
     static constexpr int R_FLOATS = NW * R_PER_WAVE;
     static constexpr int LDS_FLOATS = (T_FLOATS > R_FLOATS ? T_FLOATS : R_FLOATS);
+    // the flat gradient of the padded shape: every parameter, then the kExtra loss slots; thread t of 256 owns t, t + 256, ...
+    static constexpr int PMAX = DP * LP + LP + (SIG ? 2 : 1) * (LP * DP + DP) + LP + 1 + kExtra;
+    static constexpr int NOUT = (PMAX + 255) / 256;
 };
 
 // (DP, LP, SIG, EXACT) of every instantiation; a context takes the smallest that holds it (EXACT: only its own D, L)
@@ -54,5 +59,19 @@ struct MGeom {
 #else
 #define VAEK_MFMA_SHAPES(X) X(12, 20, 0, 1)
 #endif
+
+// The row of a variant table built from VAEK_MFMA_SHAPES (fields dp, lp, sig, exact) that a context takes: the smallest padded shape
+// that holds it and whose `bytes` field fits the LDS of a CU.
+constexpr size_t kLdsLimit = 160 * 1024;
+template <class V, size_t N>
+const V* pick_shape(const V (&table)[N], const vaek_ctx* c, size_t V::*bytes) {
+    const V* best = nullptr;
+    for (const V& v : table) {
+        if (v.sig != (c->cfg.sigmoid_decoder ? 1 : 0) || v.dp < c->D || v.lp < c->L || v.*bytes > kLdsLimit) continue;
+        if (v.exact && (v.dp != c->D || v.lp != c->L)) continue;
+        if (!best || v.dp * v.lp < best->dp * best->lp) best = &v;
+    }
+    return best;
+}
 
 }  // namespace vaek
