@@ -8,7 +8,7 @@
 #include <new>
 #include <utility>
 
-#include "eval_check.h"      // check_struct_size, check_replica_count of the train-loop entry points; vaek_internal.h through it
+#include "eval_check.h"      // the checks of the training entry points and their order; vaek_internal.h through it
 
 namespace vaek {
 
@@ -718,9 +718,8 @@ int vaek_adam_step(vaek_ctx* ctx, float* params, const float* grads, float* m, f
 int vaek_train_step_grads_only(vaek_ctx* ctx, const float* params, float* grads, int32_t* step_dev, const float* x,
                                const float* z1, const float* z2, void* workspace, void* stream) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !step_dev || !x || !z1 || !z2) { set_error("vaek_train_step_grads_only: null argument"); return VAEK_ERR_INVALID; }
-    int rc = check_ws(ctx, workspace);
-    if (rc) return rc;
+    int rc = check_train_state("vaek_train_step_grads_only", ctx, params, grads, nullptr, nullptr, step_dev, 0, false);
+    if (rc || (rc = check_given("vaek_train_step_grads_only", "x", x, "z1", z1, "z2", z2)) || (rc = check_ws(ctx, workspace))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (ctx->fused)
         return whole_step(ctx, const_cast<float*>(params), grads, nullptr, nullptr, step_dev, x, z1, z2, 0.f, false,
@@ -732,16 +731,15 @@ int vaek_train_step_grads_only(vaek_ctx* ctx, const float* params, float* grads,
 int vaek_train_step_apply(vaek_ctx* ctx, float* params, const float* grads, float* m, float* v,
                           const int32_t* step_dev, float lr, void* stream) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev) { set_error("vaek_train_step_apply: null argument"); return VAEK_ERR_INVALID; }
+    if (int rc = check_train_state("vaek_train_step_apply", ctx, params, grads, m, v, step_dev)) return rc;
     return launch_adam(params, grads, m, v, ctx->P, lr, 0, step_dev, 1.f, (hipStream_t)stream);
 }
 
 int vaek_train_step(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x,
                     const float* z1, const float* z2, float lr, void* workspace, void* stream) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev || !x || !z1 || !z2) { set_error("vaek_train_step: null argument"); return VAEK_ERR_INVALID; }
-    int rc = check_ws(ctx, workspace);
-    if (rc) return rc;
+    int rc = check_train_state("vaek_train_step", ctx, params, grads, m, v, step_dev);
+    if (rc || (rc = check_given("vaek_train_step", "x", x, "z1", z1, "z2", z2)) || (rc = check_ws(ctx, workspace))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (ctx->cfg.world > 1) {
         if (!ctx->comm.ready) {
@@ -768,19 +766,17 @@ int vaek_train_step_gen(vaek_ctx* ctx, float* params, float* grads, float* m, fl
                         int32_t did, int32_t pad, float var_added, float* x_next, float* z1_next, float* z2_next, int64_t row0,
                         uint64_t seed, int32_t* counter, int32_t which, uint32_t tag, void* stream) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev || !x || !z1 || !z2 || !x_next || !z1_next || !z2_next || !counter) {
-        set_error("vaek_train_step_gen: null argument");
-        return VAEK_ERR_INVALID;
-    }
+    const char* const who = "vaek_train_step_gen";
+    int rc = check_train_state(who, ctx, params, grads, m, v, step_dev);
+    if (rc || (rc = check_given(who, "x", x, "z1", z1, "z2", z2, "x_next", x_next, "z1_next", z1_next, "z2_next", z2_next, "counter", counter))) return rc;
     if (x_next == x || z1_next == z1 || z2_next == z2) {
-        set_error("vaek_train_step_gen: the next batch must not alias the current one");
+        set_error("%s: the next batch must not alias the current one", who);
         return VAEK_ERR_INVALID;
     }
-    BatchArgs gen;
-    int rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, x_next, z1_next, z2_next, ctx->B, row0, seed, nullptr, 0, counter,
-                             which, tag, &gen);
-    if (rc) return rc;
-    if ((rc = check_ws(ctx, workspace))) return rc;
+    BatchArgs gen;      // a draw to memory: vaek_make_batch_next's check, under its name
+    if ((rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, x_next, z1_next, z2_next, ctx->B, row0, seed, nullptr, 0, counter, which, tag, &gen)) ||
+        (rc = check_ws(ctx, workspace)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool comm_ok = ctx->cfg.world == 1 || (ctx->comm.ready && !ctx->mlp3);
     if (ctx->fused && comm_ok)
@@ -799,13 +795,13 @@ int vaek_supports_train_steps(const vaek_ctx* ctx, int32_t* yes) {
 int vaek_train_steps(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* const* xs,
                      const float* const* z1s, const float* const* z2s, int32_t n_steps, float lr, void* workspace, void* stream) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev || !xs || !z1s || !z2s || n_steps < 0) { set_error("vaek_train_steps: invalid argument"); return VAEK_ERR_INVALID; }
+    int rc = check_train_state("vaek_train_steps", ctx, params, grads, m, v, step_dev, n_steps);
+    if (rc || (rc = check_given("vaek_train_steps", "xs", xs, "z1s", z1s, "z2s", z2s))) return rc;
     if (!lin_steps_supported(ctx)) {
         set_error("vaek_train_steps: this context is not a single-GPU float32 linear VAE with L + 2 D + 1 <= 64 (use vaek_train_step)");
         return VAEK_ERR_INVALID;
     }
-    int rc = check_ws(ctx, workspace);
-    if (rc) return rc;
+    if ((rc = check_ws(ctx, workspace))) return rc;
     for (int i = 0; i < n_steps; ++i)
         if (!xs[i] || !z1s[i] || !z2s[i] || ((reinterpret_cast<uintptr_t>(xs[i]) | reinterpret_cast<uintptr_t>(z1s[i]) | reinterpret_cast<uintptr_t>(z2s[i])) & 15)) {
             set_error("vaek_train_steps: batch %d has a null or not 16-byte aligned pointer", i);
@@ -825,18 +821,16 @@ int vaek_train_steps_gen(vaek_ctx* ctx, float* params, float* grads, float* m, f
                          int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
                          float lr, void* workspace, void* stream) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev || n_steps < 0) { set_error("vaek_train_steps_gen: invalid argument"); return VAEK_ERR_INVALID; }
+    int rc = check_train_state("vaek_train_steps_gen", ctx, params, grads, m, v, step_dev, n_steps);
+    if (rc) return rc;
     if (!lin_steps_gen_supported(ctx, kind)) {
         set_error("vaek_train_steps_gen: needs a context vaek_train_steps' persistent form covers and dataset kind 0 or 2 (use vaek_train_step_gen)");
         return VAEK_ERR_INVALID;
     }
-    int rc = check_ws(ctx, workspace);
-    if (rc) return rc;
     BatchArgs gen;
-    // (the generator's own output pointers stay unused: a dummy non-null x / z pair passes its argument check)
-    float* dummy = reinterpret_cast<float*>(workspace);
-    if ((rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, dummy, dummy, dummy, ctx->B, row0, seed, step_dev, 0, nullptr, 0, tag, &gen))) return rc;
-    gen.x = gen.z1 = gen.z2 = nullptr;
+    if ((rc = check_train_draw("vaek_train_steps_gen", ctx, kind, A, dd, did, pad, var_added, row0, seed, step_dev, tag, &gen)) ||
+        (rc = check_ws(ctx, workspace)))
+        return rc;
     if (n_steps == 0) return VAEK_OK;
     return lin_train_steps_gen(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream);
 }
@@ -845,28 +839,6 @@ int vaek_supports_train_loop_gen(const vaek_ctx* ctx, int32_t kind, int32_t* yes
     if (!ctx || !yes) { set_error("null argument"); return VAEK_ERR_INVALID; }
     *yes = ctx->resident && kind >= 0 && kind <= 2 ? 1 : 0;
     return VAEK_OK;
-}
-
-int vaek_train_loop_gen(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
-                        int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
-                        float lr, void* workspace, void* stream) {
-    ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev || n_steps < 0) { set_error("vaek_train_loop_gen: invalid argument"); return VAEK_ERR_INVALID; }
-    if (!ctx->resident) {
-        set_error("vaek_train_loop_gen: needs a single-GPU float32 linear VAE (no hidden layers, one or two decoders) with D, L <= 32 and "
-                  "1 <= batch <= 256 (use vaek_train_step_gen)");
-        return VAEK_ERR_INVALID;
-    }
-    int rc = check_ws(ctx, workspace);
-    if (rc) return rc;
-    BatchArgs gen;
-    // (the kernel points the generator at its own batch image: a dummy non-null x / z pair passes the argument check,
-    // which also fences kind to 0 .. 2 and dd, did to <= 16)
-    float* dummy = reinterpret_cast<float*>(workspace);
-    if ((rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, dummy, dummy, dummy, ctx->B, row0, seed, step_dev, 0, nullptr, 0, tag, &gen))) return rc;
-    gen.x = gen.z1 = gen.z2 = nullptr;
-    if (n_steps == 0) return VAEK_OK;
-    return resident_train_loop(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream);
 }
 
 int vaek_train_loop_steps_per_launch(void) { return resident_steps_per_launch(); }
@@ -889,10 +861,13 @@ int vaek_trajectory_record_len(const vaek_ctx* ctx, int64_t* floats) {
     return VAEK_OK;
 }
 
+static const char* const kLoopNeeds = "needs a single-GPU float32 linear VAE (no hidden layers, one or two decoders) with D, L <= 32 and "
+                                      "1 <= batch <= 256 (see vaek_supports_train_loop_gen; else vaek_train_step_gen)";
+
 // A vaek_trajectory checked against the context (`replicas`: the replica form, where replica_stride counts) and turned into the
-// kernel's TrajArgs: after it every store of the launch lands inside the caller's ring.  Needs a non-null context.
+// kernel's TrajArgs: after it every store of the launch lands inside the caller's ring.  Needs a non-null context; its struct_size
+// was checked before the context (eval_check.h).
 static int check_trajectory(const char* who, const vaek_ctx* ctx, const vaek_trajectory* traj, bool replicas, TrajArgs* out) {
-    if (int rc = check_struct_size(who, "vaek_trajectory", traj->struct_size, sizeof(vaek_trajectory))) return rc;
     const int64_t len = 2 * (int64_t)ctx->P + kExtra;
     if (traj->every < 1) { set_error("%s: trajectory every = %d, need >= 1", who, traj->every); return VAEK_ERR_INVALID; }
     if (traj->cap < 1) { set_error("%s: trajectory cap = %lld, need >= 1", who, (long long)traj->cap); return VAEK_ERR_INVALID; }
@@ -916,91 +891,59 @@ static int check_trajectory(const char* who, const vaek_ctx* ctx, const vaek_tra
     return VAEK_OK;
 }
 
-// vaek_train_loop_gen_replicas (traj == nullptr) and vaek_train_loop_gen_replicas_traj: one list of checks, in one order
-static int train_loop_gen_replicas_impl(const char* who, vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
-                                        const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                                        float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream,
-                                        const vaek_trajectory* traj) {
+// The two loop pairs: the traced entry is the implementation, and traj == nullptr the untraced one, answering in its own name
+int vaek_train_loop_gen_replicas_traj(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
+                                      const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
+                                      float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream,
+                                      const vaek_trajectory* traj) {
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev || !rep || n_steps < 0) {
-        set_error("%s: invalid argument", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_struct_size(who, "vaek_replicas", rep->struct_size, sizeof(vaek_replicas))) return rc;
-    if (!ctx->resident) {
-        set_error("%s: needs a context vaek_train_loop_gen covers (see vaek_supports_train_loop_gen)", who);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_replica_count(who, rep->n)) return rc;
-    if (rep->state_stride < ctx->P || rep->grads_stride < ctx->P + kExtra) {
-        set_error("%s: state_stride %lld < P = %lld or grads_stride %lld < grad_len = %lld", who, (long long)rep->state_stride,
-                  (long long)ctx->P, (long long)rep->grads_stride, (long long)(ctx->P + kExtra));
-        return VAEK_ERR_INVALID;
-    }
-    if (!rep->seeds) { set_error("%s: seeds is NULL", who); return VAEK_ERR_INVALID; }
-    if (rep->a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)rep->a_stride); return VAEK_ERR_INVALID; }
-    if (rep->loss_hist && rep->loss_hist_cap < 1) {
-        set_error("%s: loss_hist given with loss_hist_cap %lld < 1", who, (long long)rep->loss_hist_cap);
-        return VAEK_ERR_INVALID;
-    }
+    const char* const who = traj ? "vaek_train_loop_gen_replicas_traj" : "vaek_train_loop_gen_replicas";
+    const ReplicaRules rules{ctx && ctx->resident, kLoopNeeds, resident_max_replicas(), "vaek_train_loop_max_replicas", false, true};
+    int rc = check_replicas(who, ctx, params, grads, m, v, step_dev, n_steps, rep, traj, rules);
+    TrajArgs tj{};
+    BatchArgs gen;      // (the kernel puts seeds[r] in place of the seed)
+    if (rc || (traj && (rc = check_trajectory(who, ctx, traj, true, &tj))) ||
+        (rc = check_train_draw(who, ctx, kind, A, dd, did, pad, var_added, row0, 0, step_dev, tag, &gen)))
+        return rc;
     const size_t ws_bytes = resident_replicas_workspace_bytes(ctx, rep->n);
     if (ws_bytes && (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15))) {
         set_error("%s: this context stages its batches in memory: workspace must be a 16-byte aligned device "
                   "pointer of vaek_train_loop_replicas_workspace_bytes() = %zu bytes", who, ws_bytes);
         return VAEK_ERR_INVALID;
     }
-    TrajArgs tj{};
-    if (traj) { const int trc = check_trajectory(who, ctx, traj, true, &tj); if (trc) return trc; }
-    BatchArgs gen;
-    // (as vaek_train_loop_gen: the kernel points the generator at its own batch image, and puts seeds[r] in place of the seed; the
-    // dummy non-null x / z pair passes the argument check, which also fences kind to 0 .. 2 and dd, did to <= 16)
-    float* dummy = params;
-    int rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, dummy, dummy, dummy, ctx->B, row0, 0, step_dev, 0, nullptr, 0, tag, &gen);
-    if (rc) return rc;
-    gen.x = gen.z1 = gen.z2 = nullptr;
     if (n_steps == 0) return VAEK_OK;
-    return resident_train_loop_replicas(ctx, params, grads, m, v, step_dev, gen, rep->n, rep->state_stride, rep->grads_stride,
-                                        reinterpret_cast<const unsigned long long*>(rep->seeds), rep->lrs, rep->a_stride, rep->loss_hist,
-                                        rep->loss_hist_cap, n_steps, lr, workspace, (hipStream_t)stream, traj ? &tj : nullptr);
+    return resident_train_loop(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream, rep, traj ? &tj : nullptr);
 }
 
 int vaek_train_loop_gen_replicas(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
                                  const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
                                  float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream) {
-    return train_loop_gen_replicas_impl("vaek_train_loop_gen_replicas", ctx, params, grads, m, v, step_dev, rep, kind, A, dd, did, pad, var_added,
-                                        row0, tag, n_steps, lr, workspace, stream, nullptr);
-}
-
-int vaek_train_loop_gen_replicas_traj(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev,
-                                      const vaek_replicas* rep, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                                      float var_added, int64_t row0, uint32_t tag, int32_t n_steps, float lr, void* workspace, void* stream,
-                                      const vaek_trajectory* traj) {
-    return train_loop_gen_replicas_impl(traj ? "vaek_train_loop_gen_replicas_traj" : "vaek_train_loop_gen_replicas", ctx, params, grads, m, v,
-                                        step_dev, rep, kind, A, dd, did, pad, var_added, row0, tag, n_steps, lr, workspace, stream, traj);
+    return vaek_train_loop_gen_replicas_traj(ctx, params, grads, m, v, step_dev, rep, kind, A, dd, did, pad, var_added, row0, tag, n_steps, lr,
+                                             workspace, stream, nullptr);
 }
 
 int vaek_train_loop_gen_traj(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
                              int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
                              float lr, void* workspace, void* stream, const vaek_trajectory* traj) {
-    if (!traj) return vaek_train_loop_gen(ctx, params, grads, m, v, step_dev, kind, A, dd, did, pad, var_added, row0, seed, tag, n_steps, lr,
-                                          workspace, stream);
     ProfBind pb(ctx);
-    if (!ctx || !params || !grads || !m || !v || !step_dev || n_steps < 0) { set_error("vaek_train_loop_gen_traj: invalid argument"); return VAEK_ERR_INVALID; }
-    if (!ctx->resident) {
-        set_error("vaek_train_loop_gen_traj: needs a context vaek_train_loop_gen covers (see vaek_supports_train_loop_gen)");
-        return VAEK_ERR_INVALID;
-    }
+    const char* const who = traj ? "vaek_train_loop_gen_traj" : "vaek_train_loop_gen";
+    int rc = traj ? check_struct_size(who, "vaek_trajectory", traj->struct_size, sizeof(vaek_trajectory)) : VAEK_OK;
+    if (rc || (rc = check_train_state(who, ctx, params, grads, m, v, step_dev, n_steps))) return rc;
+    if (!ctx->resident) { set_error("%s: %s", who, kLoopNeeds); return VAEK_ERR_INVALID; }
     TrajArgs tj{};
-    int rc = check_trajectory("vaek_train_loop_gen_traj", ctx, traj, false, &tj);
-    if (rc) return rc;
-    if ((rc = check_ws(ctx, workspace))) return rc;
     BatchArgs gen;
-    // (as vaek_train_loop_gen: a dummy non-null x / z pair passes the generator's argument check)
-    float* dummy = reinterpret_cast<float*>(workspace);
-    if ((rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, dummy, dummy, dummy, ctx->B, row0, seed, step_dev, 0, nullptr, 0, tag, &gen))) return rc;
-    gen.x = gen.z1 = gen.z2 = nullptr;
+    if ((traj && (rc = check_trajectory(who, ctx, traj, false, &tj))) ||
+        (rc = check_train_draw(who, ctx, kind, A, dd, did, pad, var_added, row0, seed, step_dev, tag, &gen)) || (rc = check_ws(ctx, workspace)))
+        return rc;
     if (n_steps == 0) return VAEK_OK;
-    return resident_train_loop(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream, &tj);
+    return resident_train_loop(ctx, params, grads, m, v, step_dev, gen, n_steps, lr, workspace, (hipStream_t)stream, nullptr, traj ? &tj : nullptr);
+}
+
+int vaek_train_loop_gen(vaek_ctx* ctx, float* params, float* grads, float* m, float* v, int32_t* step_dev, int32_t kind, const float* A,
+                        int32_t dd, int32_t did, int32_t pad, float var_added, int64_t row0, uint64_t seed, uint32_t tag, int32_t n_steps,
+                        float lr, void* workspace, void* stream) {
+    return vaek_train_loop_gen_traj(ctx, params, grads, m, v, step_dev, kind, A, dd, did, pad, var_added, row0, seed, tag, n_steps, lr, workspace,
+                                    stream, nullptr);
 }
 
 // ---- the replica form of the mlp3 step (fused_mlp3.hip): n models of one shape per step, blockIdx.y = replica ----------------------
@@ -1027,60 +970,31 @@ int vaek_train_step_gen_replicas(vaek_ctx* ctx, float* params, float* grads, flo
                                  float* z1_next, float* z2_next, int64_t row0, int32_t* counter, int32_t which, uint32_t tag, void* stream) {
     ProfBind pb(ctx);
     const char* const fn = "vaek_train_step_gen_replicas";
-    if (!ctx || !params || !grads || !m || !v || !step_dev || !rep || !x || !z1 || !z2) {
-        set_error("%s: null argument", fn);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_struct_size(fn, "vaek_replicas", rep->struct_size, sizeof(vaek_replicas))) return rc;
-    if (!ctx->mlp3 || ctx->cfg.world != 1) {
-        set_error("%s: needs a single-GPU context whose train step path is \"mlp3\" (see vaek_supports_train_step_replicas)", fn);
-        return VAEK_ERR_INVALID;
-    }
-    if (rep->n < 1 || rep->n > mlp3_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_step_max_replicas)", fn, rep->n, mlp3_max_replicas());
-        return VAEK_ERR_INVALID;
-    }
-    if (rep->state_stride < ctx->P || rep->state_stride % 4 != 0) {
-        // a multiple of 4 floats: every replica's parameters then have the base pointer's 16-byte alignment, so every replica takes the
-        // dX load form a solo call on its slice would take (the two forms are not bitwise equal)
-        set_error("%s: state_stride %lld must be >= P = %lld and a multiple of 4", fn, (long long)rep->state_stride, (long long)ctx->P);
-        return VAEK_ERR_INVALID;
-    }
-    if (rep->grads_stride < ctx->P + kExtra) {
-        set_error("%s: grads_stride %lld < grad_len = %lld", fn, (long long)rep->grads_stride, (long long)(ctx->P + kExtra));
-        return VAEK_ERR_INVALID;
-    }
-    if (rep->loss_hist && rep->loss_hist_cap < 1) {
-        set_error("%s: loss_hist given with loss_hist_cap %lld < 1", fn, (long long)rep->loss_hist_cap);
-        return VAEK_ERR_INVALID;
-    }
-    if (rep->a_stride < 0) { set_error("%s: a_stride %lld < 0", fn, (long long)rep->a_stride); return VAEK_ERR_INVALID; }
-    if (dd > 16 || did > 16) { set_error("%s: dd %d or did %d > 16", fn, dd, did); return VAEK_ERR_INVALID; }
-    const int n_next = (x_next ? 1 : 0) + (z1_next ? 1 : 0) + (z2_next ? 1 : 0);
+    const int n_next = (x_next ? 1 : 0) + (z1_next ? 1 : 0) + (z2_next ? 1 : 0);      // 3: the drawing form, which reads seeds and counter
+    const ReplicaRules rules{ctx && ctx->mlp3 && ctx->cfg.world == 1,
+                             "needs a single-GPU context whose train step path is \"mlp3\" (see vaek_supports_train_step_replicas)",
+                             mlp3_max_replicas(), "vaek_train_step_max_replicas", true, n_next == 3};
+    int rc = check_replicas(fn, ctx, params, grads, m, v, step_dev, 0, rep, nullptr, rules);
+    if (rc || (rc = check_given(fn, "x", x, "z1", z1, "z2", z2))) return rc;
     if (n_next != 0 && n_next != 3) {
         set_error("%s: x_next, z1_next and z2_next must be all NULL (no draw) or all given", fn);
         return VAEK_ERR_INVALID;
     }
+    if (n_next && (rc = check_given(fn, "counter", counter))) return rc;
+    if (n_next && (x_next == x || z1_next == z1 || z2_next == z2)) {
+        set_error("%s: the next batch must not alias the current one", fn);
+        return VAEK_ERR_INVALID;
+    }
+    if (dd > 16 || did > 16) { set_error("%s: dd %d or did %d > 16", fn, dd, did); return VAEK_ERR_INVALID; }
+    BatchArgs gen;      // a draw to memory: vaek_make_batch_next's check, under its name (the kernel puts seeds[r] in place of the seed)
+    if (n_next && (rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, x_next, z1_next, z2_next, ctx->B, row0, 0, nullptr, 0, counter, which, tag, &gen)))
+        return rc;
     if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 15)) {
         set_error("%s: workspace must be a 16-byte aligned device pointer of vaek_train_step_replicas_workspace_bytes() = %zu bytes", fn,
                   mlp3_replicas_workspace_bytes(ctx, rep->n));
         return VAEK_ERR_INVALID;
     }
-    BatchArgs gen;
-    if (n_next) {
-        if (!rep->seeds || !counter) { set_error("%s: the drawing form needs seeds and counter", fn); return VAEK_ERR_INVALID; }
-        if (x_next == x || z1_next == z1 || z2_next == z2) {
-            set_error("%s: the next batch must not alias the current one", fn);
-            return VAEK_ERR_INVALID;
-        }
-        // (the kernel puts seeds[r] in place of the seed; this also fences kind to 0 .. 2, `which` to 0 / 1 and the dataset dimension)
-        int rc = make_batch_args(ctx, kind, A, dd, did, pad, var_added, x_next, z1_next, z2_next, ctx->B, row0, 0, nullptr, 0, counter, which,
-                                 tag, &gen);
-        if (rc) return rc;
-    }
-    return mlp3_train_step_replicas(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, workspace, (hipStream_t)stream, n_next ? &gen : nullptr,
-                                    rep->n, rep->state_stride, rep->grads_stride, reinterpret_cast<const unsigned long long*>(rep->seeds),
-                                    rep->lrs, rep->a_stride, rep->loss_hist, rep->loss_hist_cap);
+    return mlp3_train_step_replicas(ctx, params, grads, m, v, step_dev, x, z1, z2, lr, workspace, (hipStream_t)stream, n_next ? &gen : nullptr, *rep);
 }
 
 int vaek_train_steps_moment_len(const vaek_ctx* ctx, int64_t* len) {

@@ -234,7 +234,7 @@ typedef void (*SpectrumKernel)(const SpectrumArgs);
 struct SpectrumVariant { int dp, lp, sig; SpectrumKernel fn, fn_vec; };
 #define VAEK_SPECTRUM_ROW(DP, LP, SIG, EXACT) \
     {up4(DP), up4(LP), SIG, spectrum_event_kernel<up4(DP), up4(LP), (SIG) != 0>, spectrum_event_kernel<up4(DP), up4(LP), (SIG) != 0, true>},
-static const SpectrumVariant kSpectrumVariants[] = {VAEK_MFMA_SHAPES(VAEK_SPECTRUM_ROW)};
+static const SpectrumVariant kSpectrumVariants[] = {VAEK_EVAL_SHAPES(VAEK_SPECTRUM_ROW)};
 #undef VAEK_SPECTRUM_ROW
 
 // vaek_supports_log_likelihood's predicate: float32, no hidden layers, one or two decoders, D, L <= 32, D <= 28 with two decoders

@@ -17,11 +17,13 @@ constexpr int kLogLikMaxRows = 4096;         // rows per call and ...
 constexpr int kLogLikMaxSamples = 1024;      // ... samples per row: they bound one launch on a shared machine -- caps, not tuned values
 
 // the dataset arguments of an in-kernel draw under tag x_tag, as `who` refuses them: a_stride, kind, A, dd / did / pad, dimension, tag
+// (empty_did: a linear_gaussian dataset of did < 1 latent dimensions passes, as it always has in the training calls)
 int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                       int64_t a_stride, uint32_t x_tag);
-// ... and the BatchArgs of that draw: kind, A, dd, did, pad, noise_std, tag, rows, D, L; seed / step / pointers are the kernel's
+                       int64_t a_stride, uint32_t x_tag, bool empty_did = false);
+// ... and the BatchArgs of that draw: kind, A, dd, did, pad, noise_std, tag, rows, D, L, and the stream a training kernel draws from
+// (row0, seed, step_dev; an evaluation kernel puts in its own); the pointers are the kernel's
 void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                    float var_added, uint32_t x_tag);
+                    float var_added, uint32_t x_tag, int64_t row0 = 0, uint64_t seed = 0, const int32_t* step_dev = nullptr);
 
 // Hidden: the library's dynamic symbol list gains nothing.  (The two above were exported before this block existed, as every vaek::
 // function is -- the library is built without -fvisibility=hidden -- and stay so.)
@@ -67,7 +69,7 @@ void fill_rows_source(BatchArgs* gen, long long* a_stride_out, const vaek_ctx* c
                       int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, int64_t a_stride);
 
 // One range check per counted quantity, for a call and for its workspace query alike
-int check_replica_count(const char* who, int32_t n);                                                           // 1 .. resident_max_replicas()
+int check_replica_count(const char* who, int32_t n, int cap = resident_max_replicas(), const char* cap_query = "vaek_train_loop_max_replicas");
 int check_row_count(const char* who, int32_t rows, int rows_min, int rows_cap, const char* rows_query);
 int check_sample_count(const char* who, int32_t samples);                                                      // 1 .. kLogLikMaxSamples
 // n * rows * per_row columns (`unit`: what per_row counts) against `cap`
@@ -77,6 +79,34 @@ int check_struct_size(const char* who, const char* name, int32_t got, size_t wan
 int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows); // explicit rows: 0 (shared) or >= rows * D
 int check_tag(const char* who, uint32_t tag);                                             // >= 2^30
 int check_aligned8(const char* who, const char* what, uintptr_t addrs);                   // `addrs`: the outputs `what` names, ORed
+
+// ---- the training entry points of api.hip ----------------------------------------------------------------------------------------------
+// The seven whose batches a generator feeds (vaek_train_step_gen, vaek_train_steps_gen, vaek_train_loop_gen[_traj],
+// vaek_train_loop_gen_replicas[_traj], vaek_train_step_gen_replicas) refuse in this order, with the first that fails:
+//    1. a NULL vaek_replicas                                      6. the vaek_replicas fields: n, state_stride, grads_stride, seeds,
+//    2. its struct_size, then a given vaek_trajectory's              a_stride, loss_hist_cap -- a message each
+//    3. a NULL context                                            7. the vaek_trajectory fields
+//    4. a NULL params / grads / m / v / step_dev, n_steps < 0     8. the entry's own pointers and aliasing rules
+//    5. a context the entry does not cover                        9. the dataset draw
+//                                                                10. the workspace
+// An entry without a description starts at 3; the four calls that are handed their batches run 3 and 4, then their own checks.
+// the first NULL of (name, pointer) pairs, named
+inline int check_given(const char*) { return VAEK_OK; }
+template <class... Rest>
+int check_given(const char* who, const char* name, const void* p, Rest... rest) {
+    if (!p) { set_error("%s: %s is NULL", who, name); return VAEK_ERR_INVALID; }
+    return check_given(who, rest...);
+}
+// 3 and 4 (moments false: a call without m and v)
+int check_train_state(const char* who, const vaek_ctx* ctx, const float* params, const float* grads, const float* m, const float* v,
+                      const int32_t* step_dev, int32_t n_steps = 0, bool moments = true);
+// 1 .. 6 of the two replica calls; a `_query` is the name of the function a message points to
+struct ReplicaRules { bool covered; const char* needs; int cap; const char* cap_query; bool stride4, reads_seeds; };
+int check_replicas(const char* who, const vaek_ctx* ctx, const float* params, const float* grads, const float* m, const float* v,
+                   const int32_t* step_dev, int32_t n_steps, const vaek_replicas* rep, const vaek_trajectory* traj, const ReplicaRules& r);
+// 9 for the calls whose kernel draws its own batches of ctx->B rows: the dataset arguments checked and made into the kernel's BatchArgs
+int check_train_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, float var_added,
+                     int64_t row0, uint64_t seed, const int32_t* step_dev, uint32_t tag, BatchArgs* gen);
 #pragma GCC visibility pop
 
 }  // namespace vaek

@@ -1,5 +1,5 @@
 // Host only: the one refusal list of the evaluation entry points (eval_check.h), the adapters of the seven description structs and
-// the small checks they and the train-loop entry points of api.hip share.  No kernels.
+// the small checks they and the training entry points of api.hip share, and those entry points' own list.  No kernels.
 #include "eval_check.h"
 
 namespace vaek {
@@ -129,9 +129,9 @@ void fill_rows_source(BatchArgs* gen, long long* a_stride_out, const vaek_ctx* c
 }
 
 // ---- the counted quantities ------------------------------------------------------------------------------------------------------------
-int check_replica_count(const char* who, int32_t n) {
-    if (n < 1 || n > resident_max_replicas()) {
-        set_error("%s: %d replicas, need 1 .. %d (vaek_train_loop_max_replicas)", who, n, resident_max_replicas());
+int check_replica_count(const char* who, int32_t n, int cap, const char* cap_query) {
+    if (n < 1 || n > cap) {
+        set_error("%s: %d replicas, need 1 .. %d (%s)", who, n, cap, cap_query);
         return VAEK_ERR_INVALID;
     }
     return VAEK_OK;
@@ -164,11 +164,11 @@ int check_column_count(const char* who, int32_t n, int32_t rows, int32_t per_row
 
 // ---- the in-kernel dataset draw --------------------------------------------------------------------------------------------------------
 int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                       int64_t a_stride, uint32_t x_tag) {
+                       int64_t a_stride, uint32_t x_tag, bool empty_did) {
     if (a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)a_stride); return VAEK_ERR_INVALID; }
     if (kind < 0 || kind > 2) { set_error("%s: kind %d outside 0 .. 2", who, kind); return VAEK_ERR_INVALID; }
     if (kind != 2 && !A) { set_error("%s: A is NULL (only kind 2 has no matrix)", who); return VAEK_ERR_INVALID; }
-    if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1) || pad < 0) {
+    if (dd < 1 || dd > 16 || did > 16 || (kind == 0 && did < 1 && !empty_did) || pad < 0) {
         set_error("%s: dd = %d, did = %d, pad = %d: need 1 <= dd <= 16, did <= 16, pad >= 0", who, dd, did, pad);
         return VAEK_ERR_INVALID;
     }
@@ -180,10 +180,11 @@ int check_dataset_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const
 }
 
 void fill_draw_args(BatchArgs* g, const vaek_ctx* ctx, int rows, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad,
-                    float var_added, uint32_t x_tag) {
+                    float var_added, uint32_t x_tag, int64_t row0, uint64_t seed, const int32_t* step_dev) {
     g->kind = kind; g->A = kind == 2 ? nullptr : A; g->dd = dd; g->did = did; g->pad = pad;
     g->noise_std = var_added > 0.f ? sqrtf(var_added) : 0.f;
-    g->rows = rows; g->row0 = 0; g->D = ctx->D; g->L = ctx->L; g->tag = x_tag;
+    g->rows = rows; g->row0 = row0; g->D = ctx->D; g->L = ctx->L; g->tag = x_tag;
+    g->seed = seed; g->step_dev = step_dev;
 }
 
 // ---- the small checks, also the train-loop entry points' -------------------------------------------------------------------------------
@@ -206,6 +207,52 @@ int check_tag(const char* who, uint32_t tag) {
 
 int check_aligned8(const char* who, const char* what, uintptr_t addrs) {
     if ((addrs & 7u) != 0) { set_error("%s: %s is not 8-byte aligned", who, what); return VAEK_ERR_INVALID; }
+    return VAEK_OK;
+}
+
+// ---- the training entry points (the order is in eval_check.h) -------------------------------------------------------------------------
+int check_train_state(const char* who, const vaek_ctx* ctx, const float* params, const float* grads, const float* m, const float* v,
+                      const int32_t* step_dev, int32_t n_steps, bool moments) {
+    if (!ctx) { set_error("%s: null context", who); return VAEK_ERR_INVALID; }
+    if (int rc = moments ? check_given(who, "params", params, "grads", grads, "m", m, "v", v, "step_dev", step_dev)
+                         : check_given(who, "params", params, "grads", grads, "step_dev", step_dev)) return rc;
+    if (n_steps < 0) { set_error("%s: n_steps %d < 0", who, n_steps); return VAEK_ERR_INVALID; }
+    return VAEK_OK;
+}
+
+int check_replicas(const char* who, const vaek_ctx* ctx, const float* params, const float* grads, const float* m, const float* v,
+                   const int32_t* step_dev, int32_t n_steps, const vaek_replicas* rep, const vaek_trajectory* traj, const ReplicaRules& r) {
+    if (!rep) { set_error("%s: null description", who); return VAEK_ERR_INVALID; }
+    if (int rc = check_struct_size(who, "vaek_replicas", rep->struct_size, sizeof(vaek_replicas))) return rc;
+    if (traj)
+        if (int rc = check_struct_size(who, "vaek_trajectory", traj->struct_size, sizeof(vaek_trajectory))) return rc;
+    if (int rc = check_train_state(who, ctx, params, grads, m, v, step_dev, n_steps)) return rc;
+    if (!r.covered) { set_error("%s: %s", who, r.needs); return VAEK_ERR_INVALID; }
+    if (int rc = check_replica_count(who, rep->n, r.cap, r.cap_query)) return rc;
+    // (stride4: every replica's parameters then have the base pointer's 16-byte alignment and take the load form a solo call would)
+    if (rep->state_stride < ctx->P || (r.stride4 && rep->state_stride % 4 != 0)) {
+        set_error("%s: state_stride %lld: need >= P = %lld (vaek_param_count)%s", who, (long long)rep->state_stride, (long long)ctx->P,
+                  r.stride4 ? " and a multiple of 4" : "");
+        return VAEK_ERR_INVALID;
+    }
+    if (rep->grads_stride < ctx->P + kExtra) {
+        set_error("%s: grads_stride %lld < grad_len = %lld (vaek_grad_len)", who, (long long)rep->grads_stride, (long long)(ctx->P + kExtra));
+        return VAEK_ERR_INVALID;
+    }
+    if (r.reads_seeds && !rep->seeds) { set_error("%s: seeds is NULL", who); return VAEK_ERR_INVALID; }
+    if (rep->a_stride < 0) { set_error("%s: a_stride %lld < 0", who, (long long)rep->a_stride); return VAEK_ERR_INVALID; }
+    if (rep->loss_hist && rep->loss_hist_cap < 1) {
+        set_error("%s: loss_hist given with loss_hist_cap %lld < 1", who, (long long)rep->loss_hist_cap);
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_train_draw(const char* who, const vaek_ctx* ctx, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, float var_added,
+                     int64_t row0, uint64_t seed, const int32_t* step_dev, uint32_t tag, BatchArgs* gen) {
+    if (int rc = check_dataset_draw(who, ctx, kind, A, dd, did, pad, 0, tag, true)) return rc;
+    *gen = BatchArgs{};
+    fill_draw_args(gen, ctx, ctx->B, kind, A, dd, did, pad, var_added, tag, row0, seed, step_dev);
     return VAEK_OK;
 }
 

@@ -15,7 +15,7 @@ constexpr int kLogLikSums = 3;               // float64 row sums
 
 constexpr int up4(int n) { return (n + 3) & ~3; }
 
-// the smallest padded shape of a variant table ({dp, lp, sig, fn} rows, built from VAEK_MFMA_SHAPES) that holds (D, L)
+// the smallest padded shape of a variant table ({dp, lp, sig, fn} rows, built from VAEK_EVAL_SHAPES) that holds (D, L)
 template <typename V, int N>
 const V* pick_smallest_shape(const V (&table)[N], int D, int L, bool sig) {
     const V* best = nullptr;

@@ -223,7 +223,7 @@ struct ExactLogLikVariant { int dp, lp, sig; ExactLogLikKernel fn; };
 template <int DP, int LP, int SIG> struct ExactLogLikPick { static constexpr ExactLogLikKernel fn = exact_loglik_kernel<DP, LP>; };
 template <int DP, int LP> struct ExactLogLikPick<DP, LP, 1> { static constexpr ExactLogLikKernel fn = nullptr; };
 #define VAEK_EXACT_ROW(DP, LP, SIG, EXACT) {up4(DP), up4(LP), SIG, ExactLogLikPick<up4(DP), up4(LP), SIG>::fn},
-static const ExactLogLikVariant kExactLogLikVariants[] = {VAEK_MFMA_SHAPES(VAEK_EXACT_ROW)};
+static const ExactLogLikVariant kExactLogLikVariants[] = {VAEK_EVAL_SHAPES(VAEK_EXACT_ROW)};
 #undef VAEK_EXACT_ROW
 
 // vaek_supports_log_likelihood's predicate AND one decoder: the sigmoid second decoder has no closed form

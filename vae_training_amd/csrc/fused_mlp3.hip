@@ -468,15 +468,13 @@ size_t mlp3_replica_region_floats(const vaek_ctx* c) { return ((mlp3_workspace_b
 size_t mlp3_replicas_workspace_bytes(const vaek_ctx* c, int n) { return (size_t)n * mlp3_replica_region_floats(c) * sizeof(float); }
 
 int mlp3_train_step_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x,
-                             const float* z1, const float* z2, float lr, void* ws, hipStream_t st, const BatchArgs* gen, int n,
-                             long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
-                             long long a_stride, float* loss_hist, long long loss_hist_cap) {
+                             const float* z1, const float* z2, float lr, void* ws, hipStream_t st, const BatchArgs* gen, const vaek_replicas& r) {
     Mlp3ReplicaHost rep{};
-    rep.n = n;
-    rep.rp.state_stride = state_stride; rep.rp.grads_stride = grads_stride; rep.rp.a_stride = a_stride;
+    rep.n = r.n;
+    rep.rp.state_stride = r.state_stride; rep.rp.grads_stride = r.grads_stride; rep.rp.a_stride = r.a_stride;
     rep.rp.region_floats = (long long)mlp3_replica_region_floats(c);
-    rep.rp.seeds = seeds; rep.rp.lrs = lrs;
-    rep.loss_hist = loss_hist; rep.loss_hist_cap = loss_hist_cap;
+    rep.rp.seeds = reinterpret_cast<const unsigned long long*>(r.seeds); rep.rp.lrs = r.lrs;
+    rep.loss_hist = r.loss_hist; rep.loss_hist_cap = r.loss_hist_cap;
     return mlp3_step_impl(c, params, grads, m, v, step_dev, x, z1, z2, lr, true, ws, st, gen, &rep);
 }
 

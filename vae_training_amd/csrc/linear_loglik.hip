@@ -190,7 +190,7 @@ __global__ __launch_bounds__(64) void loglik_finalize_kernel(const LogLikFinalAr
 typedef void (*LogLikKernel)(const LogLikArgs);
 struct LogLikVariant { int dp, lp, sig; LogLikKernel fn; };
 #define VAEK_LOGLIK_ROW(DP, LP, SIG, EXACT) {up4(DP), up4(LP), SIG, linear_loglik_kernel<up4(DP), up4(LP), (SIG) != 0>},
-static const LogLikVariant kLogLikVariants[] = {VAEK_MFMA_SHAPES(VAEK_LOGLIK_ROW)};
+static const LogLikVariant kLogLikVariants[] = {VAEK_EVAL_SHAPES(VAEK_LOGLIK_ROW)};
 #undef VAEK_LOGLIK_ROW
 
 // float32, no hidden layers, one or two decoders, a padded shape holds (D, L); two decoders: D <= 28, the bound of every other

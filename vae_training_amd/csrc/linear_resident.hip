@@ -282,6 +282,11 @@ struct ResidentVariant {
      linear_resident_kernel<DP, LP, (SIG) != 0, (EXACT) != 0, ReplicaArgs, TrajArgs>},
 static const ResidentVariant kResidentVariants[] = {VAEK_MFMA_SHAPES(VAEK_RESIDENT_ROW)};
 #undef VAEK_RESIDENT_ROW
+// every row can be picked: its operand and parameter images fit the LDS of a CU (pick_shape skips a row that does not)
+#define VAEK_RESIDENT_FITS(DP, LP, SIG, EXACT) \
+    static_assert(sizeof(float) * RGeom<DP, LP, (SIG) != 0>::BASE_FLOATS <= kLdsLimit, "a resident variant no context can take");
+VAEK_MFMA_SHAPES(VAEK_RESIDENT_FITS)
+#undef VAEK_RESIDENT_FITS
 
 static const ResidentVariant* pick_resident(const vaek_ctx* c) { return pick_shape(kResidentVariants, c, &ResidentVariant::base_bytes); }
 
@@ -303,7 +308,7 @@ size_t resident_workspace_bytes(const vaek_ctx* c) {
 
 int resident_steps_per_launch() { return kResidentMaxSteps; }
 
-// What both forms do before their launches: pick the variant, size its LDS (raising the kernel's limit the first time a device sees
+// What every form does before its launches: pick the variant, size its LDS (raising the kernel's limit the first time a device sees
 // it), and fill the launch arguments.  ws + ws_offset: where the batch image goes if LDS has no room for it.
 struct ResidentLaunch { const ResidentVariant* var; size_t lds; ResidentArgs a; };
 static int resident_setup(vaek_ctx* c, bool replicas, const TrajArgs* traj, float* params, float* grads, float* m, float* v, int32_t* step_dev,
@@ -328,24 +333,6 @@ static int resident_setup(vaek_ctx* c, bool replicas, const TrajArgs* traj, floa
     return VAEK_OK;
 }
 
-int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
-                        int n_steps, float lr, void* ws, hipStream_t st, const TrajArgs* traj) {
-    ResidentLaunch rl;
-    if (int rc = resident_setup(c, false, traj, params, grads, m, v, step_dev, c->loss_hist, c->loss_hist_cap,
-                                ws, c->ws_resident, gen, lr, rl)) return rc;
-    ResidentArgs& a = rl.a;
-    // every launch leaves params / m / v / grads / *step_dev / the ring in HBM: the next one starts from memory alone
-    for (int left = n_steps; left > 0; left -= kResidentMaxSteps) {
-        a.n_steps = left < kResidentMaxSteps ? left : kResidentMaxSteps;
-        // the traced launch finds the slot of every record from the step counter it reads itself: nothing to carry between launches
-        ProfScope ps(traj ? "linear_resident_traj" : "linear_resident", st);
-        if (traj) launch_k(ps, rl.var->fn_traj, dim3(1), dim3(256), rl.lds, st, a, *traj);
-        else launch_k(ps, rl.var->fn, dim3(1), dim3(256), rl.lds, st, a);
-        VAEK_HIP_CHECK(hipGetLastError());
-    }
-    return VAEK_OK;
-}
-
 // ---- the replica form: vaek_train_loop_gen_replicas -------------------------------------------------------------------------
 // 1024 replicas = 4 rounds of 256 workgroups on the MI355X's 256 CUs: a cap that bounds the length of one launch on a shared
 // machine, not a tuned value.  More replicas than CUs is legal: the workgroups are independent, the extra ones queue.
@@ -357,23 +344,30 @@ int resident_max_replicas() { return kResidentMaxReplicas; }
 // 16-byte alignment of the base.
 size_t resident_replicas_workspace_bytes(const vaek_ctx* c, int n) { return (size_t)n * resident_workspace_bytes(c); }
 
-int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
-                                 int n, long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
-                                 long long a_stride, float* loss_hist, long long loss_hist_cap, int n_steps, float lr, void* ws,
-                                 hipStream_t st, const TrajArgs* traj) {
+// All four forms.  rep == nullptr: one model on the context's workspace region and ring; else rep->n of them, one workgroup each, on
+// the caller's rings and the call's own workspace, never the context's.
+int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
+                        int n_steps, float lr, void* ws, hipStream_t st, const vaek_replicas* rep, const TrajArgs* traj) {
     ResidentLaunch rl;
-    if (int rc = resident_setup(c, true, traj, params, grads, m, v, step_dev, loss_hist, loss_hist ? loss_hist_cap : 0,      // the caller's rings, never the context's
-                                ws, 0, gen, lr, rl)) return rc;
+    if (int rc = resident_setup(c, rep != nullptr, traj, params, grads, m, v, step_dev, rep ? rep->loss_hist : c->loss_hist,
+                                !rep ? c->loss_hist_cap : rep->loss_hist ? rep->loss_hist_cap : 0, ws, rep ? 0 : c->ws_resident, gen, lr, rl)) return rc;
     ResidentArgs& a = rl.a;
     ReplicaArgs rp{};
-    rp.state_stride = state_stride; rp.grads_stride = grads_stride; rp.a_stride = a_stride;
-    rp.stage_stride = stage_floats(c->B, c->D, c->L);
-    rp.seeds = seeds; rp.lrs = lrs;
+    if (rep) {
+        rp.state_stride = rep->state_stride; rp.grads_stride = rep->grads_stride; rp.a_stride = rep->a_stride;
+        rp.stage_stride = stage_floats(c->B, c->D, c->L);
+        rp.seeds = reinterpret_cast<const unsigned long long*>(rep->seeds); rp.lrs = rep->lrs;
+    }
+    const dim3 grid(rep ? (unsigned)rep->n : 1u), block(256);
+    // every launch leaves params / m / v / grads / *step_dev / the ring in HBM: the next one starts from memory alone
     for (int left = n_steps; left > 0; left -= kResidentMaxSteps) {
         a.n_steps = left < kResidentMaxSteps ? left : kResidentMaxSteps;
-        ProfScope ps(traj ? "linear_resident_replicas_traj" : "linear_resident_replicas", st);
-        if (traj) launch_k(ps, rl.var->fn_replicas_traj, dim3((unsigned)n), dim3(256), rl.lds, st, a, rp, *traj);
-        else launch_k(ps, rl.var->fn_replicas, dim3((unsigned)n), dim3(256), rl.lds, st, a, rp);
+        // the traced launch finds the slot of every record from the step counter it reads itself: nothing to carry between launches
+        ProfScope ps(rep ? (traj ? "linear_resident_replicas_traj" : "linear_resident_replicas") : traj ? "linear_resident_traj" : "linear_resident", st);
+        if (rep && traj) launch_k(ps, rl.var->fn_replicas_traj, grid, block, rl.lds, st, a, rp, *traj);
+        else if (rep) launch_k(ps, rl.var->fn_replicas, grid, block, rl.lds, st, a, rp);
+        else if (traj) launch_k(ps, rl.var->fn_traj, grid, block, rl.lds, st, a, *traj);
+        else launch_k(ps, rl.var->fn, grid, block, rl.lds, st, a);
         VAEK_HIP_CHECK(hipGetLastError());
     }
     return VAEK_OK;

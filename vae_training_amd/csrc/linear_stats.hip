@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void linear_stats_kernel(const StatsArgs a) {
 typedef void (*StatsKernel)(const StatsArgs);
 struct StatsVariant { int dp, lp, sig; StatsKernel fn; };
 #define VAEK_STATS_ROW(DP, LP, SIG, EXACT) {up4(DP), up4(LP), SIG, linear_stats_kernel<up4(DP), up4(LP), (SIG) != 0>},
-static const StatsVariant kStatsVariants[] = {VAEK_MFMA_SHAPES(VAEK_STATS_ROW)};
+static const StatsVariant kStatsVariants[] = {VAEK_EVAL_SHAPES(VAEK_STATS_ROW)};
 #undef VAEK_STATS_ROW
 
 static const StatsVariant* pick_stats(const vaek_ctx* c) { return pick_smallest_shape(kStatsVariants, c->D, c->L, c->cfg.sigmoid_decoder != 0); }

@@ -55,9 +55,13 @@ struct MGeom {
     /* zero-padded coverage of every other D, L <= 32 */                                             \
     X(16, 16, 0, 0) X(32, 32, 0, 0) X(12, 4, 0, 0)                                                   \
     /* sigmoid dataset (two decoders): sigmoid_vae_padding_expts.sh shapes */                        \
-    X(8, 8, 1, 0) X(12, 12, 1, 0) X(16, 16, 1, 0) X(20, 8, 1, 0) X(24, 16, 1, 0) X(28, 24, 1, 1) X(32, 32, 1, 0)
+    X(8, 8, 1, 0) X(12, 12, 1, 0) X(16, 16, 1, 0) X(20, 8, 1, 0) X(24, 16, 1, 0) X(28, 24, 1, 1)
+// ... and of the evaluation kernels (linear_stats / linear_loglik / cov_spectrum / exact_loglik), which keep no MGeom image in LDS and
+// so also hold the largest two-decoder shape
+#define VAEK_EVAL_SHAPES(X) VAEK_MFMA_SHAPES(X) X(32, 32, 1, 0)
 #else
 #define VAEK_MFMA_SHAPES(X) X(12, 20, 0, 1)
+#define VAEK_EVAL_SHAPES(X) VAEK_MFMA_SHAPES(X)
 #endif
 
 // The row of a variant table built from VAEK_MFMA_SHAPES (fields dp, lp, sig, exact) that a context takes: the smallest padded shape
@@ -73,5 +77,11 @@ const V* pick_shape(const V (&table)[N], const vaek_ctx* c, size_t V::*bytes) {
     }
     return best;
 }
+// ... and every row can be picked: MGeom<32, 32, true> needs 165,120 bytes, so the table has no such row, and a two-decoder shape with
+// D > 24 or L > 16 other than 28 x 24 has no matrix-core kernel
+#define VAEK_MFMA_FITS(DP, LP, SIG, EXACT) \
+    static_assert(sizeof(float) * MGeom<DP, LP, (SIG) != 0>::LDS_FLOATS <= kLdsLimit, "a matrix-core shape no context can take");
+VAEK_MFMA_SHAPES(VAEK_MFMA_FITS)
+#undef VAEK_MFMA_FITS
 
 }  // namespace vaek

@@ -399,16 +399,13 @@ struct TrajArgs {
     int every;
     long long cap, record_stride, replica_stride;
 };
-int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen, int n_steps,
-                        float lr, void* ws, hipStream_t st, const TrajArgs* traj = nullptr);
-// the same loop for n independent models of the context's shape, one workgroup each (vaek_train_loop_gen_replicas); `ws` is the
-// call's own workspace of resident_replicas_workspace_bytes(c, n) bytes, not the context's
+// rep != nullptr (a checked vaek_replicas): the same loop for rep->n independent models of the context's shape, one workgroup each
+// (vaek_train_loop_gen_replicas); `ws` is then the call's own workspace of resident_replicas_workspace_bytes(c, n) bytes, not the
+// context's, and the rings are the caller's
 int resident_max_replicas();
 size_t resident_replicas_workspace_bytes(const vaek_ctx* c, int n);
-int resident_train_loop_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen,
-                                 int n, long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
-                                 long long a_stride, float* loss_hist, long long loss_hist_cap, int n_steps, float lr, void* ws,
-                                 hipStream_t st, const TrajArgs* traj = nullptr);
+int resident_train_loop(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const BatchArgs& gen, int n_steps,
+                        float lr, void* ws, hipStream_t st, const vaek_replicas* rep, const TrajArgs* traj);
 
 // ---- rng.hip ------------------------------------------------------------------------------
 // validates the arguments of vaek_make_batch* and fills `out`
@@ -442,9 +439,7 @@ int mlp3_max_replicas();
 size_t mlp3_replica_region_floats(const vaek_ctx* c);
 size_t mlp3_replicas_workspace_bytes(const vaek_ctx* c, int n);
 int mlp3_train_step_replicas(vaek_ctx* c, float* params, float* grads, float* m, float* v, int32_t* step_dev, const float* x,
-                             const float* z1, const float* z2, float lr, void* ws, hipStream_t st, const BatchArgs* gen, int n,
-                             long long state_stride, long long grads_stride, const unsigned long long* seeds, const float* lrs,
-                             long long a_stride, float* loss_hist, long long loss_hist_cap);
+                             const float* z1, const float* z2, float lr, void* ws, hipStream_t st, const BatchArgs* gen, const vaek_replicas& rep);
 
 // ---- what the two log-likelihood calls share (linear_loglik.hip); the checks of the evaluation calls are eval_check.h's ----------
 // the last launch of both calls under the profile label `label`: n workgroups add the tile partials part[n][tiles][4] in tile order
