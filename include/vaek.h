@@ -783,8 +783,8 @@ int vaek_exact_log_likelihood_replicas(vaek_ctx* ctx, const float* params, const
  * equal, drawing mode equals explicit mode on the rows vaek_make_batch writes, nothing depends on ctx.batch.  Asynchronous on `stream`,
  * allocates nothing, does not synchronise, capturable into a hipGraph; profile labels elbo_hvp_replicas / elbo_hessian_replicas.
  * vaek_supports_elbo_hessian: vaek_supports_exact_log_likelihood's predicate (float32, no hidden layers, ONE decoder, D, L <= 32) --
- * whatever ctx.batch, world and force_generic are.  NOT covered: two-decoder and MLP models (no closed form), bf16, D or L > 32, more
- * than 32 steps, Ritz vectors, the Hessian of the sampled loss.
+ * whatever ctx.batch, world and force_generic are.  NOT covered: two-decoder and MLP models (no closed form; two-decoder linear models
+ * have vaek_sampled_elbo_hessian_lanczos_replicas below), bf16, D or L > 32, more than 32 steps, Ritz vectors.
  * VAEK_ERR_INVALID (message names the call, nothing touched): a NULL or unsupported context, NULL params or description, a wrong
  * struct_size, n or rows out of range, state_stride < P; explicit rows: x_stride < 0 or 0 < x_stride < rows * D; drawing mode: NULL
  * x_seeds or x_steps, a_stride < 0, NULL A for kind 0 or 1, dd or did > 16, dd + pad (+ 1 for kind 1) != data_dim, kind outside 0 .. 2,
@@ -840,6 +840,116 @@ int vaek_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vaek_elbo_h
                            int32_t did, int32_t pad, float var_added, uint32_t x_tag, void* stream);
 int vaek_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* params, const vaek_elbo_hessian* hs, int32_t kind, const float* A,
                                        int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, void* stream);
+/* HESSIAN OF THE SAMPLE-AVERAGE ELBO of N linear VAEs with ONE OR TWO decoders (csrc/sampled_hessian.hip): the ELBO of a model with the
+ * sigmoid second decoder has no closed form in the moments of the rows, so fix the rows AND K latent samples xi_ik per row (common random
+ * numbers): the Monte-Carlo ELBO is then a smooth deterministic function f_K of the parameters, and its gradient and Hessian-vector
+ * products are exact derivatives of that function, forward-over-reverse differentiation written out by hand.  Nothing is
+ * finite-differenced.  theta is the flat parameter vector in the leaf order E [D][L], b_e [L], K [L][D], b_d [D], with two decoders K_s
+ * [L][D], b_s [D] (SigDecoder/FC0), then p = epsilon_p [L] and, under tunable_eps, c = epsilon [1]; P = vaek_param_count.  Leaves, rows
+ * and samples are widened to float64 once and everything below is float64; eps = c * eps_cli in float64 as in vaek_elbo_hvp_replicas.
+ * With N = rows * K columns (i, k), c0 = e^{-eps} / N, c1 = 1 / N, sd = e^{p / 2}, w = e^{p}:
+ *   mu = x E + b_e     s = mu + sd xi     y = s K + b_d     u = s K_s + b_s     sg = sigmoid(u)     r = y [+ sg] - x
+ *   f_K = sum_ik c1 |mu|^2 / 2 + 1/2 sum_l (w_l - 1 - p_l) + 1/2 sum_ik c0 |r|^2 + 1/2 D (eps + log 2 pi)
+ * (the decoder noise z2 is integrated out: f_K uses the convention of the f of vaek_elbo_hvp_replicas, and for ONE decoder f_K = f
+ * identically in theta whenever each row's samples have mean 0 and second moment I, e.g. the 2 L sigma points +- sqrt(L) e_l).
+ *   g_y = c0 r     g_a = g_y sg'     g_s = g_y K^T + g_a K_s^T     g_mu = g_s + c1 mu          sg' = sg (1 - sg)   sg'' = sg' (1 - 2 sg)
+ *   df/dE = sum x^T g_mu   df/db_e = sum g_mu   df/dK = sum s^T g_y   df/db_d = sum g_y   df/dK_s = sum s^T g_a   df/db_s = sum g_a
+ *   df/dp_l = 1/2 (w_l - 1) + sum g_s,l (sd_l xi_l / 2)          df/dc = eps_cli (D / 2 - 1/2 sum c0 |r|^2)
+ * and for a direction v = (dE, db_e, dK, db_d, dK_s, db_s, dp, dc) with deps = eps_cli dc (0 without tunable_eps):
+ *   dmu = x dE + db_e     ds = dmu + dp sd xi / 2     dy = ds K + s dK + db_d     du = ds K_s + s dK_s + db_s     dr = dy + sg' du
+ *   dg_y = c0 (dr - deps r)     dg_a = dg_y sg' + g_y sg'' du     dg_s = dg_y K^T + g_y dK^T + dg_a K_s^T + g_a dK_s^T     dg_mu = dg_s + c1 dmu
+ *   (Hv)_E = sum x^T dg_mu   (Hv)_b_e = sum dg_mu   (Hv)_K = sum (ds^T g_y + s^T dg_y)   (Hv)_b_d = sum dg_y
+ *   (Hv)_K_s = sum (ds^T g_a + s^T dg_a)   (Hv)_b_s = sum dg_a
+ *   (Hv)_p_l = 1/2 w_l dp_l + sum (dg_s,l sd_l xi_l / 2 + g_s,l dp_l sd_l xi_l / 4)
+ *   (Hv)_c = eps_cli sum c0 r . (deps r / 2 - dr).
+ * COLUMN TILES: column q = i K + k; a workgroup of 256 threads takes 256 columns of one replica, 32 at a time, and stores ONE PARTIAL of
+ * the P elements (and of f_K) into the workspace; the products (columns x D by D x L and back) and the contractions over the columns run
+ * on v_mfma_f64_16x16x4_f64, and every element of a partial is ONE chain over the tile's columns in column order.  A second launch of n
+ * workgroups adds the tiles' partials in tile order.  The partials cross a launch boundary: nothing stored in a launch is read back in it,
+ * no atomic, counter, wait or spin.  ROWS: the two modes of vaek_elbo_hvp_replicas.  SAMPLES: xi != NULL: xi + r * xi_stride as
+ * [rows * samples][L] floats (xi_stride == 0: shared); xi == NULL: sample k of row i by the BLOCK RULE of vaek_log_likelihood_replicas
+ * under (z_seeds[r], z_steps[r], z_tag), so sample 0 of row i is the z1 vaek_make_batch writes.
+ * vaek_sampled_elbo_hvp_replicas: vaek_elbo_hvp_replicas' outputs (hv, grad, the 4-double record f_K, |grad f_K|_2, eps, rows), the same
+ * stride rules; v and hv must not overlap (refused); nvec = 0 .. 64, nvec = 0 gives the gradient and the record only.  LAUNCHES: 2 + 2 nvec.
+ * vaek_sampled_elbo_hessian_lanczos_replicas: the Lanczos run of vaek_elbo_hessian_lanczos_replicas (full reorthogonalisation, classical
+ * Gram-Schmidt twice, every dot one fixed tree, the same breakdown test, k = min(steps, P, breakdown), v0 = 0 or not finite: k = 0, basis
+ * rows >= k not written, T solved by the SOLVE RULE with an odd k padded) with the recursion ACROSS launches: per step one tile launch and
+ * one launch of n workgroups; a replica that is done leaves a flag in the workspace and later launches do nothing for it.  LAUNCHES: 3 + 2
+ * steps.  RECORD of vaek_sampled_elbo_hessian_record_len() = 142 doubles: [0, 140) exactly the slots of vaek_elbo_hessian_record_len's
+ * record, [140] K, [141] 1.0 with two decoders, else 0.0.
+ * Both calls: rows 1 .. 4096, samples 1 .. vaek_log_likelihood_max_samples() = 1024, rows * samples <= 2^16 per replica and n * rows *
+ * samples <= vaek_sampled_elbo_hessian_max_columns() = 2^22 (caps on the length of a launch, not tuned values).  The workspace of
+ * vaek_sampled_elbo_hessian_workspace_bytes(ctx, n, rows, samples) bytes is the call's own, 16-byte aligned.  Replica r's outputs are
+ * BITWISE what a call with n = 1 on its slices leaves, two runs are bitwise equal, drawing mode equals explicit mode on the bits
+ * vaek_make_batch and the block rule produce, nothing depends on ctx.batch.  Doubles between two replicas' blocks are not touched.
+ * Asynchronous on `stream`, allocates nothing, does not synchronise, capturable into a hipGraph.
+ * vaek_supports_sampled_elbo_hessian: vaek_supports_log_likelihood's predicate (float32, no hidden layers, one OR two decoders, D, L <=
+ * 32, D <= 28 with two, kind 0 .. 2), whatever ctx.batch, world and force_generic are.  NOT covered: MLP models, bf16, D or L > 32, Ritz
+ * vectors, more than 32 steps, data parallelism.
+ * VAEK_ERR_INVALID (message names the call, the field, its value, the bound and the query function; nothing touched): the list of
+ * vaek_elbo_hvp_replicas / vaek_elbo_hessian_lanczos_replicas, plus samples or the column products out of range, 0 < xi_stride < rows *
+ * samples * L or a negative one, NULL z_seeds or z_steps with xi == NULL, z_tag >= 2^30, overlapping v and hv, a NULL or misaligned
+ * workspace (a short one cannot be detected). */
+typedef struct vaek_sampled_elbo_hvp {
+    int32_t struct_size;                  /* = sizeof(vaek_sampled_elbo_hvp), ABI guard                 */
+    int32_t n;                            /* replicas                                                   */
+    int32_t rows;                         /* data rows, 1 .. vaek_log_likelihood_max_rows()             */
+    int32_t nvec;                         /* directions per replica, 0 .. vaek_elbo_hvp_max_vectors()   */
+    int64_t state_stride;                 /* floats between two replicas' params, >= P                  */
+    const uint64_t* x_seeds;              /* device [n]: seed of the rows (drawing mode)                */
+    const uint32_t* x_steps;              /* device [n]: their RNG step (drawing mode)                  */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared (drawing mode)  */
+    const float* x;                       /* device [rows][D] per replica: explicit rows; NULL = draw   */
+    int64_t x_stride;                     /* floats between two replicas' rows; 0 = shared              */
+    const double* v;                      /* device [nvec][P] per replica: the directions               */
+    int64_t v_stride;                     /* doubles between two replicas' directions; 0 = shared       */
+    double* hv;                           /* device [nvec][P] per replica: H v                          */
+    int64_t hv_stride;                    /* doubles, >= nvec * P                                       */
+    double* grad;                         /* device [P] per replica, or NULL                            */
+    int64_t grad_stride;                  /* doubles, >= P                                              */
+    double* out;                          /* device: record r at out + r * out_stride                   */
+    int64_t out_stride;                   /* doubles, >= vaek_elbo_hvp_record_len()                     */
+    int32_t samples;                      /* K: samples per row, 1 .. vaek_log_likelihood_max_samples() */
+    int32_t reserved;
+    const uint64_t* z_seeds;              /* device [n]: seed of the samples (xi == NULL)               */
+    const uint32_t* z_steps;              /* device [n]: their RNG step (xi == NULL)                    */
+    const float* xi;                      /* device [rows * samples][L] per replica; NULL = draw        */
+    int64_t xi_stride;                    /* floats between two replicas' samples; 0 = shared           */
+} vaek_sampled_elbo_hvp;
+typedef struct vaek_sampled_elbo_hessian {
+    int32_t struct_size;                  /* = sizeof(vaek_sampled_elbo_hessian), ABI guard             */
+    int32_t n;                            /* replicas                                                   */
+    int32_t rows;                         /* data rows, 1 .. vaek_log_likelihood_max_rows()             */
+    int32_t steps;                        /* Lanczos steps, 1 .. vaek_elbo_hessian_max_steps()          */
+    int64_t state_stride;                 /* floats between two replicas' params, >= P                  */
+    const uint64_t* x_seeds;              /* device [n]: seed of the rows (drawing mode)                */
+    const uint32_t* x_steps;              /* device [n]: their RNG step (drawing mode)                  */
+    int64_t a_stride;                     /* floats between two replicas' A; 0 = shared (drawing mode)  */
+    const float* x;                       /* device [rows][D] per replica: explicit rows; NULL = draw   */
+    int64_t x_stride;                     /* floats between two replicas' rows; 0 = shared              */
+    const double* v0;                     /* device [P] per replica: the start vector                   */
+    int64_t v0_stride;                    /* doubles between two replicas' start vectors; 0 = shared    */
+    double* basis;                        /* device [steps][P] per replica: the Lanczos vectors (output)*/
+    int64_t basis_stride;                 /* doubles, >= steps * P (vaek_elbo_hessian_basis_doubles)    */
+    double* out;                          /* device: record r at out + r * out_stride                   */
+    int64_t out_stride;                   /* doubles, >= vaek_sampled_elbo_hessian_record_len()         */
+    int32_t samples;                      /* K: samples per row, 1 .. vaek_log_likelihood_max_samples() */
+    int32_t reserved;
+    const uint64_t* z_seeds;              /* device [n]: seed of the samples (xi == NULL)               */
+    const uint32_t* z_steps;              /* device [n]: their RNG step (xi == NULL)                    */
+    const float* xi;                      /* device [rows * samples][L] per replica; NULL = draw        */
+    int64_t xi_stride;                    /* floats between two replicas' samples; 0 = shared           */
+} vaek_sampled_elbo_hessian;
+int vaek_supports_sampled_elbo_hessian(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_sampled_elbo_hessian_max_columns(void);
+int vaek_sampled_elbo_hessian_record_len(void);
+int vaek_sampled_elbo_hessian_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, int32_t samples, size_t* bytes);
+int vaek_sampled_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vaek_sampled_elbo_hvp* hp, int32_t kind, const float* A,
+                                   int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag, void* workspace,
+                                   void* stream);
+int vaek_sampled_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* params, const vaek_sampled_elbo_hessian* hs, int32_t kind,
+                                               const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
+                                               uint32_t z_tag, void* workspace, void* stream);
 /* DECODER JACOBIAN SPECTRA of N THREE-HIDDEN-LAYER MLP VAEs of the context's shape in one call (csrc/mlp3_jacobian.hip): how many
  * directions of the latent space the decoder moves its output along, row by row.  For a latent row z of replica r
  *   J(z) = d Decoder(z) / dz  (D x L)  = K3^T M3 K2^T M2 K1^T M1 K0^T,   M_i = diag(pre_i(z) > 0),

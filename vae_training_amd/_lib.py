@@ -107,6 +107,22 @@ class VaekElboHessian(C.Structure):
     ]
 
 
+class VaekSampledElboHvp(C.Structure):
+    """vaek_sampled_elbo_hvp of include/vaek.h: vaek_elbo_hvp's fields, then the samples and their source (device pointers)."""
+    _fields_ = list(VaekElboHvp._fields_) + [
+        ("samples", C.c_int32), ("reserved", C.c_int32), ("z_seeds", C.c_void_p), ("z_steps", C.c_void_p), ("xi", C.c_void_p),
+        ("xi_stride", C.c_int64),
+    ]
+
+
+class VaekSampledElboHessian(C.Structure):
+    """vaek_sampled_elbo_hessian of include/vaek.h: vaek_elbo_hessian's fields, then the samples and their source (device pointers)."""
+    _fields_ = list(VaekElboHessian._fields_) + [
+        ("samples", C.c_int32), ("reserved", C.c_int32), ("z_seeds", C.c_void_p), ("z_steps", C.c_void_p), ("xi", C.c_void_p),
+        ("xi_stride", C.c_int64),
+    ]
+
+
 ELBO_HESSIAN_RECORD_HEAD = 12      # doubles of a Lanczos record in front of the four blocks of 32: theta, rho, alpha, beta
 ELBO_HESSIAN_MAX_STEPS = 32
 DECODER_JACOBIAN_RECORD_HEAD = 8   # doubles of a decoder-Jacobian model record in front of the L mean eigenvalues and the L mean diagonals
@@ -231,6 +247,14 @@ SIGNATURES = {
     "vaek_elbo_hvp_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekElboHvp), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32, _vp]),
     "vaek_elbo_hessian_lanczos_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekElboHessian), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
                                                      _vp]),
+    "vaek_supports_sampled_elbo_hessian": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_sampled_elbo_hessian_max_columns": (C.c_int, []),
+    "vaek_sampled_elbo_hessian_record_len": (C.c_int, []),
+    "vaek_sampled_elbo_hessian_workspace_bytes": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "vaek_sampled_elbo_hvp_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSampledElboHvp), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
+                                                 C.c_uint32, _vp, _vp]),
+    "vaek_sampled_elbo_hessian_lanczos_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSampledElboHessian), _i32, _vp, _i32, _i32, _i32, _f32,
+                                                             C.c_uint32, C.c_uint32, _vp, _vp]),
     "vaek_supports_mlp3_decoder_jacobian": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_decoder_jacobian_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
     "vaek_decoder_jacobian_row_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),

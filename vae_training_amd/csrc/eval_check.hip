@@ -1,4 +1,4 @@
-// Host only: the one refusal list of the evaluation entry points (eval_check.h), the adapters of the seven description structs and
+// Host only: the one refusal list of the evaluation entry points (eval_check.h), the adapters of the nine description structs and
 // the small checks they and the training entry points of api.hip share, and those entry points' own list.  No kernels.
 #include "eval_check.h"
 
@@ -41,7 +41,7 @@ EvalDesc describe(const vaek_log_likelihood* d) {
     return e;
 }
 
-// the three descriptions of the exact calls: x rows, no z_seeds / z_steps, no sample_eps, records of doubles
+// the descriptions of the exact calls and of the sampled Hessian's: x rows, no z_seeds / z_steps, no sample_eps, records of doubles
 template <class T>
 static EvalDesc describe_exact(const char* name, const T* d) {
     EvalDesc e{};
@@ -54,6 +54,9 @@ static EvalDesc describe_exact(const char* name, const T* d) {
 EvalDesc describe(const vaek_exact_log_likelihood* d) { return describe_exact("vaek_exact_log_likelihood", d); }
 EvalDesc describe(const vaek_elbo_hvp* d) { return describe_exact("vaek_elbo_hvp", d); }
 EvalDesc describe(const vaek_elbo_hessian* d) { return describe_exact("vaek_elbo_hessian", d); }
+// the sampled calls: the exact calls' head; samples, z_seeds / z_steps and xi are read by their unit (xi == NULL is what draws them)
+EvalDesc describe(const vaek_sampled_elbo_hvp* d) { return describe_exact("vaek_sampled_elbo_hvp", d); }
+EvalDesc describe(const vaek_sampled_elbo_hessian* d) { return describe_exact("vaek_sampled_elbo_hessian", d); }
 
 EvalDesc describe(const vaek_decoder_jacobian* d) {
     EvalDesc e{};

@@ -662,6 +662,92 @@ class Engine:
         _lib.check(self.lib.vaek_elbo_hessian_lanczos_replicas(self.h, _ptr(params), C.byref(hs), int(kind), _ptr(A), int(dd), int(did),
                                                                int(pad), float(var_added), int(x_tag), _stream()))
 
+    def supports_sampled_elbo_hessian(self, kind):
+        """True where sampled_elbo_hvp_replicas and sampled_elbo_hessian_lanczos_replicas cover this engine and dataset kind: exactly
+        where supports_log_likelihood does -- one OR two decoders (vaek_supports_sampled_elbo_hessian)."""
+        return self._flag(self.lib.vaek_supports_sampled_elbo_hessian, int(kind))
+
+    @property
+    def sampled_elbo_hessian_max_columns(self):
+        """The cap on n * rows * samples of one sampled-Hessian call (vaek_sampled_elbo_hessian_max_columns); rows * samples of one
+        replica is at most 2^16 besides."""
+        return int(self.lib.vaek_sampled_elbo_hessian_max_columns())
+
+    @property
+    def sampled_elbo_hessian_record_len(self):
+        """Doubles in one sampled Lanczos record (vaek_sampled_elbo_hessian_record_len): the 140 of elbo_hessian_record_len, then K and
+        1.0 with two decoders."""
+        return int(self.lib.vaek_sampled_elbo_hessian_record_len())
+
+    def sampled_elbo_hessian_workspace(self, n, rows, samples):
+        """Bytes of the workspace the two sampled-Hessian calls need (their own buffer, 16-byte aligned, not self.workspace)."""
+        return self._count(self.lib.vaek_sampled_elbo_hessian_workspace_bytes, int(n), int(rows), int(samples), ctype=C.c_size_t)
+
+    @staticmethod
+    def _describe_samples(d, rows, samples, xi, xi_stride, z_seeds, z_steps):
+        """The fields the sampled descriptions add: samples (default: xi's), the explicit samples xi (float32 [rows, K, L] shared by all
+        replicas, or [n, rows, K, L]) or the streams that draw them."""
+        assert xi is None or xi.dtype == torch.float32
+        if samples is None:
+            samples = xi.shape[-2]
+        d.samples = int(samples)
+        d.xi = _ptr(xi)
+        if xi_stride is None:
+            xi_stride = 0 if xi is None or xi.dim() < 4 else xi.shape[-3] * xi.shape[-2] * xi.shape[-1]
+        d.xi_stride = int(xi_stride)
+        assert z_seeds is None or z_seeds.dtype == torch.int64
+        assert z_steps is None or z_steps.dtype == torch.int32
+        d.z_seeds, d.z_steps = _ptr(z_seeds), _ptr(z_steps)
+
+    def sampled_elbo_hvp_replicas(self, params, rows, out, workspace, samples=None, v=None, hv=None, grad=None, nvec=None, kind=2, A=None,
+                                  dd=0, did=0, pad=0, var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, z_seeds=None,
+                                  z_steps=None, xi=None, xi_stride=None, a_stride=0, x_tag=11, z_tag=12, n=None, state_stride=None,
+                                  v_stride=None, hv_stride=None, grad_stride=None, out_stride=None, struct_size=None):
+        """Hessian-vector products of the SAMPLE-AVERAGE ELBO f_K of EACH of n linear VAEs (one or two decoders) of this engine's shape
+        (vaek_sampled_elbo_hvp_replicas): elbo_hvp_replicas' arguments and outputs on `rows` data rows with `samples` latent samples
+        each -- xi: float32 [rows, K, L] shared or [n, rows, K, L], or None: drawn by the block rule under (z_seeds[r], z_steps[r],
+        z_tag), sample 0 being make_batch's z1.  workspace: uint8 of sampled_elbo_hessian_workspace(n, rows, samples) bytes.  2 + 2 nvec
+        launches.  Asynchronous; capturable."""
+        hp = _describe(_lib.VaekSampledElboHvp(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size,
+                       a_stride=a_stride, draws=dict(x=(x_seeds, x_steps)), given=("x", x, x_stride), raw_out=True)
+        self._describe_samples(hp, rows, samples, xi, xi_stride, z_seeds, z_steps)
+        f64 = torch.float64
+        if nvec is None:
+            nvec = 0 if v is None else v.shape[-2]
+        hp.nvec = int(nvec)
+        hp.v, hp.hv, hp.grad = _addr(v, f64), _addr(hv, f64), _addr(grad, f64)
+        if v_stride is None:
+            v_stride = 0 if v is None or isinstance(v, int) or v.dim() < 3 else v.shape[-2] * v.shape[-1]
+        if hv_stride is None:
+            hv_stride = 0 if hv is None or isinstance(hv, int) else hv.shape[-2] * hv.shape[-1]
+        hp.v_stride, hp.hv_stride = int(v_stride), int(hv_stride)
+        hp.grad_stride = _last_dim(grad, grad_stride)
+        _lib.check(self.lib.vaek_sampled_elbo_hvp_replicas(self.h, _ptr(params), C.byref(hp), int(kind), _ptr(A), int(dd), int(did), int(pad),
+                                                           float(var_added), int(x_tag), int(z_tag), _addr(workspace), _stream()))
+
+    def sampled_elbo_hessian_lanczos_replicas(self, params, rows, steps, v0, basis, out, workspace, samples=None, kind=2, A=None, dd=0, did=0,
+                                              pad=0, var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, z_seeds=None,
+                                              z_steps=None, xi=None, xi_stride=None, a_stride=0, x_tag=11, z_tag=12, n=None,
+                                              state_stride=None, v0_stride=None, basis_stride=None, out_stride=None, struct_size=None):
+        """`steps` <= 32 Lanczos steps with full reorthogonalisation on the Hessian of the SAMPLE-AVERAGE ELBO f_K of EACH of n linear
+        VAEs (one or two decoders) of this engine's shape (vaek_sampled_elbo_hessian_lanczos_replicas): elbo_hessian_lanczos_replicas'
+        arguments and outputs with the samples of sampled_elbo_hvp_replicas; out: float64 [n, out_stride >=
+        sampled_elbo_hessian_record_len].  3 + 2 steps launches, the recursion across them.  Asynchronous; capturable."""
+        hs = _describe(_lib.VaekSampledElboHessian(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size,
+                       a_stride=a_stride, draws=dict(x=(x_seeds, x_steps)), given=("x", x, x_stride), raw_out=True)
+        self._describe_samples(hs, rows, samples, xi, xi_stride, z_seeds, z_steps)
+        f64 = torch.float64
+        hs.steps = int(steps)
+        hs.v0, hs.basis = _addr(v0, f64), _addr(basis, f64)
+        if v0_stride is None:
+            v0_stride = 0 if v0 is None or isinstance(v0, int) or v0.dim() < 2 else v0.shape[-1]
+        if basis_stride is None:
+            basis_stride = 0 if basis is None or isinstance(basis, int) else basis.shape[-2] * basis.shape[-1]
+        hs.v0_stride, hs.basis_stride = int(v0_stride), int(basis_stride)
+        _lib.check(self.lib.vaek_sampled_elbo_hessian_lanczos_replicas(self.h, _ptr(params), C.byref(hs), int(kind), _ptr(A), int(dd),
+                                                                       int(did), int(pad), float(var_added), int(x_tag), int(z_tag),
+                                                                       _addr(workspace), _stream()))
+
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""
         return self._flag(self.lib.vaek_supports_train_step_replicas)

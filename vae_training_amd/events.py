@@ -1,11 +1,11 @@
 """The evaluations of the n_print events, each ONE library call for R models of one shape: the fused stats events (ReplicaStats,
 ReplicaStatsMlp3) and the observables that observables.py tables -- ReplicaLogLik / ReplicaLogLikMlp3, ReplicaExactLogLik,
-ReplicaElboHessian, ReplicaSpectrum / ReplicaSubspace and ReplicaJacobianMlp3 -- on one spine, ReplicaEvent.  trainer.py re-exports
+ReplicaElboHessian, ReplicaSampledElboHessian, ReplicaSpectrum / ReplicaSubspace and ReplicaJacobianMlp3 -- on one spine, ReplicaEvent.  trainer.py re-exports
 every name of this module.
 
 The RNG tags: 0 the train loop, 1 the dataset's batches, 2 the latents (ReplicaStats draws what compute_stats draws), 3 / 4 the
 log-likelihood (rows / samples; the exact event and, after it, the Hessian can draw tag 3's rows again), 5 / 6 the spectra,
-7 / 8 the Jacobian, 9 / 10 the Hessian."""
+7 / 8 the Jacobian, 9 / 10 the Hessian, 11 / 12 / 13 the sampled Hessian (rows / samples / start vector)."""
 from __future__ import annotations
 
 import numpy as np
@@ -488,6 +488,103 @@ class ReplicaElboHessian(ReplicaEvent):
         if not exact:
             return self.event()
         return self.event(step=[m._loglik_draws if iwae else m._exact_loglik_draws for m in self.ms])
+
+
+class ReplicaSampledElboHessian(ReplicaEvent):
+    """The curvature of the SAMPLE-AVERAGE ELBO of R linear VAEModels of one shape with ONE OR TWO decoders
+    (vaek_sampled_elbo_hessian_lanczos_replicas, csrc/sampled_hessian.hip): the rows and `samples` latent samples per row are fixed
+    (common random numbers), so the Monte-Carlo ELBO f_K is a smooth function of the parameters; `steps` <= 32 Lanczos steps with full
+    reorthogonalisation on its exact Hessian give what ReplicaElboHessian gives for the closed form -- which a model with the sigmoid
+    second decoder does not have.
+
+    event() draws each model's start vector with vaek_rng_fill, makes ONE Lanczos call (3 + 2 steps launches) and ONE device -> host
+    copy of the [R, 142] float64 records.  It does NOT perturb the run: its draws have a counter of their own,
+    `m._sampled_hessian_draws`, and the tags 11 (rows), 12 (samples) and 13 (start vector).  event(step=s) draws the ROWS under step s
+    and ReplicaExactLogLik's row tag (or `x_tag`) instead; samples and start vector stay under the own counter.  Returns per model
+    {"Sampled ELBO Hessian Ritz Values" (float64 [k], ascending), "Sampled ELBO Hessian Ritz Residuals" (float64 [k]), "Sampled
+    Sharpness" (the largest Ritz value), "Sampled ELBO Hessian Min Ritz", "Sampled ELBO Gradient Norm"}.  Raises RuntimeError naming
+    the model where the solve of T ended with off_F > 2^-40 |T|_F."""
+
+    KEYS = ("Sampled ELBO Hessian Ritz Values", "Sampled ELBO Hessian Ritz Residuals", "Sampled Sharpness", "Sampled ELBO Hessian Min Ritz",
+            "Sampled ELBO Gradient Norm")
+    GAP = "Sharpness Sampling Gap"
+    X_TAG, Z_TAG, V_TAG = 11, 12, 13
+    NAME = "ReplicaSampledElboHessian"
+    NOUN = "call"
+    COUNTER = "_sampled_hessian_draws"
+    HEAD, BLOCK = 12, 32
+    MAX_REPLICA_COLUMNS = 1 << 16
+
+    def __init__(self, vae_models, steps=32, samples=8, rows=None):
+        self.steps, self.samples = int(steps), int(samples)
+        super().__init__(vae_models, rows)
+
+    def _check_args(self):
+        if not 1 <= self.steps <= self.eng.elbo_hessian_max_steps:
+            raise RuntimeError(f"{self.NAME}: {self.steps} Lanczos steps, need 1 .. {self.eng.elbo_hessian_max_steps} "
+                               "(vaek_elbo_hessian_max_steps)")
+        if not 1 <= self.samples <= self.eng.log_likelihood_max_samples:
+            raise RuntimeError(f"{self.NAME}: {self.samples} samples per row, need 1 .. {self.eng.log_likelihood_max_samples} "
+                               "(vaek_log_likelihood_max_samples)")
+
+    def _allocate(self, R, dev):
+        cols, cap = R * self.rows * self.samples, self.eng.sampled_elbo_hessian_max_columns
+        if self.rows * self.samples > self.MAX_REPLICA_COLUMNS or cols > cap:
+            raise RuntimeError(f"{self.NAME}: {R} models x {self.rows} rows x {self.samples} samples = {cols} columns, at most {cap} fit one "
+                               f"call and {self.MAX_REPLICA_COLUMNS} one model (vaek_sampled_elbo_hessian_max_columns)")
+        self.P = P = self.params.shape[1]
+        self.record_len = self.eng.sampled_elbo_hessian_record_len
+        self.v0 = torch.zeros(R, P, dtype=torch.float64, device=dev)
+        self.basis = torch.zeros(R, self.steps, P, dtype=torch.float64, device=dev)
+        self.out = torch.zeros(R, self.record_len, dtype=torch.float64, device=dev)
+        self.workspace = torch.zeros(self.eng.sampled_elbo_hessian_workspace(R, self.rows, self.samples), dtype=torch.uint8, device=dev)
+
+    def _check_covered(self):
+        if not self.eng.supports_sampled_elbo_hessian(self.kind):
+            raise RuntimeError("ReplicaSampledElboHessian: vaek_sampled_elbo_hessian_lanczos_replicas does not cover this model / dataset (it "
+                               "needs a float32 linear VAE -- no hidden layers -- with one or two decoders and D, L <= 32, D <= 28 with two; "
+                               f"this model's step path: {getattr(self.eng, 'step_path', '?')})")
+
+    def event(self, step=None, x_tag=None):
+        """One evaluation of every model.  step: draw the ROWS under this RNG step (one int, or one per model) and ReplicaExactLogLik's
+        row tag (x_tag: another event's) instead of the own counter and tag 11."""
+        given = self._given_steps(step)
+        self._stack_params()
+        seeds, own = self._seeds(), self._own_steps()
+        for r in range(self.R):
+            self.v0[r].copy_(self.eng.rng_fill(self.P, seeds[r], step=own[r], tag=self.V_TAG))      # widened on the copy
+        z_seeds, z_steps = _seed_step_tensors(seeds, own, self.eng.device)
+        x_seeds, x_steps = _seed_step_tensors(seeds, own if given is None else given, self.eng.device)
+        tag = self.X_TAG if given is None else (ReplicaExactLogLik.X_TAG if x_tag is None else int(x_tag))
+        self.eng.sampled_elbo_hessian_lanczos_replicas(self.params, self.rows, self.steps, self.v0, self.basis, self.out, self.workspace,
+                                                       samples=self.samples, x_seeds=x_seeds, x_steps=x_steps, z_seeds=z_seeds,
+                                                       z_steps=z_steps, x_tag=tag, z_tag=self.Z_TAG, **self._drawn())
+        rec = self._records().numpy()
+        stats = []
+        for r in range(self.R):
+            row = rec[r]
+            self._check_solve(r, "solve of the Lanczos matrix T", "T", row[4], row[5], self.OFF_BOUND * row[6])
+            k, h, b = int(row[2]), self.HEAD, self.BLOCK
+            stats.append({self.KEYS[0]: row[h:h + k].copy(), self.KEYS[1]: row[h + b:h + b + k].copy(), self.KEYS[2]: float(row[9]),
+                          self.KEYS[3]: float(row[10]), self.KEYS[4]: float(row[1])})
+        return stats
+
+    def event_after(self, ran):
+        """event() of an n_print event.  ran: {observable name: what it returned} of the observables that already ran at this step.
+        After a ReplicaElboHessian over the SAME models (one-decoder models only) the rows are the ones that event used -- its own, or
+        the exact / IWAE event's where it followed one -- and every dict gains "Sharpness Sampling Gap" = Sampled Sharpness - Sharpness:
+        how far K samples are from the closed form."""
+        exact_stats = ran.get("elbo_hessian")
+        if exact_stats is None:
+            return self.event()
+        if "exact_log_likelihood" in ran:
+            attr, tag = "_loglik_draws" if "log_likelihood_samples" in ran else "_exact_loglik_draws", ReplicaExactLogLik.X_TAG
+        else:
+            attr, tag = ReplicaElboHessian.COUNTER, ReplicaElboHessian.X_TAG
+        stats = self.event(step=[getattr(m, attr) for m in self.ms], x_tag=tag)
+        for st, ex in zip(stats, exact_stats):
+            st[self.GAP] = st[self.KEYS[2]] - float(ex[ReplicaElboHessian.KEYS[2]])
+        return stats
 
 
 class ReplicaJacobianMlp3(ReplicaEvent):

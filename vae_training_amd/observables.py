@@ -16,6 +16,9 @@ quotes the model's data_dim, not its step path; linear_hint: the refusal of a li
 path)` for further refusals (what it returns goes to `attrs`), `attrs(args, value, checked)` -> the attributes it sets (default
 {dest: value}), the banners of a single model (m) and of a sweep (event, n_models, cfg), and save_flag: model_save_data reads it.
 
+OBSERVABLES holds the seven flags tests/test_observables_host.py pins by equality; an observable added since stands in
+LATER_OBSERVABLES with the name of the entry it follows, and TABLE is the two merged: everything below reads TABLE.
+
 The table's order is the order the results are merged into the stats dict -- the stats line and the keys of losses.npz -- and the
 order both callers issue the device calls in.  Every event draws under its own counter and tags (events.py), so the order of the
 calls changes no result: each record is bitwise what the event alone would give.  To add an observable: one entry here, its event
@@ -101,6 +104,35 @@ def _jacobian_column_cap(fl, m, eng, at, n_models, path):
         raise RuntimeError(f"{fl.flag}: {n_models} models x {m.print_batch_size} rows x {eng.L} latents = {cols} columns, at most "
                            f"{eng.mlp3_decoder_jacobian_max_columns} fit one call (vaek_mlp3_decoder_jacobian_max_columns; this model's "
                            f"step path: {path})")
+
+
+SAMPLED_HESSIAN_DEFAULT_SAMPLES = 8
+
+
+def sampled_elbo_hessian_samples(args):
+    """K of --sampled_elbo_hessian: --sampled_elbo_hessian_samples, else 8."""
+    k = getattr(args, "sampled_elbo_hessian_samples", None)
+    return SAMPLED_HESSIAN_DEFAULT_SAMPLES if k is None else int(k)
+
+
+def _sampled_caps(fl, m, eng, steps, n_models, path):
+    """What the refusal of K needs, for _sampled_attrs (which sees the arguments)."""
+    return dict(flag=fl.flag, n=n_models, rows=m.print_batch_size, max_samples=eng.log_likelihood_max_samples,
+                max_columns=eng.sampled_elbo_hessian_max_columns, path=path)
+
+
+def _sampled_attrs(args, steps, caps):
+    samples = sampled_elbo_hessian_samples(args)
+    if caps is not None:
+        if samples > caps["max_samples"]:
+            raise RuntimeError(f"{caps['flag']}_samples {samples}: at most {caps['max_samples']} samples per row fit one call "
+                               f"(vaek_log_likelihood_max_samples; this model's step path: {caps['path']})")
+        cols = caps["n"] * caps["rows"] * samples
+        if cols > caps["max_columns"] or caps["rows"] * samples > 1 << 16:
+            raise RuntimeError(f"{caps['flag']}_samples {samples}: {caps['n']} models x {caps['rows']} rows x {samples} samples = {cols} "
+                               f"columns, at most {caps['max_columns']} fit one call and {1 << 16} one model "
+                               f"(vaek_sampled_elbo_hessian_max_columns; this model's step path: {caps['path']})")
+    return {"sampled_elbo_hessian": steps, "sampled_elbo_hessian_samples": samples}
 
 
 def _subspace_k(fl, m, eng, k, n_models, path):
@@ -210,7 +242,38 @@ OBSERVABLES = (
         line=("Decoder Jacobian Rank", "(mean)")),
 )
 
-FLAGS = {fl.dest: (ob, fl) for ob in OBSERVABLES for fl in ob.flags}
+# (the entry it follows, the observable)
+LATER_OBSERVABLES = (
+    ("elbo_hessian", Observable(
+        flags=(Flag("--sampled_elbo_hessian", "sampled_elbo_hessian",
+                    "a model vaek_sampled_elbo_hessian_lanczos_replicas covers (vaek_supports_sampled_elbo_hessian): a float32 linear VAE -- "
+                    "no hidden layers -- with one or two decoders, D, L <= 32 (D <= 28 with two decoders), -dd / -did <= 16, on one GPU",
+                    extra=_sampled_caps, attrs=_sampled_attrs,
+                    banner_one=lambda m: f"Sampled ELBO Hessian events: {m.sampled_elbo_hessian} Lanczos steps on {m.print_batch_size} rows "
+                                         f"x {m.sampled_elbo_hessian_samples} samples (vaek_sampled_elbo_hessian_lanczos_replicas)",
+                    banner_sweep=lambda ev, n, cfg: f"Sampled ELBO Hessian events: {ev.steps} Lanczos steps on {ev.rows} rows x {ev.samples} "
+                                                    f"samples per model, one call for {n} models "
+                                                    "(vaek_sampled_elbo_hessian_lanczos_replicas)"),),
+        events=(("sampled_elbo_hessian", "_sampled_hessian", "ReplicaSampledElboHessian"),),
+        covered=lambda eng, kind: eng.supports_sampled_elbo_hessian(kind),
+        build=lambda cls, ms, cfg: cls(ms, cfg.sampled_elbo_hessian,
+                                       getattr(cfg, "sampled_elbo_hessian_samples", SAMPLED_HESSIAN_DEFAULT_SAMPLES)),
+        # on the rows the exact Hessian just used where there was one (then also "Sharpness Sampling Gap")
+        run=lambda ev, ran, cfg: ev.event_after(ran),
+        array_keys=lambda cls: cls.KEYS[:2])),
+)
+
+
+def _merged():
+    table = []
+    for ob in OBSERVABLES:
+        table.append(ob)
+        table.extend(later for after, later in LATER_OBSERVABLES if after == ob.name)
+    return tuple(table)
+
+
+TABLE = _merged()
+FLAGS = {fl.dest: (ob, fl) for ob in TABLE for fl in ob.flags}
 
 
 # ---- the refusals ---------------------------------------------------------------------------------------------------------------
@@ -242,7 +305,7 @@ def attach(args, models, cfg, build):
     """For every observable flag in `args`, in table order: check_model on model 0 (refusing before any step), set the flag's
     attributes on `cfg` (the model itself for a single model, the sweep's settings for a sweep) and yield the flag.  With `build`
     an observable's event object is built as soon as its flags are checked -- before any step; without, on its first event."""
-    for ob in OBSERVABLES:
+    for ob in TABLE:
         for fl in ob.flags:
             value = fl.value(args)
             if value is not None:
@@ -269,7 +332,7 @@ def _event(ob, models, cfg):
 
 def active(models, cfg):
     """(observable, its event object) of every observable set on `cfg`, in table order."""
-    for ob in OBSERVABLES:
+    for ob in TABLE:
         ev = _event(ob, models, cfg)
         if ev is not None:
             yield ob, ev
@@ -292,10 +355,11 @@ def array_keys(dest):
     return tuple(ob.array_keys(ob.event_class()))
 
 
-def stats_line_rules():
-    """({array key: the text write_stats puts in front of element 0 of its value, or None: nothing on the line})."""
+def stats_line_rules(table=OBSERVABLES):
+    """({array key: the text write_stats puts in front of element 0 of its value, or None: nothing on the line}) of `table` (model.py
+    passes TABLE)."""
     rules = {}
-    for ob in OBSERVABLES:
+    for ob in table:
         for key in ob.array_keys(ob.event_class()):
             rules[key] = f"{key} {ob.line[1]}" if ob.line is not None and ob.line[0] == key else None
     return rules

@@ -4,8 +4,8 @@ losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never read
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
 --fused_stats, --mlp_fused_stats, and the observables of the n_print events, which observables.py tables: --log_likelihood_samples,
---mlp_log_likelihood_samples, --exact_log_likelihood, --elbo_hessian, --eigenvalues, --subspace, --decoder_jacobian (with
---decoder_jacobian_tol)."""
+--mlp_log_likelihood_samples, --exact_log_likelihood, --elbo_hessian, --sampled_elbo_hessian (with --sampled_elbo_hessian_samples),
+--eigenvalues, --subspace, --decoder_jacobian (with --decoder_jacobian_tol)."""
 from __future__ import annotations
 
 import argparse
@@ -110,6 +110,20 @@ def build_parser():
                         "rows.  The evaluation has its own RNG counter and tags, so the training run and every other stat are bitwise "
                         "the ones without the flag.  Alone or with --sweep_dataset_seeds (one launch for all models); refused where "
                         "--exact_log_likelihood is: MLP and two-decoder models and data parallelism, before any step")
+    p.add_argument("--sampled_elbo_hessian", dest="sampled_elbo_hessian", nargs="?", type=_hessian_steps, const=ELBO_HESSIAN_MAX_STEPS,
+                   default=None, metavar="STEPS",
+                   help="--elbo_hessian for the models it refuses: at every n_print step run STEPS (1 .. 32, default 32) Lanczos steps on "
+                        "the Hessian of the SAMPLE-AVERAGE ELBO of the model(s) -- a print batch of rows and K fixed latent samples per "
+                        "row (--sampled_elbo_hessian_samples), float64, exact derivatives of that function "
+                        "(trainer.ReplicaSampledElboHessian, vaek_sampled_elbo_hessian_lanczos_replicas): losses.npz gains 'Sampled ELBO "
+                        "Hessian Ritz Values' and 'Sampled ELBO Hessian Ritz Residuals' (k each), 'Sampled Sharpness', 'Sampled ELBO "
+                        "Hessian Min Ritz' and 'Sampled ELBO Gradient Norm'.  Linear VAEs with one OR two decoders (the sigmoid second "
+                        "decoder included), D, L <= 32.  With --elbo_hessian on a one-decoder model both events use the same rows and "
+                        "'Sharpness Sampling Gap' = Sampled Sharpness - Sharpness is added.  Its own RNG counter and tags: the training "
+                        "run and every other stat are bitwise the ones without the flag.  Alone or with --sweep_dataset_seeds; MLP "
+                        "models, data parallelism and models x rows x K above 2^22 (rows x K above 2^16) are refused before any step")
+    p.add_argument("--sampled_elbo_hessian_samples", dest="sampled_elbo_hessian_samples", type=_positive_int, default=None, metavar="K",
+                   help="with --sampled_elbo_hessian: K latent samples per row (default 8); refused without --sampled_elbo_hessian")
     p.add_argument("--mlp_log_likelihood_samples", dest="mlp_log_likelihood_samples", type=_positive_int, default=None, metavar="K",
                    help="--log_likelihood_samples for three-hidden-layer MLP VAEs (trainer.ReplicaLogLikMlp3, "
                         "vaek_mlp3_log_likelihood_replicas): the same three stats from the same draws, the training run bitwise the one "
@@ -369,6 +383,7 @@ LOGLIK_NEEDS = FLAGS["log_likelihood_samples"][1].needs
 MLP_LOGLIK_NEEDS = FLAGS["mlp_log_likelihood_samples"][1].needs
 EXACT_LOGLIK_NEEDS = FLAGS["exact_log_likelihood"][1].needs
 ELBO_HESSIAN_NEEDS = FLAGS["elbo_hessian"][1].needs
+SAMPLED_ELBO_HESSIAN_NEEDS = FLAGS["sampled_elbo_hessian"][1].needs
 EIGEN_NEEDS = FLAGS["eigenvalues"][1].needs
 SUBSPACE_NEEDS = FLAGS["subspace"][1].needs
 JACOBIAN_NEEDS = FLAGS["decoder_jacobian"][1].needs
@@ -393,6 +408,11 @@ def check_exact_log_likelihood_model(m):
 def check_elbo_hessian_model(m):
     """--elbo_hessian: refuse, before any step, a model the Lanczos call does not cover."""
     check_model("elbo_hessian", m)
+
+
+def check_sampled_elbo_hessian_model(m, steps=ELBO_HESSIAN_MAX_STEPS, n_models=1):
+    """--sampled_elbo_hessian: refuse, before any step, a model the sampled Lanczos call does not cover."""
+    check_model("sampled_elbo_hessian", m, steps, n_models)
 
 
 def check_eigenvalues_model(m):
@@ -423,6 +443,12 @@ def check_decoder_jacobian_flags(args):
     """--decoder_jacobian_tol without --decoder_jacobian: refused before anything is created."""
     if getattr(args, "decoder_jacobian_tol", None) is not None and getattr(args, "decoder_jacobian", None) is None:
         raise RuntimeError("--decoder_jacobian_tol sets the rank threshold of --decoder_jacobian prior|posterior: give that flag too")
+
+
+def check_sampled_elbo_hessian_flags(args):
+    """--sampled_elbo_hessian_samples without --sampled_elbo_hessian: refused before anything is created."""
+    if getattr(args, "sampled_elbo_hessian_samples", None) is not None and getattr(args, "sampled_elbo_hessian", None) is None:
+        raise RuntimeError("--sampled_elbo_hessian_samples sets the samples per row of --sampled_elbo_hessian [STEPS]: give that flag too")
 
 
 def main_sweep(args):
@@ -514,6 +540,7 @@ def main(args):
     check_fused_stats_args(args)
     check_log_likelihood_flags(args)
     check_decoder_jacobian_flags(args)
+    check_sampled_elbo_hessian_flags(args)
     if getattr(args, "sweep_dataset_seeds", None):
         return main_sweep(args)
     from .utils import get_output_dir, make_output_dir

@@ -46,7 +46,7 @@ import torch
 
 # The evaluations of the n_print events live in events.py; their names stay importable from here.
 from .events import (ReplicaElboHessian, ReplicaEvent, ReplicaExactLogLik, ReplicaJacobianMlp3, ReplicaLogLik,      # noqa: F401
-                     ReplicaLogLikMlp3, ReplicaSpectrum, ReplicaStats, ReplicaStatsMlp3, ReplicaSubspace, _replica_setup,
+                     ReplicaLogLikMlp3, ReplicaSampledElboHessian, ReplicaSpectrum, ReplicaStats, ReplicaStatsMlp3, ReplicaSubspace, _replica_setup,
                      _seed_step_tensors, _signature, _wrap_signed)
 
 
