@@ -950,6 +950,52 @@ int vaek_sampled_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vae
 int vaek_sampled_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* params, const vaek_sampled_elbo_hessian* hs, int32_t kind,
                                                const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
                                                uint32_t z_tag, void* workspace, void* stream);
+/* HESSIAN OF THE SAMPLE-AVERAGE ELBO of N THREE-HIDDEN-LAYER MLP VAEs (csrc/mlp3_hessian.hip): the f_K of the block above with the two
+ * linear maps replaced by the four-Dense relu stacks of networks.py:26-44, Enc and Dec.  The two descriptions are the structs above,
+ * unchanged, every field with the same meaning; theta is the flat parameter vector in the library's leaf order (Encoder FC0 kernel [D][h0],
+ * bias, .. FC3, Decoder FC0 .. FC3, then p = epsilon_p [L] and, under tunable_eps, c = epsilon [1]).  With N = rows * K columns q = i K + k,
+ * c0 = e^{-eps} / N, c1 = 1 / N, sd = e^{p / 2}, w = e^{p}, eps = c * eps_cli:
+ *   mu = Enc(x)     s = mu + sd xi     y = Dec(s)     r = y - x
+ *   f_K = sum c1 |mu|^2 / 2 + 1/2 sum_l (w_l - 1 - p_l) + 1/2 sum c0 |r|^2 + 1/2 D (eps + log 2 pi)
+ * (z2 integrated out as above; with K = 1, xi = z1 and z2 = 0 this is the loss vaek_train_step differentiates).  Per Dense layer i of a
+ * stack (W_i [n_in][n_out], b_i; relu after layers 0 .. 2) and a direction (dW_i, db_i):
+ *   forward   a_i = h_{i-1} W_i + b_i                     h_i = M_i . a_i        M_i = [a_i > 0]   (no mask on layer 3)
+ *   tangent   da_i = dh_{i-1} W_i + h_{i-1} dW_i + db_i   dh_i = M_i . da_i
+ *   backward  g_a_i = M_i . g_h_i     g_h_{i-1} = g_a_i W_i^T     df/dW_i = sum h_{i-1}^T g_a_i     df/db_i = sum g_a_i
+ *   tangent   dg_a_i = M_i . dg_h_i   dg_h_{i-1} = dg_a_i W_i^T + g_a_i dW_i^T
+ *             (Hv)_W_i = sum (dh_{i-1}^T g_a_i + h_{i-1}^T dg_a_i)     (Hv)_b_i = sum dg_a_i
+ * (relu has no second derivative away from the kink, so the tangent-backward pass needs the masks only).  The head is the block
+ * above's with one decoder: ds = dmu + dp sd xi / 2, g_y = c0 r, dg_y = c0 (dy - deps r), g_mu = g_s + c1 mu, dg_mu = dg_s + c1 dmu with
+ * g_s / dg_s what the decoder stack hands back at its input, and the p and c leaves of the gradient and of H v are the formulas above
+ * unchanged.  Leaves, rows, samples and directions are widened to float64 once and everything below is float64 on
+ * v_mfma_f64_16x16x4_f64: a unit is LIVE iff its FLOAT64 pre-activation is > 0 (the derivative at exactly 0 is 0) -- the float32
+ * definition of "live" of vaek_mlp3_decoder_jacobian_replicas does not apply here.  Nothing is finite-differenced.
+ * LAUNCHES.  A CHAIN launch, grid (ceil(rows K / 8), n): a workgroup carries 8 columns through both stacks, forward and backward, as a
+ * [unit][8 primal | 8 tangent] float64 image and stores every layer's input and masked output gradient to the workspace; a CONTRACTION
+ * launch: a workgroup owns 16 x 64 elements of one layer's [kernel | bias] and sums over ALL the replica's columns in column order; one
+ * more workgroup a replica adds the per-tile partials of the p and c leaves and of f_K in tile order.  Nothing stored in a launch is read
+ * back in it; no atomic, counter, wait or spin.  vaek_mlp3_sampled_elbo_hvp_replicas: the outputs and rules of
+ * vaek_sampled_elbo_hvp_replicas; LAUNCHES: 3 + 2 nvec.  vaek_mlp3_sampled_elbo_hessian_lanczos_replicas: the Lanczos run and the
+ * 142-double RECORD of vaek_sampled_elbo_hessian_lanczos_replicas slot for slot ([140] K, [141] 0.0), with every length-P vector
+ * operation spread over chunks of 2048 elements (grid (ceil(P / 2048), n)) and every dot a per-chunk partial added in chunk order by
+ * the next launch; LAUNCHES: 6 + 6 steps, whatever the replicas do (a replica that is done is skipped by the launches that follow).
+ * Both calls: rows 1 .. 4096, samples 1 .. 1024, nvec 0 .. 64, steps 1 .. 32, rows * samples <= 2^13 per replica and n * rows * samples
+ * <= vaek_mlp3_sampled_elbo_hessian_max_columns() = 2^14 (caps on the length of a launch and on the workspace -- a column costs
+ * 2 sum_layers (n_in + n_out) doubles, 51 KB at the widest shape --, not tuned values).  The workspace of
+ * vaek_mlp3_sampled_elbo_hessian_workspace_bytes(ctx, n, rows, samples) bytes is the call's own, 16-byte aligned.  The guarantees of the
+ * block above hold: replica r BITWISE what n = 1 leaves, two runs bitwise equal, drawing mode bitwise explicit mode, sample 0 of row i
+ * vaek_make_batch's z1, nothing depends on ctx.batch, doubles between two replicas' blocks untouched, asynchronous, allocates nothing,
+ * capturable.  vaek_supports_mlp3_sampled_elbo_hessian: vaek_supports_mlp3_log_likelihood's predicate.  NOT covered: other depths, two
+ * decoders, bf16, D or L > 32, Ritz vectors, more than 32 steps, data parallelism.  VAEK_ERR_INVALID: the list of the block above. */
+int vaek_supports_mlp3_sampled_elbo_hessian(const vaek_ctx* ctx, int32_t kind, int32_t* yes);
+int vaek_mlp3_sampled_elbo_hessian_max_columns(void);
+int vaek_mlp3_sampled_elbo_hessian_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, int32_t samples, size_t* bytes);
+int vaek_mlp3_sampled_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vaek_sampled_elbo_hvp* hp, int32_t kind, const float* A,
+                                        int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
+                                        void* workspace, void* stream);
+int vaek_mlp3_sampled_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* params, const vaek_sampled_elbo_hessian* hs, int32_t kind,
+                                                    const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
+                                                    uint32_t z_tag, void* workspace, void* stream);
 /* DECODER JACOBIAN SPECTRA of N THREE-HIDDEN-LAYER MLP VAEs of the context's shape in one call (csrc/mlp3_jacobian.hip): how many
  * directions of the latent space the decoder moves its output along, row by row.  For a latent row z of replica r
  *   J(z) = d Decoder(z) / dz  (D x L)  = K3^T M3 K2^T M2 K1^T M1 K0^T,   M_i = diag(pre_i(z) > 0),

@@ -255,6 +255,13 @@ SIGNATURES = {
                                                  C.c_uint32, _vp, _vp]),
     "vaek_sampled_elbo_hessian_lanczos_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSampledElboHessian), _i32, _vp, _i32, _i32, _i32, _f32,
                                                              C.c_uint32, C.c_uint32, _vp, _vp]),
+    "vaek_supports_mlp3_sampled_elbo_hessian": (C.c_int, [_vp, _i32, C.POINTER(_i32)]),
+    "vaek_mlp3_sampled_elbo_hessian_max_columns": (C.c_int, []),
+    "vaek_mlp3_sampled_elbo_hessian_workspace_bytes": (C.c_int, [_vp, _i32, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "vaek_mlp3_sampled_elbo_hvp_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSampledElboHvp), _i32, _vp, _i32, _i32, _i32, _f32, C.c_uint32,
+                                                      C.c_uint32, _vp, _vp]),
+    "vaek_mlp3_sampled_elbo_hessian_lanczos_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekSampledElboHessian), _i32, _vp, _i32, _i32, _i32,
+                                                                  _f32, C.c_uint32, C.c_uint32, _vp, _vp]),
     "vaek_supports_mlp3_decoder_jacobian": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_decoder_jacobian_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),
     "vaek_decoder_jacobian_row_record_len": (C.c_int, [_vp, C.POINTER(_i64)]),

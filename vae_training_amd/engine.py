@@ -702,7 +702,7 @@ class Engine:
     def sampled_elbo_hvp_replicas(self, params, rows, out, workspace, samples=None, v=None, hv=None, grad=None, nvec=None, kind=2, A=None,
                                   dd=0, did=0, pad=0, var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, z_seeds=None,
                                   z_steps=None, xi=None, xi_stride=None, a_stride=0, x_tag=11, z_tag=12, n=None, state_stride=None,
-                                  v_stride=None, hv_stride=None, grad_stride=None, out_stride=None, struct_size=None):
+                                  v_stride=None, hv_stride=None, grad_stride=None, out_stride=None, struct_size=None, _fn=None):
         """Hessian-vector products of the SAMPLE-AVERAGE ELBO f_K of EACH of n linear VAEs (one or two decoders) of this engine's shape
         (vaek_sampled_elbo_hvp_replicas): elbo_hvp_replicas' arguments and outputs on `rows` data rows with `samples` latent samples
         each -- xi: float32 [rows, K, L] shared or [n, rows, K, L], or None: drawn by the block rule under (z_seeds[r], z_steps[r],
@@ -722,13 +722,15 @@ class Engine:
             hv_stride = 0 if hv is None or isinstance(hv, int) else hv.shape[-2] * hv.shape[-1]
         hp.v_stride, hp.hv_stride = int(v_stride), int(hv_stride)
         hp.grad_stride = _last_dim(grad, grad_stride)
-        _lib.check(self.lib.vaek_sampled_elbo_hvp_replicas(self.h, _ptr(params), C.byref(hp), int(kind), _ptr(A), int(dd), int(did), int(pad),
-                                                           float(var_added), int(x_tag), int(z_tag), _addr(workspace), _stream()))
+        fn = _fn or self.lib.vaek_sampled_elbo_hvp_replicas            # _fn: the MLP call of the same description (below)
+        _lib.check(fn(self.h, _ptr(params), C.byref(hp), int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(x_tag),
+                      int(z_tag), _addr(workspace), _stream()))
 
     def sampled_elbo_hessian_lanczos_replicas(self, params, rows, steps, v0, basis, out, workspace, samples=None, kind=2, A=None, dd=0, did=0,
                                               pad=0, var_added=0.0, x_seeds=None, x_steps=None, x=None, x_stride=None, z_seeds=None,
                                               z_steps=None, xi=None, xi_stride=None, a_stride=0, x_tag=11, z_tag=12, n=None,
-                                              state_stride=None, v0_stride=None, basis_stride=None, out_stride=None, struct_size=None):
+                                              state_stride=None, v0_stride=None, basis_stride=None, out_stride=None, struct_size=None,
+                                              _fn=None):
         """`steps` <= 32 Lanczos steps with full reorthogonalisation on the Hessian of the SAMPLE-AVERAGE ELBO f_K of EACH of n linear
         VAEs (one or two decoders) of this engine's shape (vaek_sampled_elbo_hessian_lanczos_replicas): elbo_hessian_lanczos_replicas'
         arguments and outputs with the samples of sampled_elbo_hvp_replicas; out: float64 [n, out_stride >=
@@ -744,9 +746,39 @@ class Engine:
         if basis_stride is None:
             basis_stride = 0 if basis is None or isinstance(basis, int) else basis.shape[-2] * basis.shape[-1]
         hs.v0_stride, hs.basis_stride = int(v0_stride), int(basis_stride)
-        _lib.check(self.lib.vaek_sampled_elbo_hessian_lanczos_replicas(self.h, _ptr(params), C.byref(hs), int(kind), _ptr(A), int(dd),
-                                                                       int(did), int(pad), float(var_added), int(x_tag), int(z_tag),
-                                                                       _addr(workspace), _stream()))
+        fn = _fn or self.lib.vaek_sampled_elbo_hessian_lanczos_replicas
+        _lib.check(fn(self.h, _ptr(params), C.byref(hs), int(kind), _ptr(A), int(dd), int(did), int(pad), float(var_added), int(x_tag),
+                      int(z_tag), _addr(workspace), _stream()))
+
+    def supports_mlp3_sampled_elbo_hessian(self, kind):
+        """True where mlp3_sampled_elbo_hvp_replicas and mlp3_sampled_elbo_hessian_lanczos_replicas cover this engine and dataset kind:
+        exactly where supports_mlp3_log_likelihood does (vaek_supports_mlp3_sampled_elbo_hessian)."""
+        return self._flag(self.lib.vaek_supports_mlp3_sampled_elbo_hessian, int(kind))
+
+    @property
+    def mlp3_sampled_elbo_hessian_max_columns(self):
+        """The cap on n * rows * samples of one MLP sampled-Hessian call (vaek_mlp3_sampled_elbo_hessian_max_columns) = 2^14; rows *
+        samples of one replica is at most 2^13 besides."""
+        return int(self.lib.vaek_mlp3_sampled_elbo_hessian_max_columns())
+
+    def mlp3_sampled_elbo_hessian_workspace(self, n, rows, samples):
+        """Bytes of the workspace the two MLP sampled-Hessian calls need (their own buffer, 16-byte aligned, not self.workspace)."""
+        return self._count(self.lib.vaek_mlp3_sampled_elbo_hessian_workspace_bytes, int(n), int(rows), int(samples), ctype=C.c_size_t)
+
+    def mlp3_sampled_elbo_hvp_replicas(self, params, rows, out, workspace, samples=None, x_tag=14, z_tag=15, **kw):
+        """sampled_elbo_hvp_replicas for n three-hidden-layer MLP VAEs of this engine's shape (vaek_mlp3_sampled_elbo_hvp_replicas): the
+        same arguments, description and outputs; workspace: uint8 of mlp3_sampled_elbo_hessian_workspace(n, rows, samples) bytes.
+        3 + 2 nvec launches.  Asynchronous; capturable."""
+        self.sampled_elbo_hvp_replicas(params, rows, out, workspace, samples=samples, x_tag=x_tag, z_tag=z_tag,
+                                       _fn=self.lib.vaek_mlp3_sampled_elbo_hvp_replicas, **kw)
+
+    def mlp3_sampled_elbo_hessian_lanczos_replicas(self, params, rows, steps, v0, basis, out, workspace, samples=None, x_tag=14, z_tag=15,
+                                                   **kw):
+        """sampled_elbo_hessian_lanczos_replicas for n three-hidden-layer MLP VAEs of this engine's shape
+        (vaek_mlp3_sampled_elbo_hessian_lanczos_replicas): the same arguments, description and 142-double record.  6 + 6 steps launches,
+        every vector operation spread over chunks of P.  Asynchronous; capturable."""
+        self.sampled_elbo_hessian_lanczos_replicas(params, rows, steps, v0, basis, out, workspace, samples=samples, x_tag=x_tag, z_tag=z_tag,
+                                                   _fn=self.lib.vaek_mlp3_sampled_elbo_hessian_lanczos_replicas, **kw)
 
     def supports_train_step_replicas(self):
         """True where train_step_gen_replicas covers this engine: the step path is "mlp3" and world == 1."""

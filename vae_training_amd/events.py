@@ -1,11 +1,12 @@
 """The evaluations of the n_print events, each ONE library call for R models of one shape: the fused stats events (ReplicaStats,
 ReplicaStatsMlp3) and the observables that observables.py tables -- ReplicaLogLik / ReplicaLogLikMlp3, ReplicaExactLogLik,
-ReplicaElboHessian, ReplicaSampledElboHessian, ReplicaSpectrum / ReplicaSubspace and ReplicaJacobianMlp3 -- on one spine, ReplicaEvent.  trainer.py re-exports
+ReplicaElboHessian, ReplicaSampledElboHessian / ReplicaSampledElboHessianMlp3, ReplicaSpectrum / ReplicaSubspace and ReplicaJacobianMlp3 -- on one spine, ReplicaEvent.  trainer.py re-exports
 every name of this module.
 
 The RNG tags: 0 the train loop, 1 the dataset's batches, 2 the latents (ReplicaStats draws what compute_stats draws), 3 / 4 the
 log-likelihood (rows / samples; the exact event and, after it, the Hessian can draw tag 3's rows again), 5 / 6 the spectra,
-7 / 8 the Jacobian, 9 / 10 the Hessian, 11 / 12 / 13 the sampled Hessian (rows / samples / start vector)."""
+7 / 8 the Jacobian, 9 / 10 the Hessian, 11 / 12 / 13 the sampled Hessian (rows / samples / start vector),
+14 / 15 / 16 the MLP sampled Hessian."""
 from __future__ import annotations
 
 import numpy as np
@@ -514,6 +515,8 @@ class ReplicaSampledElboHessian(ReplicaEvent):
     COUNTER = "_sampled_hessian_draws"
     HEAD, BLOCK = 12, 32
     MAX_REPLICA_COLUMNS = 1 << 16
+    ENTRY = "sampled_elbo_hessian"               # the engine's supports_<ENTRY>, <ENTRY>_max_columns, _workspace and _lanczos_replicas
+    COVERS = ("a float32 linear VAE -- no hidden layers -- with one or two decoders and D, L <= 32, D <= 28 with two")
 
     def __init__(self, vae_models, steps=32, samples=8, rows=None):
         self.steps, self.samples = int(steps), int(samples)
@@ -528,21 +531,21 @@ class ReplicaSampledElboHessian(ReplicaEvent):
                                "(vaek_log_likelihood_max_samples)")
 
     def _allocate(self, R, dev):
-        cols, cap = R * self.rows * self.samples, self.eng.sampled_elbo_hessian_max_columns
+        cols, cap = R * self.rows * self.samples, getattr(self.eng, self.ENTRY + "_max_columns")
         if self.rows * self.samples > self.MAX_REPLICA_COLUMNS or cols > cap:
             raise RuntimeError(f"{self.NAME}: {R} models x {self.rows} rows x {self.samples} samples = {cols} columns, at most {cap} fit one "
-                               f"call and {self.MAX_REPLICA_COLUMNS} one model (vaek_sampled_elbo_hessian_max_columns)")
+                               f"call and {self.MAX_REPLICA_COLUMNS} one model (vaek_{self.ENTRY}_max_columns)")
         self.P = P = self.params.shape[1]
         self.record_len = self.eng.sampled_elbo_hessian_record_len
         self.v0 = torch.zeros(R, P, dtype=torch.float64, device=dev)
         self.basis = torch.zeros(R, self.steps, P, dtype=torch.float64, device=dev)
         self.out = torch.zeros(R, self.record_len, dtype=torch.float64, device=dev)
-        self.workspace = torch.zeros(self.eng.sampled_elbo_hessian_workspace(R, self.rows, self.samples), dtype=torch.uint8, device=dev)
+        self.workspace = torch.zeros(getattr(self.eng, self.ENTRY + "_workspace")(R, self.rows, self.samples), dtype=torch.uint8, device=dev)
 
     def _check_covered(self):
-        if not self.eng.supports_sampled_elbo_hessian(self.kind):
-            raise RuntimeError("ReplicaSampledElboHessian: vaek_sampled_elbo_hessian_lanczos_replicas does not cover this model / dataset (it "
-                               "needs a float32 linear VAE -- no hidden layers -- with one or two decoders and D, L <= 32, D <= 28 with two; "
+        if not getattr(self.eng, "supports_" + self.ENTRY)(self.kind):
+            raise RuntimeError(f"{self.NAME}: vaek_{self.ENTRY}_lanczos_replicas does not cover this model / dataset (it "
+                               f"needs {self.COVERS}; "
                                f"this model's step path: {getattr(self.eng, 'step_path', '?')})")
 
     def event(self, step=None, x_tag=None):
@@ -556,9 +559,9 @@ class ReplicaSampledElboHessian(ReplicaEvent):
         z_seeds, z_steps = _seed_step_tensors(seeds, own, self.eng.device)
         x_seeds, x_steps = _seed_step_tensors(seeds, own if given is None else given, self.eng.device)
         tag = self.X_TAG if given is None else (ReplicaExactLogLik.X_TAG if x_tag is None else int(x_tag))
-        self.eng.sampled_elbo_hessian_lanczos_replicas(self.params, self.rows, self.steps, self.v0, self.basis, self.out, self.workspace,
-                                                       samples=self.samples, x_seeds=x_seeds, x_steps=x_steps, z_seeds=z_seeds,
-                                                       z_steps=z_steps, x_tag=tag, z_tag=self.Z_TAG, **self._drawn())
+        getattr(self.eng, self.ENTRY + "_lanczos_replicas")(self.params, self.rows, self.steps, self.v0, self.basis, self.out, self.workspace,
+                                                            samples=self.samples, x_seeds=x_seeds, x_steps=x_steps, z_seeds=z_seeds,
+                                                            z_steps=z_steps, x_tag=tag, z_tag=self.Z_TAG, **self._drawn())
         rec = self._records().numpy()
         stats = []
         for r in range(self.R):
@@ -585,6 +588,29 @@ class ReplicaSampledElboHessian(ReplicaEvent):
         for st, ex in zip(stats, exact_stats):
             st[self.GAP] = st[self.KEYS[2]] - float(ex[ReplicaElboHessian.KEYS[2]])
         return stats
+
+
+class ReplicaSampledElboHessianMlp3(ReplicaSampledElboHessian):
+    """ReplicaSampledElboHessian for R THREE-HIDDEN-LAYER MLP VAEModels of one shape (vaek_mlp3_sampled_elbo_hessian_lanczos_replicas,
+    csrc/mlp3_hessian.hip): the same event, record and five keys -- the two classes cover disjoint models, as the two log-likelihood
+    classes do -- with the R-op through both relu stacks.  ONE call per event for all models (6 + 6 steps launches) and ONE device -> host
+    copy.  The default is K = 1 sample per row: the training loss's own estimator, and a column costs 39 KB of workspace at
+    200|200|200.  It does NOT perturb the run: its draws have a counter of their own, `m._mlp_hessian_draws`, and the tags 14 (rows),
+    15 (samples) and 16 (start vector).  At most 2^13 columns a model and 2^14 a call."""
+
+    X_TAG, Z_TAG, V_TAG = 14, 15, 16
+    NAME = "ReplicaSampledElboHessianMlp3"
+    COUNTER = "_mlp_hessian_draws"
+    MAX_REPLICA_COLUMNS = 1 << 13
+    ENTRY = "mlp3_sampled_elbo_hessian"
+    COVERS = "float32, one decoder, exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, D, L <= 32"
+
+    def __init__(self, vae_models, steps=32, samples=1, rows=None):
+        super().__init__(vae_models, steps, samples, rows)
+
+    def event_after(self, ran):
+        """event() of an n_print event: no other observable shares its rows."""
+        return self.event()
 
 
 class ReplicaJacobianMlp3(ReplicaEvent):

@@ -17,7 +17,10 @@ path)` for further refusals (what it returns goes to `attrs`), `attrs(args, valu
 {dest: value}), the banners of a single model (m) and of a sweep (event, n_models, cfg), and save_flag: model_save_data reads it.
 
 OBSERVABLES holds the seven flags tests/test_observables_host.py pins by equality; an observable added since stands in
-LATER_OBSERVABLES with the name of the entry it follows, and TABLE is the two merged: everything below reads TABLE.
+LATER_OBSERVABLES with the name of the entry it follows, and TABLE is the two merged.  tests/test_sampled_hessian_host.py in turn pins
+len(TABLE) == len(OBSERVABLES) + 1 and the row of sampled_elbo_hessian, so those three stay exactly as they are: what came after
+(--mlp_sampled_elbo_hessian) stands in MLP_OBSERVABLES, again with the name of the entry it follows, and ALL_OBSERVABLES is the merged
+whole: everything below reads ALL_OBSERVABLES.
 
 The table's order is the order the results are merged into the stats dict -- the stats line and the keys of losses.npz -- and the
 order both callers issue the device calls in.  Every event draws under its own counter and tags (events.py), so the order of the
@@ -273,7 +276,69 @@ def _merged():
 
 
 TABLE = _merged()
-FLAGS = {fl.dest: (ob, fl) for ob in TABLE for fl in ob.flags}
+
+MLP_HESSIAN_DEFAULT_SAMPLES = 1              # the training loss's own estimator; a column costs 39 KB of workspace at 200|200|200
+MLP_HESSIAN_MAX_REPLICA_COLUMNS = 1 << 13
+
+
+def mlp_sampled_elbo_hessian_samples(args):
+    """K of --mlp_sampled_elbo_hessian: --mlp_sampled_elbo_hessian_samples, else 1."""
+    k = getattr(args, "mlp_sampled_elbo_hessian_samples", None)
+    return MLP_HESSIAN_DEFAULT_SAMPLES if k is None else int(k)
+
+
+def _mlp_sampled_caps(fl, m, eng, steps, n_models, path):
+    return dict(flag=fl.flag, n=n_models, rows=m.print_batch_size, max_samples=eng.log_likelihood_max_samples,
+                max_columns=eng.mlp3_sampled_elbo_hessian_max_columns, path=path)
+
+
+def _mlp_sampled_attrs(args, steps, caps):
+    samples = mlp_sampled_elbo_hessian_samples(args)
+    if caps is not None:
+        if samples > caps["max_samples"]:
+            raise RuntimeError(f"{caps['flag']}_samples {samples}: at most {caps['max_samples']} samples per row fit one call "
+                               f"(vaek_log_likelihood_max_samples; this model's step path: {caps['path']})")
+        cols = caps["n"] * caps["rows"] * samples
+        if cols > caps["max_columns"] or caps["rows"] * samples > MLP_HESSIAN_MAX_REPLICA_COLUMNS:
+            raise RuntimeError(f"{caps['flag']}_samples {samples}: {caps['n']} models x {caps['rows']} rows x {samples} samples = {cols} "
+                               f"columns, at most {caps['max_columns']} fit one call and {MLP_HESSIAN_MAX_REPLICA_COLUMNS} one model "
+                               f"(vaek_mlp3_sampled_elbo_hessian_max_columns; this model's step path: {caps['path']})")
+    return {"mlp_sampled_elbo_hessian": steps, "mlp_sampled_elbo_hessian_samples": samples}
+
+
+# (the entry it follows, the observable): the same event and keys as sampled_elbo_hessian for an mlp3 model -- the two flags cover
+# disjoint models, as the two log-likelihood flags do
+MLP_OBSERVABLES = (
+    ("sampled_elbo_hessian", Observable(
+        flags=(Flag("--mlp_sampled_elbo_hessian", "mlp_sampled_elbo_hessian",
+                    "a model vaek_mlp3_sampled_elbo_hessian_lanczos_replicas covers (vaek_supports_mlp3_sampled_elbo_hessian): " + _MLP3_MODEL,
+                    extra=_mlp_sampled_caps, attrs=_mlp_sampled_attrs,
+                    linear_hint="this is a linear VAE: use --sampled_elbo_hessian",
+                    banner_one=lambda m: f"Sampled ELBO Hessian events: {m.mlp_sampled_elbo_hessian} Lanczos steps on {m.print_batch_size} "
+                                         f"rows x {m.mlp_sampled_elbo_hessian_samples} samples "
+                                         "(vaek_mlp3_sampled_elbo_hessian_lanczos_replicas)",
+                    banner_sweep=lambda ev, n, cfg: f"Sampled ELBO Hessian events: {ev.steps} Lanczos steps on {ev.rows} rows x {ev.samples} "
+                                                    f"samples per model, one call for {n} models "
+                                                    "(vaek_mlp3_sampled_elbo_hessian_lanczos_replicas)"),),
+        events=(("mlp_sampled_elbo_hessian", "_mlp_sampled_hessian", "ReplicaSampledElboHessianMlp3"),),
+        covered=lambda eng, kind: eng.supports_mlp3_sampled_elbo_hessian(kind),
+        build=lambda cls, ms, cfg: cls(ms, cfg.mlp_sampled_elbo_hessian,
+                                       getattr(cfg, "mlp_sampled_elbo_hessian_samples", MLP_HESSIAN_DEFAULT_SAMPLES)),
+        run=lambda ev, ran, cfg: ev.event_after(ran),
+        array_keys=lambda cls: cls.KEYS[:2])),
+)
+
+
+def _merged_all():
+    table = []
+    for ob in TABLE:
+        table.append(ob)
+        table.extend(later for after, later in MLP_OBSERVABLES if after == ob.name)
+    return tuple(table)
+
+
+ALL_OBSERVABLES = _merged_all()
+FLAGS = {fl.dest: (ob, fl) for ob in ALL_OBSERVABLES for fl in ob.flags}
 
 
 # ---- the refusals ---------------------------------------------------------------------------------------------------------------
@@ -305,7 +370,7 @@ def attach(args, models, cfg, build):
     """For every observable flag in `args`, in table order: check_model on model 0 (refusing before any step), set the flag's
     attributes on `cfg` (the model itself for a single model, the sweep's settings for a sweep) and yield the flag.  With `build`
     an observable's event object is built as soon as its flags are checked -- before any step; without, on its first event."""
-    for ob in TABLE:
+    for ob in ALL_OBSERVABLES:
         for fl in ob.flags:
             value = fl.value(args)
             if value is not None:
@@ -332,7 +397,7 @@ def _event(ob, models, cfg):
 
 def active(models, cfg):
     """(observable, its event object) of every observable set on `cfg`, in table order."""
-    for ob in TABLE:
+    for ob in ALL_OBSERVABLES:
         ev = _event(ob, models, cfg)
         if ev is not None:
             yield ob, ev
@@ -357,7 +422,7 @@ def array_keys(dest):
 
 def stats_line_rules(table=OBSERVABLES):
     """({array key: the text write_stats puts in front of element 0 of its value, or None: nothing on the line}) of `table` (model.py
-    passes TABLE)."""
+    passes ALL_OBSERVABLES)."""
     rules = {}
     for ob in table:
         for key in ob.array_keys(ob.event_class()):

@@ -4,7 +4,7 @@ losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never read
 (--num_epochs, --padding_type, -ii, -ufc, -wsl, -off, -ws) are accepted and inert, except -ws
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
 --fused_stats, --mlp_fused_stats, and the observables of the n_print events, which observables.py tables: --log_likelihood_samples,
---mlp_log_likelihood_samples, --exact_log_likelihood, --elbo_hessian, --sampled_elbo_hessian (with --sampled_elbo_hessian_samples),
+--mlp_log_likelihood_samples, --exact_log_likelihood, --elbo_hessian, --sampled_elbo_hessian (with --sampled_elbo_hessian_samples), --mlp_sampled_elbo_hessian (with --mlp_sampled_elbo_hessian_samples),
 --eigenvalues, --subspace, --decoder_jacobian (with --decoder_jacobian_tol)."""
 from __future__ import annotations
 
@@ -124,6 +124,19 @@ def build_parser():
                         "models, data parallelism and models x rows x K above 2^22 (rows x K above 2^16) are refused before any step")
     p.add_argument("--sampled_elbo_hessian_samples", dest="sampled_elbo_hessian_samples", type=_positive_int, default=None, metavar="K",
                    help="with --sampled_elbo_hessian: K latent samples per row (default 8); refused without --sampled_elbo_hessian")
+    p.add_argument("--mlp_sampled_elbo_hessian", dest="mlp_sampled_elbo_hessian", nargs="?", type=_hessian_steps,
+                   const=ELBO_HESSIAN_MAX_STEPS, default=None, metavar="STEPS",
+                   help="--sampled_elbo_hessian for three-hidden-layer MLP VAEs (trainer.ReplicaSampledElboHessianMlp3, "
+                        "vaek_mlp3_sampled_elbo_hessian_lanczos_replicas): at every n_print step STEPS (1 .. 32, default 32) Lanczos steps "
+                        "on the Hessian of the sample-average ELBO of the model(s) on a print batch of rows and K fixed latent samples per "
+                        "row (--mlp_sampled_elbo_hessian_samples), float64 through both relu stacks; the same five keys in losses.npz.  Its "
+                        "own RNG counter and tags: the training run and every other stat are bitwise the ones without the flag.  Alone or "
+                        "with --sweep_dataset_seeds; combines with the other mlp3 flags.  Linear models (use --sampled_elbo_hessian), other "
+                        "MLPs, data parallelism and models x rows x K above 2^14 (rows x K above 2^13) are refused before any step")
+    p.add_argument("--mlp_sampled_elbo_hessian_samples", dest="mlp_sampled_elbo_hessian_samples", type=_positive_int, default=None,
+                   metavar="K",
+                   help="with --mlp_sampled_elbo_hessian: K latent samples per row (default 1, the training loss's own estimator); refused "
+                        "without --mlp_sampled_elbo_hessian")
     p.add_argument("--mlp_log_likelihood_samples", dest="mlp_log_likelihood_samples", type=_positive_int, default=None, metavar="K",
                    help="--log_likelihood_samples for three-hidden-layer MLP VAEs (trainer.ReplicaLogLikMlp3, "
                         "vaek_mlp3_log_likelihood_replicas): the same three stats from the same draws, the training run bitwise the one "
@@ -377,13 +390,14 @@ def check_mlp_fused_stats_loop(loop, fused_stats=False):
                            "vaek_supports_mlp3_stats_event does not cover")
 
 
-# ---- the observables of the n_print events: observables.OBSERVABLES holds their NEEDS texts, refusals and banners; the names below
+# ---- the observables of the n_print events: observables.ALL_OBSERVABLES holds their NEEDS texts, refusals and banners; the names below
 # are what callers and tests import
 LOGLIK_NEEDS = FLAGS["log_likelihood_samples"][1].needs
 MLP_LOGLIK_NEEDS = FLAGS["mlp_log_likelihood_samples"][1].needs
 EXACT_LOGLIK_NEEDS = FLAGS["exact_log_likelihood"][1].needs
 ELBO_HESSIAN_NEEDS = FLAGS["elbo_hessian"][1].needs
 SAMPLED_ELBO_HESSIAN_NEEDS = FLAGS["sampled_elbo_hessian"][1].needs
+MLP_SAMPLED_ELBO_HESSIAN_NEEDS = FLAGS["mlp_sampled_elbo_hessian"][1].needs
 EIGEN_NEEDS = FLAGS["eigenvalues"][1].needs
 SUBSPACE_NEEDS = FLAGS["subspace"][1].needs
 JACOBIAN_NEEDS = FLAGS["decoder_jacobian"][1].needs
@@ -413,6 +427,11 @@ def check_elbo_hessian_model(m):
 def check_sampled_elbo_hessian_model(m, steps=ELBO_HESSIAN_MAX_STEPS, n_models=1):
     """--sampled_elbo_hessian: refuse, before any step, a model the sampled Lanczos call does not cover."""
     check_model("sampled_elbo_hessian", m, steps, n_models)
+
+
+def check_mlp_sampled_elbo_hessian_model(m, steps=ELBO_HESSIAN_MAX_STEPS, n_models=1):
+    """--mlp_sampled_elbo_hessian: refuse, before any step, a model the MLP sampled Lanczos call does not cover."""
+    return check_model("mlp_sampled_elbo_hessian", m, steps, n_models)
 
 
 def check_eigenvalues_model(m):
@@ -449,6 +468,13 @@ def check_sampled_elbo_hessian_flags(args):
     """--sampled_elbo_hessian_samples without --sampled_elbo_hessian: refused before anything is created."""
     if getattr(args, "sampled_elbo_hessian_samples", None) is not None and getattr(args, "sampled_elbo_hessian", None) is None:
         raise RuntimeError("--sampled_elbo_hessian_samples sets the samples per row of --sampled_elbo_hessian [STEPS]: give that flag too")
+
+
+def check_mlp_sampled_elbo_hessian_flags(args):
+    """--mlp_sampled_elbo_hessian_samples without --mlp_sampled_elbo_hessian: refused before anything is created."""
+    if getattr(args, "mlp_sampled_elbo_hessian_samples", None) is not None and getattr(args, "mlp_sampled_elbo_hessian", None) is None:
+        raise RuntimeError("--mlp_sampled_elbo_hessian_samples sets the samples per row of --mlp_sampled_elbo_hessian [STEPS]: give that "
+                           "flag too")
 
 
 def main_sweep(args):
@@ -541,6 +567,7 @@ def main(args):
     check_log_likelihood_flags(args)
     check_decoder_jacobian_flags(args)
     check_sampled_elbo_hessian_flags(args)
+    check_mlp_sampled_elbo_hessian_flags(args)
     if getattr(args, "sweep_dataset_seeds", None):
         return main_sweep(args)
     from .utils import get_output_dir, make_output_dir

@@ -46,8 +46,8 @@ import torch
 
 # The evaluations of the n_print events live in events.py; their names stay importable from here.
 from .events import (ReplicaElboHessian, ReplicaEvent, ReplicaExactLogLik, ReplicaJacobianMlp3, ReplicaLogLik,      # noqa: F401
-                     ReplicaLogLikMlp3, ReplicaSampledElboHessian, ReplicaSpectrum, ReplicaStats, ReplicaStatsMlp3, ReplicaSubspace, _replica_setup,
-                     _seed_step_tensors, _signature, _wrap_signed)
+                     ReplicaLogLikMlp3, ReplicaSampledElboHessian, ReplicaSampledElboHessianMlp3, ReplicaSpectrum, ReplicaStats,
+                     ReplicaStatsMlp3, ReplicaSubspace, _replica_setup, _seed_step_tensors, _signature, _wrap_signed)
 
 
 def _trajectory_capacity(loop_name, models, every, capacity):
