@@ -41,6 +41,11 @@ SHAPES = {
     "linear_20": dict(sig=False, tdv=True, eps=-1.0, kind=0, D=20, L=20, dd=3, did=3, pad=17, var=0.0),
     "sphere": dict(sig=False, tdv=False, eps=-1.0, kind=2, D=6, L=6, dd=3, did=3, pad=3, var=0.0),
 }
+# a mixing matrix that is not square, did > 4 with noise (noise normals from Philox block 3), L % 4 = 1 and 3: property (iii) alone
+OFF_SQUARE = {
+    "did9_L5": dict(sig=False, tdv=True, eps=-1.0, kind=0, D=7, L=5, dd=5, did=9, pad=2, var=0.25),
+    "did9_L7": dict(sig=False, tdv=True, eps=-1.0, kind=0, D=7, L=7, dd=5, did=9, pad=2, var=0.25),
+}
 EVENT_ROWS = 1000
 
 
@@ -119,7 +124,7 @@ class _EventCase:
 
     def __init__(self, name, batch=100):
         from vae_training_amd.engine import Engine
-        s = self.s = SHAPES[name]
+        s = self.s = SHAPES[name] if name in SHAPES else OFF_SQUARE[name]
         self.eng = e = Engine(batch, s["D"], s["L"], (), (), s["eps"], s["tdv"], s["sig"])
         assert e.supports_spectrum_event(s["kind"]) and e.supports_cov_spectrum()
         self.len = e.cov_spectrum_record_len
@@ -232,6 +237,20 @@ def test_fused_event_properties_and_the_fake_side(name):
     print(f"{name}: worst fake-side |dC| / max(C_kk + m_k^2) {worst_c:.2e} (bound {T3:.0e}), worst |d lambda| {worst_e:.3f} of its bound")
     assert torch.equal(c.params, before), "params were written"
     assert c.A is None or torch.equal(c.A, a_before), "A was written"
+
+
+@pytest.mark.parametrize("name", list(OFF_SQUARE))
+def test_real_side_equals_make_batch_rows_off_the_square_matrix(name):
+    """(iii) of test_fused_event_properties_and_the_fake_side, bitwise, at dd = 5, did = 9 with dataset noise: the event's own draw of
+    the real rows is vaek_make_batch's."""
+    c = _case(name)
+    ln, rows = c.len, 257
+    got = c.records(rows).cpu().numpy()
+    for r in range(R):
+        x = c.x_rows(r, rows).cpu().numpy()
+        assert x[:, c.s["dd"]:].all()                                            # noise reaches the padding columns
+        real = _rows_call(c.eng, x[None])[0]
+        assert np.array_equal(real, got[r, ln:2 * ln]), f"replica {r}: the real record is not vaek_cov_spectrum_rows on make_batch's x"
 
 
 def test_fused_event_at_other_row_counts_and_captured():

@@ -30,7 +30,9 @@ SENT = -12345.0
 R = 3
 X_TAG = 3
 PAD_OUT, PAD_ROW = 3, 5                     # sentinel doubles behind a record and behind a row block
-DRAW = {(12, 20): dict(kind=0, dd=3, did=3, pad=9, var=0.01), (7, 7): dict(kind=2, dd=4, did=4, pad=3, var=0.0)}
+DRAW = {(12, 20): dict(kind=0, dd=3, did=3, pad=9, var=0.01), (7, 7): dict(kind=2, dd=4, did=4, pad=3, var=0.0),
+        # a mixing matrix that is not square, did > 4 with noise (noise normals from Philox block 3), L % 4 = 1 and 3
+        (8, 5): dict(kind=0, dd=5, did=9, pad=3, var=0.25), (8, 7): dict(kind=0, dd=5, did=9, pad=3, var=0.25)}
 
 
 @functools.lru_cache(maxsize=None)
@@ -225,6 +227,24 @@ def test_records_are_bitwise_reproducible(D, L, rows):
         assert torch.equal(o2, d) and torch.equal(o3, a), batch
     assert torch.equal(c.params, before), "params were written"
     assert c.A is None or torch.equal(c.A, a_before), "A was written"
+
+
+@pytest.mark.parametrize("D,L", [(8, 5), (8, 7)], ids=["did9_L5", "did9_L7"])
+def test_drawn_rows_equal_make_batch_rows_off_the_square_matrix(D, L):
+    """Drawing mode = explicit mode on vaek_make_batch's rows, bitwise as in test_records_are_bitwise_reproducible, at dd = 5,
+    did = 9 with dataset noise."""
+    c = _case(D, L, -8.0)
+    rows = 257
+    d, rd = c.out(), c.row_out(rows)
+    c.call_draw(d, rows, row_out=rd)
+    torch.cuda.synchronize()
+    assert bool((d[:, :c.len] != SENT).all()) and bool(torch.isfinite(d[:, :c.len]).all())
+    xs = torch.stack([c.drawn_rows(r, rows) for r in range(R)]).contiguous()
+    assert not torch.equal(xs[0], xs[1]) and bool((xs[:, :, c.draw["dd"]:] != 0).all())      # noise reaches the padding columns
+    e, re_ = c.out(), c.row_out(rows)
+    c.call(e, rows, x=xs, row_out=re_)
+    torch.cuda.synchronize()
+    assert torch.equal(e, d) and torch.equal(re_, rd)
 
 
 def test_exact_log_likelihood_is_capturable():

@@ -53,6 +53,12 @@ SHAPES = {
     # beyond the issue's four: the 32 x 32 two-decoder instantiation, the only one whose registers reach into the AGPRs
     "two_decoder_wide": dict(sig=True, tdv=True, eps=-1.0, kind=1, D=28, L=32, dd=7, did=1, pad=20, var=0.0),
 }
+# a mixing matrix that is not square (the A[d * did + k] stride), did > 4 with noise (the noise normals start at Philox block 3, not
+# 1), latent streams with L % 4 = 1 and L % 4 = 3: only the drawn-against-supplied comparison runs on these
+OFF_SQUARE = {
+    "did9_L5": dict(sig=False, tdv=True, eps=-1.0, kind=0, D=7, L=5, dd=5, did=9, pad=2, var=0.25),
+    "did9_L7": dict(sig=False, tdv=True, eps=-1.0, kind=0, D=7, L=7, dd=5, did=9, pad=2, var=0.25),
+}
 ROWS = (1, 37, 256, 257, 1000)
 KS = (1, 2, 5, 64)
 
@@ -97,7 +103,7 @@ class _Case:
 
     def __init__(self, name, batch=100, **ekw):
         from vae_training_amd.engine import Engine
-        s = self.s = SHAPES[name]
+        s = self.s = SHAPES[name] if name in SHAPES else OFF_SQUARE[name]
         self.eng = e = Engine(batch, s["D"], s["L"], (), (), s["eps"], s["tdv"], s["sig"], **ekw)
         assert e.supports_log_likelihood(s["kind"])
         assert e.log_likelihood_record_len == 4
@@ -287,6 +293,19 @@ def test_records_are_bitwise_reproducible(name, rows, K):
     assert torch.equal(shared[0], a[0]) and not torch.equal(shared[1], a[1])
     assert torch.equal(c.params, before), "params were written"
     assert c.A is None or torch.equal(c.A, a_before), "A was written"
+
+
+@pytest.mark.parametrize("name", list(OFF_SQUARE))
+def test_drawn_rows_equal_make_batch_rows_off_the_square_matrix(name):
+    """Drawing mode = explicit mode on vaek_make_batch's rows, bitwise as in test_records_are_bitwise_reproducible, where the in-launch
+    draw leaves the line every other shape is on: dd = 5, did = 9, dataset noise, L % 4 = 1 and 3."""
+    c = _case(name)
+    rows, K = 257, 5
+    a = c.records(rows, K)
+    assert bool((a[:, :4] != SENT).all()) and bool(torch.isfinite(a[:, :4]).all())
+    xs = torch.stack([c.x_rows(r, rows) for r in range(R)]).contiguous()
+    assert not torch.equal(xs[0], xs[1]) and bool((xs[:, :, c.s["dd"]:] != 0).all())         # noise reaches the padding columns
+    assert torch.equal(c.records(rows, K, x=xs), a)
 
 
 def test_log_likelihood_is_capturable():

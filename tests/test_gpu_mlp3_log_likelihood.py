@@ -57,6 +57,12 @@ SHAPES = {
     "mixed": dict(enc=(64, 256, 100), dec=(130, 72, 200), tdv=True, eps=-1.0, kind=2, D=9, L=5, dd=4, did=4, pad=5, var=0.0),
     "notdv": dict(enc=H200, dec=H200, tdv=False, eps=-1.0, kind=2, D=6, L=6, dd=3, did=3, pad=3, var=0.0),
 }
+# a mixing matrix that is not square (the A[d * did + k] stride), did > 4 with noise (the noise normals start at Philox block 3, not
+# 1), latent streams with L % 4 = 1 and L % 4 = 3: only the drawn-against-supplied comparison runs on these
+OFF_SQUARE = {
+    "did9_L5": dict(enc=(64, 64, 64), dec=(64, 64, 64), tdv=True, eps=-1.0, kind=0, D=7, L=5, dd=5, did=9, pad=2, var=0.25),
+    "did9_L7": dict(enc=(64, 64, 64), dec=(64, 64, 64), tdv=True, eps=-1.0, kind=0, D=7, L=7, dd=5, did=9, pad=2, var=0.25),
+}
 ROWS = (1, 16, 37, 130)
 KS = (1, 5, 16, 67)
 MAXR = max(ROWS)
@@ -149,7 +155,7 @@ def _cfg(s):
 
 def make_flats(name):
     """The R float32 parameter vectors of shape `name` (NumPy only: the CPU experiment of the module docstring uses them too)."""
-    s = SHAPES[name]
+    s = SHAPES[name] if name in SHAPES else OFF_SQUARE[name]
     cfg = _cfg(s)
     rng = np.random.default_rng(23)
     flats = []
@@ -208,7 +214,7 @@ class _Case:
     buffer."""
 
     def __init__(self, name, batch=100, **ekw):
-        s = self.s = SHAPES[name]
+        s = self.s = SHAPES[name] if name in SHAPES else OFF_SQUARE[name]
         self.name = name
         self.eng = e = _engine(s, batch, **ekw)
         assert e.supports_mlp3_log_likelihood(s["kind"]) and not e.supports_log_likelihood(s["kind"])
@@ -392,6 +398,19 @@ def test_records_are_bitwise_reproducible(name, rows, K):
     assert bool((p4[:, c.P:] == SENT).all())
     assert torch.equal(c.params, before), "params, or the floats between two replicas' parameters, were written"
     assert c.A is None or torch.equal(c.A, a_before), "A was written"
+
+
+@pytest.mark.parametrize("name", list(OFF_SQUARE))
+def test_drawn_rows_equal_make_batch_rows_off_the_square_matrix(name):
+    """Drawing mode = explicit mode on vaek_make_batch's rows, bitwise as in test_records_are_bitwise_reproducible, where the in-launch
+    draw leaves the line every other shape is on: dd = 5, did = 9, dataset noise, L % 4 = 1 and 3."""
+    c = _case(name)
+    rows, K = 130, 5
+    a = c.records(rows, K)
+    assert bool((a[:, :4] != SENT).all()) and bool(torch.isfinite(a[:, :4]).all())
+    xs = torch.stack([c.x_rows(r, rows) for r in range(R)]).contiguous()
+    assert not torch.equal(xs[0], xs[1]) and bool((xs[:, :, c.s["dd"]:] != 0).all())         # noise reaches the padding columns
+    assert torch.equal(c.records(rows, K, x=xs), a)
 
 
 def test_mlp3_log_likelihood_is_capturable():

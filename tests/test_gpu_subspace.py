@@ -281,6 +281,35 @@ def test_fused_event_on_a_planted_subspace(name):
     assert torch.equal(c.params, before), "params were written"
 
 
+@pytest.mark.parametrize("L", [5, 7])
+def test_real_side_equals_make_batch_rows_off_the_square_matrix(L):
+    """The first check of test_fused_event_on_a_planted_subspace, bitwise, where the event's own draw of the real rows leaves the line
+    the planted cases are on: a 5 x 9 mixing matrix (the A[d * did + k] stride), dataset noise whose normals start at Philox block 3,
+    latent streams with L % 4 = 1 and 3."""
+    from vae_training_amd.engine import Engine
+    n, D, dd, did, pad, var = 3, 7, 5, 9, 2, 0.25
+    eng = Engine(ROWS, D, L, (), (), -1.0, True, False)
+    assert eng.supports_spectrum_event(0)
+    ln = eng.cov_eigen_record_len
+    g = torch.Generator().manual_seed(17)
+    params = (torch.randn(n, eng.P, generator=g) * 0.3).cuda().contiguous()
+    A = torch.randn(n, dd * did, generator=g).cuda().contiguous()
+    x_seeds, x_steps = [77, 2 ** 63 + 5, 1000003], [1, 4, 2 ** 31 + 7]
+    out = torch.full((n, 2 * ln + 3), SENT, dtype=torch.float64, device="cuda")
+    eng.eigen_event_replicas(params=params, rows=ROWS, kind=0, A=A, dd=dd, did=did, pad=pad, var_added=var, x_seeds=_i64(x_seeds),
+                             x_steps=_i32(x_steps), z_seeds=_i64([2 ** 64 - 3, 991, 31337]), z_steps=_i32([3, 2 ** 32 - 1, 2]),
+                             sample_eps=torch.full((n,), -1.0, dtype=torch.float32, device="cuda"), out=out, a_stride=dd * did,
+                             x_tag=X_TAG, z_tag=Z_TAG)
+    torch.cuda.synchronize()
+    got = out.cpu().numpy()
+    assert np.all(got[:, 2 * ln:] == SENT) and np.isfinite(got[:, :2 * ln]).all()
+    for r in range(n):
+        x = eng.make_batch(0, A[r].clone(), dd, did, pad, var, ROWS, x_seeds[r], step=x_steps[r], tag=X_TAG, want_z=False)[0].cpu().numpy()
+        assert x[:, dd:].all()                                                   # noise reaches the padding columns
+        real = _rows_call(eng.cov_eigen_rows, ln, x[None])[0]
+        assert np.array_equal(real, got[r, ln:2 * ln]), f"replica {r}: the real record is not vaek_cov_eigen_rows on make_batch's x"
+
+
 def test_refusals_leave_the_buffers_untouched():
     """Every refusal of the three entry points returns VAEK_ERR_INVALID with a message naming the function and leaves the sentinel
     buffers unchanged; exactly one profile record per launch, under the new labels."""

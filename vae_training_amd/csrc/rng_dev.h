@@ -17,14 +17,22 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
     return c;
 }
 
-// Box-Muller on one Philox block: 4 words -> 4 normals.  u1 in (0,1) from 24 bits, u2 in [0,1) from 32.
+// Box-Muller on one Philox block: 4 words -> 4 normals.  Both uniforms are float32 and both round: u1 = ((w >> 8) + 0.5) 2^-24 is a
+// tie from w >> 8 = 2^23 on and goes to even, down or up by 2^-25 -- for w >> 8 = 2^24 - 1 to 1.0, where v_log gives 0, r = 0 and a sphere row of
+// dd <= 2 became 0 / 0 once in 2^24 rows -- so u1 is clamped to the largest float32 below 1 (one v_min a pair; every other draw keeps
+// its bits): u1 in [2^-25, 1 - 2^-24], r in [3.45e-4, 5.89].  u2 = w 2^-32 in [0, 1], 1.0 for w >= 2^32 - 128 (a whole revolution: the
+// same point as 0).  oracle/philox.py's kernel_uniforms reproduces both bit for bit.
 // On the hardware transcendentals: r = sqrt(-2 ln u1) = v_sqrt(-2 ln 2 * v_log(u1)) (v_log_f32 is log2), and v_sin_f32 / v_cos_f32 take
 // their argument in REVOLUTIONS, so cos(2 pi u2) is one instruction on u2 -- 6 quarter-rate instructions per block where the
 // library's logf / sincospif spent ~200 (the draw inside vaek_train_steps_gen's streamers runs at two waves per SIMD: nothing hides
-// a long dependent chain there).  Within 5e-6 of the float64 Box-Muller of oracle/philox.py (tests/test_rng.py); every generator
-// entry point shares this function, so they stay bit-identical to each other.
+// a long dependent chain there).  Against the KERNEL-UNIFORM reference (float64 Box-Muller on these float32 uniforms:
+// oracle/philox.py's normals_kernel_uniform) a normal is within the EPS_N of tests/rng_cases.py, measured in
+// profiles/rng_conformance.txt (tests/test_gpu_rng_conformance.py); the ideal Box-Muller on the exact 24-bit integer
+// (normals_from_bits) is further away by design wherever u1 rounded, up to 1.2e-4 at the clamp.  Every generator entry point shares
+// this function, so they stay bit-identical to each other.
 __device__ __forceinline__ void normals4(uint4 b, float (&n)[4]) {
-    const float u1a = ((float)(b.x >> 8) + 0.5f) * 5.9604644775390625e-08f, u1b = ((float)(b.z >> 8) + 0.5f) * 5.9604644775390625e-08f;
+    const float u1a = fminf(((float)(b.x >> 8) + 0.5f) * 5.9604644775390625e-08f, 0x1.fffffep-1f);
+    const float u1b = fminf(((float)(b.z >> 8) + 0.5f) * 5.9604644775390625e-08f, 0x1.fffffep-1f);
     const float ra = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1a));
     const float rb = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u1b));
     const float ta = (float)b.y * 2.3283064365386963e-10f, tb = (float)b.w * 2.3283064365386963e-10f;

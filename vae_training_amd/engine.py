@@ -912,12 +912,14 @@ class Engine:
                                             _ptr(step_dev), int(step), int(tag), _stream()))
         return x, z1, z2
 
-    def rng_fill(self, n, seed, step=0, tag=0, bits=False):
-        out_n = torch.empty(n, dtype=torch.float32, device=self.device)
+    def rng_fill(self, n, seed, step=0, tag=0, bits=False, normals=True):
+        """n normals of the raw stream (vaek_rng_fill: block b under counter (b lo, b hi, step, tag)), with bits=True also the
+        Philox words they were formed from; normals=False gives the words alone."""
+        out_n = torch.empty(n, dtype=torch.float32, device=self.device) if normals else None
         out_u = torch.empty(n, dtype=torch.int32, device=self.device) if bits else None
         _lib.check(self.lib.vaek_rng_fill(self.h, _ptr(out_n), _ptr(out_u), int(n), int(seed) & (2**64 - 1), int(step),
                                           int(tag), _stream()))
-        return (out_n, out_u) if bits else out_n
+        return (out_n, out_u) if bits and normals else (out_n if normals else out_u)
 
     def set_loss_history(self, buf):
         self._loss_hist = buf                      # keep it alive
