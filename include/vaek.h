@@ -1070,6 +1070,49 @@ int vaek_mlp3_decoder_jacobian_max_columns(void);
 int vaek_mlp3_decoder_jacobian_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes);
 int vaek_mlp3_decoder_jacobian_replicas(vaek_ctx* ctx, const float* params, const vaek_decoder_jacobian* dj, uint32_t z_tag,
                                         void* workspace, void* stream);
+/* DECODER JACOBIAN SPECTRA of N LINEAR VAEs of the context's shape, ONE OR TWO DECODERS, in one call (csrc/linear_jacobian.hip):
+ * vaek_mlp3_decoder_jacobian_replicas for the models without hidden layers -- the description struct, the ROW RECORD (2 L + 4 doubles),
+ * the MODEL RECORD (2 L + 8 doubles), their two length queries and the two row modes (explicit z; z == NULL: the z1 vaek_make_batch
+ * writes under (z_seeds[r], z_steps[r], z_tag), bit for bit) are those of the block above, unchanged.  For networks.py:73-83
+ *   x_hat(z) = z K_d + b_d [+ sigmoid(z K_s + b_s)],      J(z) = K_d^T [+ diag(g(u(z))) K_s^T],   u = z K_s + b_s,
+ *   g(u) = sigmoid'(u) = e / ((1 + e)(1 + e)),  e = exp(-|u|)
+ * (symmetric in u, no 1 - s cancellation, never inf or NaN for a finite u, exactly 0 for a saturated head; the quotient is rounded
+ * essentially once, 1 + e and its square carried as pairs of doubles: error well below 1 ulp of exp's e), and G(z) = J^T J with its
+ * eigenvalues as above.  With one decoder J is K_d^T at every z: all row records of a replica are bitwise equal and their lambda are
+ * the eigenvalues of K^T K in the record of vaek_exact_log_likelihood_replicas (two Jacobi solves apart); z, where given, is checked
+ * and not read.  With two decoders J changes from row to row through the D slopes g(u_d).
+ * ARITHMETIC: float64 from u onward (J costs one exp per output column, so nothing forces the float32 J of the MLP call):
+ * u_d = b_s[d] + sum_l z_l K_s[l][d] in l order, J[l][d] = K_d[l][d] + g_d K_s[l][d], G_ij a sum over d in d order, then the cyclic
+ * Jacobi of the covariance spectra (stop at off_F <= 2^-43 |G|_F or vaek_cov_spectrum_max_sweeps), the counting rank and the tails: the
+ * text of the MLP call's solve launch (csrc/jacobian_dev.h), instantiated for a float64 J.
+ * TWO launches per call whatever n is (profile labels linear_jacobian_rows, linear_jacobian_finalize): a workgroup per (row, replica)
+ * does all of the above and stores the row record into the workspace and, where given, row_out; n workgroups add the rows in a binary
+ * tree per 256 rows, then the tiles in order -- the MLP call's finalize launch, the same code.  Nothing stored in a launch is read back
+ * in it; no atomic, counter, wait or status word.
+ * DEFINING PROPERTIES: a row's record depends on its latent's and the parameters' bits only: replica r's records are BITWISE what a
+ * call with n = 1 on its slices leaves, two runs are bitwise equal, drawing mode equals explicit mode on the z1 vaek_make_batch writes,
+ * and the records do not depend on ctx.batch, state_stride, the number of rows in the call or whether row_out is given.  A two-decoder
+ * context with K_s = 0, or with every head saturated (g = 0), leaves bitwise the row records of the one-decoder context holding the same
+ * K_d.  Rows l >= k of K_d and K_s exactly zero give diag G[l] = 0.0 exactly and rank <= k; all kernels zero ends at 0 sweeps, rank 0.
+ * lambda and diag G agree with the float64 NumPy evaluation (numpy.linalg.eigvalsh) within (2^-43 + 8 x the reference's own error
+ * of G against long double + 64 L 2^-53) |G|_F -- measured per case in tests/test_gpu_linear_jacobian.py.
+ * rows is 1 .. vaek_stats_event_max_rows() = 4096, n 1 .. vaek_train_loop_max_replicas(), and n * rows <=
+ * vaek_linear_decoder_jacobian_max_rows() = 2^20, one workgroup each (a cap on the length of a launch on a shared machine, not a tuned
+ * value).  `workspace`: device memory of vaek_linear_decoder_jacobian_workspace_bytes(ctx, n, rows) bytes -- the row records only --,
+ * 16-byte aligned, the call's own, no need to clear.  The weights are read one dword at a time: state_stride has no alignment rule.
+ * Asynchronous on `stream`, allocates nothing, does not synchronise, capturable into a hipGraph.
+ * vaek_supports_linear_decoder_jacobian: vaek_supports_log_likelihood's predicate without the kind (the call draws no data rows):
+ * float32, no hidden layers, one or two decoders, D, L <= 32, D <= 28 with two decoders -- whatever ctx.batch, world and force_generic
+ * are.  NOT covered: models with hidden layers (vaek_mlp3_decoder_jacobian_replicas has the three-layer ones), bf16, D or L > 32, left
+ * or right singular vectors, tangent-space alignment, data parallelism.
+ * VAEK_ERR_INVALID (message names vaek_linear_decoder_jacobian_replicas, nothing touched): the list of the block above with n * rows in
+ * the place of n * rows * L.  vaek_linear_decoder_jacobian_workspace_bytes refuses an unsupported context and sizes outside those
+ * ranges and leaves *bytes alone. */
+int vaek_supports_linear_decoder_jacobian(const vaek_ctx* ctx, int32_t* yes);
+int vaek_linear_decoder_jacobian_max_rows(void);
+int vaek_linear_decoder_jacobian_workspace_bytes(const vaek_ctx* ctx, int32_t n, int32_t rows, size_t* bytes);
+int vaek_linear_decoder_jacobian_replicas(vaek_ctx* ctx, const float* params, const vaek_decoder_jacobian* dj, uint32_t z_tag,
+                                          void* workspace, void* stream);
 /* One train step of N INDEPENDENT three-hidden-layer MLP VAEs of the context's shape (csrc/fused_mlp3.hip, step path "mlp3"): the
  * two launches of that step with gridDim.y = N, blockIdx.y = r training replica r.  A solo step keeps 7 of the MI355X's 256 CUs
  * busy for most of its length (one chain workgroup per 16 batch rows at batch 100); neither launch has a counter, a wait or an

@@ -268,6 +268,10 @@ SIGNATURES = {
     "vaek_mlp3_decoder_jacobian_max_columns": (C.c_int, []),
     "vaek_mlp3_decoder_jacobian_workspace_bytes": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_size_t)]),
     "vaek_mlp3_decoder_jacobian_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekDecoderJacobian), C.c_uint32, _vp, _vp]),
+    "vaek_supports_linear_decoder_jacobian": (C.c_int, [_vp, C.POINTER(_i32)]),
+    "vaek_linear_decoder_jacobian_max_rows": (C.c_int, []),
+    "vaek_linear_decoder_jacobian_workspace_bytes": (C.c_int, [_vp, _i32, _i32, C.POINTER(C.c_size_t)]),
+    "vaek_linear_decoder_jacobian_replicas": (C.c_int, [_vp, _vp, C.POINTER(VaekDecoderJacobian), C.c_uint32, _vp, _vp]),
     "vaek_supports_train_step_replicas": (C.c_int, [_vp, C.POINTER(_i32)]),
     "vaek_train_step_max_replicas": (C.c_int, []),
     "vaek_train_step_replicas_workspace_bytes": (C.c_int, [_vp, _i32, C.POINTER(C.c_size_t)]),

@@ -1,4 +1,4 @@
-// The host-side checks of the twelve vaek_*_replicas evaluation entry points, once (eval_check.hip; no kernels).  An entry point copies
+// The host-side checks of the thirteen vaek_*_replicas evaluation entry points, once (eval_check.hip; no kernels).  An entry point copies
 // its description into an EvalDesc (describe), states what it adds in an EvalRules and calls check_eval; its own refusals (samples,
 // columns, nvec, steps, further buffers, rank_tol) follow in its unit.  check_eval refuses, in this order and with the first that fails:
 //    1. a NULL description                          7. a NULL seeds / steps / sample_eps array the mode needs, a NULL out

@@ -5,6 +5,8 @@
 // the four kernels with the three 0/1 masks of the primal pass between them.  L tangent columns per row go through three layers of
 // up to 256 units, so every product is v_mfma_f32_16x16x4_f32 (exact f32) through ml_dense of mlp3_dev.h, the Dense chain of the
 // log-likelihood and stats kernels, and the symmetric solve is jacobi_solve of eigen_dev.h; both headers as they are.
+// The bodies of the solve and finalize launches are the shared text of jacobian_dev.h, which vaek_linear_decoder_jacobian_replicas
+// runs too.
 //
 // SCHEME (a): primal and tangents travel together.  A latent row takes L + 1 adjacent columns of a 64-column [unit][column] image: its
 // primal column (z, then the activations) and its L tangent columns (e_l, then d activation / d z_l), so a tile holds 64 / (L + 1)
@@ -30,12 +32,12 @@
 #include "mlp3_dev.h"
 #include "eigen_dev.h"
 #include "eval_check.h"
+#include "jacobian_dev.h"
 
 namespace vaek {
 
 constexpr int kMjMaxColumns = 1 << 20;       // n * rows * L: bounds the workspace (128 MB of J) and the length of a call -- a cap, not a tuned value
 constexpr int MJ_NC = 64;                    // columns of a tangent tile: rows * (L + 1) of them are used
-constexpr int MJ_QS = 8;                     // sums one tree pass of the finalize launch carries
 
 struct MjArgs {
     const float* params; long long state_stride;
@@ -52,13 +54,6 @@ struct MjSolveArgs {
     double* rec;                             // [n][rows][2 L + 4]: the workspace's row records
     double* row_out; long long row_out_stride;      // the caller's copy (may be NULL), replica r at row_out + r * row_out_stride
     int rows, D, L;
-    double rank_tol;
-};
-
-struct MjFinalArgs {
-    const double* rec;                       // [n][rows][2 L + 4]
-    double* out; long long out_stride;
-    int rows, L;
     double rank_tol;
 };
 
@@ -144,13 +139,10 @@ __global__ __launch_bounds__(ML_NT) void mlp3_jacobian_tangent_kernel(const MjAr
     }
 }
 
-// ---- launch 2: J of one row -> its record -----------------------------------------------------------------------------------------------
+// ---- launch 2: J of one row -> its record (jacobian_solve_row of jacobian_dev.h on the float32 J) ------------------------------------------
 __global__ __launch_bounds__(256) void mlp3_jacobian_solve_kernel(const MjSolveArgs a) {
-    __shared__ double mat[2 * kMatDoubles];
+    __shared__ JacobianSolveLds s;
     __shared__ float Js[kSpectrumMaxDim * kSpectrumMaxDim];
-    __shared__ double red[256];
-    __shared__ double rot_c[kSpectrumMaxDim], rot_s[kSpectrumMaxDim], eig[kSpectrumMaxDim], dg[kSpectrumMaxDim];
-    __shared__ int rot_mate[kSpectrumMaxDim];
     const int t = threadIdx.x;
     const int row = blockIdx.x;
     const long long r = blockIdx.y;
@@ -159,153 +151,24 @@ __global__ __launch_bounds__(256) void mlp3_jacobian_solve_kernel(const MjSolveA
     const float* const Jg = a.J + rr * (L * D);
     for (int e = t; e < L * D; e += 256) Js[e] = Jg[e];
     __syncthreads();
-
-    // ---- G = J^T J for i <= j, mirrored, zero outside [L] x [L]; the products of two floats are exact in float64 ---------------------
-    double sq = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int idx = t + 256 * k, i = idx >> 5, j = idx & 31;
-        if (i <= j) {
-            double v = 0.0;
-            if (j < L) {
-                for (int d = 0; d < D; ++d) v += (double)Js[i * D + d] * (double)Js[j * D + d];
-            }
-            mat[i * kMatStride + j] = v;
-            mat[j * kMatStride + i] = v;
-            if (i == j) dg[i] = v;
-            sq += i == j ? v * v : 2.0 * v * v;
-        }
-    }
-    const double norm_g = sqrt(block_sum256(sq, red, t));            // its barriers also publish the first buffer
-
-    int cur, sweeps;
-    double off_f;
-    jacobi_solve<false>(mat, nullptr, L + (L & 1), norm_g, red, rot_c, rot_s, rot_mate, t, cur, sweeps, off_f);
-
-    // ---- eigenvalues descending: the rank of a diagonal element is the count of those before it, ties by index -----------------------
-    const double* const A = mat + cur * kMatDoubles;
-    if (t < kSpectrumMaxDim) eig[t] = t < L ? A[t * kMatStride + t] : 0.0;
-    __syncthreads();
     double* const rec = a.rec + rr * (2 * L + 4);
     double* const ro = a.row_out ? a.row_out + r * a.row_out_stride + (long long)row * (2 * L + 4) : nullptr;
-    if (t < L) {
-        const double e = eig[t];
-        int rank = 0;
-        for (int j = 0; j < L; ++j) {
-            const double o = eig[j];
-            rank += (o > e || (o == e && j < t)) ? 1 : 0;
-        }
-        rec[rank] = e;
-        rec[L + t] = dg[t];
-        if (ro) { ro[rank] = e; ro[L + t] = dg[t]; }
-    }
-    if (t >= 64 && t < 68) {
-        const int s = t - 64;
-        double tail;
-        if (s == 0) {                            // the numerical rank: #{k : lambda_k > rank_tol lambda_1}, 0 where lambda_1 = 0
-            double top = 0.0;
-            for (int j = 0; j < L; ++j) top = fmax(top, eig[j]);
-            int cnt = 0;
-            for (int j = 0; j < L; ++j) cnt += (top > 0.0 && eig[j] > a.rank_tol * top) ? 1 : 0;
-            tail = (double)cnt;
-        } else {
-            tail = s == 1 ? (double)sweeps : (s == 2 ? off_f : norm_g);
-        }
-        rec[2 * L + s] = tail;
-        if (ro) ro[2 * L + s] = tail;
-    }
+    jacobian_solve_row<float>(Js, s, D, L, a.rank_tol, rec, ro, t);
 }
 
-// ---- launch 3: the row records of a replica -> its model record ------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void mlp3_jacobian_finalize_kernel(const MjFinalArgs a) {
-    __shared__ double red[MJ_QS][256];
-    __shared__ double mred[256];
-    __shared__ double res[2 * kSpectrumMaxDim + 8];
-    const int t = threadIdx.x;
-    const long long r = blockIdx.x;
-    const int L = a.L, rows = a.rows, len = 2 * L + 4;
-    const double* const rec = a.rec + r * rows * (long long)len;
-    const int tiles = (rows + 255) / 256;
-    const int nq = 2 * L + 2;                    // sums: lambda_k (L), diag (L), rank, |J|_F^2 = the diagonal added in l order
-
-    for (int q0 = 0; q0 < nq; q0 += MJ_QS) {
-        double acc[MJ_QS];
-#pragma unroll
-        for (int k = 0; k < MJ_QS; ++k) acc[k] = 0.0;
-        for (int tile = 0; tile < tiles; ++tile) {
-            const int row = tile * 256 + t;
-            const double* const rw = rec + (long long)min(row, rows - 1) * len;
-#pragma unroll
-            for (int k = 0; k < MJ_QS; ++k) {
-                const int q = q0 + k;
-                double v = 0.0;
-                if (row < rows && q < nq) {
-                    if (q <= 2 * L) {
-                        v = rw[q];
-                    } else {
-                        for (int l = 0; l < L; ++l) v += rw[L + l];
-                    }
-                }
-                red[k][t] = v;
-            }
-            tree_sum256(red, t);
-#pragma unroll
-            for (int k = 0; k < MJ_QS; ++k) acc[k] += red[k][0];         // the tiles in tile order
-            __syncthreads();
-        }
-        if (t == 0) {
-#pragma unroll
-            for (int k = 0; k < MJ_QS; ++k) {
-                const int q = q0 + k;
-                if (q < nq) {
-                    const double mean = acc[k] / (double)rows;
-                    if (q < 2 * L) res[8 + q] = mean;
-                    else if (q == 2 * L) res[1] = mean;
-                    else res[4] = mean;
-                }
-            }
-        }
-    }
-
-    // ---- the extremes: every one a maximum of values >= 0 (the smallest rank as L - the largest of L - rank) -------------------------
-    double mx_rank = 0.0, mx_def = 0.0, mx_sweeps = 0.0, mx_ratio = 0.0;
-    for (int tile = 0; tile < tiles; ++tile) {
-        const int row = tile * 256 + t;
-        double rk = (double)L, sw = 0.0, ratio = 0.0, has = 0.0;
-        if (row < rows) {
-            const double* const rw = rec + (long long)row * len;
-            rk = rw[2 * L]; sw = rw[2 * L + 1];
-            const double ng = rw[2 * L + 3];
-            ratio = ng > 0.0 ? rw[2 * L + 2] / ng : 0.0;
-            has = 1.0;
-        }
-        mx_rank = fmax(mx_rank, block_max256(has * rk, mred, t));
-        mx_def = fmax(mx_def, block_max256((double)L - rk, mred, t));
-        mx_sweeps = fmax(mx_sweeps, block_max256(sw, mred, t));
-        mx_ratio = fmax(mx_ratio, block_max256(ratio, mred, t));
-    }
-    if (t == 0) {
-        res[0] = (double)rows;
-        res[2] = (double)L - mx_def;
-        res[3] = mx_rank;
-        res[5] = mx_sweeps;
-        res[6] = mx_ratio;
-        res[7] = a.rank_tol;
-    }
-    __syncthreads();
-    if (t < 2 * L + 8) a.out[r * a.out_stride + t] = res[t];
+// ---- launch 3: the row records of a replica -> its model record (jacobian_finalize_replica of jacobian_dev.h) --------------------------
+__global__ __launch_bounds__(256) void mlp3_jacobian_finalize_kernel(const JacobianFinalArgs a) {
+    __shared__ JacobianFinalLds s;
+    jacobian_finalize_replica(a, s, blockIdx.x, threadIdx.x);
 }
 
 static int mj_rows_per_tile(int L) { return MJ_NC / (L + 1); }
-static int64_t mj_record_len(const vaek_ctx* c) { return 2 * (int64_t)c->L + 8; }
-static int64_t mj_row_record_len(const vaek_ctx* c) { return 2 * (int64_t)c->L + 4; }
-static size_t mj_up16(size_t b) { return (b + 15) & ~(size_t)15; }
 // the workspace: J [n][rows][L][D] floats, then the row records [n][rows][2 L + 4] doubles, each 16-byte aligned
 struct MjWs { size_t rec, total; };
 static MjWs mj_workspace(const vaek_ctx* c, int n, int rows) {
     MjWs w;
-    w.rec = mj_up16(sizeof(float) * (size_t)n * rows * c->L * c->D);
-    w.total = w.rec + mj_up16(sizeof(double) * (size_t)n * rows * (size_t)mj_row_record_len(c));
+    w.rec = jacobian_up16(sizeof(float) * (size_t)n * rows * c->L * c->D);
+    w.total = w.rec + jacobian_up16(sizeof(double) * (size_t)n * rows * (size_t)jacobian_row_record_len(c));
     return w;
 }
 // the column product as `who` refuses it: the call's and its workspace query's
@@ -330,13 +193,13 @@ int vaek_supports_mlp3_decoder_jacobian(const vaek_ctx* ctx, int32_t* yes) {
 
 int vaek_decoder_jacobian_record_len(const vaek_ctx* ctx, int64_t* doubles) {
     if (!ctx || !doubles) { set_error("vaek_decoder_jacobian_record_len: null argument"); return VAEK_ERR_INVALID; }
-    *doubles = mj_record_len(ctx);
+    *doubles = jacobian_record_len(ctx);
     return VAEK_OK;
 }
 
 int vaek_decoder_jacobian_row_record_len(const vaek_ctx* ctx, int64_t* doubles) {
     if (!ctx || !doubles) { set_error("vaek_decoder_jacobian_row_record_len: null argument"); return VAEK_ERR_INVALID; }
-    *doubles = mj_row_record_len(ctx);
+    *doubles = jacobian_row_record_len(ctx);
     return VAEK_OK;
 }
 
@@ -361,22 +224,12 @@ int vaek_mlp3_decoder_jacobian_replicas(vaek_ctx* ctx, const float* params, cons
     EvalRules r{};
     r.covered = ctx && ctx->mlp3_loglik; r.needs = kMjNeeds;
     r.rows_min = 1; r.rows_cap = kSpectrumMaxRows; r.rows_query = "vaek_stats_event_max_rows";
-    r.records = 1; r.record_len = ctx ? mj_record_len(ctx) : 0; r.record_query = "vaek_decoder_jacobian_record_len";
+    r.records = 1; r.record_len = ctx ? jacobian_record_len(ctx) : 0; r.record_query = "vaek_decoder_jacobian_record_len";
     r.has_z_tag = true; r.z_tag = z_tag;                             // no dataset draw: the rows are latents
     r.workspace = workspace; r.ws_align = 16; r.ws_query = "vaek_mlp3_decoder_jacobian_workspace_bytes";
     if (int rc = check_eval(who, ctx, params, d, r)) return rc;
     if (int rc = mj_check_columns(who, ctx, dj->n, dj->rows)) return rc;
-    const int64_t rlen = mj_row_record_len(ctx);
-    if (dj->row_out && dj->row_out_stride < (int64_t)dj->rows * rlen) {
-        set_error("%s: row_out_stride %lld < rows x row record length = %lld (vaek_decoder_jacobian_row_record_len)", who,
-                  (long long)dj->row_out_stride, (long long)dj->rows * rlen);
-        return VAEK_ERR_INVALID;
-    }
-    if (int rc = check_aligned8(who, "row_out", (uintptr_t)dj->row_out)) return rc;
-    if (!(dj->rank_tol >= 0.0 && dj->rank_tol < 1.0)) {
-        set_error("%s: rank_tol %g, need 0 <= rank_tol < 1", who, dj->rank_tol);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_jacobian_outputs(who, ctx, dj)) return rc;
     const int n = dj->n, rows = dj->rows, L = ctx->L, D = ctx->D;
     const MjWs w = mj_workspace(ctx, n, rows);
     char* const ws = static_cast<char*>(workspace);
@@ -390,7 +243,7 @@ int vaek_mlp3_decoder_jacobian_replicas(vaek_ctx* ctx, const float* params, cons
     MjSolveArgs s{};
     s.J = a.J; s.rec = reinterpret_cast<double*>(ws + w.rec); s.row_out = dj->row_out; s.row_out_stride = dj->row_out_stride;
     s.rows = rows; s.D = D; s.L = L; s.rank_tol = dj->rank_tol;
-    MjFinalArgs f{};
+    JacobianFinalArgs f{};
     f.rec = s.rec; f.out = dj->out; f.out_stride = dj->out_stride; f.rows = rows; f.L = L; f.rank_tol = dj->rank_tol;
 
     constexpr size_t lds = sizeof(float) * 2 * ML_W * MJ_NC;

@@ -462,6 +462,14 @@ class Engine:
         only), seeds int64 [n], steps int32 [n], out / row_out: float64, workspace: uint8 of mlp3_decoder_jacobian_workspace(n, rows)
         bytes -- all device tensors; n and the strides default to the tensors' shapes.  Three launches whatever n is.  Asynchronous;
         capturable."""
+        dj = self._decoder_jacobian_desc(params, rows, out, z_seeds, z_steps, z, z_stride, rank_tol, row_out, row_out_stride, n, state_stride,
+                                         out_stride, struct_size)
+        _lib.check(self.lib.vaek_mlp3_decoder_jacobian_replicas(self.h, _ptr(params), C.byref(dj), int(z_tag), _addr(workspace), _stream()))
+
+    @staticmethod
+    def _decoder_jacobian_desc(params, rows, out, z_seeds, z_steps, z, z_stride, rank_tol, row_out, row_out_stride, n, state_stride, out_stride,
+                               struct_size):
+        """The vaek_decoder_jacobian both decoder-Jacobian calls take."""
         dj = _describe(_lib.VaekDecoderJacobian(), params, rows, out, torch.float64, n, state_stride, out_stride, struct_size,
                        draws=dict(z=(z_seeds, z_steps)), given=("z", z, z_stride))
         assert row_out is None or row_out.dtype == torch.float64
@@ -470,7 +478,33 @@ class Engine:
         if row_out_stride is None:
             row_out_stride = 0 if row_out is None else row_out.shape[-2] * row_out.shape[-1]
         dj.row_out_stride = int(row_out_stride)
-        _lib.check(self.lib.vaek_mlp3_decoder_jacobian_replicas(self.h, _ptr(params), C.byref(dj), int(z_tag), _addr(workspace), _stream()))
+        return dj
+
+    def supports_linear_decoder_jacobian(self):
+        """True where linear_decoder_jacobian_replicas covers this engine: supports_log_likelihood's predicate without the dataset kind
+        (float32, no hidden layers, one or two decoders, D, L <= 32, D <= 28 with two decoders) -- whatever the engine's batch, world and
+        force_generic are (vaek_supports_linear_decoder_jacobian)."""
+        return self._flag(self.lib.vaek_supports_linear_decoder_jacobian)
+
+    @property
+    def linear_decoder_jacobian_max_rows(self):
+        """The cap on n * rows of one linear_decoder_jacobian_replicas call (vaek_linear_decoder_jacobian_max_rows)."""
+        return int(self.lib.vaek_linear_decoder_jacobian_max_rows())
+
+    def linear_decoder_jacobian_workspace(self, n, rows):
+        """Bytes of the workspace linear_decoder_jacobian_replicas needs (its own buffer, 16-byte aligned, not self.workspace)."""
+        return self._count(self.lib.vaek_linear_decoder_jacobian_workspace_bytes, int(n), int(rows), ctype=C.c_size_t)
+
+    def linear_decoder_jacobian_replicas(self, params, rows, out, workspace, z_seeds=None, z_steps=None, z=None, z_stride=None, rank_tol=1e-4,
+                                         row_out=None, row_out_stride=None, z_tag=5, n=None, state_stride=None, out_stride=None,
+                                         struct_size=None):
+        """mlp3_decoder_jacobian_replicas for linear VAEs with one or two decoders (vaek_linear_decoder_jacobian_replicas): the same
+        records, row modes and arguments, with J(z) = K_d^T + diag(sigmoid'(z K_s + b_s)) K_s^T (one decoder: K_d^T at every z) formed
+        and solved in float64; workspace: uint8 of linear_decoder_jacobian_workspace(n, rows) bytes.  Two launches whatever n is.
+        Asynchronous; capturable."""
+        dj = self._decoder_jacobian_desc(params, rows, out, z_seeds, z_steps, z, z_stride, rank_tol, row_out, row_out_stride, n, state_stride,
+                                         out_stride, struct_size)
+        _lib.check(self.lib.vaek_linear_decoder_jacobian_replicas(self.h, _ptr(params), C.byref(dj), int(z_tag), _addr(workspace), _stream()))
 
     def supports_cov_spectrum(self):
         """True where cov_spectrum_rows covers this engine: data_dim <= 32, whatever its architecture, dtype, batch and world are

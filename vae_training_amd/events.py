@@ -1,6 +1,6 @@
 """The evaluations of the n_print events, each ONE library call for R models of one shape: the fused stats events (ReplicaStats,
 ReplicaStatsMlp3) and the observables that observables.py tables -- ReplicaLogLik / ReplicaLogLikMlp3, ReplicaExactLogLik,
-ReplicaElboHessian, ReplicaSampledElboHessian / ReplicaSampledElboHessianMlp3, ReplicaSpectrum / ReplicaSubspace and ReplicaJacobianMlp3 -- on one spine, ReplicaEvent.  trainer.py re-exports
+ReplicaElboHessian, ReplicaSampledElboHessian / ReplicaSampledElboHessianMlp3, ReplicaSpectrum / ReplicaSubspace and ReplicaJacobianMlp3 / ReplicaJacobianLinear -- on one spine, ReplicaEvent.  trainer.py re-exports
 every name of this module.
 
 The RNG tags: 0 the train loop, 1 the dataset's batches, 2 the latents (ReplicaStats draws what compute_stats draws), 3 / 4 the
@@ -613,18 +613,19 @@ class ReplicaSampledElboHessianMlp3(ReplicaSampledElboHessian):
         return self.event()
 
 
-class ReplicaJacobianMlp3(ReplicaEvent):
-    """The decoder Jacobian spectra of R three-hidden-layer MLP VAEModels of one shape in ONE library call
-    (vaek_mlp3_decoder_jacobian_replicas, csrc/mlp3_jacobian.hip): per model, over `rows` latent rows z, the eigenvalues of J^T J with
-    J = d Decoder(z) / dz -- the squared singular values of the decoder's local linear map --, their numerical rank and the
-    sensitivity |d Decoder / d z_l|^2 of every latent: how many directions of the latent space the decoder uses, and which are off.
+class ReplicaJacobian(ReplicaEvent):
+    """The decoder Jacobian spectra of R VAEModels of one shape in ONE library call: per model, over `rows` latent rows z, the
+    eigenvalues of J^T J with J = d Decoder(z) / dz -- the squared singular values of the decoder's local linear map --, their
+    numerical rank and the sensitivity |d Decoder / d z_l|^2 of every latent: how many directions of the latent space the decoder
+    uses, and which are off.  The spine of ReplicaJacobianMlp3 and ReplicaJacobianLinear, which name the library call (ENTRY), its cap
+    (_check_cap) and the models it covers (_check_covered); the two never meet on one model, so they share a counter and tags.
 
     `at` chooses the latents:
       "prior"      the call draws them: the z1 vaek_make_batch writes under the event's seed, step and latent tag -- the latents
                    sample_batch decodes at a stats event;
       "posterior"  per model the event's real rows are drawn with make_batch (row tag), mu comes from vaek_forward(sampling=0) and goes
                    to the call as explicit rows: the Jacobian on the encoded data manifold.
-    event() makes ONE vaek_mlp3_decoder_jacobian_replicas call for all models and ONE device -> host copy of the [R, 2 L + 8] float64
+    event() makes ONE library call for all models and ONE device -> host copy of the [R, 2 L + 8] float64
     records.  It does NOT perturb the run: `m.key`, the dataset's `_draws`, `m._latent_draws` and the other events' counters are left
     alone.  Its draws have a counter of their own, `m._jacobian_draws`, and the tags 7 (rows) and 8 (latents).  Returns per model
     {"Decoder Jacobian Spectrum" (float64 [L], descending), "Decoder Jacobian Rank" (float64 [3]: mean, min, max), "Latent
@@ -633,7 +634,6 @@ class ReplicaJacobianMlp3(ReplicaEvent):
 
     KEYS = ("Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity")
     X_TAG, Z_TAG = 7, 8
-    NAME = "ReplicaJacobianMlp3"
     NOUN = "call"
     ROWS = (1, "stats_event_max_rows", "")
     COUNTER = "_jacobian_draws"
@@ -650,22 +650,12 @@ class ReplicaJacobianMlp3(ReplicaEvent):
 
     def _allocate(self, R, dev):
         self.L = self.eng.L
-        cols, cap = R * self.rows * self.L, self.eng.mlp3_decoder_jacobian_max_columns
-        if cols > cap:
-            raise RuntimeError(f"{self.NAME}: {R} models x {self.rows} rows x {self.L} latents = {cols} columns, at most {cap} fit one call "
-                               "(vaek_mlp3_decoder_jacobian_max_columns)")
+        self._check_cap(R)
         self.record_len = self.eng.decoder_jacobian_record_len
         self.out = torch.zeros(R, self.record_len, dtype=torch.float64, device=dev)
-        self.workspace = torch.empty(max(self.eng.mlp3_decoder_jacobian_workspace(R, self.rows), 16), dtype=torch.uint8, device=dev)
+        self.workspace = torch.empty(max(getattr(self.eng, self.ENTRY + "_workspace")(R, self.rows), 16), dtype=torch.uint8, device=dev)
         if self.at == "posterior":
             self.z = torch.zeros(R, self.rows, self.L, dtype=torch.float32, device=dev)
-
-    def _check_covered(self):
-        if not self.eng.supports_mlp3_decoder_jacobian():
-            raise RuntimeError("ReplicaJacobianMlp3: vaek_mlp3_decoder_jacobian_replicas does not cover this model (it needs a float32 "
-                               "VAE with one decoder and exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, "
-                               "D, L <= 32; the Jacobian of a linear decoder is its kernel: ReplicaExactLogLik's record holds the "
-                               f"eigenvalues of K^T K; this model's step path: {getattr(self.eng, 'step_path', '?')})")
 
     def event(self):
         """One evaluation of every model: [{"Decoder Jacobian Spectrum", "Decoder Jacobian Rank", "Latent Sensitivity"} of model 0, ...]."""
@@ -683,8 +673,8 @@ class ReplicaJacobianMlp3(ReplicaEvent):
             src = dict(z=self.z)
         else:
             src = dict(zip(("z_seeds", "z_steps"), _seed_step_tensors(seeds, steps, self.eng.device)))
-        self.eng.mlp3_decoder_jacobian_replicas(self.params, self.rows, self.out, self.workspace, rank_tol=self.rank_tol, z_tag=self.Z_TAG,
-                                                **src)
+        getattr(self.eng, self.ENTRY + "_replicas")(self.params, self.rows, self.out, self.workspace, rank_tol=self.rank_tol,
+                                                    z_tag=self.Z_TAG, **src)
         rec = self._records().numpy()
         stats = []
         for r, m in enumerate(self.ms):
@@ -695,6 +685,50 @@ class ReplicaJacobianMlp3(ReplicaEvent):
             self._append(m, jacobian_spectra=st[self.KEYS[0]], jacobian_ranks=st[self.KEYS[1]], latent_sensitivities=st[self.KEYS[2]])
             stats.append(st)
         return stats
+
+
+class ReplicaJacobianMlp3(ReplicaJacobian):
+    """ReplicaJacobian for three-hidden-layer MLP VAEModels (vaek_mlp3_decoder_jacobian_replicas, csrc/mlp3_jacobian.hip):
+    J(z) = K3^T M3 K2^T M2 K1^T M1 K0^T, the four decoder kernels with the relu masks of z between them, in float32."""
+
+    NAME = "ReplicaJacobianMlp3"
+    ENTRY = "mlp3_decoder_jacobian"
+
+    def _check_cap(self, R):
+        cols, cap = R * self.rows * self.L, self.eng.mlp3_decoder_jacobian_max_columns
+        if cols > cap:
+            raise RuntimeError(f"{self.NAME}: {R} models x {self.rows} rows x {self.L} latents = {cols} columns, at most {cap} fit one call "
+                               "(vaek_mlp3_decoder_jacobian_max_columns)")
+
+    def _check_covered(self):
+        if not self.eng.supports_mlp3_decoder_jacobian():
+            raise RuntimeError("ReplicaJacobianMlp3: vaek_mlp3_decoder_jacobian_replicas does not cover this model (it needs a float32 "
+                               "VAE with one decoder and exactly three hidden layers of 64 .. 256 units in the encoder and in the decoder, "
+                               "D, L <= 32; the Jacobian of a linear decoder is its kernel: ReplicaExactLogLik's record holds the "
+                               "eigenvalues of K^T K; per-row records and two-decoder linear models are what ReplicaJacobianLinear "
+                               f"(--linear_decoder_jacobian) is for; this model's step path: {getattr(self.eng, 'step_path', '?')})")
+
+
+class ReplicaJacobianLinear(ReplicaJacobian):
+    """ReplicaJacobian for linear VAEModels with one or two decoders (vaek_linear_decoder_jacobian_replicas, csrc/linear_jacobian.hip):
+    J(z) = K_d^T + diag(sigmoid'(z K_s + b_s)) K_s^T in float64 -- with one decoder K_d^T at every z, with two a matrix that changes
+    from row to row: the rank and the dead latents of the generators of the sigmoid experiment."""
+
+    NAME = "ReplicaJacobianLinear"
+    ENTRY = "linear_decoder_jacobian"
+
+    def _check_cap(self, R):
+        total, cap = R * self.rows, self.eng.linear_decoder_jacobian_max_rows
+        if total > cap:
+            raise RuntimeError(f"{self.NAME}: {R} models x {self.rows} rows = {total} rows, at most {cap} fit one call "
+                               "(vaek_linear_decoder_jacobian_max_rows)")
+
+    def _check_covered(self):
+        if not self.eng.supports_linear_decoder_jacobian():
+            raise RuntimeError("ReplicaJacobianLinear: vaek_linear_decoder_jacobian_replicas does not cover this model (it needs a float32 "
+                               "linear VAE -- no hidden layers -- with one or two decoders, D, L <= 32, D <= 28 with two decoders; a "
+                               "three-hidden-layer MLP model takes ReplicaJacobianMlp3 (--decoder_jacobian); this model's step path: "
+                               f"{getattr(self.eng, 'step_path', '?')})")
 
 
 class ReplicaSpectrum(ReplicaEvent):

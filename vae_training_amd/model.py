@@ -74,7 +74,7 @@ class Model:
 # the keys whose values are arrays whatever their length, from the table of observables: they stay off the stats line
 HESSIAN_ARRAY_KEYS = observables.array_keys("elbo_hessian")
 JACOBIAN_KEYS = observables.array_keys("decoder_jacobian")
-_ARRAY_KEY_LINES = observables.stats_line_rules(observables.ALL_OBSERVABLES)
+_ARRAY_KEY_LINES = observables.stats_line_rules(observables.EVERY_OBSERVABLE)
 
 
 class GenerativeModel(Model):
@@ -133,8 +133,8 @@ class GenerativeModel(Model):
 
     def _stats_event(self):
         """The stats of an n_print event: compute_stats(), then every observable whose attribute run.py set on this model
-        (observables.ALL_OBSERVABLES: `log_likelihood_samples`, `mlp_log_likelihood_samples`, `exact_log_likelihood`, `elbo_hessian`,
-        `sampled_elbo_hessian`, `mlp_sampled_elbo_hessian`, `eigenvalues` / `subspace`, `decoder_jacobian`), one device call each, in the table's order.  Each event object is built on
+        (observables.EVERY_OBSERVABLE: `log_likelihood_samples`, `mlp_log_likelihood_samples`, `exact_log_likelihood`, `elbo_hessian`,
+        `sampled_elbo_hessian`, `mlp_sampled_elbo_hessian`, `eigenvalues` / `subspace`, `decoder_jacobian`, `linear_decoder_jacobian`), one device call each, in the table's order.  Each event object is built on
         its first event and kept on the model; none of them splits the model's key or advances a draw counter of the run."""
         stats = self.compute_stats()
         stats.update(observables.run_events([self], self)[0])

@@ -19,8 +19,9 @@ path)` for further refusals (what it returns goes to `attrs`), `attrs(args, valu
 OBSERVABLES holds the seven flags tests/test_observables_host.py pins by equality; an observable added since stands in
 LATER_OBSERVABLES with the name of the entry it follows, and TABLE is the two merged.  tests/test_sampled_hessian_host.py in turn pins
 len(TABLE) == len(OBSERVABLES) + 1 and the row of sampled_elbo_hessian, so those three stay exactly as they are: what came after
-(--mlp_sampled_elbo_hessian) stands in MLP_OBSERVABLES, again with the name of the entry it follows, and ALL_OBSERVABLES is the merged
-whole: everything below reads ALL_OBSERVABLES.
+(--mlp_sampled_elbo_hessian) stands in MLP_OBSERVABLES, again with the name of the entry it follows, and ALL_OBSERVABLES is the two
+merged.  tests/test_mlp3_hessian_host.py pins len(ALL_OBSERVABLES) == len(TABLE) + 1, so the next one (--linear_decoder_jacobian)
+stands in LINEAR_OBSERVABLES by the same pattern and EVERY_OBSERVABLE is the merged whole: everything below reads EVERY_OBSERVABLE.
 
 The table's order is the order the results are merged into the stats dict -- the stats line and the keys of losses.npz -- and the
 order both callers issue the device calls in.  Every event draws under its own counter and tags (events.py), so the order of the
@@ -231,7 +232,8 @@ OBSERVABLES = (
                     "a model vaek_mlp3_decoder_jacobian_replicas covers (vaek_supports_mlp3_decoder_jacobian): " + _MLP3_MODEL,
                     extra=_jacobian_column_cap,
                     linear_hint="this is a linear VAE, whose J is the decoder kernel itself at every z: use --exact_log_likelihood, whose "
-                                "record holds the eigenvalues of K^T K",
+                                "record holds the eigenvalues of K^T K; per-row records and two-decoder models, which "
+                                "--exact_log_likelihood refuses, are what --linear_decoder_jacobian is for",
                     attrs=lambda args, at, checked: {"decoder_jacobian": at, "decoder_jacobian_tol": decoder_jacobian_tol(args)},
                     banner_one=lambda m: f"Decoder Jacobian events: {m.print_batch_size} {m.decoder_jacobian} latent rows, rank threshold "
                                          f"{m.decoder_jacobian_tol:g} (vaek_mlp3_decoder_jacobian_replicas)",
@@ -338,7 +340,58 @@ def _merged_all():
 
 
 ALL_OBSERVABLES = _merged_all()
-FLAGS = {fl.dest: (ob, fl) for ob in ALL_OBSERVABLES for fl in ob.flags}
+
+
+def linear_decoder_jacobian_tol(args):
+    """The rank threshold of --linear_decoder_jacobian: --linear_decoder_jacobian_tol, else 1e-4."""
+    tol = getattr(args, "linear_decoder_jacobian_tol", None)
+    return JACOBIAN_DEFAULT_TOL if tol is None else float(tol)
+
+
+def _linear_jacobian_extra(fl, m, eng, at, n_models, path):
+    total = n_models * m.print_batch_size
+    if total > eng.linear_decoder_jacobian_max_rows:
+        raise RuntimeError(f"{fl.flag}: {n_models} models x {m.print_batch_size} rows = {total} rows, at most "
+                           f"{eng.linear_decoder_jacobian_max_rows} fit one call (vaek_linear_decoder_jacobian_max_rows; this model's "
+                           f"step path: {path})")
+
+
+# (the entry it follows, the observable): the same event and keys as decoder_jacobian for a linear model -- the two flags cover
+# disjoint models, as the two log-likelihood flags do (run.check_decoder_jacobian_flags refuses the two together).  Its NEEDS text
+# ends with the hint for an MLP model: Flag.linear_hint is the hint for the opposite mistake
+LINEAR_OBSERVABLES = (
+    ("decoder_jacobian", Observable(
+        flags=(Flag("--linear_decoder_jacobian", "linear_decoder_jacobian",
+                    "a model vaek_linear_decoder_jacobian_replicas covers (vaek_supports_linear_decoder_jacobian): a float32 linear VAE -- "
+                    "no hidden layers -- with one or two decoders, D, L <= 32 (D <= 28 with two decoders), -dd / -did <= 16, on one GPU; "
+                    "a three-hidden-layer MLP model takes --decoder_jacobian",
+                    extra=_linear_jacobian_extra,
+                    attrs=lambda args, at, checked: {"linear_decoder_jacobian": at,
+                                                     "linear_decoder_jacobian_tol": linear_decoder_jacobian_tol(args)},
+                    banner_one=lambda m: f"Decoder Jacobian events: {m.print_batch_size} {m.linear_decoder_jacobian} latent rows, rank "
+                                         f"threshold {m.linear_decoder_jacobian_tol:g} (vaek_linear_decoder_jacobian_replicas)",
+                    banner_sweep=lambda ev, n, cfg: f"Decoder Jacobian events: {ev.rows} {ev.at} latent rows per model, rank threshold "
+                                                    f"{ev.rank_tol:g}, one call for {n} models (vaek_linear_decoder_jacobian_replicas)"),),
+        events=(("linear_decoder_jacobian", "_linear_jacobian", "ReplicaJacobianLinear"),),
+        covered=lambda eng, kind: eng.supports_linear_decoder_jacobian(),
+        build=lambda cls, ms, cfg: cls(ms, at=cfg.linear_decoder_jacobian,
+                                       rank_tol=getattr(cfg, "linear_decoder_jacobian_tol", JACOBIAN_DEFAULT_TOL)),
+        run=lambda ev, ran, cfg: ev.event(),
+        array_keys=lambda cls: cls.KEYS,               # arrays whatever L is; the stats line shows the mean rank
+        line=("Decoder Jacobian Rank", "(mean)"))),
+)
+
+
+def _merged_every():
+    table = []
+    for ob in ALL_OBSERVABLES:
+        table.append(ob)
+        table.extend(later for after, later in LINEAR_OBSERVABLES if after == ob.name)
+    return tuple(table)
+
+
+EVERY_OBSERVABLE = _merged_every()
+FLAGS = {fl.dest: (ob, fl) for ob in EVERY_OBSERVABLE for fl in ob.flags}
 
 
 # ---- the refusals ---------------------------------------------------------------------------------------------------------------
@@ -370,7 +423,7 @@ def attach(args, models, cfg, build):
     """For every observable flag in `args`, in table order: check_model on model 0 (refusing before any step), set the flag's
     attributes on `cfg` (the model itself for a single model, the sweep's settings for a sweep) and yield the flag.  With `build`
     an observable's event object is built as soon as its flags are checked -- before any step; without, on its first event."""
-    for ob in ALL_OBSERVABLES:
+    for ob in EVERY_OBSERVABLE:
         for fl in ob.flags:
             value = fl.value(args)
             if value is not None:
@@ -397,7 +450,7 @@ def _event(ob, models, cfg):
 
 def active(models, cfg):
     """(observable, its event object) of every observable set on `cfg`, in table order."""
-    for ob in ALL_OBSERVABLES:
+    for ob in EVERY_OBSERVABLE:
         ev = _event(ob, models, cfg)
         if ev is not None:
             yield ob, ev
@@ -422,7 +475,7 @@ def array_keys(dest):
 
 def stats_line_rules(table=OBSERVABLES):
     """({array key: the text write_stats puts in front of element 0 of its value, or None: nothing on the line}) of `table` (model.py
-    passes ALL_OBSERVABLES)."""
+    passes EVERY_OBSERVABLE)."""
     rules = {}
     for ob in table:
         for key in ob.array_keys(ob.event_class()):

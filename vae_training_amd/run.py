@@ -5,7 +5,8 @@ losses.npz, model.pkl, output_*.png}.  Flags the reference parses but never read
 which is rejected (out of scope).  Additions: --device, --force_generic, --sweep_dataset_seeds (main_sweep), --trajectory_every,
 --fused_stats, --mlp_fused_stats, and the observables of the n_print events, which observables.py tables: --log_likelihood_samples,
 --mlp_log_likelihood_samples, --exact_log_likelihood, --elbo_hessian, --sampled_elbo_hessian (with --sampled_elbo_hessian_samples), --mlp_sampled_elbo_hessian (with --mlp_sampled_elbo_hessian_samples),
---eigenvalues, --subspace, --decoder_jacobian (with --decoder_jacobian_tol)."""
+--eigenvalues, --subspace, --decoder_jacobian (with --decoder_jacobian_tol), --linear_decoder_jacobian (with
+--linear_decoder_jacobian_tol)."""
 from __future__ import annotations
 
 import argparse
@@ -172,6 +173,19 @@ def build_parser():
     p.add_argument("--decoder_jacobian_tol", dest="decoder_jacobian_tol", type=_rank_tol, default=None, metavar="T",
                    help="with --decoder_jacobian: an eigenvalue of J^T J counts towards the rank where it exceeds T times the largest "
                         "(0 <= T < 1, default 1e-4); refused without --decoder_jacobian")
+    p.add_argument("--linear_decoder_jacobian", dest="linear_decoder_jacobian", default=None, choices=["prior", "posterior"],
+                   help="--decoder_jacobian for linear VAEs with one or two decoders (trainer.ReplicaJacobianLinear, "
+                        "vaek_linear_decoder_jacobian_replicas): at every n_print step the spectrum of J(z) = K_d^T + "
+                        "diag(sigmoid'(z K_s + b_s)) K_s^T on a print batch of latent rows, formed and solved in float64; the same three "
+                        "keys in losses.npz, the mean rank on the stats line.  With two decoders (-sig) J changes from row to row: the rank "
+                        "says how many latent directions the generator moves its output along, 'Latent Sensitivity' which latents are "
+                        "off.  prior / posterior as for --decoder_jacobian.  Its own RNG counter and tags: the training run and every "
+                        "other stat are bitwise the ones without the flag.  Alone or with --sweep_dataset_seeds; combines with the other "
+                        "linear flags.  D, L <= 32 (D <= 28 with two decoders); MLP models (use --decoder_jacobian), --decoder_jacobian "
+                        "itself, data parallelism, -dd / -did > 16 and models x rows above 2^20 are refused before any step")
+    p.add_argument("--linear_decoder_jacobian_tol", dest="linear_decoder_jacobian_tol", type=_rank_tol, default=None, metavar="T",
+                   help="with --linear_decoder_jacobian: an eigenvalue of J^T J counts towards the rank where it exceeds T times the "
+                        "largest (0 <= T < 1, default 1e-4); refused without --linear_decoder_jacobian")
     return p
 
 
@@ -390,7 +404,7 @@ def check_mlp_fused_stats_loop(loop, fused_stats=False):
                            "vaek_supports_mlp3_stats_event does not cover")
 
 
-# ---- the observables of the n_print events: observables.ALL_OBSERVABLES holds their NEEDS texts, refusals and banners; the names below
+# ---- the observables of the n_print events: observables.EVERY_OBSERVABLE holds their NEEDS texts, refusals and banners; the names below
 # are what callers and tests import
 LOGLIK_NEEDS = FLAGS["log_likelihood_samples"][1].needs
 MLP_LOGLIK_NEEDS = FLAGS["mlp_log_likelihood_samples"][1].needs
@@ -401,6 +415,7 @@ MLP_SAMPLED_ELBO_HESSIAN_NEEDS = FLAGS["mlp_sampled_elbo_hessian"][1].needs
 EIGEN_NEEDS = FLAGS["eigenvalues"][1].needs
 SUBSPACE_NEEDS = FLAGS["subspace"][1].needs
 JACOBIAN_NEEDS = FLAGS["decoder_jacobian"][1].needs
+LINEAR_JACOBIAN_NEEDS = FLAGS["linear_decoder_jacobian"][1].needs
 
 
 def check_log_likelihood_model(m, samples):
@@ -450,6 +465,12 @@ def check_decoder_jacobian_model(m, n_models=1):
     check_model("decoder_jacobian", m, None, n_models)
 
 
+def check_linear_decoder_jacobian_model(m, n_models=1):
+    """--linear_decoder_jacobian: refuse, before any step, a model the call does not cover or more rows (models x print rows) than one
+    call takes."""
+    check_model("linear_decoder_jacobian", m, None, n_models)
+
+
 def check_log_likelihood_flags(args):
     """--log_likelihood_samples and --mlp_log_likelihood_samples cover disjoint models: both together are refused before anything is
     created."""
@@ -459,9 +480,16 @@ def check_log_likelihood_flags(args):
 
 
 def check_decoder_jacobian_flags(args):
-    """--decoder_jacobian_tol without --decoder_jacobian: refused before anything is created."""
+    """--decoder_jacobian_tol without --decoder_jacobian, --linear_decoder_jacobian_tol without --linear_decoder_jacobian, and the two
+    Jacobian flags together (they cover disjoint models and write the same keys): refused before anything is created."""
     if getattr(args, "decoder_jacobian_tol", None) is not None and getattr(args, "decoder_jacobian", None) is None:
         raise RuntimeError("--decoder_jacobian_tol sets the rank threshold of --decoder_jacobian prior|posterior: give that flag too")
+    if getattr(args, "linear_decoder_jacobian_tol", None) is not None and getattr(args, "linear_decoder_jacobian", None) is None:
+        raise RuntimeError("--linear_decoder_jacobian_tol sets the rank threshold of --linear_decoder_jacobian prior|posterior: give that "
+                           "flag too")
+    if getattr(args, "decoder_jacobian", None) is not None and getattr(args, "linear_decoder_jacobian", None) is not None:
+        raise RuntimeError("--decoder_jacobian (three-hidden-layer MLP VAEs) and --linear_decoder_jacobian (linear VAEs) cover disjoint "
+                           "models: give the one that matches the model's step path")
 
 
 def check_sampled_elbo_hessian_flags(args):

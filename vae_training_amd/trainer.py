@@ -45,8 +45,8 @@ from __future__ import annotations
 import torch
 
 # The evaluations of the n_print events live in events.py; their names stay importable from here.
-from .events import (ReplicaElboHessian, ReplicaEvent, ReplicaExactLogLik, ReplicaJacobianMlp3, ReplicaLogLik,      # noqa: F401
-                     ReplicaLogLikMlp3, ReplicaSampledElboHessian, ReplicaSampledElboHessianMlp3, ReplicaSpectrum, ReplicaStats,
+from .events import (ReplicaElboHessian, ReplicaEvent, ReplicaExactLogLik, ReplicaJacobian, ReplicaJacobianLinear,      # noqa: F401
+                     ReplicaJacobianMlp3, ReplicaLogLik, ReplicaLogLikMlp3, ReplicaSampledElboHessian, ReplicaSampledElboHessianMlp3, ReplicaSpectrum, ReplicaStats,
                      ReplicaStatsMlp3, ReplicaSubspace, _replica_setup, _seed_step_tensors, _signature, _wrap_signed)
 
 
