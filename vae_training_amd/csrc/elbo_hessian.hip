@@ -12,24 +12,16 @@
 //   HVP.  Plain float64 fmas on the 256 threads, three phases with a barrier between them; thread t owns elements t, t + 256, ... of a
 //     phase's output and every sum runs in index order.  The one reduction across threads (tr(SR^T dR) for the epsilon row) is
 //     block_sum256's fixed tree.
-//   LANCZOS.  Full reorthogonalisation: classical Gram-Schmidt twice against every earlier vector, each dot through block_sum256.  The
-//     basis lives in the caller's buffer ([steps][P] doubles per replica) and is read back by the workgroup that stored it, behind a
-//     barrier; the vector being built lives in LDS.  T goes into the Jacobi buffers (over the dead direction images) and is solved by
-//     jacobi_solve<true>, eigen_dev.h's text, included and not edited.
+//   LANCZOS.  lanczos_dev.h's recursion, the whole of it in this launch: full reorthogonalisation (classical Gram-Schmidt twice against
+//     every earlier vector, each dot through block_sum256), the breakdown rule, the Ritz tail, omega and the record.  The basis lives in
+//     the caller's buffer ([steps][P] doubles per replica) and is read back by the workgroup that stored it, behind a barrier; the vector
+//     being built lives in LDS.  T goes into the Jacobi buffers (over the dead direction images).
 //
 // The kernels read rows / parameters / directions and store only the named outputs, with per-lane vector stores.
-#include "eigen_dev.h"
+#include "lanczos_dev.h"
 #include "eval_check.h"
 
 namespace vaek {
-
-constexpr int kHessMaxSteps = 32;            // the Jacobi routine's size
-constexpr int kHvpMaxVectors = 64;           // bounds one launch -- a cap, not a tuned value
-constexpr int kHvpRecord = 4;
-constexpr int kHessHead = 12;
-constexpr int kHessRecord = kHessHead + 4 * kHessMaxSteps;
-constexpr double kHessBreakdown = 0x1p-40;
-constexpr double kHessLog2Pi = 1.8378770664093454835606594728112;
 
 constexpr int kIm = 33;                      // doubles between two rows of an image
 constexpr int kImg = kIm * kIm;
@@ -331,7 +323,7 @@ __global__ __launch_bounds__(256) void elbo_hessian_kernel(const HessArgs a) {
     if (t < L) wv[a.off_p + t] = 0.5 * (wl[t] - 1.0) + 0.5 * ea * wl[t] * k2[t];
     if (t == 0 && a.off_c >= 0) wv[a.off_c] = eps_cli * (0.5 * (double)D - 0.5 * ea * Q);
     const double trusu = block_sum256(part, red, t);                  // its barriers also publish the gradient
-    const double f = 0.5 * trusu + 0.5 * klc + 0.5 * ea * Q + 0.5 * (double)D * (eps + kHessLog2Pi);
+    const double f = 0.5 * trusu + 0.5 * klc + 0.5 * ea * Q + 0.5 * (double)D * (eps + kLog2PiF64);
     part = 0.0;
     for (int e = t; e < P; e += 256) part = fma(wv[e], wv[e], part);
     const double gnorm = sqrt(block_sum256(part, red, t));
@@ -358,135 +350,30 @@ __global__ __launch_bounds__(256) void elbo_hessian_kernel(const HessArgs a) {
         double* const basis = a.basis + r * a.basis_stride;
         const double* const v0 = a.v0 + r * a.v0_stride;
         // ---- v_1 = v0 / |v0|; v0 = 0 (or not a number): k = 0 -------------------------------------------------------------------------------
-        part = 0.0;
-        for (int e = t; e < P; e += 256) part = fma(v0[e], v0[e], part);
-        const double n0 = sqrt(block_sum256(part, red, t));
-        const int kmax = n0 > 0.0 && n0 < INFINITY ? (a.steps < P ? a.steps : P) : 0;
-        if (kmax > 0)
-            for (int e = t; e < P; e += 256) basis[e] = v0[e] / n0;
+        const int kmax = lanczos_start(v0, basis, P, a.steps, red, t);
         // The basis is stored to global memory and read back by other lanes of THIS workgroup (the products, the Gram-Schmidt passes,
         // omega) behind __syncthreads() alone: that relies on workgroup-scope visibility of global stores, which holds where a workgroup
         // shares one CU's vector L1 (the default mode) and would not under threadgroup-split (tgsplit) mode.
         __syncthreads();
+        // T goes into the Jacobi buffers over the direction images, dead once the last product is done
+        LanczosLds s;
+        s.mat = pool + oDU; s.vec = s.mat + 2 * kMatDoubles; s.red = red; s.alpha = alpha; s.beta = beta;
+        s.rot_c = rot_c; s.rot_s = rot_s; s.eig = eig; s.rot_mate = rot_mate;
         int k = 0;
         double scale = 0.0;
         for (int j = 0; j < kmax; ++j) {
-            const double* const vj = basis + (long long)j * P;
-            hess_hvp(m, vj, wv, t);
-            // classical Gram-Schmidt, twice, against v_1 .. v_j: alpha_j is what the two passes take out along v_j
-            double al = 0.0;
-            for (int pass = 0; pass < 2; ++pass) {
-                for (int i = 0; i <= j; ++i) {
-                    const double* const vi = basis + (long long)i * P;
-                    double d = 0.0;
-                    for (int e = t; e < P; e += 256) d = fma(vi[e], wv[e], d);
-                    d = block_sum256(d, red, t);
-                    if (t == 0) coef[i] = d;
-                    if (i == j) al += d;
-                }
-                __syncthreads();
-                for (int e = t; e < P; e += 256) {
-                    double s = wv[e];
-                    for (int i = 0; i <= j; ++i) s = fma(-coef[i], basis[(long long)i * P + e], s);
-                    wv[e] = s;
-                }
-                __syncthreads();
-            }
-            part = 0.0;
-            for (int e = t; e < P; e += 256) part = fma(wv[e], wv[e], part);
-            const double be = sqrt(block_sum256(part, red, t));
+            hess_hvp(m, basis + (long long)j * P, wv, t);
+            double al, be;
+            lanczos_orthogonalise(wv, basis, P, j, coef, red, t, al, be);
             if (t == 0) { alpha[j] = al; beta[j] = be; }
             k = j + 1;
-            scale = fmax(scale, fabs(al));
-            if (be <= kHessBreakdown * scale || k == kmax) break;       // the same values in every thread: the decision is uniform
-            scale = fmax(scale, be);
-            double* const vn = basis + (long long)k * P;
-            for (int e = t; e < P; e += 256) vn[e] = wv[e] / be;
+            if (lanczos_next(wv, basis, P, k, kmax, al, be, scale, t)) break;
             __syncthreads();
         }
         __syncthreads();
-
-        // ---- T (k x k, tridiagonal, zero outside) into Jacobi buffer 0 over the dead direction images, V = I, the solve ------------------
-        double* const mat = pool + oDU;
-        double* const vec = mat + 2 * kMatDoubles;
-        double sq = 0.0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int idx = t + 256 * q, i = idx >> 5, j = idx & 31;
-            double v = 0.0;
-            if (i < k && j < k) {                                       // the pad row and column of an odd k are zero
-                if (i == j) v = alpha[i];
-                else if (i + 1 == j) v = beta[i];
-                else if (j + 1 == i) v = beta[j];
-            }
-            mat[i * kMatStride + j] = v;
-            if (i <= j) sq += i == j ? v * v : 2.0 * v * v;
-            const double id = i == j ? 1.0 : 0.0;
-            vec[i * kMatStride + j] = id;                               // the solve may end in either buffer
-            vec[kMatDoubles + i * kMatStride + j] = id;
-        }
-        const double norm_t = sqrt(block_sum256(sq, red, t));           // its barriers also publish T and V
-        int cur = 0, sweeps = 0;
-        double off_f = 0.0;
-        if (k > 0) jacobi_solve<true>(mat, vec, k + (k & 1), norm_t, red, rot_c, rot_s, rot_mate, t, cur, sweeps, off_f);
-        const double* const A = mat + cur * kMatDoubles;
-        const double* const V = vec + cur * kMatDoubles;
-        if (t < kHessMaxSteps) eig[t] = t < k ? A[t * kMatStride + t] : 0.0;
-        __syncthreads();
-        const double beta_k = k > 0 ? beta[k - 1] : 0.0;
-        // ---- Ritz values ascending by counting ranks (the pad of an odd k is index k: not counted), residual bounds in the same order ------
-        if (t < kHessMaxSteps) {
-            if (t < k) {
-                const double e = eig[t];
-                int rank = 0;
-                for (int j = 0; j < k; ++j) {
-                    const double o = eig[j];
-                    rank += (o < e || (o == e && j < t)) ? 1 : 0;
-                }
-                out[kHessHead + rank] = e;
-                out[kHessHead + kHessMaxSteps + rank] = fabs(beta_k * V[(k - 1) * kMatStride + t]);
-                if (rank == k - 1) out[9] = e;
-                if (rank == 0) out[10] = e;
-            } else {
-                out[kHessHead + t] = 0.0;
-                out[kHessHead + kHessMaxSteps + t] = 0.0;
-            }
-            out[kHessHead + 2 * kHessMaxSteps + t] = t < k ? alpha[t] : 0.0;
-            out[kHessHead + 3 * kHessMaxSteps + t] = t < k ? beta[t] : 0.0;
-        }
-        // ---- omega = max_{i < j < k} |v_i . v_j|: a wave per pair, lanes over the elements, one fixed butterfly ---------------------------
-        double wmax = 0.0;
-        {
-            const int wave = t >> 6, lane = t & 63, npairs = k * (k - 1) / 2;
-            for (int q = wave; q < npairs; q += 4) {
-                int j = 1, first = 0;
-                while (first + j <= q) { first += j; ++j; }
-                const double* const vi = basis + (long long)(q - first) * P;
-                const double* const vj = basis + (long long)j * P;
-                double s = 0.0;
-                for (int e = lane; e < P; e += 64) s = fma(vi[e], vj[e], s);
-                for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-                wmax = fmax(wmax, fabs(s));
-            }
-        }
-        const double omega = block_max256(wmax, red, t);
-        if (t < kHessHead) {
-            double v;
-            switch (t) {
-                case 0: v = f; break;
-                case 1: v = gnorm; break;
-                case 2: v = (double)k; break;
-                case 3: v = beta_k; break;
-                case 4: v = (double)sweeps; break;
-                case 5: v = off_f; break;
-                case 6: v = norm_t; break;
-                case 7: v = (double)rows; break;
-                case 8: v = eps; break;
-                case 11: v = omega; break;
-                default: v = 0.0; break;                                // theta_max, theta_min where k = 0
-            }
-            if (t < 9 || t == 11 || k == 0) out[t] = v;
-        }
+        const RitzResult rz = lanczos_ritz(s, k, out, t);
+        const double omega = lanczos_omega(basis, P, k, red, t);
+        lanczos_head_store(out, t, k, f, gnorm, eps, rows, omega, rz);
     }
 }
 
@@ -523,18 +410,6 @@ static int hessian_common(const char* who, const EvalDesc& d, int record, const 
     return VAEK_OK;
 }
 
-// a double buffer of `len` doubles per replica at stride `stride`; shared_ok: stride 0 means one buffer for all replicas
-static int check_doubles(const char* who, const char* what, const void* ptr, int64_t stride, int64_t len, bool shared_ok) {
-    if (!ptr) { set_error("%s: %s is NULL", who, what); return VAEK_ERR_INVALID; }
-    if (int rc = check_aligned8(who, what, (uintptr_t)ptr)) return rc;
-    const bool shared = stride == 0 && shared_ok;
-    if (stride < 0 || (!shared && stride < len)) {
-        set_error("%s: %s stride %lld < its length %lld%s", who, what, (long long)stride, (long long)len, shared_ok ? " (0: shared)" : "");
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
-}
-
 template <bool LANCZOS>
 static int hessian_launch(const char* label, const HessArgs& a, int n, hipStream_t st) {
     static thread_local PerDeviceOnce attr_set;
@@ -561,14 +436,14 @@ int vaek_supports_elbo_hessian(const vaek_ctx* ctx, int32_t kind, int32_t* yes) 
 
 int vaek_elbo_hvp_max_vectors(void) { return kHvpMaxVectors; }
 int vaek_elbo_hvp_record_len(void) { return kHvpRecord; }
-int vaek_elbo_hessian_max_steps(void) { return kHessMaxSteps; }
-int vaek_elbo_hessian_record_len(void) { return kHessRecord; }
+int vaek_elbo_hessian_max_steps(void) { return kLanczosMaxSteps; }
+int vaek_elbo_hessian_record_len(void) { return kLanczosRecord; }
 
 int vaek_elbo_hessian_basis_doubles(const vaek_ctx* ctx, int32_t steps, int64_t* doubles) {
     if (!ctx || !doubles) { set_error("vaek_elbo_hessian_basis_doubles: null argument"); return VAEK_ERR_INVALID; }
-    if (!elbo_hessian_covered(ctx) || steps < 1 || steps > kHessMaxSteps) {
+    if (!elbo_hessian_covered(ctx) || steps < 1 || steps > kLanczosMaxSteps) {
         set_error("vaek_elbo_hessian_basis_doubles: an unsupported context (see vaek_supports_elbo_hessian) or %d steps outside 1 .. %d", steps,
-                  kHessMaxSteps);
+                  kLanczosMaxSteps);
         return VAEK_ERR_INVALID;
     }
     *doubles = (int64_t)steps * ctx->P;
@@ -582,17 +457,7 @@ int vaek_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vaek_elbo_h
     HessArgs a{};
     if (int rc = hessian_common(who, describe(hp), kHvpRecord, "vaek_elbo_hvp_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag, &a))
         return rc;
-    if (hp->nvec < 0 || hp->nvec > kHvpMaxVectors) {
-        set_error("%s: %d vectors, need 0 .. %d (vaek_elbo_hvp_max_vectors)", who, hp->nvec, kHvpMaxVectors);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t P = ctx->P;
-    if (hp->nvec > 0) {
-        if (int rc = check_doubles(who, "v", hp->v, hp->v_stride, hp->nvec * P, true)) return rc;
-        if (int rc = check_doubles(who, "hv", hp->hv, hp->hv_stride, hp->nvec * P, false)) return rc;
-    }
-    if (hp->grad)
-        if (int rc = check_doubles(who, "grad", hp->grad, hp->grad_stride, P, false)) return rc;
+    if (int rc = check_hvp_buffers(who, hp, ctx->P, false)) return rc;      // one launch: v and hv may overlap, as they always could
     a.out = hp->out; a.out_stride = hp->out_stride;
     a.v = hp->v; a.v_stride = hp->v_stride; a.hv = hp->hv; a.hv_stride = hp->hv_stride;
     a.grad = hp->grad; a.grad_stride = hp->grad_stride; a.nvec = hp->nvec;
@@ -604,15 +469,9 @@ int vaek_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* params, const
     const char* who = "vaek_elbo_hessian_lanczos_replicas";
     ProfBind pb(ctx);
     HessArgs a{};
-    if (int rc = hessian_common(who, describe(hs), kHessRecord, "vaek_elbo_hessian_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag, &a))
+    if (int rc = hessian_common(who, describe(hs), kLanczosRecord, "vaek_elbo_hessian_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag, &a))
         return rc;
-    if (hs->steps < 1 || hs->steps > kHessMaxSteps) {
-        set_error("%s: %d steps, need 1 .. %d (vaek_elbo_hessian_max_steps)", who, hs->steps, kHessMaxSteps);
-        return VAEK_ERR_INVALID;
-    }
-    const int64_t P = ctx->P;
-    if (int rc = check_doubles(who, "v0", hs->v0, hs->v0_stride, P, true)) return rc;
-    if (int rc = check_doubles(who, "basis", hs->basis, hs->basis_stride, hs->steps * P, false)) return rc;
+    if (int rc = check_lanczos_buffers(who, hs, ctx->P)) return rc;
     a.out = hs->out; a.out_stride = hs->out_stride;
     a.v0 = hs->v0; a.v0_stride = hs->v0_stride; a.basis = hs->basis; a.basis_stride = hs->basis_stride; a.steps = hs->steps;
     return hessian_launch<true>("elbo_hessian_replicas", a, hs->n, (hipStream_t)stream);

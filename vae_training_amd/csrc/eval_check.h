@@ -1,6 +1,8 @@
 // The host-side checks of the thirteen vaek_*_replicas evaluation entry points, once (eval_check.hip; no kernels).  An entry point copies
 // its description into an EvalDesc (describe), states what it adds in an EvalRules and calls check_eval; its own refusals (samples,
-// columns, nvec, steps, further buffers, rank_tol) follow in its unit.  check_eval refuses, in this order and with the first that fails:
+// columns, rank_tol) follow in its unit, those of the six Hessian entry points through the helpers below: 13. samples and columns (the
+// four sampled calls), 14. the samples' source: xi_stride, else z_seeds / z_steps (the same four), 15. nvec, v, hv, their overlap (the
+// sampled calls only), grad -- or steps, v0, basis.  check_eval refuses, in this order and with the first that fails:
 //    1. a NULL description                          7. a NULL seeds / steps / sample_eps array the mode needs, a NULL out
 //    2. a struct_size of another header             8. state_stride < P, out_stride below the record(s)
 //    3. a NULL context or params                    9. an out that is not 8-byte aligned, where the records are doubles
@@ -81,6 +83,37 @@ int check_struct_size(const char* who, const char* name, int32_t got, size_t wan
 int check_x_stride(const char* who, const vaek_ctx* ctx, int64_t x_stride, int32_t rows); // explicit rows: 0 (shared) or >= rows * D
 int check_tag(const char* who, uint32_t tag);                                             // >= 2^30
 int check_aligned8(const char* who, const char* what, uintptr_t addrs);                   // `addrs`: the outputs `what` names, ORed
+
+// ---- 13 .. 15: what the six Hessian entry points check behind check_eval ---------------------------------------------------------------
+// a buffer `what` of `len` doubles per replica at `stride`: NULL, alignment, stride (shared_ok: 0 means one buffer for all replicas)
+int check_doubles(const char* who, const char* what, const void* ptr, int64_t stride, int64_t len, bool shared_ok);
+// the samples of a sampled call and where they come from: explicit xi, or (xi == NULL) drawn from z_seeds / z_steps
+struct SampleSource { int32_t samples; const uint64_t* z_seeds; const uint32_t* z_steps; const float* xi; int64_t xi_stride; };
+// read from a vaek_sampled_elbo_hvp / vaek_sampled_elbo_hessian, or all zero where check_eval is going to refuse the description unread
+template <class T>
+SampleSource sample_source(const EvalDesc& d, const T* s) {
+    const bool read = d.given && d.struct_size == (int32_t)d.want;
+    return read ? SampleSource{s->samples, s->z_seeds, s->z_steps, s->xi, s->xi_stride} : SampleSource{};
+}
+// 13: samples, rows * samples against the unit's per-replica cap 2^cap_log2, n * rows * samples against its per-call cap; for a call
+// and for its workspace query alike
+int check_sampled_columns(const char* who, int32_t n, int32_t rows, int32_t samples, int cap_log2, int call_cap, const char* call_cap_query);
+// 14: xi_stride where xi is given, else z_seeds / z_steps
+int check_sample_source(const char* who, const SampleSource& x, int32_t rows, int L);
+// 15, an HVP call (hp: vaek_elbo_hvp or vaek_sampled_elbo_hvp): nvec, then v, hv and, where refuse_overlap, their overlap (nvec > 0),
+// then grad where given
+int check_hvp_buffers(const char* who, int32_t n, int64_t P, int32_t nvec, const double* v, int64_t v_stride, const double* hv, int64_t hv_stride,
+                      const double* grad, int64_t grad_stride, bool refuse_overlap);
+template <class T>
+int check_hvp_buffers(const char* who, const T* hp, int64_t P, bool refuse_overlap) {
+    return check_hvp_buffers(who, hp->n, P, hp->nvec, hp->v, hp->v_stride, hp->hv, hp->hv_stride, hp->grad, hp->grad_stride, refuse_overlap);
+}
+// 15, a Lanczos call (hs: vaek_elbo_hessian or vaek_sampled_elbo_hessian): steps, then v0, then basis
+int check_lanczos_buffers(const char* who, int64_t P, int32_t steps, const double* v0, int64_t v0_stride, const double* basis, int64_t basis_stride);
+template <class T>
+int check_lanczos_buffers(const char* who, const T* hs, int64_t P) {
+    return check_lanczos_buffers(who, P, hs->steps, hs->v0, hs->v0_stride, hs->basis, hs->basis_stride);
+}
 
 // ---- the training entry points of api.hip ----------------------------------------------------------------------------------------------
 // The seven whose batches a generator feeds (vaek_train_step_gen, vaek_train_steps_gen, vaek_train_loop_gen[_traj],

@@ -1,6 +1,8 @@
 // Host only: the one refusal list of the evaluation entry points (eval_check.h), the adapters of the nine description structs and
-// the small checks they and the training entry points of api.hip share, and those entry points' own list.  No kernels.
+// the small checks they and the training entry points of api.hip share, the Hessian entry points' further buffer checks, and the
+// training entry points' own list.  No kernels (lanczos_dev.h for the two caps the Hessian checks print).
 #include "eval_check.h"
+#include "lanczos_dev.h"
 
 namespace vaek {
 
@@ -211,6 +213,77 @@ int check_tag(const char* who, uint32_t tag) {
 int check_aligned8(const char* who, const char* what, uintptr_t addrs) {
     if ((addrs & 7u) != 0) { set_error("%s: %s is not 8-byte aligned", who, what); return VAEK_ERR_INVALID; }
     return VAEK_OK;
+}
+
+// ---- the Hessian entry points' further arguments (13 .. 15 of eval_check.h) -----------------------------------------------------------
+int check_doubles(const char* who, const char* what, const void* ptr, int64_t stride, int64_t len, bool shared_ok) {
+    if (!ptr) { set_error("%s: %s is NULL", who, what); return VAEK_ERR_INVALID; }
+    if (int rc = check_aligned8(who, what, (uintptr_t)ptr)) return rc;
+    const bool shared = stride == 0 && shared_ok;
+    if (stride < 0 || (!shared && stride < len)) {
+        set_error("%s: %s stride %lld < its length %lld%s", who, what, (long long)stride, (long long)len, shared_ok ? " (0: shared)" : "");
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+// do the n replicas' spans of two buffers of doubles, each `len` at `stride`, share a byte?
+static bool doubles_overlap(const double* p, int64_t stride, int64_t len, const double* q, int64_t qstride, int64_t qlen, int n) {
+    const uintptr_t a0 = (uintptr_t)p, a1 = a0 + sizeof(double) * (size_t)((n - 1) * stride + len);
+    const uintptr_t b0 = (uintptr_t)q, b1 = b0 + sizeof(double) * (size_t)((n - 1) * qstride + qlen);
+    return a0 < b1 && b0 < a1;
+}
+
+int check_sampled_columns(const char* who, int32_t n, int32_t rows, int32_t samples, int cap_log2, int call_cap, const char* call_cap_query) {
+    if (int rc = check_sample_count(who, samples)) return rc;
+    if ((long long)rows * samples > 1 << cap_log2) {
+        set_error("%s: %d rows x %d samples = %lld columns per replica, at most %d (rows * samples <= 2^%d; %s bounds n * rows * samples)", who,
+                  rows, samples, (long long)rows * samples, 1 << cap_log2, cap_log2, call_cap_query);
+        return VAEK_ERR_INVALID;
+    }
+    return check_column_count(who, n, rows, samples, "samples", call_cap, call_cap_query);
+}
+
+int check_sample_source(const char* who, const SampleSource& x, int32_t rows, int L) {
+    if (x.xi) {
+        const int64_t len = (int64_t)rows * x.samples * L;
+        if (x.xi_stride < 0 || (x.xi_stride > 0 && x.xi_stride < len)) {
+            set_error("%s: xi_stride %lld: need 0 (shared samples) or >= rows * samples * L = %lld", who, (long long)x.xi_stride, (long long)len);
+            return VAEK_ERR_INVALID;
+        }
+    } else if (!x.z_seeds || !x.z_steps) {
+        set_error("%s: %s is NULL (xi == NULL draws the samples and reads it)", who, x.z_seeds ? "z_steps" : "z_seeds");
+        return VAEK_ERR_INVALID;
+    }
+    return VAEK_OK;
+}
+
+int check_hvp_buffers(const char* who, int32_t n, int64_t P, int32_t nvec, const double* v, int64_t v_stride, const double* hv, int64_t hv_stride,
+                      const double* grad, int64_t grad_stride, bool refuse_overlap) {
+    if (nvec < 0 || nvec > kHvpMaxVectors) {
+        set_error("%s: %d vectors, need 0 .. %d (vaek_elbo_hvp_max_vectors)", who, nvec, kHvpMaxVectors);
+        return VAEK_ERR_INVALID;
+    }
+    if (nvec > 0) {                                                     // nvec = 0: v and hv may be NULL and are not touched
+        if (int rc = check_doubles(who, "v", v, v_stride, nvec * P, true)) return rc;
+        if (int rc = check_doubles(who, "hv", hv, hv_stride, nvec * P, false)) return rc;
+        if (refuse_overlap && doubles_overlap(v, v_stride, nvec * P, hv, hv_stride, nvec * P, n)) {
+            set_error("%s: v and hv overlap: a direction is read by launches that follow the store of an earlier product", who);
+            return VAEK_ERR_INVALID;
+        }
+    }
+    if (grad)
+        if (int rc = check_doubles(who, "grad", grad, grad_stride, P, false)) return rc;
+    return VAEK_OK;
+}
+
+int check_lanczos_buffers(const char* who, int64_t P, int32_t steps, const double* v0, int64_t v0_stride, const double* basis, int64_t basis_stride) {
+    if (steps < 1 || steps > kLanczosMaxSteps) {
+        set_error("%s: %d steps, need 1 .. %d (vaek_elbo_hessian_max_steps)", who, steps, kLanczosMaxSteps);
+        return VAEK_ERR_INVALID;
+    }
+    if (int rc = check_doubles(who, "v0", v0, v0_stride, P, true)) return rc;
+    return check_doubles(who, "basis", basis, basis_stride, steps * P, false);
 }
 
 // ---- the training entry points (the order is in eval_check.h) -------------------------------------------------------------------------

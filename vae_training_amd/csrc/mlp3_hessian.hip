@@ -27,23 +27,20 @@
 //     step's Gram-Schmidt would read ~170 MB through a single CU, so every launch that touches such a vector has grid (chunks of 2048
 //     elements, n); dots are per-chunk partials that cross a launch boundary and are added in chunk order by whoever needs them.  Per
 //     step: chain, contraction (w = H v_j into the workspace), then four vector launches (dots; Gram-Schmidt pass 1 + the dots of pass 2;
-//     pass 2 + |w|^2; alpha, beta, elbo_hessian.hip's breakdown test, v_{j+1} into the caller's basis).  A replica that is done has a flag
-//     per later step in its state block and those launches return at once.  Then the chunks' partial Gram matrices of the basis, and n
-//     workgroups that build T, call jacobi_solve<true> (eigen_dev.h, included and not edited), take omega from the Gram partials and
-//     store the record.
+//     pass 2 + |w|^2; alpha, beta, lanczos_dev.h's breakdown rule, v_{j+1} into the caller's basis).  A replica that is done has a flag
+//     per later step in its state block and those launches return at once.  Then the chunks' partial Gram matrices of the basis (the
+//     header's pair order), and n workgroups that run the header's Ritz tail and record store with omega from the Gram partials.  The
+//     start rule, the record layout and the constants are the header's too; the chunked arithmetic is this unit's own.
 //
 // Nothing stored in a launch is read back in it; there is no atomic, counter, wait or spin.  Launches: 3 + 2 nvec (hvp call), 6 + 6 steps
 // (Lanczos call).
-#include "eigen_dev.h"
+#include "lanczos_dev.h"
 #include "eval_check.h"
 
 namespace vaek {
 
-constexpr int kHsMaxVectors = 64;                     // bounds one call -- a cap, not a tuned value
 constexpr int kHsMaxColumns = 1 << 14;                // n * rows * samples of one call ...
-constexpr int kHsMaxReplicaColumns = 1 << 13;         // ... and rows * samples of one replica: caps on the launch length and the workspace
-constexpr int kHsHvpRecord = 4;
-constexpr double kHsLog2Pi = 1.8378770664093454835606594728112;
+constexpr int kHsReplicaColumnsLog2 = 13;             // ... and rows * samples of one replica, 2^13: caps on the launch length and the workspace
 constexpr int kHsCols = 8;                            // columns of a chain tile
 constexpr int kHsPitch = 16;                          // doubles between two units of the image: primal | tangent
 constexpr int kHsW = 256;                             // widest layer
@@ -53,12 +50,9 @@ constexpr int kHsHead = 8;                            // doubles at the head of 
 constexpr size_t kHsLds = sizeof(double) * 2 * kHsW * kHsPitch;
 constexpr int kHsDepth = 8;                            // k-steps of a product whose operands are fetched together (weights come from L2)
 constexpr int kHsTileK = 16, kHsTileM = 64;           // a contraction workgroup's tile of [kernel | bias]
-constexpr int kHsMaxSteps = 32;                       // the Jacobi routine's size
-constexpr int kHsRecHead = 12;
-constexpr int kHsRecord = kHsRecHead + 4 * kHsMaxSteps + 2;
-constexpr double kHsBreakdown = 0x1p-40;
+constexpr int kHsRecord = kLanczosRecord + 2;         // the Lanczos record, then samples and the two-decoder flag (0 here)
 constexpr int kHsChunk = 2048;                        // elements of a length-P vector one workgroup of a vector launch owns: 8 a thread
-constexpr int kHsPairs = kHsMaxSteps * (kHsMaxSteps - 1) / 2;      // 496 pairs of basis rows
+constexpr int kHsPairs = kLanczosMaxSteps * (kLanczosMaxSteps - 1) / 2;      // 496 pairs of basis rows
 constexpr int kHsPairPitch = 512;
 constexpr int kHsGramSub = 64;                        // elements of a chunk staged at a time by the Gram launch
 // a replica's Lanczos state, in doubles: [1] k  [3] f_K  [4] |grad f_K|  [5] eps, then alpha, beta, and per step j the scale and the done
@@ -423,7 +417,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_contract_kernel(const HsArgs
             const double eps = a.off_c >= 0 ? (double)p[a.off_c] * eps_cli : eps_cli;
             double klc = 0.0;
             for (int l = 0; l < a.L; ++l) { const double pl = (double)p[a.off_p + l]; klc += exp(pl) - 1.0 - pl; }
-            blk[0] = hs_tail(a, blk, 33) + 0.5 * hs_tail(a, blk, 32) + 0.5 * klc + 0.5 * (double)a.D * (eps + kHsLog2Pi);
+            blk[0] = hs_tail(a, blk, 33) + 0.5 * hs_tail(a, blk, 32) + 0.5 * klc + 0.5 * (double)a.D * (eps + kLog2PiF64);
         }
         return;
     }
@@ -488,7 +482,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_record_kernel(const HsArgs a
     if (grad)
         for (int e = t; e < a.P; e += 256) grad[e] = g[e];
     const double gnorm = hs_grad_norm(g, a.P, red, t);
-    if (t < kHsHvpRecord) {
+    if (t < kHvpRecord) {
         const float* const p = a.params + r * a.state_stride;
         const double eps_cli = (double)a.eps_cli;
         const double eps = a.off_c >= 0 ? (double)p[a.off_c] * eps_cli : eps_cli;
@@ -519,7 +513,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_init_dots_kernel(const HsArg
         if (e < a.P) pv = fma(v0[e], v0[e], pv);
     }
     pv = block_sum256(pv, red, t);
-    if (t == 0) blk[a.dotA_off + chunk * kHsMaxSteps] = pv;
+    if (t == 0) blk[a.dotA_off + chunk * kLanczosMaxSteps] = pv;
 }
 
 // second launch: v_1 = v0 / |v0| into the basis; chunk 0 writes the state block
@@ -529,8 +523,8 @@ __global__ __launch_bounds__(256) void mlp3_hessian_init_kernel(const HsArgs a) 
     const long long r = blockIdx.y;
     double* const blk = a.ws + r * a.block;
     double* const state = blk + a.state_off;
-    const double n0 = sqrt(hs_chunk_sum(blk + a.dotA_off, a.chunks, kHsMaxSteps));
-    const int kmax = n0 > 0.0 && n0 < INFINITY ? (a.steps < a.P ? a.steps : a.P) : 0;
+    const double n0 = sqrt(hs_chunk_sum(blk + a.dotA_off, a.chunks, kLanczosMaxSteps));
+    const int kmax = lanczos_kmax(n0, a.steps, a.P);
     if (kmax > 0) {
         double* const basis = a.basis + r * a.basis_stride;
         const double* const v0 = a.v0 + r * a.v0_stride;
@@ -549,7 +543,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_init_kernel(const HsArgs a) 
         else if (t == 5) {
             const double eps_cli = (double)a.eps_cli;
             v = a.off_c >= 0 ? (double)a.params[r * a.state_stride + a.off_c] * eps_cli : eps_cli;
-        } else if (t >= hsDone && t <= hsDone + kHsMaxSteps) v = kmax > 0 ? 0.0 : 1.0;
+        } else if (t >= hsDone && t <= hsDone + kLanczosMaxSteps) v = kmax > 0 ? 0.0 : 1.0;
         state[t] = v;
     }
 }
@@ -561,7 +555,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_init_kernel(const HsArgs a) 
 //   MODE 3  alpha = coef_j of both passes, beta = |w|, the breakdown test, v_{j+2} = w / beta; chunk 0 writes the state
 template <int MODE>
 __global__ __launch_bounds__(256) void mlp3_hessian_lanczos_kernel(const HsArgs a) {
-    __shared__ double red[256], coef[kHsMaxSteps];
+    __shared__ double red[256], coef[kLanczosMaxSteps];
     const int t = threadIdx.x, chunk = blockIdx.x, j = a.j;
     const long long r = blockIdx.y;
     double* const blk = a.ws + r * a.block;
@@ -581,7 +575,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_lanczos_kernel(const HsArgs 
         we[i] = e < P ? w[e] : 0.0;
     }
     if (MODE == 1 || MODE == 2) {
-        if (t <= j) coef[t] = hs_chunk_sum((MODE == 1 ? dotA : dotB) + t, a.chunks, kHsMaxSteps);
+        if (t <= j) coef[t] = hs_chunk_sum((MODE == 1 ? dotA : dotB) + t, a.chunks, kLanczosMaxSteps);
         __syncthreads();
         for (int i = 0; i <= j; ++i) {
             const double* const vi = basis + (long long)i * P;
@@ -595,7 +589,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_lanczos_kernel(const HsArgs 
             if (ei[q] >= 0) w[ei[q]] = we[q];
     }
     if (MODE == 0 || MODE == 1) {
-        double* const out = (MODE == 0 ? dotA : dotB) + chunk * kHsMaxSteps;
+        double* const out = (MODE == 0 ? dotA : dotB) + chunk * kLanczosMaxSteps;
         for (int i = 0; i <= j; ++i) {
             const double* const vi = basis + (long long)i * P;
             double d = 0.0;
@@ -614,12 +608,11 @@ __global__ __launch_bounds__(256) void mlp3_hessian_lanczos_kernel(const HsArgs 
         if (t == 0) blk[a.nrm_off + chunk] = d;
     }
     if (MODE == 3) {
-        const double al = hs_chunk_sum(dotA + j, a.chunks, kHsMaxSteps) + hs_chunk_sum(dotB + j, a.chunks, kHsMaxSteps);
+        const double al = hs_chunk_sum(dotA + j, a.chunks, kLanczosMaxSteps) + hs_chunk_sum(dotB + j, a.chunks, kLanczosMaxSteps);
         const double be = sqrt(hs_chunk_sum(blk + a.nrm_off, a.chunks, 1));
         const int k = j + 1, kmax = a.steps < P ? a.steps : P;
-        double scale = fmax(state[hsScale + j], fabs(al));
-        const bool stop = be <= kHsBreakdown * scale || k == kmax;     // the same values in every thread of every chunk
-        scale = fmax(scale, be);
+        double scale = state[hsScale + j];
+        const bool stop = lanczos_stop(al, be, k, kmax, scale);        // the same values in every thread of every chunk
         if (!stop) {
             double* const vn = basis + (long long)k * P;
 #pragma unroll
@@ -628,14 +621,14 @@ __global__ __launch_bounds__(256) void mlp3_hessian_lanczos_kernel(const HsArgs 
         }
         if (chunk == 0) {
             if (t == 0) { state[hsAlpha + j] = al; state[hsBeta + j] = be; state[1] = (double)k; state[hsScale + k] = scale; }
-            if (stop && t > j && t <= kHsMaxSteps) state[hsDone + t] = 1.0;
+            if (stop && t > j && t <= kLanczosMaxSteps) state[hsDone + t] = 1.0;
         }
     }
 }
 
 // after the last step: the chunk's partial of v_i . v_j for every pair i < j < k, kHsGramSub elements staged at a time
 __global__ __launch_bounds__(256) void mlp3_hessian_gram_kernel(const HsArgs a) {
-    __shared__ double tile[kHsMaxSteps][kHsGramSub + 1];
+    __shared__ double tile[kLanczosMaxSteps][kHsGramSub + 1];
     const int t = threadIdx.x, chunk = blockIdx.x;
     const long long r = blockIdx.y;
     double* const blk = a.ws + r * a.block;
@@ -644,14 +637,11 @@ __global__ __launch_bounds__(256) void mlp3_hessian_gram_kernel(const HsArgs a) 
     int pi[2], pj[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const int q = t + 256 * h;
-        int j = 1, first = 0;
-        while (first + j <= q) { first += j; ++j; }
-        pi[h] = q - first; pj[h] = j;                                  // pair q = (i, j), i < j
+        lanczos_pair(t + 256 * h, pi[h], pj[h]);
     }
     double acc[2] = {0.0, 0.0};
     for (int s0 = 0; s0 < kHsChunk; s0 += kHsGramSub) {
-        for (int idx = t; idx < kHsMaxSteps * kHsGramSub; idx += 256) {
+        for (int idx = t; idx < kLanczosMaxSteps * kHsGramSub; idx += 256) {
             const int row = idx / kHsGramSub, c = idx % kHsGramSub;
             const int e = chunk * kHsChunk + s0 + c;
             tile[row][c] = row < k && e < a.P ? basis[(long long)row * a.P + e] : 0.0;
@@ -672,8 +662,7 @@ __global__ __launch_bounds__(256) void mlp3_hessian_gram_kernel(const HsArgs a) 
         if (t + 256 * h < kHsPairs) blk[a.gram_off + (long long)chunk * kHsPairPitch + t + 256 * h] = acc[h];
 }
 
-// the last launch, n workgroups: T from the state block, the solve, the Ritz values and their bounds, omega, the record
-// (sampled_hessian.hip's text, omega from the Gram partials in chunk order)
+// the last launch, n workgroups: T from the state block, then lanczos_dev.h's tail with omega from the Gram partials in chunk order
 __global__ __launch_bounds__(256) void mlp3_hessian_final_kernel(const HsArgs a) {
     __shared__ double mat[2 * kMatDoubles], vecs[2 * kMatDoubles];
     __shared__ double red[256], alpha[kSpectrumMaxDim], beta[kSpectrumMaxDim], rot_c[kSpectrumMaxDim], rot_s[kSpectrumMaxDim], eig[kSpectrumMaxDim];
@@ -684,76 +673,17 @@ __global__ __launch_bounds__(256) void mlp3_hessian_final_kernel(const HsArgs a)
     const double* const state = blk + a.state_off;
     double* const out = a.out + r * a.out_stride;
     const int k = (int)state[1];
-    if (t < kHsMaxSteps) { alpha[t] = t < k ? state[hsAlpha + t] : 0.0; beta[t] = t < k ? state[hsBeta + t] : 0.0; }
+    if (t < k) { alpha[t] = state[hsAlpha + t]; beta[t] = state[hsBeta + t]; }
     __syncthreads();
-    double sq = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int idx = t + 256 * q, i = idx >> 5, j = idx & 31;
-        double v = 0.0;
-        if (i < k && j < k) {                                           // the pad row and column of an odd k are zero
-            if (i == j) v = alpha[i];
-            else if (i + 1 == j) v = beta[i];
-            else if (j + 1 == i) v = beta[j];
-        }
-        mat[i * kMatStride + j] = v;
-        if (i <= j) sq += i == j ? v * v : 2.0 * v * v;
-        const double id = i == j ? 1.0 : 0.0;
-        vecs[i * kMatStride + j] = id;                                  // the solve may end in either buffer
-        vecs[kMatDoubles + i * kMatStride + j] = id;
-    }
-    const double norm_t = sqrt(block_sum256(sq, red, t));               // its barriers also publish T and V
-    int cur = 0, sweeps = 0;
-    double off_f = 0.0;
-    if (k > 0) jacobi_solve<true>(mat, vecs, k + (k & 1), norm_t, red, rot_c, rot_s, rot_mate, t, cur, sweeps, off_f);
-    const double* const A = mat + cur * kMatDoubles;
-    const double* const V = vecs + cur * kMatDoubles;
-    if (t < kHsMaxSteps) eig[t] = t < k ? A[t * kMatStride + t] : 0.0;
-    __syncthreads();
-    const double beta_k = k > 0 ? beta[k - 1] : 0.0;
-    if (t < kHsMaxSteps) {
-        if (t < k) {
-            const double e = eig[t];
-            int rank = 0;
-            for (int j = 0; j < k; ++j) {
-                const double o = eig[j];
-                rank += (o < e || (o == e && j < t)) ? 1 : 0;
-            }
-            out[kHsRecHead + rank] = e;
-            out[kHsRecHead + kHsMaxSteps + rank] = fabs(beta_k * V[(k - 1) * kMatStride + t]);
-            if (rank == k - 1) out[9] = e;
-            if (rank == 0) out[10] = e;
-        } else {
-            out[kHsRecHead + t] = 0.0;
-            out[kHsRecHead + kHsMaxSteps + t] = 0.0;
-        }
-        out[kHsRecHead + 2 * kHsMaxSteps + t] = alpha[t];
-        out[kHsRecHead + 3 * kHsMaxSteps + t] = beta[t];
-    }
-    // omega = max_{i < j < k} |v_i . v_j|: thread t the pairs t and t + 256, the chunks' partials in chunk order
+    LanczosLds s;
+    s.mat = mat; s.vec = vecs; s.red = red; s.alpha = alpha; s.beta = beta;
+    s.rot_c = rot_c; s.rot_s = rot_s; s.eig = eig; s.rot_mate = rot_mate;
+    const RitzResult rz = lanczos_ritz(s, k, out, t);
+    // omega = max_{i < j < k} |v_i . v_j|: thread t the pairs t and t + 256 of lanczos_pair's order, the chunks' partials in chunk order
     double wmax = 0.0;
-    {
-        const int npairs = k * (k - 1) / 2;                             // the pairs (i, j), j < k, are the first k (k - 1) / 2
-        for (int q = t; q < npairs; q += 256) wmax = fmax(wmax, fabs(hs_chunk_sum(blk + a.gram_off + q, a.chunks, kHsPairPitch)));
-    }
+    for (int q = t; q < k * (k - 1) / 2; q += 256) wmax = fmax(wmax, fabs(hs_chunk_sum(blk + a.gram_off + q, a.chunks, kHsPairPitch)));
     const double omega = block_max256(wmax, red, t);
-    if (t < kHsRecHead) {
-        double v;
-        switch (t) {
-            case 0: v = state[3]; break;
-            case 1: v = state[4]; break;
-            case 2: v = (double)k; break;
-            case 3: v = beta_k; break;
-            case 4: v = (double)sweeps; break;
-            case 5: v = off_f; break;
-            case 6: v = norm_t; break;
-            case 7: v = (double)a.rows; break;
-            case 8: v = state[5]; break;
-            case 11: v = omega; break;
-            default: v = 0.0; break;                                    // theta_max, theta_min where k = 0
-        }
-        if (t < 9 || t == 11 || k == 0) out[t] = v;
-    }
+    lanczos_head_store(out, t, k, state[3], state[4], state[5], a.rows, omega, rz);
     if (t == 12) out[kHsRecord - 2] = (double)a.samples;
     if (t == 13) out[kHsRecord - 1] = 0.0;
 }
@@ -783,8 +713,8 @@ static long long hs_plan(const vaek_ctx* c, int rows, int samples, HsArgs* a) {
     const long long tail = off;
     off += (long long)tiles * kHsTail;
     const int chunks = (int)((c->P + kHsChunk - 1) / kHsChunk);
-    const long long state = off, wvec = state + kHsState, dotA = wvec + ((c->P + 1) & ~(int64_t)1), dotB = dotA + (long long)chunks * kHsMaxSteps,
-                    nrm = dotB + (long long)chunks * kHsMaxSteps, gram = nrm + ((chunks + 1) & ~1);
+    const long long state = off, wvec = state + kHsState, dotA = wvec + ((c->P + 1) & ~(int64_t)1), dotB = dotA + (long long)chunks * kLanczosMaxSteps,
+                    nrm = dotB + (long long)chunks * kLanczosMaxSteps, gram = nrm + ((chunks + 1) & ~1);
     off = gram + (long long)chunks * kHsPairPitch;
     int tile = 0;
     for (int i = 0; i < 8; ++i) {
@@ -806,37 +736,10 @@ static long long hs_plan(const vaek_ctx* c, int rows, int samples, HsArgs* a) {
 }
 
 static int hs_check_size(const char* who, int32_t n, int32_t rows, int32_t samples) {
-    if (int rc = check_sample_count(who, samples)) return rc;
-    if ((long long)rows * samples > kHsMaxReplicaColumns) {
-        set_error("%s: %d rows x %d samples = %lld columns per replica, at most %d (rows * samples <= 2^13; "
-                  "vaek_mlp3_sampled_elbo_hessian_max_columns bounds n * rows * samples)", who, rows, samples, (long long)rows * samples,
-                  kHsMaxReplicaColumns);
-        return VAEK_ERR_INVALID;
-    }
-    return check_column_count(who, n, rows, samples, "samples", kHsMaxColumns, "vaek_mlp3_sampled_elbo_hessian_max_columns");
+    return check_sampled_columns(who, n, rows, samples, kHsReplicaColumnsLog2, kHsMaxColumns, "vaek_mlp3_sampled_elbo_hessian_max_columns");
 }
 
-// a double buffer of `len` doubles per replica at stride `stride`; shared_ok: stride 0 means one buffer for all replicas
-static int hs_check_doubles(const char* who, const char* what, const void* ptr, int64_t stride, int64_t len, bool shared_ok) {
-    if (!ptr) { set_error("%s: %s is NULL", who, what); return VAEK_ERR_INVALID; }
-    if (int rc = check_aligned8(who, what, (uintptr_t)ptr)) return rc;
-    const bool shared = stride == 0 && shared_ok;
-    if (stride < 0 || (!shared && stride < len)) {
-        set_error("%s: %s stride %lld < its length %lld%s", who, what, (long long)stride, (long long)len, shared_ok ? " (0: shared)" : "");
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
-}
-
-static bool hs_overlap(const double* p, int64_t stride, int64_t len, const double* q, int64_t qstride, int64_t qlen, int n) {
-    const uintptr_t a0 = (uintptr_t)p, a1 = a0 + sizeof(double) * (size_t)((n - 1) * stride + len);
-    const uintptr_t b0 = (uintptr_t)q, b1 = b0 + sizeof(double) * (size_t)((n - 1) * qstride + qlen);
-    return a0 < b1 && b0 < a1;
-}
-
-struct HsExtra { int32_t samples; const uint64_t* z_seeds; const uint32_t* z_steps; const float* xi; int64_t xi_stride; };
-
-static int hs_common(const char* who, const EvalDesc& d, const HsExtra& x, int record, const char* record_query, vaek_ctx* ctx, const float* params,
+static int hs_common(const char* who, const EvalDesc& d, const SampleSource& x, int record, const char* record_query, vaek_ctx* ctx, const float* params,
                      int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag, uint32_t z_tag,
                      void* workspace, HsArgs* a) {
     char needs[256];
@@ -851,16 +754,7 @@ static int hs_common(const char* who, const EvalDesc& d, const HsExtra& x, int r
     r.workspace = workspace; r.ws_align = 16; r.ws_query = "vaek_mlp3_sampled_elbo_hessian_workspace_bytes";
     if (int rc = check_eval(who, ctx, params, d, r)) return rc;
     if (int rc = hs_check_size(who, d.n, d.rows, x.samples)) return rc;
-    if (x.xi) {
-        const int64_t len = (int64_t)d.rows * x.samples * ctx->L;
-        if (x.xi_stride < 0 || (x.xi_stride > 0 && x.xi_stride < len)) {
-            set_error("%s: xi_stride %lld: need 0 (shared samples) or >= rows * samples * L = %lld", who, (long long)x.xi_stride, (long long)len);
-            return VAEK_ERR_INVALID;
-        }
-    } else if (!x.z_seeds || !x.z_steps) {
-        set_error("%s: %s is NULL (xi == NULL draws the samples and reads it)", who, x.z_seeds ? "z_steps" : "z_seeds");
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_sample_source(who, x, d.rows, ctx->L)) return rc;
     a->params = params; a->state_stride = d.state_stride;
     a->x_seeds = reinterpret_cast<const unsigned long long*>(d.x_seeds); a->x_steps = d.x_steps;
     a->z_seeds = reinterpret_cast<const unsigned long long*>(x.z_seeds); a->z_steps = x.z_steps;
@@ -937,27 +831,12 @@ int vaek_mlp3_sampled_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, cons
     ProfBind pb(ctx);
     HsArgs a{};
     const EvalDesc d = describe(hp);
-    const bool read = d.given && d.struct_size == (int32_t)d.want;
-    const HsExtra x = read ? HsExtra{hp->samples, hp->z_seeds, hp->z_steps, hp->xi, hp->xi_stride} : HsExtra{};
-    if (int rc = hs_common(who, d, x, kHsHvpRecord, "vaek_elbo_hvp_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag, z_tag,
-                           workspace, &a))
+    if (int rc = hs_common(who, d, sample_source(d, hp), kHvpRecord, "vaek_elbo_hvp_record_len", ctx, params, kind, A, dd, did, pad, var_added,
+                           x_tag, z_tag, workspace, &a))
         return rc;
-    if (hp->nvec < 0 || hp->nvec > kHsMaxVectors) {
-        set_error("%s: %d vectors, need 0 .. %d (vaek_elbo_hvp_max_vectors)", who, hp->nvec, kHsMaxVectors);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_hvp_buffers(who, hp, ctx->P, true)) return rc;
     const int64_t P = ctx->P;
     const int n = hp->n;
-    if (hp->nvec > 0) {
-        if (int rc = hs_check_doubles(who, "v", hp->v, hp->v_stride, hp->nvec * P, true)) return rc;
-        if (int rc = hs_check_doubles(who, "hv", hp->hv, hp->hv_stride, hp->nvec * P, false)) return rc;
-        if (hs_overlap(hp->v, hp->v_stride, hp->nvec * P, hp->hv, hp->hv_stride, hp->nvec * P, n)) {
-            set_error("%s: v and hv overlap: a direction is read by launches that follow the store of an earlier product", who);
-            return VAEK_ERR_INVALID;
-        }
-    }
-    if (hp->grad)
-        if (int rc = hs_check_doubles(who, "grad", hp->grad, hp->grad_stride, P, false)) return rc;
     hipStream_t st = (hipStream_t)stream;
     a.out = hp->out; a.out_stride = hp->out_stride;
     a.grad = hp->grad; a.grad_stride = hp->grad_stride;
@@ -978,19 +857,12 @@ int vaek_mlp3_sampled_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* 
     ProfBind pb(ctx);
     HsArgs a{};
     const EvalDesc d = describe(hs);
-    const bool read = d.given && d.struct_size == (int32_t)d.want;
-    const HsExtra x = read ? HsExtra{hs->samples, hs->z_seeds, hs->z_steps, hs->xi, hs->xi_stride} : HsExtra{};
-    if (int rc = hs_common(who, d, x, kHsRecord, "vaek_sampled_elbo_hessian_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag,
-                           z_tag, workspace, &a))
+    if (int rc = hs_common(who, d, sample_source(d, hs), kHsRecord, "vaek_sampled_elbo_hessian_record_len", ctx, params, kind, A, dd, did, pad,
+                           var_added, x_tag, z_tag, workspace, &a))
         return rc;
-    if (hs->steps < 1 || hs->steps > kHsMaxSteps) {
-        set_error("%s: %d steps, need 1 .. %d (vaek_elbo_hessian_max_steps)", who, hs->steps, kHsMaxSteps);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_lanczos_buffers(who, hs, ctx->P)) return rc;
     const int64_t P = ctx->P;
     const int n = hs->n;
-    if (int rc = hs_check_doubles(who, "v0", hs->v0, hs->v0_stride, P, true)) return rc;
-    if (int rc = hs_check_doubles(who, "basis", hs->basis, hs->basis_stride, hs->steps * P, false)) return rc;
     hipStream_t st = (hipStream_t)stream;
     a.out = hs->out; a.out_stride = hs->out_stride;
     a.v0 = hs->v0; a.v0_stride = hs->v0_stride; a.basis = hs->basis; a.basis_stride = hs->basis_stride; a.steps = hs->steps;

@@ -12,27 +12,21 @@
 //     sub-tiles.  Every element of the tile's PARTIAL of H v (or of grad f_K and f_K) is ONE chain over the tile's columns in column order.
 //   COMBINE.  One workgroup per replica adds the tiles' partials in tile order.  The partials cross a launch boundary: nothing stored in
 //     a launch is read back in it, and there is no atomic, counter, wait or spin.
-//   LANCZOS.  Per step one tile launch (H v_j) and one per-replica launch: combine, classical Gram-Schmidt twice against v_1 .. v_j with
-//     every dot through block_sum256's fixed tree, alpha_j, beta_j, the breakdown test of elbo_hessian.hip, v_{j+1} into the caller's
-//     basis.  A replica that is done leaves a flag in its state block of the workspace; the later launches read it and do nothing.  The
-//     last launch solves T with jacobi_solve<true> (eigen_dev.h, included and not edited), measures omega and stores the record.
+//   LANCZOS.  lanczos_dev.h's recursion, a launch per piece.  Per step one tile launch (H v_j) and one per-replica launch: combine, then
+//     the header's step (classical Gram-Schmidt twice against v_1 .. v_j, alpha_j, beta_j, the breakdown rule, v_{j+1} into the caller's
+//     basis).  A replica that is done leaves a flag in its state block of the workspace; the later launches read it and do nothing.  The
+//     last launch runs the header's Ritz tail, omega and record store on the alpha and beta of the state block.
 //
 // The kernels read rows / samples / parameters / directions and store only the named outputs and the workspace, with per-lane vector
 // stores.  Launches: 2 + 2 nvec (hvp call), 3 + 2 steps (Lanczos call).
-#include "eigen_dev.h"
+#include "lanczos_dev.h"
 #include "eval_check.h"
 
 namespace vaek {
 
-constexpr int kSampMaxSteps = 32;            // the Jacobi routine's size
-constexpr int kSampMaxVectors = 64;          // bounds one call -- a cap, not a tuned value
 constexpr int kSampMaxColumns = 1 << 22;     // n * rows * samples of one call ...
-constexpr int kSampMaxReplicaColumns = 1 << 16;      // ... and rows * samples of one replica: caps on the length of a launch
-constexpr int kSampHvpRecord = 4;
-constexpr int kSampHead = 12;
-constexpr int kSampRecord = kSampHead + 4 * kSampMaxSteps + 2;
-constexpr double kSampBreakdown = 0x1p-40;
-constexpr double kSampLog2Pi = 1.8378770664093454835606594728112;
+constexpr int kSampReplicaColumnsLog2 = 16;  // ... and rows * samples of one replica, 2^16: caps on the length of a launch
+constexpr int kSampRecord = kLanczosRecord + 2;      // the Lanczos record, then samples and the two-decoder flag
 
 constexpr int kSub = 32;                     // columns of a sub-tile: two 16-row blocks of the matrix-core products
 constexpr int kTileCols = 256;               // columns of a workgroup's tile
@@ -410,7 +404,7 @@ __global__ __launch_bounds__(256) void sampled_tile_kernel(const SampArgs a, con
             if (first) {
                 double klc = 0.0;
                 for (int l = 0; l < L; ++l) klc += vec[vEw + l] - 1.0 - vec[vPl + l];
-                f += 0.5 * klc + 0.5 * (double)D * (eps + kSampLog2Pi);
+                f += 0.5 * klc + 0.5 * (double)D * (eps + kLog2PiF64);
             }
             part[P] = f;
         }
@@ -448,7 +442,7 @@ __global__ __launch_bounds__(256) void sampled_combine_kernel(const SampArgs a, 
     }
     if constexpr (GRAD) {
         const double gnorm = sqrt(block_sum256(part, red, t));
-        if (t < kSampHvpRecord) {
+        if (t < kHvpRecord) {
             const float* const p = a.params + r * a.state_stride;
             const double eps_cli = (double)a.eps_cli;
             const double eps = a.off_c >= 0 ? (double)p[a.off_c] * eps_cli : eps_cli;
@@ -470,12 +464,7 @@ __global__ __launch_bounds__(256) void sampled_lanczos_init_kernel(const SampArg
     double part = 0.0;
     for (int e = t; e < P; e += 256) { const double s = samp_combine(a, r, n_replicas, e); part = fma(s, s, part); }
     const double gnorm = sqrt(block_sum256(part, red, t));
-    part = 0.0;
-    for (int e = t; e < P; e += 256) part = fma(v0[e], v0[e], part);
-    const double n0 = sqrt(block_sum256(part, red, t));
-    const int kmax = n0 > 0.0 && n0 < INFINITY ? (a.steps < P ? a.steps : P) : 0;
-    if (kmax > 0)
-        for (int e = t; e < P; e += 256) basis[e] = v0[e] / n0;
+    const int kmax = lanczos_start(v0, basis, P, a.steps, red, t);
     if (t < kState) {
         double v = 0.0;
         if (t == 0) v = kmax > 0 ? 0.0 : 1.0;
@@ -492,7 +481,7 @@ __global__ __launch_bounds__(256) void sampled_lanczos_init_kernel(const SampArg
 // Lanczos step j + 1 of a replica that is not done: w = the combined partials of H v_{j+1}, classical Gram-Schmidt twice, alpha, beta,
 // the breakdown test, v_{j+2} into the basis.  The basis rows it reads were stored by earlier launches.
 __global__ __launch_bounds__(256) void sampled_lanczos_step_kernel(const SampArgs a, const int n_replicas) {
-    __shared__ double red[256], wv[kSampFlat], coef[kSampMaxSteps];
+    __shared__ double red[256], wv[kSampFlat], coef[kLanczosMaxSteps];
     const int t = threadIdx.x;
     const long long r = blockIdx.x;
     const int P = a.P, j = a.j;
@@ -504,133 +493,35 @@ __global__ __launch_bounds__(256) void sampled_lanczos_step_kernel(const SampArg
     double* const basis = a.basis + r * a.basis_stride;
     for (int e = t; e < P; e += 256) wv[e] = samp_combine(a, r, n_replicas, e);
     __syncthreads();
-    double al = 0.0;
-    for (int pass = 0; pass < 2; ++pass) {
-        for (int i = 0; i <= j; ++i) {
-            const double* const vi = basis + (long long)i * P;
-            double d = 0.0;
-            for (int e = t; e < P; e += 256) d = fma(vi[e], wv[e], d);
-            d = block_sum256(d, red, t);
-            if (t == 0) coef[i] = d;
-            if (i == j) al += d;
-        }
-        __syncthreads();
-        for (int e = t; e < P; e += 256) {
-            double s = wv[e];
-            for (int i = 0; i <= j; ++i) s = fma(-coef[i], basis[(long long)i * P + e], s);
-            wv[e] = s;
-        }
-        __syncthreads();
-    }
-    double part = 0.0;
-    for (int e = t; e < P; e += 256) part = fma(wv[e], wv[e], part);
-    const double be = sqrt(block_sum256(part, red, t));
-    const int k = j + 1, kmax = a.steps < P ? a.steps : P;
-    double scale = fmax(scale0, fabs(al));
-    const bool stop = be <= kSampBreakdown * scale || k == kmax;      // the same values in every thread: the decision is uniform
-    scale = fmax(scale, be);
+    double al, be, scale = scale0;
+    lanczos_orthogonalise(wv, basis, P, j, coef, red, t, al, be);
+    const int k = j + 1;
+    const bool stop = lanczos_next(wv, basis, P, k, a.steps < P ? a.steps : P, al, be, scale, t);
     if (t == 0) {
         state[sAlpha + j] = al; state[sBeta + j] = be;
         state[1] = (double)k; state[2] = scale;
         if (stop) state[0] = 1.0;
     }
-    if (!stop) {
-        double* const vn = basis + (long long)k * P;
-        for (int e = t; e < P; e += 256) vn[e] = wv[e] / be;
-    }
 }
 
-// the last launch: T from the state block, the solve, the Ritz values and their bounds, omega, the record (elbo_hessian.hip's text)
+// the last launch: T from the state block, then lanczos_dev.h's tail: the solve, the Ritz values and their bounds, omega, the record
 __global__ __launch_bounds__(256) void sampled_lanczos_final_kernel(const SampArgs a) {
     __shared__ double mat[2 * kMatDoubles], vecs[2 * kMatDoubles];
     __shared__ double red[256], alpha[kSpectrumMaxDim], beta[kSpectrumMaxDim], rot_c[kSpectrumMaxDim], rot_s[kSpectrumMaxDim], eig[kSpectrumMaxDim];
     __shared__ int rot_mate[kSpectrumMaxDim];
     const int t = threadIdx.x;
     const long long r = blockIdx.x;
-    const int P = a.P;
     const double* const state = a.ws + r * kState;
-    const double* const basis = a.basis + r * a.basis_stride;
     double* const out = a.out + r * a.out_stride;
     const int k = (int)state[1];
-    if (t < kSampMaxSteps) { alpha[t] = t < k ? state[sAlpha + t] : 0.0; beta[t] = t < k ? state[sBeta + t] : 0.0; }
+    if (t < k) { alpha[t] = state[sAlpha + t]; beta[t] = state[sBeta + t]; }
     __syncthreads();
-    double sq = 0.0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int idx = t + 256 * q, i = idx >> 5, j = idx & 31;
-        double v = 0.0;
-        if (i < k && j < k) {                                           // the pad row and column of an odd k are zero
-            if (i == j) v = alpha[i];
-            else if (i + 1 == j) v = beta[i];
-            else if (j + 1 == i) v = beta[j];
-        }
-        mat[i * kMatStride + j] = v;
-        if (i <= j) sq += i == j ? v * v : 2.0 * v * v;
-        const double id = i == j ? 1.0 : 0.0;
-        vecs[i * kMatStride + j] = id;                                  // the solve may end in either buffer
-        vecs[kMatDoubles + i * kMatStride + j] = id;
-    }
-    const double norm_t = sqrt(block_sum256(sq, red, t));               // its barriers also publish T and V
-    int cur = 0, sweeps = 0;
-    double off_f = 0.0;
-    if (k > 0) jacobi_solve<true>(mat, vecs, k + (k & 1), norm_t, red, rot_c, rot_s, rot_mate, t, cur, sweeps, off_f);
-    const double* const A = mat + cur * kMatDoubles;
-    const double* const V = vecs + cur * kMatDoubles;
-    if (t < kSampMaxSteps) eig[t] = t < k ? A[t * kMatStride + t] : 0.0;
-    __syncthreads();
-    const double beta_k = k > 0 ? beta[k - 1] : 0.0;
-    if (t < kSampMaxSteps) {
-        if (t < k) {
-            const double e = eig[t];
-            int rank = 0;
-            for (int j = 0; j < k; ++j) {
-                const double o = eig[j];
-                rank += (o < e || (o == e && j < t)) ? 1 : 0;
-            }
-            out[kSampHead + rank] = e;
-            out[kSampHead + kSampMaxSteps + rank] = fabs(beta_k * V[(k - 1) * kMatStride + t]);
-            if (rank == k - 1) out[9] = e;
-            if (rank == 0) out[10] = e;
-        } else {
-            out[kSampHead + t] = 0.0;
-            out[kSampHead + kSampMaxSteps + t] = 0.0;
-        }
-        out[kSampHead + 2 * kSampMaxSteps + t] = alpha[t];
-        out[kSampHead + 3 * kSampMaxSteps + t] = beta[t];
-    }
-    // omega = max_{i < j < k} |v_i . v_j|: a wave per pair, lanes over the elements, one fixed butterfly
-    double wmax = 0.0;
-    {
-        const int wave = t >> 6, lane = t & 63, npairs = k * (k - 1) / 2;
-        for (int q = wave; q < npairs; q += 4) {
-            int j = 1, first = 0;
-            while (first + j <= q) { first += j; ++j; }
-            const double* const vi = basis + (long long)(q - first) * P;
-            const double* const vj = basis + (long long)j * P;
-            double s = 0.0;
-            for (int e = lane; e < P; e += 64) s = fma(vi[e], vj[e], s);
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-            wmax = fmax(wmax, fabs(s));
-        }
-    }
-    const double omega = block_max256(wmax, red, t);
-    if (t < kSampHead) {
-        double v;
-        switch (t) {
-            case 0: v = state[3]; break;
-            case 1: v = state[4]; break;
-            case 2: v = (double)k; break;
-            case 3: v = beta_k; break;
-            case 4: v = (double)sweeps; break;
-            case 5: v = off_f; break;
-            case 6: v = norm_t; break;
-            case 7: v = (double)a.rows; break;
-            case 8: v = state[5]; break;
-            case 11: v = omega; break;
-            default: v = 0.0; break;                                    // theta_max, theta_min where k = 0
-        }
-        if (t < 9 || t == 11 || k == 0) out[t] = v;
-    }
+    LanczosLds s;
+    s.mat = mat; s.vec = vecs; s.red = red; s.alpha = alpha; s.beta = beta;
+    s.rot_c = rot_c; s.rot_s = rot_s; s.eig = eig; s.rot_mate = rot_mate;
+    const RitzResult rz = lanczos_ritz(s, k, out, t);
+    const double omega = lanczos_omega(a.basis + r * a.basis_stride, a.P, k, red, t);
+    lanczos_head_store(out, t, k, state[3], state[4], state[5], a.rows, omega, rz);
     if (t == 12) out[kSampRecord - 2] = (double)a.samples;
     if (t == 13) out[kSampRecord - 1] = a.sig ? 1.0 : 0.0;
 }
@@ -659,31 +550,10 @@ static size_t samp_workspace_bytes(const vaek_ctx* c, int n, int rows, int sampl
 
 // rows, samples and their products, for a call and for the workspace query alike
 static int samp_check_size(const char* who, int32_t n, int32_t rows, int32_t samples) {
-    if (int rc = check_sample_count(who, samples)) return rc;
-    if ((long long)rows * samples > kSampMaxReplicaColumns) {
-        set_error("%s: %d rows x %d samples = %lld columns per replica, at most %d (rows * samples <= 2^16; vaek_sampled_elbo_hessian_max_columns "
-                  "bounds n * rows * samples)", who, rows, samples, (long long)rows * samples, kSampMaxReplicaColumns);
-        return VAEK_ERR_INVALID;
-    }
-    return check_column_count(who, n, rows, samples, "samples", kSampMaxColumns, "vaek_sampled_elbo_hessian_max_columns");
+    return check_sampled_columns(who, n, rows, samples, kSampReplicaColumnsLog2, kSampMaxColumns, "vaek_sampled_elbo_hessian_max_columns");
 }
 
-// a double buffer of `len` doubles per replica at stride `stride`; shared_ok: stride 0 means one buffer for all replicas
-static int samp_check_doubles(const char* who, const char* what, const void* ptr, int64_t stride, int64_t len, bool shared_ok) {
-    if (!ptr) { set_error("%s: %s is NULL", who, what); return VAEK_ERR_INVALID; }
-    if (int rc = check_aligned8(who, what, (uintptr_t)ptr)) return rc;
-    const bool shared = stride == 0 && shared_ok;
-    if (stride < 0 || (!shared && stride < len)) {
-        set_error("%s: %s stride %lld < its length %lld%s", who, what, (long long)stride, (long long)len, shared_ok ? " (0: shared)" : "");
-        return VAEK_ERR_INVALID;
-    }
-    return VAEK_OK;
-}
-
-// what the two descriptions add to the exact calls': samples, the samples' source
-struct SampExtra { int32_t samples; const uint64_t* z_seeds; const uint32_t* z_steps; const float* xi; int64_t xi_stride; };
-
-static int sampled_common(const char* who, const EvalDesc& d, const SampExtra& x, int record, const char* record_query, vaek_ctx* ctx,
+static int sampled_common(const char* who, const EvalDesc& d, const SampleSource& x, int record, const char* record_query, vaek_ctx* ctx,
                           const float* params, int32_t kind, const float* A, int32_t dd, int32_t did, int32_t pad, float var_added, uint32_t x_tag,
                           uint32_t z_tag, void* workspace, SampArgs* a) {
     EvalRules r{};
@@ -697,16 +567,7 @@ static int sampled_common(const char* who, const EvalDesc& d, const SampExtra& x
     r.workspace = workspace; r.ws_align = 16; r.ws_query = "vaek_sampled_elbo_hessian_workspace_bytes";
     if (int rc = check_eval(who, ctx, params, d, r)) return rc;
     if (int rc = samp_check_size(who, d.n, d.rows, x.samples)) return rc;
-    if (x.xi) {
-        const int64_t len = (int64_t)d.rows * x.samples * ctx->L;
-        if (x.xi_stride < 0 || (x.xi_stride > 0 && x.xi_stride < len)) {
-            set_error("%s: xi_stride %lld: need 0 (shared samples) or >= rows * samples * L = %lld", who, (long long)x.xi_stride, (long long)len);
-            return VAEK_ERR_INVALID;
-        }
-    } else if (!x.z_seeds || !x.z_steps) {
-        set_error("%s: %s is NULL (xi == NULL draws the samples and reads it)", who, x.z_seeds ? "z_steps" : "z_seeds");
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_sample_source(who, x, d.rows, ctx->L)) return rc;
     a->params = params; a->state_stride = d.state_stride;
     a->x_seeds = reinterpret_cast<const unsigned long long*>(d.x_seeds); a->x_steps = d.x_steps;
     a->z_seeds = reinterpret_cast<const unsigned long long*>(x.z_seeds); a->z_steps = x.z_steps;
@@ -740,13 +601,6 @@ static int samp_launch_replicas(const char* label, Kernel fn, int n, hipStream_t
     }
     VAEK_HIP_CHECK(hipGetLastError());
     return VAEK_OK;
-}
-
-// [lo, lo + span) of a buffer of `len` doubles per replica at `stride`
-static bool samp_overlap(const double* p, int64_t stride, int64_t len, const double* q, int64_t qstride, int64_t qlen, int n) {
-    const uintptr_t a0 = (uintptr_t)p, a1 = a0 + sizeof(double) * (size_t)((n - 1) * stride + len);
-    const uintptr_t b0 = (uintptr_t)q, b1 = b0 + sizeof(double) * (size_t)((n - 1) * qstride + qlen);
-    return a0 < b1 && b0 < a1;
 }
 
 }  // namespace vaek
@@ -784,27 +638,12 @@ int vaek_sampled_elbo_hvp_replicas(vaek_ctx* ctx, const float* params, const vae
     ProfBind pb(ctx);
     SampArgs a{};
     const EvalDesc d = describe(hp);
-    const bool read = d.given && d.struct_size == (int32_t)d.want;
-    const SampExtra x = read ? SampExtra{hp->samples, hp->z_seeds, hp->z_steps, hp->xi, hp->xi_stride} : SampExtra{};
-    if (int rc = sampled_common(who, d, x, kSampHvpRecord, "vaek_elbo_hvp_record_len", ctx, params, kind, A, dd, did, pad, var_added, x_tag, z_tag,
-                                workspace, &a))
+    if (int rc = sampled_common(who, d, sample_source(d, hp), kHvpRecord, "vaek_elbo_hvp_record_len", ctx, params, kind, A, dd, did, pad, var_added,
+                                x_tag, z_tag, workspace, &a))
         return rc;
-    if (hp->nvec < 0 || hp->nvec > kSampMaxVectors) {
-        set_error("%s: %d vectors, need 0 .. %d (vaek_elbo_hvp_max_vectors)", who, hp->nvec, kSampMaxVectors);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_hvp_buffers(who, hp, ctx->P, true)) return rc;
     const int64_t P = ctx->P;
     const int n = hp->n;
-    if (hp->nvec > 0) {
-        if (int rc = samp_check_doubles(who, "v", hp->v, hp->v_stride, hp->nvec * P, true)) return rc;
-        if (int rc = samp_check_doubles(who, "hv", hp->hv, hp->hv_stride, hp->nvec * P, false)) return rc;
-        if (samp_overlap(hp->v, hp->v_stride, hp->nvec * P, hp->hv, hp->hv_stride, hp->nvec * P, n)) {
-            set_error("%s: v and hv overlap: a direction is read by launches that follow the store of an earlier product", who);
-            return VAEK_ERR_INVALID;
-        }
-    }
-    if (hp->grad)
-        if (int rc = samp_check_doubles(who, "grad", hp->grad, hp->grad_stride, P, false)) return rc;
     hipStream_t st = (hipStream_t)stream;
     a.out = hp->out; a.out_stride = hp->out_stride;
     a.dst = hp->grad; a.dst_stride = hp->grad_stride;
@@ -826,19 +665,12 @@ int vaek_sampled_elbo_hessian_lanczos_replicas(vaek_ctx* ctx, const float* param
     ProfBind pb(ctx);
     SampArgs a{};
     const EvalDesc d = describe(hs);
-    const bool read = d.given && d.struct_size == (int32_t)d.want;
-    const SampExtra x = read ? SampExtra{hs->samples, hs->z_seeds, hs->z_steps, hs->xi, hs->xi_stride} : SampExtra{};
-    if (int rc = sampled_common(who, d, x, kSampRecord, "vaek_sampled_elbo_hessian_record_len", ctx, params, kind, A, dd, did, pad, var_added,
-                                x_tag, z_tag, workspace, &a))
+    if (int rc = sampled_common(who, d, sample_source(d, hs), kSampRecord, "vaek_sampled_elbo_hessian_record_len", ctx, params, kind, A, dd, did, pad,
+                                var_added, x_tag, z_tag, workspace, &a))
         return rc;
-    if (hs->steps < 1 || hs->steps > kSampMaxSteps) {
-        set_error("%s: %d steps, need 1 .. %d (vaek_elbo_hessian_max_steps)", who, hs->steps, kSampMaxSteps);
-        return VAEK_ERR_INVALID;
-    }
+    if (int rc = check_lanczos_buffers(who, hs, ctx->P)) return rc;
     const int64_t P = ctx->P;
     const int n = hs->n;
-    if (int rc = samp_check_doubles(who, "v0", hs->v0, hs->v0_stride, P, true)) return rc;
-    if (int rc = samp_check_doubles(who, "basis", hs->basis, hs->basis_stride, hs->steps * P, false)) return rc;
     hipStream_t st = (hipStream_t)stream;
     a.out = hs->out; a.out_stride = hs->out_stride;
     a.v0 = hs->v0; a.v0_stride = hs->v0_stride; a.basis = hs->basis; a.basis_stride = hs->basis_stride; a.steps = hs->steps;
