@@ -317,19 +317,9 @@ def _bf16_emulation_grads(cfg, p, x, z1, z2):
 def _checked_conv_calls(monkeypatch, log):
     """Wrap the three convolution entry points conv_vae.py calls: every call is compared, on ITS OWN inputs, with torch float64 with
     the operands rounded to bf16 where the kernel rounds them (not at all for the one-channel streaming kernels)."""
-    import torch.nn.functional as F
     import vae_training_amd.conv_vae as CV
-    rb = lambda t: t.to(torch.bfloat16).to(torch.float64)
-    ident = lambda t: t
-    nchw = lambda t: t.double().cpu().permute(0, 3, 1, 2)
-    oihw = lambda t: t.double().cpu().permute(3, 2, 0, 1)
-    rel = lambda a, b: float((a.double().cpu() - b).abs().max() / (b.abs().max() + 1e-30))
+    from tests.conv_cases import ref_forward, ref_transpose, ref_weight_grad, rel, streams
     o_f, o_t, o_w = CV.conv2d_forward, CV.conv2d_transpose_forward, CV.conv2d_weight_grad
-
-    def finish(ref, relu, mask):
-        ref = ref.permute(0, 2, 3, 1)
-        ref = torch.relu(ref) if relu else ref
-        return ref if mask is None else ref * (mask.cpu() > 0)
 
     def same16(t, t16):              # a bf16 copy handed along must BE the bf16 rounding of the float32 tensor
         return t16 is None or torch.equal(t16, t.to(torch.bfloat16))
@@ -337,28 +327,26 @@ def _checked_conv_calls(monkeypatch, log):
     def fwd(x, w, bias=None, relu=False, mask=None, out=None, **kw):
         res = o_f(x, w, bias, relu, mask, out, **kw)
         y, y16 = res if isinstance(res, tuple) else (res, None)
-        r = ident if x.shape[3] == 1 and 256 % w.shape[3] == 0 else rb
-        ref = F.conv2d(r(nchw(x)), r(oihw(w)), None if bias is None else bias.double().cpu(), stride=2, padding=1)
-        log.append(("forward", tuple(x.shape), rel(y, finish(ref, relu, mask))))
+        r = not streams("forward", x.shape[3], w.shape[3])
+        log.append(("forward", tuple(x.shape), rel(y, ref_forward(x, w, bias, relu, mask, r, r))))
         assert same16(x, kw.get("x16")) and same16(y, y16) and (y16 is not None) == bool(kw.get("want16"))
         return res
 
     def tfwd(y, w, bias=None, relu=False, mask=None, **kw):
         res = o_t(y, w, bias, relu, mask, **kw)
         out, out16 = res if isinstance(res, tuple) else (res, None)
-        r = ident if w.shape[2] == 1 and w.shape[3] % 4 == 0 and w.shape[3] <= 256 else rb
-        ref = F.conv_transpose2d(r(nchw(y)), r(oihw(w)), None if bias is None else bias.double().cpu(), stride=2, padding=1)
-        log.append(("transposed", tuple(y.shape), rel(out, finish(ref, relu, mask))))
+        r = not streams("transposed", w.shape[3], w.shape[2])
+        log.append(("transposed", tuple(y.shape), rel(out, ref_transpose(y, w, bias, relu, mask, r, r))))
         assert same16(y, kw.get("y16")) and same16(out, out16) and (out16 is not None) == bool(kw.get("want16"))
         return res
 
     def wgrad(x, dy, want_bias=True, dw=None, db=None, **kw):
         dw, db = o_w(x, dy, want_bias, dw, db, **kw)
-        r = ident if x.shape[3] == 1 and 256 % dy.shape[3] == 0 else rb
-        ref = torch.nn.grad.conv2d_weight(r(nchw(x)), (dy.shape[3], x.shape[3], 4, 4), r(nchw(dy)), stride=2, padding=1).permute(2, 3, 1, 0)
+        r = not streams("kernel gradient", x.shape[3], dy.shape[3])
+        ref, ref_b = ref_weight_grad(x, dy, r, r)
         log.append(("kernel gradient", tuple(x.shape), rel(dw.reshape(ref.shape), ref)))
         if db is not None:
-            log.append(("bias gradient", tuple(x.shape), rel(db, r(dy.double().cpu()).sum(dim=(0, 1, 2)))))      # a ones row of the same bf16 product
+            log.append(("bias gradient", tuple(x.shape), rel(db, ref_b)))      # a ones row of the same bf16 product
         assert same16(x, kw.get("x16")) and same16(dy, kw.get("dy16"))
         return dw, db
 

@@ -63,10 +63,10 @@ def conv2d_forward(x, w, bias=None, relu=False, mask=None, out=None, fast=True, 
     return (y, y16) if want16 else y
 
 
-def conv2d_transpose_forward(y, w, bias=None, relu=False, mask=None, fast=True, y16=None, want16=False, mask16=None, want32=True):
+def conv2d_transpose_forward(y, w, bias=None, relu=False, mask=None, fast=True, y16=None, want16=False, mask16=None, want32=True, out=None):
     """The adjoint of conv2d_forward with the same kernel array: y [B, h, w, Cin], w [4, 4, Cout, Cin] -> [B, 2 h, 2 w, Cout]
     (vaek_conv2d_transpose_forward).  With bias=None it is the convolution's input gradient; `mask` applies the relu of the layer
-    below ([mask > 0]).  y16 / want16 / mask16 / want32 / y=None: as in conv2d_forward."""
+    below ([mask > 0]).  y16 / want16 / mask16 / want32 / y=None / out: as in conv2d_forward."""
     lib = _lib.load()
     src = y if y is not None else y16
     assert src.is_cuda and w.is_cuda and w.dtype == torch.float32 and src.is_contiguous() and w.is_contiguous()
@@ -76,7 +76,8 @@ def conv2d_transpose_forward(y, w, bias=None, relu=False, mask=None, fast=True, 
     assert y16 is None or (y16.dtype == torch.bfloat16 and tuple(y16.shape) == (B, h, wd, Cin) and y16.is_contiguous())
     assert want32 or want16
     Cout = w.shape[2]
-    out = torch.empty(B, 2 * h, 2 * wd, Cout, dtype=torch.float32, device=src.device) if want32 else None
+    assert out is None or (out.dtype == torch.float32 and tuple(out.shape) == (B, 2 * h, 2 * wd, Cout) and out.is_contiguous())
+    out = (torch.empty(B, 2 * h, 2 * wd, Cout, dtype=torch.float32, device=src.device) if out is None else out) if want32 else None
     out16 = torch.empty(B, 2 * h, 2 * wd, Cout, dtype=torch.bfloat16, device=src.device) if want16 else None
     m, mbit = _mask_arg(mask, mask16, (B, 2 * h, 2 * wd, Cout))
     p = lambda t: C.c_void_p(0 if t is None else t.data_ptr())
