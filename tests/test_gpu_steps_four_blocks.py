@@ -46,7 +46,9 @@ def test_four_block_shapes_take_the_persistent_form(D, L):
 
 def test_shapes_past_the_four_block_updater_stay_where_they_were():
     assert not engine_for(_lin(22, 20), 64).supports_train_steps_gen(0)          # 65 features: no moment form at all
-    eng = engine_for(_lin(10, 40), 256)                                          # L > 32: launch-per-step form only
+    # L > 32: launch-per-step form only -- its streamers and its updater are held to the float64 reference at (10, 40) and (1, 61) by
+    # tests/test_gpu_lin_moments.py (test_stream_and_reduce, test_launch_per_step_updater)
+    eng = engine_for(_lin(10, 40), 256)
     assert eng.supports_train_steps() and not eng.supports_train_steps_gen(0) and not eng.supports_train_steps_gen(2)
 
 

@@ -314,7 +314,80 @@ int lin_steps_status(vaek_ctx* c, void* ws, int* gave_up) {
     return VAEK_OK;
 }
 
+// ---- diagnostic: the streamer and reducer roles of ONE persistent launch, every batch's M copied out ------------------------------
+// What VAEK_LIN_ROLES=3 runs (has_update = 0, the windows of a single-launch call), with the batches' M slots copied to the caller
+// in stream order.  Nobody re-zeroes the arrival counters without the updater: lin_ws_ready is dropped, the next call starts over.
+static int lin_debug_moments(vaek_ctx* c, const float* const* xs, const float* const* z1s, const float* const* z2s, int n, int32_t* step_dev,
+                             double* M_out, void* ws, hipStream_t st) {
+    const LinPlan& p = c->lin;
+    const LinWs w = lin_ws(c, ws);
+    LinPersistKernel fn = nullptr;
+    if (int rc = lin_kernel(kLinPersist, p.which_persist, &fn)) return rc;
+    if (int rc = lin_ensure_init(c, w, ws, st)) return rc;
+    const LinWindows win = lin_windows(n, 0);
+    LinArgs a{};
+    lin_fill_common(c, a, nullptr, nullptr, nullptr, nullptr, step_dev, 0.f);
+    a.persistent = 1; a.n_steps = 0; a.n_red = win.reduce.count; a.n_str = win.stream.count;
+    a.slot_upd = 0; a.slot_red = 0; a.slot_str = 0; a.d_red = 0; a.d_str = 0;
+    a.sets = kLinReduceSets;
+    a.has_update = 0; a.n_reduce = p.n_reduce; a.n_stream = p.n_stream;
+    a.comm = LinComm{}; a.comm.world = 1;                      // one rank's own batches
+    c->lin_ws_ready = nullptr;
+    a.partial_base = w.partial; a.M_base = w.M;
+    a.cnt_stream = w.cnt; a.cnt_reduce = w.cnt_reduce; a.status = w.status;
+    LinPtrs ptrs{};
+    for (int i = 0; i < n; ++i) { ptrs.x[i] = xs[i]; ptrs.z1[i] = z1s[i]; ptrs.z2[i] = z2s[i]; }
+    {
+        ProfScope ps("lin_moments_persistent", st);
+        launch_k(ps, fn, dim3((unsigned)(a.n_reduce + a.n_stream)), dim3(LNT), p.lds_persist, st, a, ptrs);
+    }
+    VAEK_HIP_CHECK(hipGetLastError());
+    VAEK_HIP_CHECK(hipMemcpyAsync(M_out, w.M, (size_t)n * p.NO * sizeof(double), hipMemcpyDeviceToDevice, st));      // batch i lives in slot i
+    return VAEK_OK;
+}
+
 }  // namespace vaek
+
+// Diagnostic entry (not part of include/vaek.h; tests/test_gpu_lin_moments.py).  op 0: the context's LinPlan into args->plan -- ok,
+// NB, NO, T, ntiles, persist, which_step, which_persist, n_stream, n_reduce.  op 1: n <= 64 batches (host arrays of device pointers,
+// as vaek_train_steps takes them) through the streamers and reducers of one persistent launch; M_out [n][NO] receives every batch's
+// moment image.  step_dev: a device int32 the reducers read (the tag of the data-parallel exchange, unused here), left as it is.
+// VAEK_ERR_INVALID where the context has no persistent form; the give-up word is vaek_train_steps_status's.
+struct vaek_lin_debug_args {
+    int32_t plan[10];
+    int32_t n, reserved;
+    const float* const* xs; const float* const* z1s; const float* const* z2s;
+    int32_t* step_dev;
+    double* M_out;
+};
+extern "C" int vaek_debug_lin(vaek_ctx* ctx, int32_t op, vaek_lin_debug_args* args, void* workspace, void* stream) {
+    using namespace vaek;
+    if (!ctx || !args) { set_error("vaek_debug_lin: null argument"); return VAEK_ERR_INVALID; }
+    const LinPlan& p = ctx->lin;
+    if (op == 0) {
+        const int v[10] = {p.ok ? 1 : 0, p.NB, p.NO, p.T, p.ntiles, p.persist ? 1 : 0, p.which_step, p.which_persist, p.n_stream, p.n_reduce};
+        for (int k = 0; k < 10; ++k) args->plan[k] = v[k];
+        return VAEK_OK;
+    }
+    if (op != 1) { set_error("vaek_debug_lin: unknown op"); return VAEK_ERR_INVALID; }
+    if (!p.ok || !p.persist || ctx->cfg.world != 1) { set_error("vaek_debug_lin: this context has no single-GPU persistent form"); return VAEK_ERR_INVALID; }
+    if (args->n < 1 || args->n > kLinMaxPersist) { set_error("vaek_debug_lin: 1 <= n <= %d", kLinMaxPersist); return VAEK_ERR_INVALID; }
+    if (!args->xs || !args->z1s || !args->z2s || !args->step_dev || !args->M_out) { set_error("vaek_debug_lin: null argument"); return VAEK_ERR_INVALID; }
+    if (reinterpret_cast<uintptr_t>(args->M_out) & 7) { set_error("vaek_debug_lin: M_out must be 8-byte aligned"); return VAEK_ERR_INVALID; }
+    for (int i = 0; i < args->n; ++i) {
+        const float *x = args->xs[i], *z1 = args->z1s[i], *z2 = args->z2s[i];
+        if (!x || !z1 || !z2 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z1) | reinterpret_cast<uintptr_t>(z2)) & 15)) {
+            set_error("vaek_debug_lin: batch %d has a null or not 16-byte aligned pointer", i);
+            return VAEK_ERR_INVALID;
+        }
+    }
+    if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255)) {
+        set_error("vaek_debug_lin: workspace must be a non-null, 256-byte aligned device pointer of vaek_workspace_bytes() bytes");
+        return VAEK_ERR_WORKSPACE;
+    }
+    ProfBind pb(ctx);
+    return lin_debug_moments(ctx, args->xs, args->z1s, args->z2s, args->n, args->step_dev, args->M_out, workspace, (hipStream_t)stream);
+}
 
 #ifdef VAEK_LIN_STAMPS
 extern "C" int vaek_debug_lin_stamps(unsigned long long* buf) {

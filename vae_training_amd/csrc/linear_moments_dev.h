@@ -753,8 +753,14 @@ struct LinUpd {
         for (int e = t; e < D * NFP; e += LNT) {              // P1 = R M
             const int d = e / NFP, f = e % NFP;
             double s = sigma * Mf[(L + D + d) * NFP + f] - Mf[(L + d) * NFP + f] + bdd[d] * Mf[fone * NFP + f];
+            // (the latent index runs to L <= 61 here -- L + 2 D + 1 <= 64 with D >= 1 -- where the data index of the other loops stops
+            // at D <= 31: bounded by 32 this sum lost the latents 32 .. L - 1 of every model lin_plan sends here with L > 32)
+            if constexpr (LT > 0) {
 #pragma unroll
-            for (int l = 0; l < (LT ? LT : 32); ++l) if (LT || l < L) s += Wdd[l * D + d] * SM[l * NFP + f];
+                for (int l = 0; l < LT; ++l) s += Wdd[l * D + d] * SM[l * NFP + f];
+            } else {
+                for (int l = 0; l < L; ++l) s += Wdd[l * D + d] * SM[l * NFP + f];
+            }
             P1[e] = s;
         }
         __syncthreads();
